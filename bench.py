@@ -23,6 +23,9 @@ Prints ONE compact JSON line (rank 0; a few KB -- everything bulky goes to the s
                 an independent aggregation of the reference's rows and alignments; the cluster records of measured entries
                 against the reference's clusterhits functions
   p100 / p10000 / iter3   N = 1 only: short child records at BASELINE configs[1] / configs[4] / configs[3]
+
+--dump-outputs DIR writes the results the timed path returned for its last step (rank 0's share) to DIR/<name>.npy, float64, at most
+64 MB (dump_outputs); the inputs depend on the arguments only, so the files of two builds can be compared array by array.
 """
 import argparse
 import json
@@ -73,7 +76,11 @@ def parse():
     ap.add_argument('--strong', action='store_true', help='strong scaling: --batch query proteomes per step in TOTAL, dealt over the ranks '
                                                           '(BASELINE configs[2] as written: one query set of proteomes split over N GPUs)')
     ap.add_argument('--record', action='store_true', help=argparse.SUPPRESS)   # child mode: one plain measurement, JSON out
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the timed path computed in its last step to DIR/<name>.npy (float64, at most 64 MB in all)')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if a.batch <= 0:
         a.batch = 4 if a.proteomes >= 1000 else 10
     return a
@@ -179,6 +186,56 @@ def back_half_check(g, last, db):
             c0 += nc
         res.update(cluster_entries=n, clusters=int(n_clu), cluster_entries_mismatching=int(bad))
     return res
+
+
+COUNTERS = ('entries', 'matched_hits', 'clusters', 'cluster_hits', 'aligned', 'accepted', 'prefilter_hits')
+
+
+def dump_outputs(path, step_outs, budget=64 * 10 ** 6, seed=0x5ED0):
+    """The results the timed path returned for its last step (this rank's ranges of it), as float64 .npy files in `path`:
+    step_counters (one row per range, columns COUNTERS), and the arrays of the step's last range -- the one search_stream(...,
+    arrays='last') copies out: per entry (entry_q, entry_t, entry_off, n_clusters), per hit (hit_q, hit_t, hit_pval, cluster_of,
+    rank) and per cluster (cluster_size, cluster_pCO, cluster_pMH; the library leaves entry e's clusters at entry_off[e], they are
+    packed here in entry order).  Past `budget` bytes the hits and the clusters are a fixed, seeded sample without replacement,
+    in order; hit_index / cluster_index then name the rows kept."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {'step_counters': np.array([[o[k_] for k_ in COUNTERS] for o in step_outs], np.float64).reshape(-1, len(COUNTERS))}
+    last = step_outs[-1] if step_outs else None
+    groups = {}
+    if last is not None and 'entry_off' in last:
+        eo = last['entry_off'].astype(np.int64)
+        co = last['cluster_out']
+        ne = len(last['entry_q'])
+        nc = co['n_clusters'].astype(np.int64) if co is not None else np.zeros(ne, np.int64)
+        arrays.update(entry_q=last['entry_q'], entry_t=last['entry_t'], entry_off=eo, n_clusters=nc)
+        hits = dict(hit_q=last['hit_q'], hit_t=last['hit_t'], hit_pval=last['hit_pval'])
+        clusters = {}
+        if co is not None:
+            hits.update(cluster_of=co['cluster_of'], rank=co['rank'])
+            at = np.repeat(eo[:-1], nc) + (np.arange(int(nc.sum())) - np.repeat(np.cumsum(nc) - nc, nc))
+            clusters = dict(cluster_size=co['size'][at], cluster_pCO=co['pCO'][at], cluster_pMH=co['pMH'][at])
+        groups = dict(hit=hits, cluster=clusters)
+    arrays = {k_: np.asarray(v_, np.float64) for k_, v_ in arrays.items()}
+    left = budget - sum(a_.nbytes for a_ in arrays.values()) - 16 * 128   # (128: an .npy header, 16 arrays at most)
+    full = sum(8 * len(v_) for g_ in groups.values() for v_ in g_.values())
+    rng = np.random.default_rng(seed)
+    sampled = False
+    for name, g_ in groups.items():
+        if not g_:
+            continue
+        n = len(next(iter(g_.values())))
+        if full > left:   # (each group's share of what is left, one extra column for the index)
+            width = 8 * (len(g_) + 1)
+            cap = max(0, int(left * (8 * len(g_) * n) / full) // width)
+            if cap < n:
+                keep = np.sort(rng.choice(n, cap, replace=False))
+                g_ = {k_: v_[keep] for k_, v_ in g_.items()}
+                g_[name + '_index'] = keep
+                sampled = True
+        arrays.update({k_: np.asarray(v_, np.float64) for k_, v_ in g_.items()})
+    for k_, v_ in arrays.items():
+        np.save(os.path.join(path, k_ + '.npy'), v_)
+    return dict(dir=path, arrays=len(arrays), bytes=int(sum(v_.nbytes for v_ in arrays.values())), sampled=sampled)
 
 
 def parity_check(gpu, host, ps, k, max_seqs, bin_size, kmer_thr, check_path, last=None, db=None):
@@ -650,7 +707,7 @@ def measure(args, rank, local_rank, world, dist, torch):
                                                'the largest in-pipeline time is %s' % max(pk.items(), key=lambda kv: kv[1]['ms'])[0])
     last_ranges = my_ranges(args.warmup + args.steps - 1)[0] if args.steps > 0 else []
     extras = dict(ps=ps, k=k, max_seqs=max_seqs, kmer_thr=kmer_thr, bin_size=int(cs.bin_size), gpu=gpu, host=host,
-                  last=outs[-1] if outs else None, db=db,
+                  last=outs[-1] if outs else None, last_step=outs[len(outs) - len(last_ranges):] if last_ranges else [], db=db,
                   # the first query set of the last measured range: its aggregated entries are checked against the reference
                   last_first_set=int(ps.set_id[last_ranges[-1][0]]) if last_ranges else None)
     del cs
@@ -740,6 +797,8 @@ def main():
             dist.destroy_process_group()
         return
     res, ex = out
+    if args.dump_outputs:
+        res['dump_outputs'] = dump_outputs(args.dump_outputs, ex['last_step'])
     if not args.no_cpu and world == 1:   # the CPU leg (and the parity sample it produces) belongs to the single-GPU run
         tmp = tempfile.gettempdir()
         ent = os.path.join(tmp, 'sd_bench_entries_%d.npz' % os.getpid())
@@ -867,7 +926,8 @@ def main():
     line['roofline'] = rf
     line['roofline_sw'] = res['roofline_sw']
     for k_ in ('sw_gcups', 'sw_gcups_fwd_plus_rev', 'sw_cells', 'prefilter', 'prefilter_queries_in_process', 'stage_wall_s', 'host_cpu_s_per_step', 'align_d2h_MB_per_step', 'host_cpu_by_stage', 'results',
-               'setup_s', 'device', 'host_cores', 'host_cpu_quota', 'gather', 'multi_gpu_note', 'index_check', 'cpu_baseline', 'parity_check'):
+               'setup_s', 'device', 'host_cores', 'host_cpu_quota', 'gather', 'multi_gpu_note', 'index_check', 'cpu_baseline', 'parity_check',
+               'dump_outputs'):
         if k_ in res:
             line[k_] = res[k_]
     line['device_memory'] = {k_: round(v_, 1) for k_, v_ in res['device_memory'].items() if k_ != 'workspaces'}
