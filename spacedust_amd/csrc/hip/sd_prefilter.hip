@@ -1076,7 +1076,7 @@ __device__ __forceinline__ uint32_t cpQueryOfSeg(uint32_t seg, uint32_t nQ, cons
 // target ranges per query for a sub-batch whose average query has avgQ hits (0: no split); see the comments where it is applied
 inline int coarseBitsFor(uint64_t avgQ, int tBits) {
     const uint64_t perVQ = getenv("SD_PF_COARSE") ? (uint64_t) atoll(getenv("SD_PF_COARSE")) : 200000;
-    const uint64_t perVQsplit = getenv("SD_PF_COARSE") ? perVQ : (getenv("SD_PF_COARSE_SPLIT") ? (uint64_t) atoll(getenv("SD_PF_COARSE_SPLIT")) : 50000);
+    const uint64_t perVQsplit = getenv("SD_PF_COARSE") ? perVQ : 50000;
     int cBits = 0;
     if (avgQ > perVQ)
         while (cBits < CP_MAX_BITS && tBits - (cBits + 1) >= 8 && (avgQ >> cBits) > perVQsplit) cBits++;
@@ -1154,7 +1154,7 @@ coarse_offsets_kernel(uint32_t nQ, const uint64_t *__restrict__ qHitBase, const 
     if (q == nQ - 1 && t == 0) vqHitBase[(size_t) nQ * C] = qHitBase[nQ];
 }
 
-// CS_PER hits per thread and step, all loads issued before the first cursor is taken: with one 8-byte load per thread in flight the
+// CS_PER = 16 hits per thread and step, all loads issued before the first cursor is taken: with one 8-byte load per thread in flight the
 // kernel moved 2.4 TB/s (32 wavefronts x 512 B per CU: a third of what the memory's latency asks for).  The order inside a range is not
 // kept anyway (see above).  KV / DIAG: the input layout and the wide-position form are compiled apart (one 8-byte load per hit, no
 // branches in the loop).
@@ -1165,7 +1165,10 @@ coarse_offsets_kernel(uint32_t nQ, const uint64_t *__restrict__ qHitBase, const 
 // the group's room in the step's per-range counters; a scan of the counters gives every range its place in the staging buffer and
 // its place in the segment's share of the output (the running cursors); the hits are written to the buffer, and then out slot by
 // slot -- 64 consecutive slots are 64 consecutive hits of one range (or of two): a store of one or two runs of lines.
-template <int CS_PER, bool KV, bool DIAG>
+// (A step of 2 048 hits, 16 KB of staging per workgroup instead of 36, gave the same throughput inside the pipeline and was
+// removed: profiles/r08y_cs_per_pipeline_ab.txt.)
+constexpr int CS_PER = 16;
+template <bool KV, bool DIAG>
 __device__ __forceinline__ void coarseScatterBody(uint64_t s, uint64_t e, uint64_t qs, uint32_t tMask, int shift, int cBits, uint32_t *cursor,
                                                   const uint32_t *__restrict__ inKey, const uint32_t *__restrict__ inVal,
                                                   const uint2 *__restrict__ inKV, uint2 *__restrict__ outKV, const uint16_t *__restrict__ hitDiag,
@@ -1252,7 +1255,6 @@ __device__ __forceinline__ void coarseScatterBody(uint64_t s, uint64_t e, uint64
     }
 }
 
-template <int CS_PER>
 __global__ void __launch_bounds__(256)
 coarse_scatter_kernel(uint32_t nQ, const uint64_t *__restrict__ qHitBase, const uint32_t *__restrict__ segBase, int tBits, int cBits,
                       const uint32_t *__restrict__ segOffset, const uint32_t *__restrict__ inKey,
@@ -1276,11 +1278,11 @@ coarse_scatter_kernel(uint32_t nQ, const uint64_t *__restrict__ qHitBase, const 
     const uint32_t tMask = (1u << tBits) - 1;
     const int shift = tBits - cBits;
     if (inKV) {
-        if (hitDiag) coarseScatterBody<CS_PER, true, true>(s, e, qs, tMask, shift, cBits, cursor, inKey, inVal, inKV, outKV, hitDiag, stage, stageRange, cnt, rstart, gbase);
-        else coarseScatterBody<CS_PER, true, false>(s, e, qs, tMask, shift, cBits, cursor, inKey, inVal, inKV, outKV, hitDiag, stage, stageRange, cnt, rstart, gbase);
+        if (hitDiag) coarseScatterBody<true, true>(s, e, qs, tMask, shift, cBits, cursor, inKey, inVal, inKV, outKV, hitDiag, stage, stageRange, cnt, rstart, gbase);
+        else coarseScatterBody<true, false>(s, e, qs, tMask, shift, cBits, cursor, inKey, inVal, inKV, outKV, hitDiag, stage, stageRange, cnt, rstart, gbase);
     } else {
-        if (hitDiag) coarseScatterBody<CS_PER, false, true>(s, e, qs, tMask, shift, cBits, cursor, inKey, inVal, inKV, outKV, hitDiag, stage, stageRange, cnt, rstart, gbase);
-        else coarseScatterBody<CS_PER, false, false>(s, e, qs, tMask, shift, cBits, cursor, inKey, inVal, inKV, outKV, hitDiag, stage, stageRange, cnt, rstart, gbase);
+        if (hitDiag) coarseScatterBody<false, true>(s, e, qs, tMask, shift, cBits, cursor, inKey, inVal, inKV, outKV, hitDiag, stage, stageRange, cnt, rstart, gbase);
+        else coarseScatterBody<false, false>(s, e, qs, tMask, shift, cBits, cursor, inKey, inVal, inKV, outKV, hitDiag, stage, stageRange, cnt, rstart, gbase);
     }
 }
 
@@ -1303,7 +1305,7 @@ coarse_scatter_kernel(uint32_t nQ, const uint64_t *__restrict__ qHitBase, const 
 //           tile i in registers (and have the loads of tile i + 1 in flight) before any survivor of tile i is written, and
 //           the survivors of tiles 0 .. i fit in front of tile i + 1, so no unread hit is overwritten.
 // False positives (Bloom collisions, bitmap aliasing) cost bandwidth downstream, never correctness: bucket_match decides.
-// (HF_PER, template parameter: hits per thread and tile of pass B; the next tile is in flight as well)
+// (HF_PER: hits per thread and tile of pass B; the next tile is in flight as well)
 constexpr int HF_PER_A = 8;                // hits per thread and step of pass A
 
 __device__ __forceinline__ uint32_t hfMix(uint32_t tgt, uint32_t d8) {
@@ -1317,19 +1319,22 @@ __device__ __forceinline__ uint32_t hfMix(uint32_t tgt, uint32_t d8) {
 // NT threads, a Bloom filter of BW 32-bit words, a hot bitmap over the low HL target bits.  The filter is sized for
 // BW * 64 / 5 keys (a proteome-scale query segment in one round); a longer segment is taken in rounds over classes of targets (a hash of the target picks the round), the
 // Bloom filter cleared in between and the hot bitmap kept: the false-positive rate stays at the design point whatever the
-// segment length, at one more read of the segment per round.
-template <int NT, int BW, int HL, int HF_PER = 4>
-__global__ void __launch_bounds__(NT)
+// segment length, at one more read of the segment per round.  One geometry: 128 KB of LDS, pass-B tiles of 8 192 hits (half the
+// barriers of 4 096: isolated 62.9 -> 60.5 ms per step); the smaller geometries were slower and were removed (DESIGN.md §4.3,
+// profiles/r07f_hf_geometry.txt, r07g_hf8.txt).
+constexpr int HF_NT = 1024;
+__global__ void __launch_bounds__(HF_NT)
 hot_filter_kernel(uint32_t nVQ, const uint64_t *__restrict__ segBase, int tBits, uint32_t *key, uint32_t *val, uint2 *kv,
                   int wpBits /* wide stream positions: the diagonal byte sits in the key above the target bits */,
                   uint32_t minSeg /* shorter segments pass unfiltered */, uint32_t *__restrict__ segCount) {
+    constexpr int NT = HF_NT, BW = 24576, HL = 18, HF_PER = 8;
     constexpr int TILE = NT * HF_PER;
     __shared__ uint32_t bloom[BW];
     __shared__ uint32_t hot[1 << (HL - 5)];
     __shared__ uint32_t outCur;
     const int t = threadIdx.x, lane = t & 63;
-    // a workgroup takes the segments blockIdx.x, blockIdx.x + gridDim.x, ...: with one workgroup per segment that is one round; with
-    // a grid of one workgroup per CU (SD_PF_HF_PERSIST) a workgroup keeps the CU it has waited for
+    // a workgroup takes the segments blockIdx.x, blockIdx.x + gridDim.x, ...: on a grid of one workgroup per CU it keeps the CU it
+    // has waited for
     for (uint32_t q = blockIdx.x; q < nVQ; q += gridDim.x) {
     __syncthreads();   // (the previous segment's last reads of hot / outCur)
     const uint64_t s = segBase[q], e = segBase[q + 1];
@@ -1950,169 +1955,6 @@ score_diag_kernel(uint32_t nCand, const uint32_t *__restrict__ cKey, const uint3
     }
     cScore[c] = best;
     cLen[c] = (uint32_t) n;
-}
-
-// K5, cooperative form (round 6; sequence queries).  The one-thread-per-candidate kernel above walks a diagonal eight cells per step
-// with three 8-byte reads that belong to this lane alone: ~38 dependent steps per candidate, every read a request of its own (PMC:
-// 17.9 MB fetched per query for 4.4 MB of diagonals).  Here a candidate is scored by EIGHT lanes: per step the group reads 64
-// consecutive cells of the three byte streams (one 64-byte run each), every lane folds its eight cells into the summary of a clamped
-// running sum -- r' = max(0, r + s) is max-plus linear in r, so a block of cells is (T, E, P, B): total, the running score it leaves
-// when entered with 0, its maximal prefix sum, the best score inside when entered with 0; entering with r gives r_out = max(r + T, E),
-// best = max(r + P, B) -- and the eight summaries are composed in order by three shuffle steps (exact integer arithmetic: the same
-// score and length as the serial walk, bit for bit).  A candidate costs ceil(n / 64) steps instead of n / 8.  The diagonal itself
-// (binary searches over the k-mer stream and the index list: dependent reads) comes from a pass of its own with a thread per
-// candidate, diag_of_kernel, so that no lane of a group waits for it.  Sequences of 32 768 residues and more (computeLongScore)
-// keep the serial walk, done by the group's first lane.
-struct SdBlk {
-    int T, E, P, B;
-};
-__device__ __forceinline__ SdBlk sdBlkThen(const SdBlk &a, const SdBlk &b) {   // a's cells, then b's
-    SdBlk r;
-    r.T = a.T + b.T;
-    r.E = max(a.E + b.T, b.E);
-    r.P = max(a.P, a.T + b.P);
-    r.B = max(max(a.B, b.B), a.E + b.P);
-    return r;
-}
-
-__global__ void __launch_bounds__(256)
-diag_of_kernel(uint32_t nCand, const uint32_t *__restrict__ cKey, const uint32_t *__restrict__ cVal, const DiagSrc ds, int tBits, uint32_t posMask,
-               uint16_t *__restrict__ cDiag, const uint8_t *__restrict__ tMasked, const uint64_t *__restrict__ tOff,
-               int diagFromTarget /* the diagonal from the target's residues (diagFromResidues) instead of the index */) {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nCand) return;
-    const uint32_t k = cKey[c], cv = cVal[c];
-    const uint32_t q = k >> tBits, sid = k & ((1u << tBits) - 1);
-    if (diagFromTarget) cDiag[c] = diagFromResidues(ds, q, cv & posMask, sid, cv >> 24, tMasked + tOff[sid], (int) (tOff[sid + 1] - tOff[sid]));
-    else cDiag[c] = diagOf(ds, q, cv & posMask, sid);
-}
-
-__global__ void __launch_bounds__(256)
-score_diag_coop_kernel(uint32_t nCand, const uint32_t *__restrict__ cKey, const uint16_t *__restrict__ cDiag, int tBits,
-                       const uint8_t *__restrict__ qRes, const uint64_t *__restrict__ qOff, const int8_t *__restrict__ diagBias,
-                       const uint8_t *__restrict__ tMasked, const uint64_t *__restrict__ tOff, const int8_t *__restrict__ mat,
-                       int32_t *__restrict__ cScore, uint32_t *__restrict__ cLen) {
-    __shared__ int8_t smat[441];
-    for (int x = threadIdx.x; x < 441; x += blockDim.x) smat[x] = mat[x];
-    __syncthreads();
-    const uint32_t c = blockIdx.x * 32u + (threadIdx.x >> 3);
-    const int sub = threadIdx.x & 7;
-    if (c >= nCand) return;   // (whole groups leave: the shuffles below stay inside a group)
-    const uint32_t k = cKey[c];
-    const uint32_t q = k >> tBits, sid = k & ((1u << tBits) - 1);
-    const uint16_t d16 = cDiag[c];
-    const int d = (int) (int16_t) d16;
-    const int qL = (int) (qOff[q + 1] - qOff[q]);
-    const int tL = (int) (tOff[sid + 1] - tOff[sid]);
-    const uint8_t *qs = qRes + qOff[q];
-    const int8_t *qb = diagBias + qOff[q];
-    const uint8_t *ts = tMasked + tOff[sid];
-    if (qL >= 32768 || tL >= 32768) {
-        // computeLongScore (UngappedAlignment.cpp:312-329), serial, by the group's first lane: every real diagonal the 16-bit one can stand for
-        if (sub != 0) return;
-        auto scoreOn = [&](int diagonal, unsigned dist, int &nOut) {
-            int n = 0, q0 = 0, t0 = 0;
-            if (diagonal >= 0 && dist < (unsigned) qL) {
-                n = min(tL, qL - (int) dist);
-                q0 = (int) dist;
-            } else if (diagonal < 0 && dist < (unsigned) tL) {
-                n = min(tL - (int) dist, qL);
-                t0 = (int) dist;
-            }
-            int score = 0, best = 0;
-            for (int x = 0; x < n; x++) {
-                score += (int) (int8_t) (smat[(int) qs[q0 + x] * 21 + ts[t0 + x]] + qb[q0 + x]);
-                score = score < 0 ? 0 : score;
-                best = score > best ? score : best;
-            }
-            nOut = n;
-            return best;
-        };
-        int n = 0, best = 0;
-        for (int dv = 1; dv <= 1 + tL / 32768; dv++) {
-            const int real = (int) d16 - dv * 65536;
-            int nn;
-            const int sc = scoreOn(real, (unsigned) abs(real), nn);
-            best = sc > best ? sc : best;
-            n += nn;
-        }
-        for (int dv = 0; dv <= qL / 65536; dv++) {
-            const int real = (int) d16 + dv * 65536;
-            int nn;
-            const int sc = scoreOn(real, (unsigned) abs(real), nn);
-            best = sc > best ? sc : best;
-            n += nn;
-        }
-        cScore[c] = best;
-        cLen[c] = (uint32_t) n;
-        return;
-    }
-    // computeSingelSequenceScores (UngappedAlignment.cpp:416-430) on the one real diagonal
-    const unsigned dist = (unsigned) (uint16_t) min((int) (uint16_t) (0 - d16), (int) (uint16_t) d16);
-    int n = 0, q0 = 0, t0 = 0;
-    if (d >= 0 && dist < (unsigned) qL) {
-        n = min(tL, qL - (int) dist);
-        q0 = (int) dist;
-    } else if (d < 0 && dist < (unsigned) tL) {
-        n = min(tL - (int) dist, qL);
-        t0 = (int) dist;
-    }
-    int run = 0, best = 0;   // the walk's state behind the chunks done so far (identical in the group's lanes)
-    for (int x0 = 0; x0 < n; x0 += 64) {
-        const int x = x0 + 8 * sub;
-        SdBlk b = {0, 0, 0, 0};
-        if (x + 8 <= n) {
-            unsigned long long wq, wb, wt;
-            __builtin_memcpy(&wq, qs + q0 + x, 8);
-            __builtin_memcpy(&wb, qb + q0 + x, 8);
-            __builtin_memcpy(&wt, ts + t0 + x, 8);
-            int sum = 0, r = 0;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int qr = (int) ((wq >> (8 * j)) & 0xFFull), tr = (int) ((wt >> (8 * j)) & 0xFFull);
-                const int8_t bj = (int8_t) (uint8_t) ((wb >> (8 * j)) & 0xFFull);
-                const int sc = (int) (int8_t) (smat[qr * 21 + tr] + bj);
-                sum += sc;
-                r = max(0, r + sc);
-                b.P = j == 0 ? sum : max(b.P, sum);
-                b.B = max(b.B, r);
-            }
-            b.T = sum;
-            b.E = r;
-        } else if (x < n) {
-            int sum = 0, r = 0;
-            for (int j = 0; x + j < n; j++) {
-                const int sc = (int) (int8_t) (smat[(int) qs[q0 + x + j] * 21 + ts[t0 + x + j]] + qb[q0 + x + j]);
-                sum += sc;
-                r = max(0, r + sc);
-                b.P = j == 0 ? sum : max(b.P, sum);
-                b.B = max(b.B, r);
-            }
-            b.T = sum;
-            b.E = r;
-        }
-        // (a lane without cells holds the neutral block: T = E = B = 0, P = 0 -- entering with r >= 0 leaves r and a best of r, which the
-        // walk has already counted)
-#pragma unroll
-        for (int off = 1; off < 8; off <<= 1) {
-            SdBlk o;
-            o.T = __shfl_down(b.T, off, 8);
-            o.E = __shfl_down(b.E, off, 8);
-            o.P = __shfl_down(b.P, off, 8);
-            o.B = __shfl_down(b.B, off, 8);
-            if ((sub & (2 * off - 1)) == 0) b = sdBlkThen(b, o);
-        }
-        b.T = __shfl(b.T, 0, 8);
-        b.E = __shfl(b.E, 0, 8);
-        b.P = __shfl(b.P, 0, 8);
-        b.B = __shfl(b.B, 0, 8);
-        best = max(best, max(run + b.P, b.B));
-        run = max(run + b.T, b.E);
-    }
-    if (sub == 0) {
-        cScore[c] = best;
-        cLen[c] = (uint32_t) n;
-    }
 }
 
 // K6: keep the first element holding the per-(query,target) maximum of min(255,score).
@@ -3245,7 +3087,6 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
         WsView<uint8_t> dHitR6(ctx, "pf.dHitR6");   // join path: a byte per hit for the coarse split's count pass (nullptr: not written)
         WsView<uint64_t> dQHitBase(ctx, "pf.dQHitBase");   // hits of query q start at dQHitBase[q] (either path)
         WsView<uint64_t> dVQHitBase(ctx, "pf.dVQHitBase");  // with a split into target ranges: hits of (query, range) start here
-        int jcBits = 0;   // join path: the scatter wrote (query, target range) sub-segments of 2^jcBits ranges per query
         if (useJoin) {
             WsView<uint32_t> dKpCounts(ctx, "pf.dKpCounts");
             WsView<uint32_t> dKpTotal(ctx, "pf.dKpTotal");
@@ -3262,8 +3103,6 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
             SD_HIP(ctx, dKpCounts.alloc((size_t) JP_WGS * KP_BINS));
             SD_HIP(ctx, dKpTotal.alloc(KP_BINS));
             SD_HIP(ctx, dKpBase.alloc(KP_BINS + 1));
-            // (SD_JJ_WGS: fewer persistent workgroups of the join -- a smaller working set of index entries per XCD, for A/Bs)
-            const int jjWgs = getenv("SD_JJ_WGS") ? std::max(8, std::min(JJ_WGS, atoi(getenv("SD_JJ_WGS")) / 8 * 8)) : JJ_WGS;
             SD_HIP(ctx, dJqCounts.alloc((size_t) JJ_WGS * bq));
             SD_HIP(ctx, dQHits.alloc(bq));
             SD_HIP(ctx, dWgTotal.alloc(JJ_WGS));
@@ -3298,9 +3137,9 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
             const uint64_t *nSortedPtr = dKpBase.p + KP_BINS;
             {
                 ProfScope ps(ctx, "prefilter_join_count");
-                hipLaunchKernelGGL(join_count_kernel, dim3(jjWgs), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr,
+                hipLaunchKernelGGL(join_count_kernel, dim3(JJ_WGS), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr,
                                    (const uint16_t *) dChunkBin.p, (const uint32_t *) T->dOffsets, dJqCounts.p, (int) bq, dWgTotal.p);
-                hipLaunchKernelGGL(col_prefix_kernel, dim3(gridFor(bq, 64)), dim3(256), 0, ctx->stream, dJqCounts.p, jjWgs, (int) bq, dQHits.p);
+                hipLaunchKernelGGL(col_prefix_kernel, dim3(gridFor(bq, 64)), dim3(256), 0, ctx->stream, dJqCounts.p, JJ_WGS, (int) bq, dQHits.p);
             }
             // overflow of the reference's hit buffer, in k-mer ordinals
             hipLaunchKernelGGL(query_splits_join_kernel, dim3(bq), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQKmerBase.p,
@@ -3308,10 +3147,10 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
                                dQSplit.p, dQParts.p, dQSplits.p, dSplitFlag.p);
             hipLaunchKernelGGL(join_stats_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQKmerBase.p,
                                (const uint32_t *) dQHits.p, dStats.p);
-            std::vector<unsigned long long> hWg((size_t) jjWgs);
+            std::vector<unsigned long long> hWg((size_t) JJ_WGS);
             std::vector<uint32_t> hQHits(bq);
             int hSplitFlagJ = 0;
-            SD_HIP(ctx, sdD2H(ctx, hWg.data(), dWgTotal.p, (size_t) jjWgs * sizeof(unsigned long long)));
+            SD_HIP(ctx, sdD2H(ctx, hWg.data(), dWgTotal.p, (size_t) JJ_WGS * sizeof(unsigned long long)));
             SD_HIP(ctx, sdD2H(ctx, hQHits.data(), dQHits.p, bq * sizeof(uint32_t)));
             SD_HIP(ctx, sdD2H(ctx, &hSplitFlagJ, dSplitFlag.p, sizeof(int)));
             SD_HIP(ctx, sdStreamSync(ctx));
@@ -3353,62 +3192,18 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
             hipLaunchKernelGGL(join_effective_totals_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQHits.p,
                                (const uint32_t *) dQSplit.p, dQEff.p);
             hipLaunchKernelGGL(small_scan_kernel, dim3(1), dim3(SS_NT), 0, ctx->stream, (const uint32_t *) dQEff.p, (int) bq, dQHitBase.p, 0u);
-            // SD_JOIN_RANGES=1 (an experiment kept for the A/B, off by default): the scatter splits every query's hits into target
-            // ranges right away (join_scatter_kernel<RANGES>) by the rule of the coarse split below, which it replaces on the join path.
-            // Measured at 1 000 proteomes, isolated, per 8 192 queries: plain scatter 72.8 + coarse split 97.9 = 171 ms against ranged
-            // count 90 + ranged scatter 150 - 197 ms, 2 379 vs 2 235 genome-pairs/s end to end -- a wavefront's 256 hits fall into ~40
-            // (query, range) columns, i.e. 48-byte pieces, where the plain scatter writes 600-byte runs and the coarse split moves
-            // 16 384-hit tiles into at most 64 ranges (2-KB runs): two streaming levels beat one fine-grained scatter.
-            if (nHits > 0 && getenv("SD_JOIN_RANGES") && atoi(getenv("SD_JOIN_RANGES")) == 1) {
-                const uint64_t avgQ = nHits / std::max<uint32_t>(bq, 1);
-                const uint64_t perVQ = getenv("SD_PF_COARSE") ? (uint64_t) atoll(getenv("SD_PF_COARSE")) : 200000;
-                const uint64_t perVQsplit = getenv("SD_PF_COARSE") ? perVQ : 100000;
-                if (avgQ > perVQ)
-                    while (jcBits < CP_MAX_BITS && tBits - (jcBits + 1) >= 8 && (avgQ >> jcBits) > perVQsplit) jcBits++;
-                while (jcBits > 0 && ((uint64_t) bq << jcBits) > (uint64_t) JX_COLS_MAX) jcBits--;   // the columns' cursors live in LDS
-            }
-            if (nHits > 0 && jcBits > 0) {
-                const int cols = (int) (bq << jcBits);
-                WsView<uint32_t> dJrCounts(ctx, "pf.dJrCounts");
-                WsView<uint32_t> dVQHits(ctx, "pf.dVQHits");
-                SD_HIP(ctx, dJrCounts.alloc((size_t) JJ_WGS * cols));
-                SD_HIP(ctx, dVQHits.alloc((size_t) cols + 1));
-                SD_HIP(ctx, dVQHitBase.alloc((size_t) cols + 1));
-                SD_HIP(ctx, dHitsKV.alloc(nHits));
-                {
-                    ProfScope ps(ctx, "prefilter_join_count");
-                    hipLaunchKernelGGL((join_scatter_kernel<false, true, true>), dim3(jjWgs), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p,
-                                       nSortedPtr, (const uint16_t *) dChunkBin.p, (const uint32_t *) T->dOffsets, (const uint2 *) T->dEntries, bq,
-                                       (const uint32_t *) nullptr, cols, (const uint64_t *) nullptr, tBits, (const uint32_t *) dQSplit.p,
-                                       (uint2 *) nullptr, jcBits, dJrCounts.p, (uint8_t *) nullptr, 0);
-                    hipLaunchKernelGGL(col_prefix_kernel, dim3(gridFor((uint64_t) cols, 64)), dim3(256), 0, ctx->stream, dJrCounts.p, jjWgs, cols, dVQHits.p);
-                    SD_HIP(ctx, hipMemsetAsync(dVQHits.p + cols, 0, sizeof(uint32_t), ctx->stream));
-                    int rcV = exclusiveScanWiden(ctx, dVQHits.p, dVQHitBase.p, (uint64_t) cols + 1, scanTmp);
-                    if (rcV != SD_OK) return rcV;
-                }
-                ProfScope ps(ctx, "prefilter_join_scatter");
-                static const bool ntStore = !(getenv("SD_JOIN_NT") && atoi(getenv("SD_JOIN_NT")) == 0);
-                auto kern = ntStore ? join_scatter_kernel<true, true, false> : join_scatter_kernel<false, true, false>;
-                hipLaunchKernelGGL(kern, dim3(jjWgs), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr,
-                                   (const uint16_t *) dChunkBin.p, (const uint32_t *) T->dOffsets, (const uint2 *) T->dEntries, bq,
-                                   (const uint32_t *) dJrCounts.p, cols, (const uint64_t *) dVQHitBase.p, tBits,
-                                   (const uint32_t *) dQSplit.p, dHitsKV.p, jcBits, (uint32_t *) nullptr, (uint8_t *) nullptr, 0);
-            } else if (nHits > 0) {
+            if (nHits > 0) {
                 SD_HIP(ctx, dHitsKV.alloc(nHits));
                 // the coarse split's count pass needs a hit's range and nothing else: one byte per hit beside the 8-byte stream (the top
                 // six target bits: any split of up to 2^6 ranges reads its range off them) -- 1.5 MB per query written here for 12.3 MB
-                // per query not read there (SD_PF_R6=0: the count pass reads the hits)
-                if (tBits >= CP_MAX_BITS + 8 && coarseBitsFor(nHits / std::max<uint32_t>(bq, 1), tBits) > 0 &&
-                    !(getenv("SD_PF_R6") && atoi(getenv("SD_PF_R6")) == 0))
+                // per query not read there
+                if (tBits >= CP_MAX_BITS + 8 && coarseBitsFor(nHits / std::max<uint32_t>(bq, 1), tBits) > 0)
                     SD_HIP(ctx, dHitR6.alloc(nHits + 8));
                 ProfScope ps(ctx, "prefilter_join_scatter");
-                // SD_JOIN_NT=0: plain stores (partial lines of neighbouring runs merge in the XCD's L2 before they are written back)
-                static const bool ntStore = !(getenv("SD_JOIN_NT") && atoi(getenv("SD_JOIN_NT")) == 0);
-                auto kern = ntStore ? join_scatter_kernel<true, false, false> : join_scatter_kernel<false, false, false>;
-                hipLaunchKernelGGL(kern, dim3(jjWgs), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr,
+                hipLaunchKernelGGL(join_scatter_kernel, dim3(JJ_WGS), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr,
                                    (const uint16_t *) dChunkBin.p, (const uint32_t *) T->dOffsets, (const uint2 *) T->dEntries, bq,
-                                   (const uint32_t *) dJqCounts.p, (int) bq, (const uint64_t *) dQHitBase.p, tBits,
-                                   (const uint32_t *) dQSplit.p, dHitsKV.p, 0, (uint32_t *) nullptr, dHitR6.p, tBits - CP_MAX_BITS);
+                                   (const uint32_t *) dJqCounts.p, (const uint64_t *) dQHitBase.p, tBits, (const uint32_t *) dQSplit.p,
+                                   dHitsKV.p, dHitR6.p, tBits - CP_MAX_BITS);
             }
             SD_HIP(ctx, hipGetLastError());
         }
@@ -3517,83 +3312,70 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
                 WsView<uint32_t> dSegBase(ctx, "pf.dSegBase");
                 WsView<uint32_t> dSegCount(ctx, "pf.dSegCount");
                 WsView<uint2> dKVC(ctx, "pf.dKVC");
-                if (useJoin && jcBits > 0) {   // the join wrote (query, target range) sub-segments: they are the virtual queries
-                    cBits = jcBits;
-                    nVQ = nVQ0 << cBits;
-                    tBitsV = tBits0 - cBits;
-                    pHitBase = dVQHitBase.p;
-                } else {
-                    // decided by the average query of the sub-batch (a few long queries are what the adaptive bucket count and
-                    // the oversize-bucket launch are for): ~100 hits per bucket at 2^11 buckets
-                    const uint64_t avgQ = nHits / std::max<uint32_t>(nVQ0, 1);
-                    // no split up to 2 * 10^5 hits per average query (the filter takes such a segment in one round); beyond that, ranges of
-                    // at most 10^5 hits: the filter's Bloom rounds, the partition and the bucket sort all run on half-size segments for one more
-                    // level of the (cheap, streaming) split -- isolated prefilter at 1 000 proteomes 443 -> 390 ms per 8 192 queries, +4 % end
-                    // to end; at 100 proteomes (1.5 * 10^5 hits per query) a split would only add its 24 B per hit (1 915 -> 1 767)
-                    // (coarseBitsFor below is this rule; the join's scatter asks it whether a split will follow)
-                    const uint64_t perVQ = getenv("SD_PF_COARSE") ? (uint64_t) atoll(getenv("SD_PF_COARSE")) : 200000;
-                    // Round 6: ranges of at most 5 * 10^4 hits (SD_PF_COARSE_SPLIT; 10^5 until then) -- 32 ranges at 1 000 proteomes.  The filter's
-                    // Bloom filter then has twice the bits per key: 7.2 % of the hit stream left instead of 12.3 % (4.7 % at 2.5 * 10^4), and what
-                    // is left comes in segments the LDS sorter takes whole (segment_match) instead of through partition_hits / bucket_match.
-                    // Isolated, per 8 192 queries, interleaved in one process (profiles/r06y_split.txt): 328 ms at 10^5 (coarse split 69, filter
-                    // 74, partition + bucket + segment match 59), **315 ms at 5 * 10^4** (80 / 67 / 43), 323 ms at 2.5 * 10^4 (92 / 66 / 37: the
-                    // split's cost grows with its ranges).  Round 5 had measured finer ranges as a loss (388 - 442 vs 385 ms): the filter read
-                    // two arrays then and the split wrote them.  (Two more bitmaps in the filter -- a target must be hit twice to be nominated --
-                    // were tried on top and removed: 7.4 % left instead of 7.2 %, the kernel 8 ms slower; what passes the filter at this
-                    // granularity are targets that do have two hits on one diagonal byte, profiles/r06x_hf_multi.txt.)
-                    const uint64_t perVQsplit = getenv("SD_PF_COARSE") ? perVQ : (getenv("SD_PF_COARSE_SPLIT") ? (uint64_t) atoll(getenv("SD_PF_COARSE_SPLIT")) : 50000);
-                    (void) perVQsplit;
-                    cBits = coarseBitsFor(avgQ, tBits0);
-                    // wide stream positions need the split: it is where the diagonal byte moves into the key (8 free bits)
-                    while (widePos && cBits < CP_MAX_BITS && tBits - (cBits + 1) >= 8 && (cBits < 1 || tBits - cBits > 24)) cBits++;
-                    if (widePos && (cBits < 1 || tBits - cBits > 24))
-                        return sdFail(ctx, SD_EUNSUPPORTED, "a query with >= 2^24 index hits against a target set of %u sequences", T->nSeq);
-                    if (cBits > 0) {
-                        // segments of CP_SEG hits per query.  The join path knows every query's hits on the host already (the read that
-                        // sized the sub-batch), the lookup path reads the segment starts back; the segment table goes up through a pinned
-                        // buffer, so nothing here waits for the stream a second time
-                        std::vector<uint64_t> hQHB(nVQ0 + 1, 0);
-                        if (useJoin) {
-                            for (uint32_t x = 0; x < nVQ0; x++)
-                                hQHB[x + 1] = hQHB[x] + ((x < hUnsupported.size() && hUnsupported[x]) ? 0ull : hStats[(size_t) x * 4 + 1]);
-                        } else {
-                            SD_HIP(ctx, sdD2H(ctx, hQHB.data(), pHitBase, (nVQ0 + 1) * sizeof(uint64_t)));
-                            SD_HIP(ctx, sdStreamSync(ctx));
-                        }
-                        ProfScope ps(ctx, "prefilter_coarse_split");
-                        const uint32_t C = 1u << cBits;
-                        uint32_t *hSegBase = nullptr;
-                        SD_HIP(ctx, pinGet(ctx, "pf.hSegBase", (size_t) nVQ0 + 1, &hSegBase));
-                        hSegBase[0] = 0;
+                // decided by the average query of the sub-batch (a few long queries are what the adaptive bucket count and
+                // the oversize-bucket launch are for): ~100 hits per bucket at 2^11 buckets
+                const uint64_t avgQ = nHits / std::max<uint32_t>(nVQ0, 1);
+                // no split up to 2 * 10^5 hits per average query (the filter takes such a segment in one round); beyond that, ranges of
+                // at most 10^5 hits: the filter's Bloom rounds, the partition and the bucket sort all run on half-size segments for one more
+                // level of the (cheap, streaming) split -- isolated prefilter at 1 000 proteomes 443 -> 390 ms per 8 192 queries, +4 % end
+                // to end; at 100 proteomes (1.5 * 10^5 hits per query) a split would only add its 24 B per hit (1 915 -> 1 767)
+                // (coarseBitsFor below is this rule; the join's scatter asks it whether a split will follow)
+                // Round 6: ranges of at most 5 * 10^4 hits (10^5 until then) -- 32 ranges at 1 000 proteomes.  The filter's
+                // Bloom filter then has twice the bits per key: 7.2 % of the hit stream left instead of 12.3 % (4.7 % at 2.5 * 10^4), and what
+                // is left comes in segments the LDS sorter takes whole (segment_match) instead of through partition_hits / bucket_match.
+                // Isolated, per 8 192 queries, interleaved in one process (profiles/r06y_split.txt): 328 ms at 10^5 (coarse split 69, filter
+                // 74, partition + bucket + segment match 59), **315 ms at 5 * 10^4** (80 / 67 / 43), 323 ms at 2.5 * 10^4 (92 / 66 / 37: the
+                // split's cost grows with its ranges).  Round 5 had measured finer ranges as a loss (388 - 442 vs 385 ms): the filter read
+                // two arrays then and the split wrote them.  (Two more bitmaps in the filter -- a target must be hit twice to be nominated --
+                // were tried on top and removed: 7.4 % left instead of 7.2 %, the kernel 8 ms slower; what passes the filter at this
+                // granularity are targets that do have two hits on one diagonal byte, profiles/r06x_hf_multi.txt.)
+                cBits = coarseBitsFor(avgQ, tBits0);
+                // wide stream positions need the split: it is where the diagonal byte moves into the key (8 free bits)
+                while (widePos && cBits < CP_MAX_BITS && tBits - (cBits + 1) >= 8 && (cBits < 1 || tBits - cBits > 24)) cBits++;
+                if (widePos && (cBits < 1 || tBits - cBits > 24))
+                    return sdFail(ctx, SD_EUNSUPPORTED, "a query with >= 2^24 index hits against a target set of %u sequences", T->nSeq);
+                if (cBits > 0) {
+                    // segments of CP_SEG hits per query.  The join path knows every query's hits on the host already (the read that
+                    // sized the sub-batch), the lookup path reads the segment starts back; the segment table goes up through a pinned
+                    // buffer, so nothing here waits for the stream a second time
+                    std::vector<uint64_t> hQHB(nVQ0 + 1, 0);
+                    if (useJoin) {
                         for (uint32_t x = 0; x < nVQ0; x++)
-                            hSegBase[x + 1] = hSegBase[x] + (uint32_t) ((hQHB[x + 1] - hQHB[x] + CP_SEG - 1) / CP_SEG);
-                        const uint32_t nSeg = hSegBase[nVQ0];
-                        nVQ = nVQ0 * C;
-                        tBitsV = tBits0 - cBits;
-                        SD_HIP(ctx, dVQHitBase.alloc((size_t) nVQ + 1));
-                        SD_HIP(ctx, dSegBase.alloc(nVQ0 + 1));
-                        SD_HIP(ctx, dSegCount.alloc((size_t) std::max<uint32_t>(nSeg, 1) * C));
-                        SD_HIP(ctx, dKVC.alloc(nHits));
-                        SD_HIP(ctx, hipMemcpyAsync(dSegBase.p, hSegBase, (nVQ0 + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-                        if (nSeg > 0)
-                            hipLaunchKernelGGL(coarse_count_kernel, dim3(nSeg), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, tBits0,
-                                               cBits, dKeyA.p, pKV, dSegCount.p, useJoin ? (const uint8_t *) dHitR6.p : (const uint8_t *) nullptr);
-                        hipLaunchKernelGGL(coarse_offsets_kernel, dim3(nVQ0), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, cBits,
-                                           dSegCount.p, dVQHitBase.p);
-                        if (nSeg > 0) {   // SD_CS_PER=8: steps of 2 048 hits (16 KB of staging per workgroup instead of 36)
-                            static const bool per8 = getenv("SD_CS_PER") && atoi(getenv("SD_CS_PER")) == 8;
-                            auto csKern = per8 ? coarse_scatter_kernel<8> : coarse_scatter_kernel<16>;
-                            hipLaunchKernelGGL(csKern, dim3(nSeg), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, tBits0,
-                                               cBits, dSegCount.p, dKeyA.p, dValA.p, pKV, dKVC.p,
-                                               widePos ? (const uint16_t *) dDiag.p : (const uint16_t *) nullptr);
-                        }
-                        // (hSegBase is pinned and persistent: the upload may still be reading it; the next sub-batch writes it only after
-                        // several waits for this stream)
-                        pHitBase = dVQHitBase.p;
-                        pKey = nullptr;   // the ranges' hits are (key, value) pairs, like the join's stream
-                        pVal = nullptr;
-                        pKV = dKVC.p;
+                            hQHB[x + 1] = hQHB[x] + ((x < hUnsupported.size() && hUnsupported[x]) ? 0ull : hStats[(size_t) x * 4 + 1]);
+                    } else {
+                        SD_HIP(ctx, sdD2H(ctx, hQHB.data(), pHitBase, (nVQ0 + 1) * sizeof(uint64_t)));
+                        SD_HIP(ctx, sdStreamSync(ctx));
                     }
+                    ProfScope ps(ctx, "prefilter_coarse_split");
+                    const uint32_t C = 1u << cBits;
+                    uint32_t *hSegBase = nullptr;
+                    SD_HIP(ctx, pinGet(ctx, "pf.hSegBase", (size_t) nVQ0 + 1, &hSegBase));
+                    hSegBase[0] = 0;
+                    for (uint32_t x = 0; x < nVQ0; x++)
+                        hSegBase[x + 1] = hSegBase[x] + (uint32_t) ((hQHB[x + 1] - hQHB[x] + CP_SEG - 1) / CP_SEG);
+                    const uint32_t nSeg = hSegBase[nVQ0];
+                    nVQ = nVQ0 * C;
+                    tBitsV = tBits0 - cBits;
+                    SD_HIP(ctx, dVQHitBase.alloc((size_t) nVQ + 1));
+                    SD_HIP(ctx, dSegBase.alloc(nVQ0 + 1));
+                    SD_HIP(ctx, dSegCount.alloc((size_t) std::max<uint32_t>(nSeg, 1) * C));
+                    SD_HIP(ctx, dKVC.alloc(nHits));
+                    SD_HIP(ctx, hipMemcpyAsync(dSegBase.p, hSegBase, (nVQ0 + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+                    if (nSeg > 0)
+                        hipLaunchKernelGGL(coarse_count_kernel, dim3(nSeg), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, tBits0,
+                                           cBits, dKeyA.p, pKV, dSegCount.p, useJoin ? (const uint8_t *) dHitR6.p : (const uint8_t *) nullptr);
+                    hipLaunchKernelGGL(coarse_offsets_kernel, dim3(nVQ0), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, cBits,
+                                       dSegCount.p, dVQHitBase.p);
+                    if (nSeg > 0)
+                        hipLaunchKernelGGL(coarse_scatter_kernel, dim3(nSeg), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, tBits0,
+                                           cBits, dSegCount.p, dKeyA.p, dValA.p, pKV, dKVC.p,
+                                           widePos ? (const uint16_t *) dDiag.p : (const uint16_t *) nullptr);
+                    // (hSegBase is pinned and persistent: the upload may still be reading it; the next sub-batch writes it only after
+                    // several waits for this stream)
+                    pHitBase = dVQHitBase.p;
+                    pKey = nullptr;   // the ranges' hits are (key, value) pairs, like the join's stream
+                    pVal = nullptr;
+                    pKV = dKVC.p;
                 }
                 // hot-target filter (hot_filter_kernel): every (virtual) query's segment is compacted in place to the hits of
                 // targets that can still emit a candidate; the bucket machinery below runs on what is left, laid out densely
@@ -3610,31 +3392,13 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
                     SD_HIP(ctx, hipMemsetAsync(dHotCount.p + nVQ, 0, sizeof(uint32_t), ctx->stream));
                     {
                         ProfScope ps(ctx, "prefilter_hot_filter");
-                        const int geo = getenv("SD_PF_HF") ? atoi(getenv("SD_PF_HF")) : 0;
-                        // One workgroup per CU that loops over the segments (SD_PF_HF_PERSIST=n: n per CU, 0: one workgroup per segment).  A
-                        // 128-KB workgroup needs a drained CU; beside the score wavefronts of the other streams every new workgroup waited for
-                        // one again, the persistent one keeps the CU it has waited for.  Round 5, interleaved runs on one box: the kernel's
-                        // time inside the pipeline 7 - 11 s -> 2.7 s per 14 steps at 1 000 proteomes, 2 417 -> 2 444 genome-pairs/s (three runs
-                        // each), 1 905 -> 1 929 at 100 proteomes (round 4 had measured the same kernel time and no gain in throughput)
-                        const int hfPersist = getenv("SD_PF_HF_PERSIST") ? atoi(getenv("SD_PF_HF_PERSIST")) : 1;
-                        const uint32_t hfGrid = hfPersist > 0 ? std::min<uint32_t>(nVQ, (uint32_t) hfPersist * (uint32_t) ctx->prop.multiProcessorCount) : nVQ;
-#define SD_HF(NT_, BW_, HL_)                                                                                                              \
-    hipLaunchKernelGGL((hot_filter_kernel<NT_, BW_, HL_>), dim3(hfGrid), dim3(NT_), 0, ctx->stream, nVQ, pHitBase, tBitsV, (uint32_t *) pKey, \
-                       (uint32_t *) pVal, (uint2 *) pKV, widePos ? tBitsV : 0, minSeg, dHotCount.p)
-                        if (geo == 1) SD_HF(512, 12288, 17);        // 64 KB
-                        else if (geo == 2) SD_HF(512, 8192, 17);    // 48 KB
-                        else if (geo == 3) SD_HF(256, 6144, 16);    // 32 KB
-                        else if (geo == 4) SD_HF(1024, 16384, 18);  // 96 KB
-                        else if (geo == 5) SD_HF(1024, 24576, 18);  // 128 KB, pass-B tiles of 4 096 hits
-                        else if (geo == 6) hipLaunchKernelGGL((hot_filter_kernel<1024, 12288, 18, 8>), dim3(hfGrid), dim3(1024), 0, ctx->stream, nVQ, pHitBase, tBitsV,
-                                                              (uint32_t *) pKey, (uint32_t *) pVal, (uint2 *) pKV, widePos ? tBitsV : 0, minSeg, dHotCount.p);   // 48 + 32 KB: two workgroups per CU
-                        else if (geo == 8) hipLaunchKernelGGL((hot_filter_kernel<1024, 12288, 17, 8>), dim3(hfGrid), dim3(1024), 0, ctx->stream, nVQ, pHitBase, tBitsV,
-                                                              (uint32_t *) pKey, (uint32_t *) pVal, (uint2 *) pKV, widePos ? tBitsV : 0, minSeg, dHotCount.p);   // 48 + 16 KB: two workgroups of 1 024 threads per CU (with SD_PF_HF_PERSIST=2)
-                        else if (geo == 7) hipLaunchKernelGGL((hot_filter_kernel<1024, 16384, 17, 8>), dim3(hfGrid), dim3(1024), 0, ctx->stream, nVQ, pHitBase, tBitsV,
-                                                              (uint32_t *) pKey, (uint32_t *) pVal, (uint2 *) pKV, widePos ? tBitsV : 0, minSeg, dHotCount.p);   // 64 + 16 KB: two workgroups per CU
-                        else hipLaunchKernelGGL((hot_filter_kernel<1024, 24576, 18, 8>), dim3(hfGrid), dim3(1024), 0, ctx->stream, nVQ, pHitBase, tBitsV,
-                                                (uint32_t *) pKey, (uint32_t *) pVal, (uint2 *) pKV, widePos ? tBitsV : 0, minSeg, dHotCount.p);   // 128 KB, tiles of 8 192: half the barriers (isolated 62.9 -> 60.5 ms per step)
-#undef SD_HF
+                        // One workgroup per CU that loops over the segments.  A 128-KB workgroup needs a drained CU; beside the score
+                        // wavefronts of the other streams every new workgroup waited for one again, the persistent one keeps the CU it has
+                        // waited for.  Round 5, interleaved runs on one box: the kernel's time inside the pipeline 7 - 11 s -> 2.7 s per 14
+                        // steps at 1 000 proteomes, 2 417 -> 2 444 genome-pairs/s (three runs each), 1 905 -> 1 929 at 100 proteomes
+                        const uint32_t hfGrid = std::min<uint32_t>(nVQ, (uint32_t) ctx->prop.multiProcessorCount);
+                        hipLaunchKernelGGL(hot_filter_kernel, dim3(hfGrid), dim3(HF_NT), 0, ctx->stream, nVQ, pHitBase, tBitsV, (uint32_t *) pKey,
+                                           (uint32_t *) pVal, (uint2 *) pKV, widePos ? tBitsV : 0, minSeg, dHotCount.p);
                     }
                     int rcF = exclusiveScanWiden(ctx, dHotCount.p, dHotBase.p, (uint64_t) nVQ + 1, scanTmp);
                     if (rcF != SD_OK) return rcF;
@@ -3685,16 +3449,14 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
                 }
                 WsView<uint8_t> dSegDone(ctx, "pf.dSegDone");
                 const uint8_t *pSegDone = nullptr;
-                if (useFilter && !(getenv("SD_PF_SEGMATCH") && atoi(getenv("SD_PF_SEGMATCH")) == 0)) {
+                if (useFilter) {
                     // filtered segments that fit the LDS sorter are matched as a whole; the rest goes through partition / bucket_match
                     SD_HIP(ctx, dSegDone.alloc((size_t) nVQ + 1));
                     ProfScope ps(ctx, "prefilter_segment_match");
-                    // (SD_PF_SM_PERSIST=n: n workgroups per CU looping over the segments; default one workgroup per segment -- measured
-                    // round 5, interleaved: the kernel's in-pipeline time 3.5 - 3.9 s -> 1.5 s per 14 steps with n = 1 or 2, the throughput
-                    // 2 347 / 2 436 (0) vs 2 434 (1) vs 2 225 / 2 330 (2): the waiting moves to the other kernels)
-                    const int smPersist = getenv("SD_PF_SM_PERSIST") ? atoi(getenv("SD_PF_SM_PERSIST")) : 0;
-                    const uint32_t smGrid = smPersist > 0 ? std::min<uint32_t>(nVQ, (uint32_t) smPersist * (uint32_t) ctx->prop.multiProcessorCount) : nVQ;
-                    hipLaunchKernelGGL((segment_match_kernel<512, 8192>), dim3(smGrid), dim3(512), 0, ctx->stream, nVQ, pHitBase, pSegCount, pOutBase,
+                    // (one workgroup per segment: a persistent grid of one or two per CU was measured, round 5, interleaved -- the
+                    // kernel's in-pipeline time 3.5 - 3.9 s -> 1.5 s per 14 steps, the throughput 2 347 / 2 436 vs 2 434 (one per CU) vs
+                    // 2 225 / 2 330 (two): the waiting moves to the other kernels; round 7 again inside the noise, profiles/r07e_sm_persist_ab.txt)
+                    hipLaunchKernelGGL((segment_match_kernel<512, 8192>), dim3(nVQ), dim3(512), 0, ctx->stream, nVQ, pHitBase, pSegCount, pOutBase,
                                        tBitsV, pKey, pVal, pKV, outK, outV, dQLog2.p, dBktStart.p, dBktCount.p, dBktEmit.p, dSegDone.p,
                                        (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p, cBits,
                                        widePos ? tBitsV : 0);
@@ -3703,11 +3465,9 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
                 {
                     ProfScope ps(ctx, "prefilter_partition_hits");
                     // large tiles where the virtual queries are large (proteome-scale target sets), the small form for small inputs
-                    const int tileMode = getenv("SD_PF_TILE") ? atoi(getenv("SD_PF_TILE")) : 1;
-                    if (nLeft / std::max<uint32_t>(nVQ, 1) >= 16384 && tileMode == 2)
-                        hipLaunchKernelGGL((partition_hits_kernel<1024, 8192>), dim3(nVQ), dim3(1024), 0, ctx->stream, nVQ, pHitBase, tBitsV, pKey,
-                                           pVal, pKV, dKVB.p, dQLog2.p, dBktStart.p, dBktCount.p, dFlag.p, pSegCount, pOutBase, pSegDone);
-                    else if (nLeft / std::max<uint32_t>(nVQ, 1) >= 16384 && tileMode == 1)
+                    // (<1024, 8192>, fastest alone, waits for whole CUs beside the other streams' score wavefronts and lost inside the
+                    // pipeline: removed)
+                    if (nLeft / std::max<uint32_t>(nVQ, 1) >= 16384)
                         hipLaunchKernelGGL((partition_hits_kernel<512, 4096>), dim3(nVQ), dim3(512), 0, ctx->stream, nVQ, pHitBase, tBitsV, pKey,
                                            pVal, pKV, dKVB.p, dQLog2.p, dBktStart.p, dBktCount.p, dFlag.p, pSegCount, pOutBase, pSegDone);
                     else
@@ -3878,27 +3638,14 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
             }
             {
                 ProfScope ps(ctx, "prefilter_score_diag");
-                // SD_PF_SCORE_COOP=1 (sequence queries): the diagonal of every candidate first (a thread each), then eight lanes per candidate
-                // down the diagonal (score_diag_coop_kernel).  Measured at 1 000 proteomes, interleaved in one process, identical rows
-                // (profiles/r06n_score_coop.txt): 41.3 ms per 8 192 queries with the one-thread-per-candidate kernel, 42.4 ms with this one --
-                // the walk is not what the kernel costs; the diagonal is (diagOf: the k-mer of the hit from the k-mer stream, its index list's
-                // start, the entry of the target: three dependent reads of a line each per candidate, 8.5 MB per query).  Off.
-                const bool coop = getenv("SD_PF_SCORE_COOP") && atoi(getenv("SD_PF_SCORE_COOP")) != 0;
+                // (one thread per candidate: a cooperative form, eight lanes per candidate down the diagonal, was no faster -- the
+                // diagonal, not the walk, is what the kernel costs -- and was removed: profiles/r06n_score_coop.txt, r07d_score_coop_res.txt)
                 // the diagonal of a candidate from the target's residues (join path: 8-byte hits without a stored diagonal; k = 6 with
-                // 24-bit ordinals beside the diagonal byte); SD_PF_DIAG_RES=0: from the index as before
-                const int diagRes = (useJoin && T->k == 6 && posMask == 0xFFFFFFu && !(getenv("SD_PF_DIAG_RES") && atoi(getenv("SD_PF_DIAG_RES")) == 0)) ? 1 : 0;
-                if (coop && !dProfAln) {
-                    WsView<uint16_t> dCDiag(ctx, "pf.dCDiag");
-                    SD_HIP(ctx, dCDiag.alloc(nCand));
-                    hipLaunchKernelGGL(diag_of_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCVal.p, diagSrc, tBits,
-                                       posMask, dCDiag.p, (const uint8_t *) T->dMasked, (const uint64_t *) T->dSeqOff, diagRes);
-                    hipLaunchKernelGGL(score_diag_coop_kernel, dim3(gridFor(nCand, 32)), dim3(256), 0, ctx->stream, nCand, dCKey.p,
-                                       (const uint16_t *) dCDiag.p, tBits, dQ.p, dQOff.p, dDB.p, T->dMasked, T->dSeqOff, dMat.p, dCScore.p, dCLen.p);
-                } else {
-                    hipLaunchKernelGGL(score_diag_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCVal.p,
-                                       diagSrc, tBits, dQ.p, dQOff.p, dDB.p, T->dMasked, T->dSeqOff, dMat.p, dCScore.p, dCLen.p,
-                                       dProfAln, posMask, diagRes);
-                }
+                // 24-bit ordinals beside the diagonal byte); otherwise from the index
+                const int diagRes = (useJoin && T->k == 6 && posMask == 0xFFFFFFu) ? 1 : 0;
+                hipLaunchKernelGGL(score_diag_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCVal.p,
+                                   diagSrc, tBits, dQ.p, dQOff.p, dDB.p, T->dMasked, T->dSeqOff, dMat.p, dCScore.p, dCLen.p,
+                                   dProfAln, posMask, diagRes);
             }
             hipLaunchKernelGGL(cand_stats_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCLen.p, tBits,
                                (unsigned long long *) dStats.p);
@@ -3945,7 +3692,7 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
         }
         {
             ProfScope ps(ctx, "prefilter_select_hits");
-            if (maxHits + 1 <= 512 && !getenv("SD_PF_SEL4096"))   // short result lists: a 12-KB sorter instead of 48 KB (more workgroups per CU)
+            if (maxHits + 1 <= 512)   // short result lists: a 12-KB sorter instead of 48 KB (more workgroups per CU)
                 hipLaunchKernelGGL(select_hits_kernel<1024>, dim3(bq), dim3(256), 0, ctx->stream, bq, dQStart.p, dKKey.p, dKVal.p, dKScore.p,
                                    diagSrc, tBits, par->binSize - 1, maxHits, par->minDiagScore, dIdent.p, dQOff.p, T->dSeqOff,
                                    par->covMode, par->covThr, dQ.p, dDB.p, dMat.p, dOut.p, dOutCount.p, dErr.p, dProfAln, posMask, useJoin ? binBits : -1,

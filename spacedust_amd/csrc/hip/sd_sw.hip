@@ -787,42 +787,18 @@ void launchScorePk(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, ui
     if (n == 0) return;
     constexpr uint32_t perWave = 2 * (64 / LW);
     dim3 grid((n + perWave - 1) / perWave), block(64);
-    // SD_SW_LDS_PAD: unused dynamic LDS per wavefront, i.e. a cap on how many score wavefronts a CU holds -- what it leaves
-    // free (LDS, wave slots) is what the memory-bound prefilter workgroups of the other streams run in
-    static const unsigned ldsPad = getenv("SD_SW_LDS_PAD") ? (unsigned) atoi(getenv("SD_SW_LDS_PAD")) : 0u;
-    hipLaunchKernelGGL((sdpk::sw_score_pk_kernel<RT, LW, MULTI, WIDE, SHARED>), grid, block, ldsPad, ctx->stream, dTasks, n, q->dRes, q->dBias,
+    hipLaunchKernelGGL((sdpk::sw_score_pk_kernel<RT, LW, MULTI, WIDE, SHARED>), grid, block, 0, ctx->stream, dTasks, n, q->dRes, q->dBias,
                        t->dRes, dMat, go, ge, dOut, dBound, dOrder, (const int8_t *) q->dProf);
 }
 
-template <int RT, int LW, int SHARED, int WAVES = 1>
+template <int RT, bool SHARED>
 void launchScorePkAligned(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, uint32_t n, const sd_seqset *q, const sd_seqset *t,
                           const int8_t *dMat, int go, int ge, int32_t *dOut) {
     if (n == 0) return;
-    constexpr uint32_t perWg = 2 * (64 / LW) * WAVES;
-    dim3 grid((n + perWg - 1) / perWg), block(64 * WAVES);
-    static const unsigned ldsPad = getenv("SD_SW_LDS_PAD") ? (unsigned) atoi(getenv("SD_SW_LDS_PAD")) : 0u;
-    hipLaunchKernelGGL((sdpk::sw_score_pk_aligned_kernel<RT, LW, SHARED, WAVES>), grid, block, ldsPad, ctx->stream, dTasks, n, q->dRes, q->dBias, t->dRes,
+    constexpr uint32_t perWave = 4;   // two 32-lane groups of a task pair each
+    dim3 grid((n + perWave - 1) / perWave), block(64);
+    hipLaunchKernelGGL((sdpk::sw_score_pk_aligned_kernel<RT, SHARED>), grid, block, 0, ctx->stream, dTasks, n, q->dRes, q->dBias, t->dRes,
                        dMat, go, ge, dOut, dOrder, (const int8_t *) q->dProf);
-}
-
-// SD_SW_CHAIN=M: a wavefront of the aligned shared-profile kernel takes M consecutive quads of the pair list and chains those of one
-// query (sw_score_pk_chain_kernel: one profile, one systolic ramp per chain); 0 / 1: one quad per wavefront
-// (measured at 1 000 proteomes, profiles/r05_experiments.txt item 13: 4.6 % fewer VALU instructions per quad at M = 4 and the same
-// throughput -- a class launch holds about six quads per wave slot, so M-quad workgroups coarsen the grid as much as they save: off.
-// Read at every call: tests switch it inside one process.)
-inline uint32_t sdSwChain() {
-    const char *e = getenv("SD_SW_CHAIN");
-    return e ? (uint32_t) std::min(64, std::max(0, atoi(e))) : 0u;
-}
-template <int RT>
-void launchScorePkChain(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, uint32_t n, const sd_seqset *q, const sd_seqset *t,
-                        const int8_t *dMat, int go, int ge, int32_t *dOut) {
-    if (n == 0) return;
-    const uint32_t nQuads = (n + 3) / 4, chainLen = sdSwChain();
-    dim3 grid((nQuads + chainLen - 1) / chainLen), block(64);
-    static const unsigned ldsPad = getenv("SD_SW_LDS_PAD") ? (unsigned) atoi(getenv("SD_SW_LDS_PAD")) : 0u;
-    hipLaunchKernelGGL((sdpk::sw_score_pk_chain_kernel<RT>), grid, block, ldsPad, ctx->stream, dTasks, n, q->dRes, q->dBias, t->dRes, dMat, go, ge,
-                       dOut, dOrder, (const int8_t *) q->dProf, chainLen);
 }
 
 int rtClass(int n) {
@@ -1554,16 +1530,6 @@ k_bound_apply(uint32_t nPairs, SwTask *__restrict__ tasks, const uint64_t *__res
 // (class, query) run together, longest target first; inside a run of a packed class consecutive tasks form pairs, an
 // odd last task stays alone.  Invalid tasks sort last (all ones).
 constexpr uint32_t PAIR_NONE = 0xFFFFFFFFu;
-// SD_SW_QUADS=0: wavefronts of two independent shared-profile pairs (round 3's form) instead of four tasks of one query
-inline bool sdSwQuads() {
-    static const bool on = !(getenv("SD_SW_QUADS") && atoi(getenv("SD_SW_QUADS")) == 0);
-    return on;
-}
-// SD_SW_WAVES=2: two wavefronts (eight tasks of one query) per workgroup of the aligned kernel share the profile
-inline int sdSwWaves() {
-    static const int w = (sdSwQuads() && getenv("SD_SW_WAVES") && atoi(getenv("SD_SW_WAVES")) == 2) ? 2 : 1;
-    return w;
-}
 constexpr int PAIR_QUERY_BITS = 17;
 __global__ void __launch_bounds__(256)
 k_pair_keys(uint32_t n, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ pairQ, uint32_t *__restrict__ key2) {
@@ -1580,22 +1546,20 @@ k_pair_heads(uint32_t n, const uint32_t *__restrict__ keyS, uint32_t *__restrict
     const bool head = p == 0 || (keyS[p] >> 9) != (keyS[p - 1] >> 9);
     headPos[p] = head ? p : 0u;
 }
-// leader[p] = pairs that start at sorted position p: 1 for every second task of a (class, query) run; with `quads` the run's
-// last task adds one EMPTY pair when the run holds an odd number of pairs, so that every wavefront of four tasks (two pairs)
-// stays inside one query (sw_score_pk_aligned_kernel<.., SHARE = 2>: one profile per wavefront)
+// leader[p] = pairs that start at sorted position p: 1 for every second task of a (class, query) run; the run's last task adds
+// one EMPTY pair when the run holds an odd number of pairs, so that every wavefront of four tasks (two pairs) stays inside one
+// query (sw_score_pk_aligned_kernel<.., SHARED = true>: one profile per wavefront)
 __global__ void __launch_bounds__(256)
-k_pair_leaders(uint32_t n, const uint32_t *__restrict__ keyS, const uint32_t *__restrict__ runStart, uint8_t *__restrict__ leader, int quads) {
+k_pair_leaders(uint32_t n, const uint32_t *__restrict__ keyS, const uint32_t *__restrict__ runStart, uint8_t *__restrict__ leader) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p > n) return;
     uint8_t v = 0;
     if (p < n && (keyS[p] >> 26) < FIRST_INT32_CLASS) {
         const uint32_t o = p - runStart[p];
         v = (o & 1u) == 0 ? 1 : 0;
-        if (quads) {   // quads = pairs per workgroup (2 per wavefront): the run is padded to a multiple with empty pairs behind it
-            const bool lastOfRun = p + 1 >= n || (keyS[p + 1] >> 9) != (keyS[p] >> 9);
-            const uint32_t pairs = (o + 1 + 1) / 2;   // pairs of the run = ceil((o + 1) / 2)
-            if (lastOfRun) v += (uint8_t) (((uint32_t) quads - pairs % (uint32_t) quads) % (uint32_t) quads);
-        }
+        const bool lastOfRun = p + 1 >= n || (keyS[p + 1] >> 9) != (keyS[p] >> 9);
+        const uint32_t pairs = (o + 1 + 1) / 2;   // pairs of the run = ceil((o + 1) / 2)
+        if (lastOfRun) v += (uint8_t) (pairs & 1u);
     }
     leader[p] = v;
 }
@@ -1643,8 +1607,7 @@ int devRunScore(sd_ctx *ctx, uint32_t nPairs, const uint32_t *dKeys, const uint3
         SD_HIP(ctx, wsGet(ctx, "sp.runstart", (size_t) nPairs, &dRunStart));
         SD_HIP(ctx, wsGet(ctx, "sp.leader", (size_t) nPairs + 1, &dLeader));
         SD_HIP(ctx, wsGet(ctx, "sp.pairidx", (size_t) nPairs + 1, &dPairIdx));
-        const int padPairs = sdSwQuads() ? 2 * sdSwWaves() : 0;   // pairs per workgroup of the shared-profile kernels
-        const size_t order2Cap = (size_t) 2 * (size_t) std::max(padPairs, 2) * nPairs + 8;   // worst case: every run one task, padded to a workgroup
+        const size_t order2Cap = (size_t) 4 * nPairs + 8;   // worst case: every run one task, padded to a wavefront (two pairs)
         SD_HIP(ctx, wsGet(ctx, "sp.order2", order2Cap, &dOrder2));
         SD_HIP(ctx, hipMemsetAsync(dOrder2, 0xFF, order2Cap * sizeof(uint32_t), ctx->stream));   // empty pairs: PAIR_NONE
         SD_HIP(ctx, wsGet(ctx, "sp.bounds", 64, &dPairBounds));
@@ -1655,8 +1618,7 @@ int devRunScore(sd_ctx *ctx, uint32_t nPairs, const uint32_t *dKeys, const uint3
         hipLaunchKernelGGL(k_pair_heads, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeysSorted, dHead);
         rc = devInclusiveMax(ctx, dHead, dRunStart, nPairs);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, dKeysSorted, dRunStart, dLeader,
-                           padPairs);
+        hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, dKeysSorted, dRunStart, dLeader);
         rc = devExclusiveScan(ctx, (const uint8_t *) dLeader, dPairIdx, (size_t) nPairs + 1);
         if (rc != SD_OK) return rc;
         hipLaunchKernelGGL(k_pair_emit, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeysSorted, dVals2, dRunStart, dPairIdx, dOrder2);
@@ -1689,13 +1651,10 @@ int devRunScore(sd_ctx *ctx, uint32_t nPairs, const uint32_t *dKeys, const uint3
         static const char *const pkNames[N_PK_CLASSES] = {"rt4x32", "rt6x32", "rt7x32", "rt8x32", "rt9x32", "rt10x32", "rt11x32", "rt12x32",
                                                           "rt8x64", "rt10x64", "rt12x64", "rt8x64s2", "rt8x64s3", "rt8x64sN"};
         static const char *const i32Names[4] = {"sw_score.rt4", "sw_score.rt8", "sw_score.rt16", "sw_score.rt32"};
-        // SD_SW_LONG32=0: queries of 385 .. 768 rows keep the 64-lane general kernels (half the LDS per wavefront, twice the ramp)
-        static const bool long32 = !(getenv("SD_SW_LONG32") && atoi(getenv("SD_SW_LONG32")) == 0);
-        static const bool useAligned = !(getenv("SD_SW_ALIGNED") && atoi(getenv("SD_SW_ALIGNED")) == 0);
         const bool shared = dPairQ != nullptr && ci < FIRST_INT32_CLASS;
         const int alignedRT = (ci >= 1 && ci < FIRST_NARROW_MULTI) ? (int) ci + 4 : 0;
-        // start-position tasks (two profiles per pair in LDS) beyond 384 rows and the A/B switches use the general kernels
-        const bool aligned = alignedRT > 0 && useAligned && (alignedRT <= 12 || (shared && long32));
+        // start-position tasks (two profiles per pair in LDS) beyond 384 rows use the general kernels
+        const bool aligned = alignedRT > 0 && (alignedRT <= 12 || shared);
         // the general kernel by rows: class 0, the multi-strip classes, and the aligned classes when they are not taken
         int generalIdx = 0;
         if (ci >= FIRST_NARROW_MULTI && ci < FIRST_WIDE_CLASS) generalIdx = (int) FIRST_MULTI_PK + (int) (ci - FIRST_NARROW_MULTI);
@@ -1717,16 +1676,11 @@ int devRunScore(sd_ctx *ctx, uint32_t nPairs, const uint32_t *dKeys, const uint3
         if (shared) launchScorePk<RT, LW, MULTI, WIDE, true>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut, dBound);     \
         else launchScorePk<RT, LW, MULTI, WIDE, false>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut, dBound);           \
     } while (0)
-#define SD_PKA(RT)                                                                                               \
-    case RT:                                                                                                     \
-        if (shared && quads && sdSwWaves() == 2) launchScorePkAligned<RT, 32, 2, 2>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);  \
-        else if (shared && quads && sdSwChain() > 1) launchScorePkChain<RT>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);  \
-        else if (shared && quads) launchScorePkAligned<RT, 32, 2>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);  \
-        else if (shared) launchScorePkAligned<RT, 32, 1>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);      \
-        else launchScorePkAligned<RT, 32, 0>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);                  \
+#define SD_PKA(RT)                                                                                       \
+    case RT:                                                                                             \
+        if (shared) launchScorePkAligned<RT, true>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);    \
+        else launchScorePkAligned<RT, false>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);          \
         break;
-#define SD_PKA16(SEG)                                                                                            \
-    case SEG: launchScorePkAligned<2 * SEG, 16, 1>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut); break;
 #define SD_PK_CLASS(WIDE, IDX)                                                \
         switch (IDX) {                                                        \
             case 0: SD_PK(4, 32, false, WIDE); break;                         \
@@ -1742,15 +1696,7 @@ int devRunScore(sd_ctx *ctx, uint32_t nPairs, const uint32_t *dKeys, const uint3
             case 10: SD_PK(12, 64, false, WIDE); break;                       \
             default: SD_PK(8, 64, true, WIDE); break;                         \
         }
-        // SD_SW_LW16: shared-profile tasks of up to this many rows per segment run on 16-lane groups (two segments per lane)
-        static const int lw16Max = getenv("SD_SW_LW16") ? atoi(getenv("SD_SW_LW16")) : (sdSwQuads() ? 0 : 8);
-        const bool quads = sdSwQuads();   // measured: beyond 8 rows per segment the LDS footprint (two segments per lane, eight tasks per wavefront) costs more occupancy than the shorter ramp returns
-        if (aligned && shared && alignedRT <= lw16Max) {
-            switch (alignedRT) {
-                SD_PKA16(5) SD_PKA16(6) SD_PKA16(7) SD_PKA16(8) SD_PKA16(9) SD_PKA16(10) SD_PKA16(11) SD_PKA16(12)
-                default: break;
-            }
-        } else if (aligned) {
+        if (aligned) {
             switch (alignedRT) {
                 SD_PKA(5) SD_PKA(6) SD_PKA(7) SD_PKA(8) SD_PKA(9) SD_PKA(10) SD_PKA(11) SD_PKA(12) SD_PKA(13) SD_PKA(14)
                 SD_PKA(15) SD_PKA(16) SD_PKA(17) SD_PKA(18) SD_PKA(19) SD_PKA(20) SD_PKA(21) SD_PKA(22) SD_PKA(23) SD_PKA(24)
@@ -1769,7 +1715,6 @@ int devRunScore(sd_ctx *ctx, uint32_t nPairs, const uint32_t *dKeys, const uint3
             }
         }
 #undef SD_PKA
-#undef SD_PKA16
 #undef SD_PK_CLASS
 #undef SD_PK
     }
@@ -2271,7 +2216,7 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
     // pairs whose byte score saturates for certain (k_pre_word) skip this pass
     uint32_t *dPass1Keys = dFwdKeys;
     uint8_t *dPreWord = nullptr;
-    if (pairDiag && usePk && !getenv("SD_SW_NO_PREWORD")) {
+    if (pairDiag && usePk) {
         uint16_t *dDiag = nullptr;
         SD_HIP(ctx, wsGet(ctx, "al.diag", N, &dDiag));
         SD_HIP(ctx, wsGet(ctx, "al.preword", N, &dPreWord));
@@ -2283,7 +2228,7 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
                            (const int8_t *) queries->dProf, (const int32_t *) dMinBias, queries->dProf ? 0 : matMin, dPreWord, dPass1Keys);
     }
     hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dPass1Keys, dCells + 0);
-    const uint32_t *dShare = (getenv("SD_SW_NOSHARE") || queries->n >= (1u << PAIR_QUERY_BITS)) ? nullptr : dPQ;   // forward passes scan whole queries: pair by query
+    const uint32_t *dShare = queries->n >= (1u << PAIR_QUERY_BITS) ? nullptr : dPQ;   // forward passes scan whole queries: pair by query
     int rc = devRunScore(ctx, nPairs, dPass1Keys, dVals, dKeysS, dOrder, dBounds, dTasks, dScanA, dScanB, queries, targets, dMat, go,
                          ge, dOut32, &nValid, dShare);
     if (rc != SD_OK) return rc;

@@ -430,32 +430,19 @@ __device__ __forceinline__ uint32_t addWord1(uint32_t base, uint32_t packed) {  
     return r;
 }
 
-// LW = 32: a lane is one segment (RT = segLen).  LW = 16: four 16-lane groups of a task pair each, a lane holds TWO segments
-// (RT = 2 segLen, Fl restarts at rows 0 and RT / 2): half the systolic ramp (15 idle steps per task instead of 31), the
-// per-column overhead spread over twice the rows, and the group boundaries are DPP row boundaries -- row_shr:1 hands G / Ff
-// down with a zero entering every group's first lane, and the residues enter there from a register that row_ror:1 rotates
-// once per column (no v_readlane / v_writelane at all).
-template <int CTRL, bool ZERO_FILL>
-__device__ __forceinline__ uint32_t dppMove(uint32_t old, uint32_t v) {
-    return (uint32_t) __builtin_amdgcn_update_dpp((int) old, (int) v, CTRL, 0xf, 0xf, ZERO_FILL);
-}
-
-// SHARE: 0 = every task has its own profile; 1 = the two tasks of a pair have the same query (one profile per group);
-// 2 = ALL tasks of the wavefront have the same query (the caller pads a query's run of pairs to whole wavefronts): one profile
-// per wavefront -- half (LW = 32) or a quarter (LW = 16) of the LDS, which is what lets the memory-bound prefilter workgroups of
-// the other streams live on the same CUs.
-// WAVES (SHARE == 2 only): wavefronts per workgroup that share the one profile -- the caller pads a query's run of pairs to whole
-// workgroups; the LDS a score wavefront holds is what bounds how many of them (and how many of the other streams' workgroups) a CU
-// takes, and half a profile per wavefront lifts that bound to the wave slots
-template <int RT, int LW, int SHARE, int WAVES = 1>
-__global__ void __launch_bounds__(64 * WAVES)
+// Two 32-lane groups of a task pair each per wavefront; a lane is one segment (RT = segLen).
+// SHARED: false = every task has its own profile; true = ALL four tasks of the wavefront have the same query (the caller pads a
+// query's run of pairs to whole wavefronts): one profile per wavefront, a quarter of the LDS, which is what lets the memory-bound
+// prefilter workgroups of the other streams live on the same CUs.  Removed variants, each measured no faster (DESIGN.md §4.1,
+// profiles/r05_experiments.txt): 16-lane groups of two segments per lane, one profile per task pair, two wavefronts per
+// workgroup sharing the profile, and quads of one query chained through one wavefront.
+template <int RT, bool SHARED>
+__global__ void __launch_bounds__(64)
 sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint8_t *__restrict__ qRes,
                            const int8_t *__restrict__ qBias, const uint8_t *__restrict__ tRes, const int8_t *__restrict__ mat,
                            int go, int ge, int32_t *__restrict__ out, const uint32_t *__restrict__ order,
                            const int8_t *__restrict__ qProf) {
-    static_assert(LW == 32 || (LW == 16 && RT % 2 == 0), "32 lanes of one segment or 16 lanes of two");
-    static_assert(WAVES == 1 || SHARE == 2, "several wavefronts per workgroup share ONE profile");
-    constexpr int SEG = RT * LW / 32;      // rows of a reference segment
+    constexpr int LW = 32;
     constexpr int WORDS = (RT + 3) / 4;
     constexpr int RTP = 4 * WORDS;
     constexpr int PSTRIDE = LW * WORDS;    // dwords per residue row of a profile
@@ -463,17 +450,18 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     constexpr int NT = 2 * NGRP;           // tasks per wavefront: a task pair per group of LW lanes
     constexpr uint32_t ROWB = PSTRIDE * 4; // bytes per residue row
     static_assert(22 * ROWB < 65536, "row offsets travel in 16 bits");
-    constexpr bool SHARED = SHARE != 0;
-    __shared__ uint32_t prof[SHARE == 2 ? 1 : (SHARE == 1 ? NGRP : NT)][22][PSTRIDE];
+    __shared__ uint32_t prof[SHARED ? 1 : NT][22][PSTRIDE];
     __shared__ int8_t smat[441];
-    for (int i = threadIdx.x; i < 441; i += 64 * WAVES) smat[i] = mat[i];
+    for (int i = threadIdx.x; i < 441; i += 64) smat[i] = mat[i];
     __syncthreads();
+    // (wave is 0 in the one-wavefront workgroup.  It stays in the task index and in a group's index below: the code then compiles to
+    // the instructions that were measured -- a wave-uniform task index turns the task loads into scalar loads)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / LW, l = lane % LW;
     SwTask tk[NT];
 #pragma unroll
     for (int x = 0; x < NT; x++) {
-        const uint32_t id = (blockIdx.x * WAVES + (uint32_t) wave) * NT + x;
+        const uint32_t id = (blockIdx.x + (uint32_t) wave) * NT + x;
         const uint32_t tid = id < nTasks ? (order ? order[id] : id) : 0xFFFFFFFFu;
         if (tid != 0xFFFFFFFFu) {
             tk[x] = tasks[tid];
@@ -506,16 +494,10 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     // ---- query profiles (SmithWaterman::createQueryProfile, :163-187)
 #pragma unroll
     for (int x = 0; x < (SHARED ? 1 : 2); x++) {
-        // (SHARE == 2: every group of every wavefront writes a share of the residue rows of the one profile; the first task of the
-        // workgroup is a real one -- a run is padded at its end -- and names the query for all of them)
-        SwTask T0 = tk[0];
-        if (WAVES > 1) {
-            const uint32_t id0 = blockIdx.x * WAVES * NT;
-            const uint32_t tid0 = id0 < nTasks ? (order ? order[id0] : id0) : 0xFFFFFFFFu;
-            if (tid0 != 0xFFFFFFFFu) T0 = tasks[tid0];
-        }
-        const SwTask &T = SHARE == 2 ? T0 : (x ? B : A);
-        uint32_t *pw = &prof[SHARE == 2 ? 0 : (SHARE == 1 ? grp : 2 * grp + x)][0][0] + l * WORDS;
+        // (SHARED: each group writes a share of the residue rows of the one profile; the first task of the wavefront is a real
+        // one -- a run is padded at its end -- and names the query for all of them)
+        const SwTask &T = SHARED ? tk[0] : (x ? B : A);
+        uint32_t *pw = &prof[SHARED ? 0 : 2 * grp + x][0][0] + l * WORDS;
 #pragma unroll
         for (int w = 0; w < WORDS; w++) {
             int res[4], cb[4];
@@ -535,7 +517,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
                     pidx[b] = idx * 21;
                 }
             }
-            const int aFirst = SHARE == 2 ? wave * NGRP + grp : 0, aStep = SHARE == 2 ? NGRP * WAVES : 1;
+            const int aFirst = SHARED ? wave * NGRP + grp : 0, aStep = SHARED ? NGRP : 1;
             if (qProf) {   // profile query: the position's own row
                 for (int a = aFirst; a < 21; a += aStep) {
                     uint32_t word = 0;
@@ -563,7 +545,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     __syncthreads();
     // LDS byte addresses of this lane's profile words (row 0); the residue stream adds the row offset
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
-    const uint32_t baseA = (uint32_t) (size_t) (lds_u32 *) (&prof[SHARE == 2 ? 0 : (SHARE == 1 ? grp : 2 * grp)][0][0] + l * WORDS);
+    const uint32_t baseA = (uint32_t) (size_t) (lds_u32 *) (&prof[SHARED ? 0 : 2 * grp][0][0] + l * WORDS);
     const uint32_t baseB = SHARED ? baseA : (uint32_t) (size_t) (lds_u32 *) (&prof[2 * grp + 1][0][0] + l * WORDS);
     auto ldsWord = [](uint32_t addr, int w) -> uint32_t { return *((const lds_u32 *) (size_t) addr + w); };
 
@@ -577,9 +559,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     uint32_t bestcm = 0, bestcol = 0;
     constexpr uint32_t NEUT = (uint32_t) PK_NEUTRAL * ROWB;
     auto loadChunk = [&](int c0) -> uint32_t {   // row offsets (bytes) of the residues of one column per lane, task A | task B << 16
-        // LW = 32: lane l holds column c0 + l.  LW = 16: lane 0 holds c0, lane 15 c0 + 1, ... lane 1 c0 + 15 -- the order in which
-        // row_ror:1 brings them to lane 0
-        const int col = c0 + (LW == 16 ? (16 - l) & 15 : l);
+        const int col = c0 + l;   // lane l holds column c0 + l
         uint32_t a = PK_NEUTRAL, b = PK_NEUTRAL;
         if (col < A.tL) a = tRes[(int64_t) A.tOff + (int64_t) col * A.tStep];
         if (col < B.tL) b = tRes[(int64_t) B.tOff + (int64_t) col * B.tStep];
@@ -589,12 +569,8 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     uint32_t chunkNext = loadChunk(LW);
     // column 0's residues enter at the first lane of either group; every other lane starts on the neutral row
     uint32_t T = NEUT | (NEUT << 16);
-    if (LW == 16) {
-        T = l == 0 ? chunk : T;
-    } else {
-        T = writeLane<0>(readLane(chunk, 0), T);
-        T = writeLane<32>(readLane(chunk, 32), T);
-    }
+    T = writeLane<0>(readLane(chunk, 0), T);
+    T = writeLane<32>(readLane(chunk, 32), T);
     uint32_t pa[WORDS], pb[WORDS];
     {
         const uint32_t aA = addWord0(baseA, T), aB = addWord1(baseB, T);
@@ -611,23 +587,13 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
                           uint32_t (&pan)[WORDS], uint32_t (&pbn)[WORDS]) {
         // ---- the residues and profile words of column k + 1 (needed one step from now)
         const int i1 = (k + 1) & (LW - 1);
-        if (LW == 16) {
-            if (i1 == 0) {
-                chunk = chunkNext;
-                chunkNext = loadChunk(k + 1 + LW);
-            } else {
-                chunk = dppMove<0x121 /* row_ror:1 */, false>(chunk, chunk);   // the next column's residues into lane 0 of every group
-            }
-            Tn = dppMove<0x111 /* row_shr:1 */, false>(chunk, Tc);   // lane 0 of a group keeps `old` = the fresh residues
-        } else {
-            if (i1 == 0) {
-                chunk = chunkNext;
-                chunkNext = loadChunk(k + 1 + LW);
-            }
-            Tn = dppShr1(Tc);
-            Tn = writeLane<0>(readLane(chunk, i1), Tn);
-            Tn = writeLane<32>(readLane(chunk, 32 + i1), Tn);
+        if (i1 == 0) {
+            chunk = chunkNext;
+            chunkNext = loadChunk(k + 1 + LW);
         }
+        Tn = dppShr1(Tc);
+        Tn = writeLane<0>(readLane(chunk, i1), Tn);
+        Tn = writeLane<32>(readLane(chunk, 32 + i1), Tn);
         {
             const uint32_t aA = addWord0(baseA, Tn), aB = addWord1(baseB, Tn);
 #pragma unroll
@@ -637,16 +603,9 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
             }
         }
         // ---- hand-off from lane l - 1 (nothing enters the first lane of a group)
-        uint32_t inG, inFf;
-        if (LW == 16) {
-            inG = dppMove<0x111, true>(0, outG);
-            inFf = dppMove<0x111, true>(0, outFf);
-        } else {
-            inG = dppShr1(outG);
-            inFf = dppShr1(outFf);
-            inG = writeLane<32>(0, inG);
-            inFf = writeLane<32>(0, inFf);
-        }
+        uint32_t inG = dppShr1(outG), inFf = dppShr1(outFf);
+        inG = writeLane<32>(0, inG);
+        inFf = writeLane<32>(0, inFf);
         uint32_t h[RTP];
 #pragma unroll
         for (int w = 0; w < WORDS; w++) {
@@ -658,12 +617,12 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
 #pragma unroll
         for (int r = 0; r < RT; r++) {
             uint32_t hpre = pkMax(h[r], E[r]);
-            if (r % SEG != 0) hpre = pkMax(hpre, Fl);   // a segment starts here: no vertical gap of the lane structure enters
+            if (r != 0) hpre = pkMax(hpre, Fl);   // row 0 starts the segment: no vertical gap of the lane structure enters
             const uint32_t g = pkMax(hpre, Ff);
             const uint32_t open = pkSubSat(hpre, goP);
             E[r] = pkMax(pkSubSat(E[r], geP), open);
-            if (r % SEG == 0) Fl = open;
-            else if ((r + 1) % SEG != 0) Fl = pkMax(pkSubSat(Fl, geP), open);
+            if (r == 0) Fl = open;
+            else if (r + 1 != RT) Fl = pkMax(pkSubSat(Fl, geP), open);
             Ff = pkMax(pkSubSat(Ff, geP), open);
             H[r] = g;
             const uint32_t code = pkRowCode(g, 31 - r);
@@ -712,312 +671,6 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
             out[3 * B.slot + 1] = v == 0 ? -1 : 0xFFFFF - (int) ((keyB >> 20) & 0xFFFFF);
             out[3 * B.slot + 2] = v == 0 ? B.n - 1 : 0xFFFFF - (int) (keyB & 0xFFFFF);
         }
-    }
-}
-
-
-// ---- chained form of the aligned kernel: the quads of one query flow through the wavefront back to back --------------------
-// sw_score_pk_aligned_kernel<RT, 32, 2> runs one quad (four tasks of one query: two 32-lane groups x two packed tasks) per wavefront
-// and pays the systolic ramp -- 31 steps in which part of the lanes work on nothing -- for every quad of ~330 columns.  Here a
-// wavefront takes up to `chainLen` CONSECUTIVE quads of the pair list and, while the query stays the same, feeds the next quad's
-// first column into lane 0 in the step after the previous quad's last one: the boundary between two targets travels down the
-// lanes one lane per step, so in the first 32 steps of a segment lane i (and only lane i, at step i) snapshots its running best
-// of the quad it has just finished and clears its DP state (H, E, the diagonal hand-off, the best).  After those 32 steps every
-// lane has handed in its snapshot and the finished quad is reduced and stored; the profile is built once per chain and the ramp
-// is paid once (the 32 draining steps behind the last quad).  A segment is the longest of its four targets, rounded up to an even
-// number of steps and to at least 32 (so that at most one boundary is in flight); columns past a target's end run on the neutral
-// profile row and cannot raise a maximum, exactly as in the one-quad kernel.  The column of a best is kept as the chain's step
-// counter (16 bits per task), so a chain ends early where the next segment would take it past 65 535.
-template <int RT>
-__global__ void __launch_bounds__(64)
-sw_score_pk_chain_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint8_t *__restrict__ qRes,
-                         const int8_t *__restrict__ qBias, const uint8_t *__restrict__ tRes, const int8_t *__restrict__ mat,
-                         int go, int ge, int32_t *__restrict__ out, const uint32_t *__restrict__ order,
-                         const int8_t *__restrict__ qProf, uint32_t chainLen) {
-    constexpr int LW = 32;
-    constexpr int WORDS = (RT + 3) / 4;
-    constexpr int RTP = 4 * WORDS;
-    constexpr int PSTRIDE = LW * WORDS;    // dwords per residue row of the profile
-    constexpr uint32_t ROWB = PSTRIDE * 4; // bytes per residue row
-    static_assert(22 * ROWB < 65536, "row offsets travel in 16 bits");
-    __shared__ uint32_t prof[22][PSTRIDE];
-    __shared__ int8_t smat[441];
-    for (int i = threadIdx.x; i < 441; i += 64) smat[i] = mat[i];
-    __syncthreads();
-    const int lane = threadIdx.x;
-    const int grp = lane >> 5, l = lane & 31;
-    const int q0 = l * RT;
-    const uint32_t goP = (uint32_t) go | ((uint32_t) go << 16), geP = (uint32_t) ge | ((uint32_t) ge << 16);
-    constexpr uint32_t NEUT = (uint32_t) PK_NEUTRAL * ROWB;
-    typedef __attribute__((address_space(3))) uint32_t lds_u32;
-    const uint32_t base = (uint32_t) (size_t) (lds_u32 *) (&prof[0][0] + l * WORDS);
-    auto ldsWord = [](uint32_t addr, int w) -> uint32_t { return *((const lds_u32 *) (size_t) addr + w); };
-
-    const uint32_t nQuads = (nTasks + 3) / 4;
-    uint32_t qd = blockIdx.x * chainLen;
-    const uint32_t qdEnd = min(qd + chainLen, nQuads);
-    auto loadQuad = [&](uint32_t quad, SwTask (&tk)[4]) {   // uniform loads; entries beyond the list and PAIR_NONE entries are empty tasks
-#pragma unroll
-        for (int x = 0; x < 4; x++) {
-            const uint32_t id = quad * 4 + x;
-            const uint32_t tid = id < nTasks ? (order ? order[id] : id) : 0xFFFFFFFFu;
-            if (tid != 0xFFFFFFFFu) {
-                tk[x] = tasks[tid];
-            } else {
-                tk[x].n = 0; tk[x].tL = 0; tk[x].qOff = 0; tk[x].tOff = 0; tk[x].qStep = 1; tk[x].tStep = 1; tk[x].segLen = 1;
-                tk[x].slot = 0; tk[x].boundOff = 0;
-            }
-        }
-    };
-    bool firstChain = true;
-    while (qd < qdEnd) {
-        SwTask tk[4];
-        loadQuad(qd, tk);
-        if (tk[0].n <= 0) {   // (a quad's first task is a real one: runs are padded at their end)
-            qd++;
-            continue;
-        }
-        // ---- the query's profile (SmithWaterman::createQueryProfile, :163-187): either group writes half of the residue rows
-        if (!firstChain) __syncthreads();
-        firstChain = false;
-        const SwTask Q = tk[0];
-        {
-            uint32_t *pw = &prof[0][0] + l * WORDS;
-#pragma unroll
-            for (int w = 0; w < WORDS; w++) {
-                int res[4], cb[4];
-                int64_t pidx[4];
-                bool valid[4];
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const int qi = q0 + 4 * w + b;
-                    valid[b] = (4 * w + b < RT) && qi < Q.n;
-                    res[b] = 20;
-                    cb[b] = 0;
-                    pidx[b] = 0;
-                    if (valid[b]) {
-                        const int64_t idx = (int64_t) Q.qOff + (int64_t) qi * Q.qStep;
-                        res[b] = qRes[idx];
-                        cb[b] = qBias[idx];
-                        pidx[b] = idx * 21;
-                    }
-                }
-                if (qProf) {   // profile query: the position's own row
-                    for (int a = grp; a < 21; a += 2) {
-                        uint32_t word = 0;
-#pragma unroll
-                        for (int b = 0; b < 4; b++) {
-                            const int v = valid[b] ? (int) qProf[pidx[b] + a] : -64;
-                            word |= (uint32_t) (uint8_t) (int8_t) v << (8 * b);
-                        }
-                        pw[a * PSTRIDE + w] = word;
-                    }
-                } else {
-                    for (int a = grp; a < 21; a += 2) {
-                        uint32_t word = 0;
-#pragma unroll
-                        for (int b = 0; b < 4; b++) {
-                            const int v = valid[b] ? (int) smat[a * 21 + res[b]] + cb[b] : -64;
-                            word |= (uint32_t) (uint8_t) (int8_t) v << (8 * b);
-                        }
-                        pw[a * PSTRIDE + w] = word;
-                    }
-                }
-                pw[PK_NEUTRAL * PSTRIDE + w] = 0xC0C0C0C0u;
-            }
-        }
-        __syncthreads();
-
-        uint32_t H[RTP], E[RTP];
-#pragma unroll
-        for (int r = 0; r < RTP; r++) {
-            H[r] = 0;
-            E[r] = 0;
-        }
-        uint32_t outG = 0, outFf = 0, prevInG = 0;
-        uint32_t bestcm = 0, bestcol = 0, savedcm = 0, savedcol = 0;
-        uint32_t T = NEUT | (NEUT << 16);
-        uint32_t pa[WORDS], pb[WORDS], T2, pa2[WORDS], pb2[WORDS];
-        // the targets of the segment in flight, as this lane's group sees them
-        uint64_t tOffA = 0, tOffB = 0;
-        int32_t tLA = 0, tLB = 0, tStepA = 1, tStepB = 1;
-        uint32_t chunk = 0, chunkNext = 0;
-        auto loadChunk = [&](int c0) -> uint32_t {   // row offsets (bytes) of the residues of column c0 + l, task A | task B << 16
-            const int col = c0 + l;
-            uint32_t a = PK_NEUTRAL, b = PK_NEUTRAL;
-            if (col < tLA) a = tRes[(int64_t) tOffA + (int64_t) col * tStepA];
-            if (col < tLB) b = tRes[(int64_t) tOffB + (int64_t) col * tStepB];
-            return (a * ROWB) | ((b * ROWB) << 16);
-        };
-        uint32_t S = 0;   // the chain's step counter at the start of the segment in flight
-        // one column step (see sw_score_pk_aligned_kernel): consumes (Tc, pac, pbc), produces the next column's (Tn, pan, pbn)
-        auto columnStep = [&](const int i, const uint32_t &Tc, const uint32_t (&pac)[WORDS], const uint32_t (&pbc)[WORDS], uint32_t &Tn,
-                              uint32_t (&pan)[WORDS], uint32_t (&pbn)[WORDS]) {
-            const int i1 = (i + 1) & (LW - 1);
-            if (i1 == 0) {
-                chunk = chunkNext;
-                chunkNext = loadChunk(i + 1 + LW);
-            }
-            Tn = dppShr1(Tc);
-            Tn = writeLane<0>(readLane(chunk, i1), Tn);
-            Tn = writeLane<32>(readLane(chunk, 32 + i1), Tn);
-            {
-                const uint32_t aA = addWord0(base, Tn), aB = addWord1(base, Tn);
-#pragma unroll
-                for (int w = 0; w < WORDS; w++) {
-                    pan[w] = ldsWord(aA, w);
-                    pbn[w] = ldsWord(aB, w);
-                }
-            }
-            uint32_t inG = dppShr1(outG), inFf = dppShr1(outFf);
-            inG = writeLane<32>(0, inG);
-            inFf = writeLane<32>(0, inFf);
-            uint32_t h[RTP];
-#pragma unroll
-            for (int w = 0; w < WORDS; w++) {
-                const uint32_t d0 = (w == 0) ? prevInG : H[4 * w - 1];
-                addProfile4(pac[w], pbc[w], d0, H[4 * w], H[4 * w + 1], H[4 * w + 2], h[4 * w], h[4 * w + 1], h[4 * w + 2], h[4 * w + 3]);
-            }
-            prevInG = inG;
-            uint32_t Fl = 0, Ff = inFf, cm = 0;
-#pragma unroll
-            for (int r = 0; r < RT; r++) {
-                uint32_t hpre = pkMax(h[r], E[r]);
-                if (r != 0) hpre = pkMax(hpre, Fl);   // a lane is a segment of the reference: no vertical gap of the lane structure enters row 0
-                const uint32_t g = pkMax(hpre, Ff);
-                const uint32_t open = pkSubSat(hpre, goP);
-                E[r] = pkMax(pkSubSat(E[r], geP), open);
-                if (r == 0) Fl = open;
-                else if (r + 1 != RT) Fl = pkMax(pkSubSat(Fl, geP), open);
-                Ff = pkMax(pkSubSat(Ff, geP), open);
-                H[r] = g;
-                const uint32_t code = pkRowCode(g, 31 - r);
-                cm = r == 0 ? code : pkMax(cm, code);
-            }
-            outG = H[RT - 1];
-            outFf = Ff;
-            const uint32_t t = bestcm | 0x001F001Fu;
-            const uint32_t m = pkAshr15(pkSub(t, cm));   // all ones where cm > t
-            const uint32_t k = S + (uint32_t) i;
-            const uint32_t kk = k | (k << 16);
-            bestcm = bfiAsm(m, cm, bestcm);
-            bestcol = bfiAsm(m, kk, bestcol);
-        };
-        // the boundary between two quads reaches lane i of either group at step i of the new segment
-        auto boundary = [&](const int i) {
-            if (l == i) {
-                savedcm = bestcm;
-                savedcol = bestcol;
-                bestcm = 0;
-                bestcol = 0;
-                prevInG = 0;
-#pragma unroll
-                for (int r = 0; r < RTP; r++) {
-                    H[r] = 0;
-                    E[r] = 0;
-                }
-            }
-        };
-        // first residues of a segment into the first lane of either group, and that lane's profile words again
-        auto enterSegment = [&]() {
-            chunk = loadChunk(0);
-            chunkNext = loadChunk(LW);
-            T = writeLane<0>(readLane(chunk, 0), T);
-            T = writeLane<32>(readLane(chunk, 32), T);
-            const uint32_t aA = addWord0(base, T), aB = addWord1(base, T);
-#pragma unroll
-            for (int w = 0; w < WORDS; w++) {
-                pa[w] = ldsWord(aA, w);
-                pb[w] = ldsWord(aB, w);
-            }
-        };
-        // the finished quad: its snapshot -> max value, then smallest column, then smallest row over the 32 lanes of a group
-        uint32_t pSlotA = 0, pSlotB = 0, pN = 0, pS = 0;
-        bool pHaveA = false, pHaveB = false, havePrev = false;
-        auto storePrev = [&]() {
-            unsigned long long keyA = 0, keyB = 0;
-            const uint32_t vA = (savedcm & 0xFFFFu) >> 5, vB = savedcm >> 21;
-            const uint32_t rowA = (uint32_t) (q0 + 31 - (int) (savedcm & 31u)), rowB = (uint32_t) (q0 + 31 - (int) ((savedcm >> 16) & 31u));
-            const uint32_t colA = (savedcol & 0xFFFFu) - (uint32_t) l - pS, colB = (savedcol >> 16) - (uint32_t) l - pS;   // step - lane - segment start
-            if (vA > 0) keyA = ((unsigned long long) vA << 40) | ((unsigned long long) (0xFFFFFu - colA) << 20) | (unsigned long long) (0xFFFFFu - rowA);
-            if (vB > 0) keyB = ((unsigned long long) vB << 40) | ((unsigned long long) (0xFFFFFu - colB) << 20) | (unsigned long long) (0xFFFFFu - rowB);
-#pragma unroll
-            for (int off = LW / 2; off >= 1; off >>= 1) {
-                const unsigned long long oa = __shfl_xor(keyA, off, LW), ob = __shfl_xor(keyB, off, LW);
-                keyA = oa > keyA ? oa : keyA;
-                keyB = ob > keyB ? ob : keyB;
-            }
-            if (l == 0) {
-                if (pHaveA) {
-                    const int v = (int) (keyA >> 40);
-                    out[3 * pSlotA + 0] = v;
-                    out[3 * pSlotA + 1] = v == 0 ? -1 : 0xFFFFF - (int) ((keyA >> 20) & 0xFFFFF);
-                    out[3 * pSlotA + 2] = v == 0 ? (int) pN - 1 : 0xFFFFF - (int) (keyA & 0xFFFFF);
-                }
-                if (pHaveB) {
-                    const int v = (int) (keyB >> 40);
-                    out[3 * pSlotB + 0] = v;
-                    out[3 * pSlotB + 1] = v == 0 ? -1 : 0xFFFFF - (int) ((keyB >> 20) & 0xFFFFF);
-                    out[3 * pSlotB + 2] = v == 0 ? (int) pN - 1 : 0xFFFFF - (int) (keyB & 0xFFFFF);
-                }
-            }
-        };
-
-        bool more = true;
-        while (more) {
-            const SwTask &A = grp ? tk[2] : tk[0];
-            const SwTask &B = grp ? tk[3] : tk[1];
-            tOffA = A.tOff; tLA = A.n > 0 ? A.tL : 0; tStepA = A.tStep;
-            tOffB = B.tOff; tLB = B.n > 0 ? B.tL : 0; tStepB = B.tStep;
-            int maxTL = 0;
-#pragma unroll
-            for (int x = 0; x < 4; x++) maxTL = max(maxTL, tk[x].n > 0 ? tk[x].tL : 0);
-            const int L = max((maxTL + 1) & ~1, LW);
-            enterSegment();
-#pragma unroll 1
-            for (int i = 0; i < LW; i += 2) {
-                boundary(i);
-                columnStep(i, T, pa, pb, T2, pa2, pb2);
-                boundary(i + 1);
-                columnStep(i + 1, T2, pa2, pb2, T, pa, pb);
-            }
-            if (havePrev) storePrev();
-#pragma unroll 1
-            for (int i = LW; i < L; i += 2) {
-                columnStep(i, T, pa, pb, T2, pa2, pb2);
-                columnStep(i + 1, T2, pa2, pb2, T, pa, pb);
-            }
-            pSlotA = A.slot; pSlotB = B.slot; pN = (uint32_t) Q.n; pS = S;
-            pHaveA = A.n > 0; pHaveB = B.n > 0; havePrev = true;
-            S += (uint32_t) L;
-            // the next quad of the list continues the chain while it belongs to the same query
-            qd++;
-            more = false;
-            if (qd < qdEnd) {
-                SwTask nk[4];
-                loadQuad(qd, nk);
-                int nTL = 0;
-#pragma unroll
-                for (int x = 0; x < 4; x++) nTL = max(nTL, nk[x].n > 0 ? nk[x].tL : 0);
-                if (nk[0].n == Q.n && nk[0].qOff == Q.qOff && nk[0].qStep == Q.qStep && S + (uint32_t) max(nTL + 1, LW) + LW <= 65535u) {
-#pragma unroll
-                    for (int x = 0; x < 4; x++) tk[x] = nk[x];
-                    more = true;
-                }
-            }
-        }
-        // ---- drain: 32 steps on the neutral row carry the boundary behind the last quad down the lanes
-        tLA = 0;
-        tLB = 0;
-        enterSegment();
-#pragma unroll 1
-        for (int i = 0; i < LW; i += 2) {
-            boundary(i);
-            columnStep(i, T, pa, pb, T2, pa2, pb2);
-            boundary(i + 1);
-            columnStep(i + 1, T2, pa2, pb2, T, pa, pb);
-        }
-        storePrev();
     }
 }
 

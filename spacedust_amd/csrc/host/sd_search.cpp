@@ -260,22 +260,20 @@ int sd_search_create_indexed(int device, const sd_search_params *par, const sd_s
     const int threads = par->threads > 0 ? par->threads : cpus;
     int rc = sd_host_create(threads, &s->host);
     if (rc != SD_OK) return rc;
-    const int pfPrio = getenv("SD_PF_PRIO") ? atoi(getenv("SD_PF_PRIO")) : 0;   // stream priority of the prefilter lanes (-1 highest; measured: no effect on the throughput)
-    rc = sd_ctx_create_prio(device, pfPrio, &s->ctxPf);
+    // prefilter lanes at the default stream priority (a higher one measured no effect on the throughput)
+    rc = sd_ctx_create_prio(device, 0, &s->ctxPf);
     if (rc != SD_OK) return rc;
-    // CUs the alignment streams leave alone (see sd_ctx_create_masked)
-    const int alReserve = getenv("SD_ALIGN_RESERVE_CUS") ? atoi(getenv("SD_ALIGN_RESERVE_CUS")) : 0;
-    rc = sd_ctx_create_masked(device, par->alignPriority, alReserve, &s->ctxAl);
+    rc = sd_ctx_create_masked(device, par->alignPriority, 0, &s->ctxAl);
     if (rc != SD_OK) return rc;
     // (two lanes per stage whatever the CPU quota: a lane thread sleeps while its kernels run -- 0.04 - 0.08 core-seconds per step
     // since the small reads go through sdD2H; before that a second lane cost 0.7 and ranks with fewer than 4 cores ran one)
     if (const char *e = getenv("SD_ALIGN_LANES")) s->alignLanes = std::max(1, std::min(4, atoi(e)));
     if (s->alignLanes > 1) {
-        rc = sd_ctx_create_masked(device, par->alignPriority, alReserve, &s->ctxAl2);
+        rc = sd_ctx_create_masked(device, par->alignPriority, 0, &s->ctxAl2);
         if (rc != SD_OK) return rc;
     }
     for (int x = 2; x < s->alignLanes; x++) {
-        rc = sd_ctx_create_masked(device, par->alignPriority, alReserve, &s->ctxAlMore[x - 2]);
+        rc = sd_ctx_create_masked(device, par->alignPriority, 0, &s->ctxAlMore[x - 2]);
         if (rc != SD_OK) return rc;
     }
     rc = sd_ctx_create(device, &s->ctxCh);
@@ -286,11 +284,11 @@ int sd_search_create_indexed(int device, const sd_search_params *par, const sd_s
     if (const char *e = getenv("SD_PF_LANES")) s->pfLanes = std::max(1, std::min(4, atoi(e)));
     else s->pfLanes = 4;
     if (s->pfLanes > 1) {
-        rc = sd_ctx_create_prio(device, pfPrio, &s->ctxPf2);
+        rc = sd_ctx_create_prio(device, 0, &s->ctxPf2);
         if (rc != SD_OK) return rc;
     }
     for (int x = 2; x < s->pfLanes; x++) {
-        rc = sd_ctx_create_prio(device, pfPrio, &s->ctxPfMore[x - 2]);
+        rc = sd_ctx_create_prio(device, 0, &s->ctxPfMore[x - 2]);
         if (rc != SD_OK) return rc;
     }
     // composition bias: on the device unless the caller asks for the host stage (deviceBias == 0).  The two kernels cost 0.13 ms per
@@ -834,18 +832,11 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
         std::shared_ptr<std::string> err;
     };
     std::vector<FinJob> finJobs;
-    static const bool finInline = getenv("SD_FIN_INLINE") && atoi(getenv("SD_FIN_INLINE")) != 0;   // A/B: finalise on the driving thread
     auto submitFinalize = [&](uint32_t r) {
         FinJob j;
         j.err.reset(new std::string());
         std::shared_ptr<std::string> e = j.err;
-        if (finInline) {
-            std::promise<int> pr;
-            j.fut = pr.get_future();
-            pr.set_value(finalize(r, e.get()));
-        } else {
-            j.fut = finStage.submit([&finalize, r, e] { return finalize(r, e.get()); });
-        }
+        j.fut = finStage.submit([&finalize, r, e] { return finalize(r, e.get()); });
         finJobs.push_back(std::move(j));
     };
     std::vector<std::pair<uint32_t, size_t> > toFinalize;   // (range, chunk whose aggregation must have finished)
@@ -1016,15 +1007,14 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
 
     // prefilter jobs submitted and not yet collected, in chunk order.  A lane's thread runs its jobs one after the other; with ONE job
     // per lane a lane that finishes chunk x + 1 before chunk x is collected (chunks are collected in order, and this thread is also the
-    // one that retires alignments and runs clusterhits) stands idle until then -- and the prefilter is the stage a step waits for.  With
-    // SD_PF_DEPTH jobs per lane it goes on with its next chunk; a finished chunk's rows wait in host memory.  Measured (round 5, 1 000
-    // proteomes, three and four lanes, depth 1 / 2 / 3): this thread's wait for the prefilter 10.4 -> 7 s per 12 steps, the throughput the
-    // same (2 575 / 2 560 / 2 550 and 2 628 / 2 620 / 2 593) -- the device, not the lanes' idle time, bounds a step: one job per lane stays.
+    // one that retires alignments and runs clusterhits) stands idle until then.  Two or three jobs per lane were
+    // measured (round 5, 1 000 proteomes, three and four lanes; profiles/r06u_depth_lanes_ab.txt): this thread's wait for the prefilter 10.4 -> 7 s per 12
+    // steps, the throughput the same (2 575 / 2 560 / 2 550 and 2 628 / 2 620 / 2 593) -- the device, not the lanes' idle time, bounds a
+    // step, so one job per lane stays and the deeper queue was removed.
     std::deque<PfFut> pfQueue;
     size_t pfSubmitted = 0;
-    static const int pfDepth = getenv("SD_PF_DEPTH") ? std::max(1, std::min(4, atoi(getenv("SD_PF_DEPTH")))) : 1;
     auto pumpPf = [&]() {
-        while (pfSubmitted < chunks.size() && (int) pfQueue.size() < pfLanes * pfDepth) pfQueue.push_back(submitPf(pfSubmitted++));
+        while (pfSubmitted < chunks.size() && (int) pfQueue.size() < pfLanes) pfQueue.push_back(submitPf(pfSubmitted++));
     };
     pumpPf();
     for (size_t ci = 0; ci < chunks.size() && status == SD_OK; ci++) {

@@ -234,47 +234,16 @@ def test_sw_device_vs_host_orchestration(gpu, host):
             assert np.array_equal(sa, sb), x
 
 
-def test_sw_packed_kernel_equals_int32_kernel(gpu, host, monkeypatch):
-    """the packed-int16 score kernels (all row classes, 32- and 64-lane variants, wide row code) against the int32
-    kernel on the same pairs, through the full align call"""
-    from spacedust_amd.synth import make_proteomes
-    ps = make_proteomes(n_proteomes=5, genes_per_proteome=400, n_families=600, seed=5, mean_len=330)
-    rng = np.random.default_rng(17)
-    pq, pt = _pairs(ps, rng, 6000)
-    sw_bias, _, _ = host.comp_bias(ps.residues, ps.offsets)
-    mat, _, _ = host.matrix(0)
-    db = int(ps.offsets[-1])
-    ss = gpu.seqset(ps.residues, ps.offsets, sw_bias)
-    par = gpu.sw_params(mat, db)
-    ident = (pq == pt)
-    a, pa = gpu.sw_align(par, ss, ss, pq, pt, identity=ident)
-    monkeypatch.setenv('SD_SW_INT32', '1')
-    b, pb = gpu.sw_align(par, ss, ss, pq, pt, identity=ident)
-    for f in ('score', 'qStart', 'qEnd', 'tStart', 'tEnd', 'identical', 'btLen', 'flags', 'evalue'):
-        assert np.array_equal(a[f], b[f]), (f, np.flatnonzero(a[f] != b[f])[:5])
-    lens = (ps.offsets[1:] - ps.offsets[:-1])[pq]
-    assert lens.min() <= 128 and lens.max() > 768   # every row class is exercised
-
-
-@pytest.mark.parametrize('chain', [2, 5, 64])
-def test_sw_chained_quads_equal_one_quad_per_wavefront(gpu, host, monkeypatch, chain):
-    """sw_score_pk_chain_kernel (SD_SW_CHAIN=M: a wavefront runs up to M consecutive quads of the pair list, those of one query back
-    to back through one systolic pipeline) against the one-quad-per-wavefront kernel: queries with long runs of targets (chains that
-    fill their M quads), runs of one to three tasks (a chain that ends after every quad, empty pairs), targets shorter than the 32
-    lanes, every aligned row class"""
-    from spacedust_amd.synth import make_proteomes
-    ps = make_proteomes(n_proteomes=5, genes_per_proteome=400, n_families=600, seed=5, mean_len=330)
-    rng = np.random.default_rng(23)
-    # the proteomes plus 40 fragments of 3 .. 40 residues (targets shorter than the 32 lanes: a segment is padded to 32 steps)
+def _query_run_pairs(ps, rng):
+    """the proteomes plus 40 fragments of 3 .. 40 residues (targets shorter than the 32 lanes), 120 queries with long runs of 5 .. 90
+    targets each (homologs and fragments among them) and 3 000 random pairs (runs of one to three tasks, empty pairs)"""
     frag_len = rng.integers(3, 41, size=40)
     frag = [ps.residues[int(o):int(o) + int(n)] for o, n in zip(ps.offsets[rng.integers(ps.n, size=40)], frag_len)]
     residues = np.concatenate([ps.residues] + frag)
     offsets = np.concatenate([ps.offsets, ps.offsets[-1] + np.cumsum(frag_len)]).astype(ps.offsets.dtype)
-    n_seq = len(offsets) - 1
-    short = np.arange(ps.n, n_seq)
-    lens = offsets[1:] - offsets[:-1]
+    short = np.arange(ps.n, len(offsets) - 1)
     pq, pt = [], []
-    for q in rng.choice(ps.n, 120, replace=False):   # long runs: 5 .. 90 targets of one query, homologs and fragments among them
+    for q in rng.choice(ps.n, 120, replace=False):
         n = int(rng.integers(5, 90))
         t = rng.integers(ps.n, size=n)
         t[:4] = rng.choice(short, 4)
@@ -283,23 +252,41 @@ def test_sw_chained_quads_equal_one_quad_per_wavefront(gpu, host, monkeypatch, c
         t[4:4 + k] = same[:k]
         pq += [int(q)] * n
         pt += [int(x) for x in t]
-    q2, t2 = _pairs(ps, rng, 3000)   # short runs
-    pq = np.concatenate([np.array(pq, np.uint32), q2])
-    pt = np.concatenate([np.array(pt, np.uint32), t2])
+    q2, t2 = _pairs(ps, rng, 3000)
+    return residues, offsets, np.concatenate([np.array(pq, np.uint32), q2]), np.concatenate([np.array(pt, np.uint32), t2])
+
+
+@pytest.mark.parametrize('pairs', ['random', 'query_runs'])
+def test_sw_packed_kernel_equals_int32_kernel(gpu, host, monkeypatch, pairs):
+    """the packed-int16 score kernels (all row classes, 32- and 64-lane variants, wide row code) against the int32
+    kernel on the same pairs, through the full align call.  query_runs: long runs of one query (many wavefronts of four tasks
+    that share one profile), runs of one to three tasks (padded with empty pairs), targets shorter than the 32 lanes"""
+    from spacedust_amd.synth import make_proteomes
+    ps = make_proteomes(n_proteomes=5, genes_per_proteome=400, n_families=600, seed=5, mean_len=330)
+    if pairs == 'random':
+        rng = np.random.default_rng(17)
+        residues, offsets = ps.residues, ps.offsets
+        pq, pt = _pairs(ps, rng, 6000)
+    else:
+        residues, offsets, pq, pt = _query_run_pairs(ps, np.random.default_rng(23))
     sw_bias, _, _ = host.comp_bias(residues, offsets)
     mat, _, _ = host.matrix(0)
+    db = int(offsets[-1])
     ss = gpu.seqset(residues, offsets, sw_bias)
-    par = gpu.sw_params(mat, int(offsets[-1]))
+    par = gpu.sw_params(mat, db)
     ident = (pq == pt)
-    monkeypatch.delenv('SD_SW_CHAIN', raising=False)
     a, pa = gpu.sw_align(par, ss, ss, pq, pt, identity=ident)
-    monkeypatch.setenv('SD_SW_CHAIN', str(chain))
+    monkeypatch.setenv('SD_SW_INT32', '1')
     b, pb = gpu.sw_align(par, ss, ss, pq, pt, identity=ident)
     for f in ('score', 'qStart', 'qEnd', 'tStart', 'tEnd', 'identical', 'btLen', 'flags', 'evalue'):
         assert np.array_equal(a[f], b[f]), (f, np.flatnonzero(a[f] != b[f])[:5])
-    assert np.array_equal(pa, pb)
-    assert lens[pq].min() <= 160 and lens[pq].max() > 768 and lens[pt].min() < 32   # the aligned row classes, targets below 32 residues
-    assert int((a['score'] > 0).sum()) > len(pq) // 2
+    lens = offsets[1:] - offsets[:-1]
+    if pairs == 'random':
+        assert lens[pq].min() <= 128 and lens[pq].max() > 768   # every row class is exercised
+    else:
+        assert np.array_equal(pa, pb)
+        assert lens[pq].min() <= 160 and lens[pq].max() > 768 and lens[pt].min() < 32   # the aligned row classes, targets below 32 residues
+        assert int((a['score'] > 0).sum()) > len(pq) // 2
 
 
 def test_sw_align_compact_equals_full(gpu, host):
