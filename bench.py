@@ -16,13 +16,19 @@ the data path.  Per-GPU work is fixed as N grows: "scaling": "weak".
 
 Prints ONE compact JSON line (rank 0; a few KB -- everything bulky goes to the side file gpurun_out/bench_detail.json):
   roofline      the prefilter kernel with the largest accumulated time (HIP events recorded by libsdgpu on its own streams)
-  cpu_baseline  the reference's own AVX2 code (oracle/_ref/libsdref.so; kind "port" if it did not travel) on a bounded
-                sample of the same workload on this box's host cores -- N = 1 only
+and, with --full only:
+  index_check   untimed: the device-built index against the host builder on sample sequences
+  roofline.isolated   untimed: the prefilter of one block of queries alone on the device; it names roofline's kernel
+  cpu_baseline  the reference's own AVX2 code (oracle/_ref/libsdref.so; kind "port" if it is absent) on a bounded
+                sample of the same workload on the host's cores -- N = 1 only
   parity_check  untimed: device prefilter rows and alignments of sample queries against the reference rows the cpu_baseline
                 leg produced for the same queries; the (query set, target set) entries of one whole measured query set against
                 an independent aggregation of the reference's rows and alignments; the cluster records of measured entries
                 against the reference's clusterhits functions
   p100 / p10000 / iter3   N = 1 only: short child records at BASELINE configs[1] / configs[4] / configs[3]
+A plain run (no --full) sets up, warms up, times the steps, writes --dump-outputs and prints the line: its headline keys are
+those of a --full run, and the legs above that take runs of their own are left out.  Within --full, --no-cpu, --no-children,
+--no-p100 / --no-p10000 / --no-iter3 and --no-index-check leave out single legs.
 
 --dump-outputs DIR writes the results the timed path returned for its last step (rank 0's share) to DIR/<name>.npy, float64, at most
 64 MB (dump_outputs); the inputs depend on the arguments only, so the files of two builds can be compared array by array.
@@ -75,6 +81,8 @@ def parse():
     ap.add_argument('--no-index-check', action='store_true', help='skip the sampled check of the device-built index against the host builder')
     ap.add_argument('--strong', action='store_true', help='strong scaling: --batch query proteomes per step in TOTAL, dealt over the ranks '
                                                           '(BASELINE configs[2] as written: one query set of proteomes split over N GPUs)')
+    ap.add_argument('--full', action='store_true', help='also the legs beside the timed steps: index check, isolated prefilter, cpu_baseline '
+                                                        'and parity_check, the child records (p100, p10000, iter3)')
     ap.add_argument('--record', action='store_true', help=argparse.SUPPRESS)   # child mode: one plain measurement, JSON out
     ap.add_argument('--dump-outputs', default='', metavar='DIR',
                     help='write what the timed path computed in its last step to DIR/<name>.npy (float64, at most 64 MB in all)')
@@ -83,6 +91,8 @@ def parse():
         ap.error('--steps must be at least 1 and --warmup at least 0')
     if a.batch <= 0:
         a.batch = 4 if a.proteomes >= 1000 else 10
+    if not a.full:   # a plain run: the headline only
+        a.no_cpu = a.no_children = a.no_index_check = True
     return a
 
 
@@ -670,7 +680,8 @@ def measure(args, rank, local_rank, world, dist, torch):
                          'payload': 'cluster records (sd_search_result_records): per cluster sets, P-values, members with alignment fields', 'tsv': tsv_info}
         res['multi_gpu_note'] = ('%s scaling over query sets; an 8-GPU curve exists only where the driver ran this command with --gpus 8'
                                  % ('strong (BASELINE configs[2] as written)' if args.strong else 'weak'))
-    res['index_check'] = index_check
+    if args.full:
+        res['index_check'] = index_check
     q_warm = int(sum(b - a for x in range(args.warmup) for a, b in my_ranges(x)[0]))
     res['prefilter_queries_in_process'] = n_queries + q_warm   # + the isolated leg's two calls, below
     if rank == 0 and not args.no_index_check:
@@ -705,6 +716,8 @@ def measure(args, rank, local_rank, world, dist, torch):
                                                           'scaled by queries / its time there'),
                                    dominant_by='largest single kernel of the prefilter stage running alone (roofline.isolated, this run); '
                                                'the largest in-pipeline time is %s' % max(pk.items(), key=lambda kv: kv[1]['ms'])[0])
+    else:
+        res['roofline']['dominant_by'] = 'largest in-pipeline time (roofline.isolated, which names it with --full, did not run)'
     last_ranges = my_ranges(args.warmup + args.steps - 1)[0] if args.steps > 0 else []
     extras = dict(ps=ps, k=k, max_seqs=max_seqs, kmer_thr=kmer_thr, bin_size=int(cs.bin_size), gpu=gpu, host=host,
                   last=outs[-1] if outs else None, last_step=outs[len(outs) - len(last_ranges):] if last_ranges else [], db=db,
@@ -846,13 +859,13 @@ def main():
     if kids and not args.no_p100 and args.proteomes != 100 and _leg_allowed(children, 'p100', t_start, args):
         # BASELINE configs[1]: 100 proteomes all-vs-all (one pass = 10 steps of 10 query proteomes), its own CPU sample and parity leg
         children['p100'] = child('p100', [sys.executable, os.path.abspath(__file__), '--record', '--proteomes', '100', '--steps', str(args.p100_steps),
-                                          '--warmup', '1', '--batch', '10', '--chunk', str(args.chunk), '--no-children'] +
+                                          '--warmup', '1', '--batch', '10', '--chunk', str(args.chunk), '--full', '--no-children'] +
                                  (['--no-cpu'] if args.no_cpu else []) + ['--cpu-seconds', str(min(args.cpu_seconds, 10.0))])
     if kids and not args.no_p10000 and args.proteomes != 10000 and _leg_allowed(children, 'p10000', t_start, args):
         # BASELINE configs[4]: 10 000 proteomes (3 * 10^7 sequences, 9 * 10^9 residues, k = 7) resident on this one GPU -- generated,
         # indexed on the device, checked on a sample against the host builder, and searched for a short step; --max-seqs 2N = 20 000
         children['p10000'] = child('p10000', [sys.executable, os.path.abspath(__file__), '--record', '--proteomes', '10000', '--steps', str(args.p10000_steps),
-                                              '--warmup', '1', '--batch', str(args.p10000_batch), '--chunk', str(args.p10000_chunk), '--no-children', '--no-cpu'])
+                                              '--warmup', '1', '--batch', str(args.p10000_batch), '--chunk', str(args.p10000_chunk), '--full', '--no-children', '--no-cpu'])
         # CPU figure and parity of this configuration: the reference's index of 3 * 10^7 sequences takes minutes to build on the host, so
         # they are not re-measured inside this run -- they come from the run of tests/test_gpu_scale.py::test_config5_size_search_...
         # (the same search against the reference classes on the GPU box, 44 queries and 300 alignments, and the seconds those
@@ -944,7 +957,7 @@ def main():
         if isinstance(line.get(k_), dict):
             line[k_] = {kk: vv for kk, vv in line[k_].items() if kk != 'against'}
     line['detail'] = detail_path if not os.path.isabs(detail_path) else os.path.relpath(detail_path, ROOT)
-    if world == 1:
+    if world == 1 and args.full:
         for name in ('p100', 'p10000', 'iter3'):
             c_ = children.get(name)
             if name == 'iter3' and isinstance(c_, dict) and 'genome_pairs_per_s' in c_:

@@ -7,8 +7,8 @@ O=gpurun_out/$TAG; mkdir -p $O
 i=0
 for e in "$@"; do
     i=$((i+1))
-    if [ "$e" = "-" ]; then python bench.py --no-children --no-cpu ${BENCH_ARGS:-} --detail-out $O/d$i.json > $O/b$i.json 2> $O/b$i.err
-    else env $e python bench.py --no-children --no-cpu ${BENCH_ARGS:-} --detail-out $O/d$i.json > $O/b$i.json 2> $O/b$i.err; fi
+    if [ "$e" = "-" ]; then python bench.py --full --no-children --no-cpu ${BENCH_ARGS:-} --detail-out $O/d$i.json > $O/b$i.json 2> $O/b$i.err
+    else env $e python bench.py --full --no-children --no-cpu ${BENCH_ARGS:-} --detail-out $O/d$i.json > $O/b$i.json 2> $O/b$i.err; fi
     python - $O/b$i.json $O/d$i.json "$e" <<'PY'
 import json, sys
 try:

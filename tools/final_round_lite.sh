@@ -3,10 +3,11 @@
 # two PMC passes (FETCH_SIZE, WRITE_SIZE; --pmc with --kernel-trace only), the driver's bench command
 TAG=${1:-r05p}
 R=$(pwd); OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
+D=${OUT%/$TAG}   # the folder of the call's top-level records
 ( time python -m pytest tests -m gpu -q ) > $OUT/pytest_full.txt 2>&1
 grep -E "passed|failed|error" $OUT/pytest_full.txt > gpurun_out/${TAG}_pytest_gpu.txt; grep real $OUT/pytest_full.txt >> gpurun_out/${TAG}_pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/${TAG}_smoke.txt 2>&1
-( time python bench.py --gpus 1 --steps 20 --warmup 5 --detail-out gpurun_out/${TAG}_bench_detail.json > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err ) 2> gpurun_out/${TAG}_bench_default.time
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail-out $D/${TAG}_bench_detail.json > $D/${TAG}_bench_default.json 2> $D/${TAG}_bench_default.err ) 2> $D/${TAG}_bench_default.time
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- python $R/bench.py --steps 6 --warmup 1 --no-cpu --no-children --detail-out $OUT/bench_under_trace_detail.json > $OUT/bench_under_trace.json 2> $OUT/bench_under_trace.err
 python $R/tools/rocprof_summary.py $(find $OUT/trace -name '*results.db' | head -1) > $OUT/kernel_trace_stats.txt 2>&1

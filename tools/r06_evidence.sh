@@ -5,6 +5,7 @@
 TAG=${1:-r06a}; shift
 WHAT=${*:-bench pmc}
 R=$(pwd); OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
+D=${OUT%/$TAG}   # the folder of the call's top-level records
 for w in $WHAT; do
 case $w in
 tests)
@@ -13,7 +14,7 @@ tests)
     python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" >> gpurun_out/${TAG}_pytest_gpu.txt 2>&1
     cat gpurun_out/${TAG}_pytest_gpu.txt ;;
 bench)
-    ( time python bench.py --gpus 1 --steps 20 --warmup 5 --detail-out gpurun_out/${TAG}_bench_detail.json > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err ) 2> gpurun_out/${TAG}_bench_default.time
+    ( time python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail-out $D/${TAG}_bench_detail.json > $D/${TAG}_bench_default.json 2> $D/${TAG}_bench_default.err ) 2> $D/${TAG}_bench_default.time
     cat gpurun_out/${TAG}_bench_default.time; tail -c 1500 gpurun_out/${TAG}_bench_default.json; tail -5 gpurun_out/${TAG}_bench_default.err ;;
 trace)
     ( cd /tmp && export TMPDIR=/tmp
