@@ -267,6 +267,32 @@ int sd_prefilter_batch(sd_ctx *ctx, const sd_target *target, const sd_prefilter_
                        const int8_t *qDiagBias, const uint32_t *identityId, sd_hit *outHits, uint32_t *outCount,
                        uint64_t *stats);
 
+/* ---- exhaustive ungapped prefilter (`ungappedprefilter`, `search --prefilter-mode 1`) -----------------------------------
+ * Replaces runFilterOnCpu with alignment mode 0 (M/src/prefiltering/ungappedprefilter.cpp:338-477): EVERY query of `queries`
+ * against EVERY target of `targets` with SmithWaterman::ungapped_alignment (M/src/alignment/StripedSmithWaterman.cpp:1722-1781),
+ *   S(i, j) = max(0, min(255 - bias, S(i-1, j-1) + matrix[t_j][q_i] + cb_i)),  score = max S,
+ * cb = the query set's swCompBias, bias = |min matrix| + |min(0, min cb)| as ssw_init sets it.  No index, no seeds.
+ * The list rule: a pair is skipped unless Util::canBeCovered(covThr, covMode, qLen, tLen); it is a hit when
+ * score > minScore or the target is identityId[q]; hits are ordered by score descending, then target key ascending
+ * (hit_t::compareHitsByScoreAndId), and cut to maxHitsPerQuery.  No E-value takes part. */
+typedef struct {
+    int8_t matrix[21 * 21];  /* blosum62 at 2 bit-factor, scoreBias 0 (ungappedprefilter.cpp:536): the Smith-Waterman matrix */
+    int32_t minScore;        /* --min-ungapped-score (15); a hit scores strictly above it */
+    int32_t maxHitsPerQuery; /* --max-seqs */
+    int32_t covMode;         /* --cov-mode */
+    float covThr;            /* -c */
+} sd_ungapped_params;
+/* targetKeys (nullable: key = index): DB key of every target, the tie-break of the order and of the cut.
+ * identityId (nullable): per query the index of the query in the target set or UINT32_MAX, as in sd_prefilter_batch.
+ * outHits: queries->n * maxHitsPerQuery slots (row q at q * maxHitsPerQuery; seqId = target index, diagonal 0),
+ * outCount[queries->n].  Sequences are at most 65 535 residues long.  The per-pair scores stay on the device. */
+int sd_ungapped_prefilter_batch(sd_ctx *ctx, const sd_ungapped_params *par, const sd_seqset *queries, const sd_seqset *targets,
+                                const uint32_t *targetKeys, const uint32_t *identityId, sd_hit *outHits, uint32_t *outCount);
+/* The scan alone, for tests and measurements: out[q * targets->n + t] = score of the pair (a byte: the ceiling is below 256). */
+int sd_ungapped_score_matrix(sd_ctx *ctx, const int8_t *matrix, const sd_seqset *queries, const sd_seqset *targets, uint8_t *out);
+/* cells (sum of query lengths x sum of target lengths) the last sd_ungapped_* call of the context evaluated */
+int sd_ungapped_last_cells(sd_ctx *ctx, uint64_t *cells);
+
 /* ---- Profile queries (`--num-iterations` > 1 feeds profile DBs to prefilter and align) ----
  * sd_host_map_profiles restates Sequence::mapProfile (M/src/commons/Sequence.cpp:241-292) for n profile DB entries
  * (25 bytes per position, Sequence.h:458-471; byteOffsets[n+1] into profileData): per position the query letter,
@@ -548,6 +574,10 @@ typedef struct {
 } sd_index_view;
 int sd_search_create_indexed(int device, const sd_search_params *par, const sd_setdb *target, const sd_index_view *index,
                              sd_search **out);
+/* The same pipeline with the exhaustive ungapped scan (sd_ungapped_prefilter_batch) as its prefilter stage: what
+ * `search --prefilter-mode 1` runs.  No k-mer index is built or held (sd_search_target returns NULL); sensitivity, kmerSize,
+ * mask and binSize of `par` are not used.  Sequence queries only. */
+int sd_search_create_ungapped(int device, const sd_search_params *par, const sd_setdb *target, sd_search **out);
 void sd_search_destroy(sd_search *s);
 const char *sd_search_last_error(sd_search *s);
 /* the device contexts of the pipeline, e.g. for sd_profile_*: 0 prefilter, 1 alignment lane 0, 2 composition bias (NULL when

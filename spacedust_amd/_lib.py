@@ -41,6 +41,11 @@ class PrefilterParams(C.Structure):
                 ('ungappedMatrix', C.c_int8 * 441)]
 
 
+class UngappedParams(C.Structure):   # sd_ungapped_params
+    _fields_ = [('matrix', C.c_int8 * 441), ('minScore', C.c_int32), ('maxHitsPerQuery', C.c_int32), ('covMode', C.c_int32),
+                ('covThr', C.c_float)]
+
+
 HIT_DTYPE = np.dtype([('seqId', '<u4'), ('score', '<i4'), ('diagonal', '<u2'), ('pad', '<u2')])
 
 
@@ -156,6 +161,10 @@ def load():
         'sd_workspace_release': (C.c_int, [_vp]),
         'sd_prefilter_batch': (C.c_int, [_vp, _vp, C.POINTER(PrefilterParams), C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp]),
+        'sd_ungapped_prefilter_batch': (C.c_int, [_vp, C.POINTER(UngappedParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+        'sd_ungapped_score_matrix': (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+        'sd_ungapped_last_cells': (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+        'sd_search_create_ungapped': (C.c_int, [C.c_int, C.POINTER(SearchParams), C.POINTER(SetDbView), C.POINTER(_vp)]),
         'sd_comp_bias_batch': (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp]),
         'sd_prefilter_profile_batch': (C.c_int, [_vp, _vp, C.POINTER(PrefilterParams), C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                                  _vp, _vp, _vp, _vp]),

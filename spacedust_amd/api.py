@@ -554,6 +554,42 @@ def prefilter(ctx, target, par, residues, offsets, kmer_bias, diag_bias, identit
     return hits, counts, stats
 
 
+def ungapped_params(host, max_hits=300, min_score=15, cov_mode=0, cov_thr=0.0):
+    """sd_ungapped_params with the Smith-Waterman matrix (blosum62 at bit factor 2, score bias 0)"""
+    p = _lib.UngappedParams()
+    m, _, _ = host.matrix(0)
+    for i in range(441):
+        p.matrix[i] = int(m[i])
+    p.minScore, p.maxHitsPerQuery, p.covMode, p.covThr = min_score, max_hits, cov_mode, cov_thr
+    return p
+
+
+def ungapped_prefilter(ctx, par, queries, targets, target_keys=None, identity_id=None):
+    """sd_ungapped_prefilter_batch: every query of the SeqSet `queries` against every target of `targets`.
+    Returns (hits[nQ, maxHits] structured array, counts[nQ])."""
+    keys = np.ascontiguousarray(target_keys, np.uint32) if target_keys is not None else None
+    ident = np.ascontiguousarray(identity_id, np.uint32) if identity_id is not None else None
+    hits = np.zeros((queries.n, par.maxHitsPerQuery), _lib.HIT_DTYPE)
+    counts = np.zeros(queries.n, np.uint32)
+    _check(ctx.h, ctx.L.sd_ungapped_prefilter_batch(ctx.h, C.byref(par), queries.h, targets.h, ptr(keys), ptr(ident), ptr(hits),
+                                                    ptr(counts)), 'sd_ungapped_prefilter_batch')
+    return hits, counts
+
+
+def ungapped_scores(ctx, matrix, queries, targets):
+    """sd_ungapped_score_matrix: the uint8 score of every (query, target) pair, [nQ, nT]"""
+    m = np.ascontiguousarray(matrix, np.int8)
+    out = np.zeros((queries.n, targets.n), np.uint8)
+    _check(ctx.h, ctx.L.sd_ungapped_score_matrix(ctx.h, ptr(m), queries.h, targets.h, ptr(out)), 'sd_ungapped_score_matrix')
+    return out
+
+
+def ungapped_last_cells(ctx):
+    c = C.c_uint64()
+    _check(ctx.h, ctx.L.sd_ungapped_last_cells(ctx.h, C.byref(c)), 'sd_ungapped_last_cells')
+    return c.value
+
+
 def prefilter_profile(ctx, target, par, prof, identity_id=None, want_stats=False):
     """sd_prefilter_profile_batch for the profiles of Host.map_profiles (the target index built with kmer_thr=0)"""
     nq = len(prof['offsets']) - 1

@@ -109,6 +109,8 @@ std::shared_ptr<SeqDb> loadTargetDb(const std::string &path, sd_host *host, std:
 // modules (each: argv after the module name -> exit code)
 int createindexModule(const Args &a);
 int prefilterModule(const Args &a);
+int ungappedprefilterModule(const Args &a);
+int ungappedPrefilterModeCheck(const Args &a);   // refuses the --prefilter-mode values that are not implemented (2, 3)
 int alignModule(const Args &a);
 int clusterhitsModule(const Args &a);
 int prefixidModule(const Args &a);

@@ -20,6 +20,7 @@ struct Module {
 };
 const Module kModules[] = {
     {"prefilter", prefilterModule, "k-mer prefilter on the GPU: <queryDB> <targetDB> <prefilterDB>"},
+    {"ungappedprefilter", ungappedprefilterModule, "exhaustive ungapped prefilter on the GPU (--prefilter-mode 1): <queryDB> <targetDB> <prefilterDB>"},
     {"align", alignModule, "Smith-Waterman alignments on the GPU: <queryDB> <targetDB> <prefilterDB> <alignmentDB>"},
     {"clusterhits", clusterhitsModule, "agglomerative hit clustering on the GPU: <querySetDB> <targetSetDB> <matchesDB> <clustersDB>"},
     {"search", searchModule, "prefilter + align (and the --num-iterations profile loop): <queryDB> <targetDB> <alignmentDB> <tmpDir>"},

@@ -331,6 +331,119 @@ int prefilterModule(const Args &a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// ungappedprefilter <queryDB> <targetDB> <resultDB> (M/src/prefiltering/ungappedprefilter.cpp:479-562 with the parameters of
+// Parameters.cpp:459-476): every query against every target with the byte-saturated ungapped scan, no k-mer index.  What
+// blastp.sh calls instead of `prefilter` under --prefilter-mode 1.
+int ungappedPrefilterModeCheck(const Args &a) {
+    const long long mode = a.integer("--prefilter-mode", 0);
+    if (mode == 2) return fail("--prefilter-mode 2 (ungapped and gapped) is not implemented");
+    if (mode == 3) return fail("--prefilter-mode 3 (exhaustive) is not implemented");
+    if (mode < 0 || mode > 3) return fail("--prefilter-mode " + std::to_string(mode) + ": 0 (k-mer) and 1 (ungapped) are implemented");
+    return 0;
+}
+
+int ungappedprefilterModule(const Args &a) {
+    if (a.pos.size() != 3) return fail("usage: ungappedprefilter <queryDB> <targetDB> <resultDB> [options]");
+    if (a.integer("--compressed", 0) != 0) return fail("--compressed 1 is not supported");
+    const std::string sm = a.multi("--sub-mat", "aa", "blosum62.out");
+    if (sm != "blosum62.out") return fail("--sub-mat " + sm + ": only blosum62.out is built into this path");
+    if (a.has("--taxon-list") && !a.str("--taxon-list", "").empty()) return fail("--taxon-list is not supported");
+    if (a.integer("--gpu-server", 0) != 0) return fail("--gpu-server 1 is not supported (the module holds the GPU itself)");
+    if (a.real("--comp-bias-corr-scale", 1.0) != 1.0) return fail("--comp-bias-corr-scale 1 only");
+    if (int rc = ungappedPrefilterModeCheck(a)) return rc;
+    // (--gpu 0 and --gpu 1 both run this path; -e and --db-load-mode are parsed and have no effect, as in the reference's mode 0)
+    const bool compBias = a.integer("--comp-bias-corr", 1) != 0;
+    const int threads = threadsOf(a);
+
+    Lap lap("ungappedprefilter");
+    HostH host;
+    if (host.open(threads) != SD_OK) return fail("sd_host_create failed");
+    std::string err;
+    const bool sameDb = a.pos[0] == a.pos[1];
+    std::shared_ptr<SeqDb> tdb = loadTargetDb(a.pos[1], host.h, &err);
+    std::unique_ptr<SeqDb> qdbOwn;
+    if (!tdb) return fail(err);
+    if (tdb->profile) return fail("profile target databases are not supported on this path");
+    SeqDb *qdb = tdb.get();
+    if (!sameDb) {
+        qdbOwn.reset(new SeqDb());
+        if (!qdbOwn->load(a.pos[0], host.h, &err)) return fail(err);
+        qdb = qdbOwn.get();
+    }
+    if (qdb->profile) return fail("profile query databases are not implemented in the ungapped prefilter");
+    lap.mark("load DBs");
+    info(a, "Query database size: %u type: Aminoacid\nTarget database size: %u type: Aminoacid\n", qdb->n, tdb->n);
+
+    sd_ungapped_params par;
+    memset(&par, 0, sizeof(par));
+    sd_host_matrix(host.h, 0, par.matrix, nullptr, nullptr);
+    par.minScore = (int32_t) a.integer("--min-ungapped-score", 15);
+    par.maxHitsPerQuery = (int32_t) std::max<long long>(1, std::min<long long>(a.integer("--max-seqs", 300), tdb->n));
+    par.covMode = (int32_t) a.integer("--cov-mode", 0);
+    par.covThr = (float) a.real("-c", 0.0);
+
+    CtxH ctx;
+    int rc = ctx.open(deviceOf(a));
+    if (rc != SD_OK) return fail("no usable HIP device (sd_ctx_create returned " + std::to_string(rc) + "); this path has no CPU fallback");
+    SeqSetH ts;
+    rc = sd_seqset_create(ctx.c, tdb->residues.data(), tdb->offsets.data(), tdb->n, nullptr, &ts.s);
+    if (rc != SD_OK) return failCtx(ctx.c, rc, "sd_seqset_create (targets)");
+    lap.mark("targets resident");
+
+    sddb::Writer out;
+    if (!out.open(a.pos[2], sddb::DBTYPE_PREFILTER_RES, &err)) return fail(err);
+    const uint32_t chunk = (uint32_t) std::max<long long>(1, a.integer("--chunk-queries", 16384));
+    std::vector<sd_hit> hits;
+    std::vector<uint32_t> counts, ident;
+    std::vector<int8_t> swBias;
+    std::vector<uint64_t> off;
+    std::string text;
+    uint64_t totalHits = 0, cells = 0;
+    for (uint32_t c0 = 0; c0 < qdb->n; c0 += chunk) {
+        const uint32_t c1 = std::min(qdb->n, c0 + chunk), nq = c1 - c0;
+        const uint64_t r0 = qdb->offsets[c0], r1 = qdb->offsets[c1];
+        off.resize((size_t) nq + 1);
+        for (uint32_t i = 0; i <= nq; i++) off[i] = qdb->offsets[c0 + i] - r0;
+        // the identity pair exists for equal DB paths only: --add-self-matches is not a parameter of this module
+        ident.assign(nq, UINT32_MAX);
+        if (sameDb)
+            for (uint32_t i = 0; i < nq; i++) ident[i] = c0 + i;
+        if (compBias) {
+            swBias.assign(r1 - r0 + 1, 0);
+            sd_host_sw_comp_bias(host.h, 0, qdb->residues.data() + r0, off.data(), nq, swBias.data());
+        }
+        SeqSetH qs;
+        rc = sd_seqset_create(ctx.c, qdb->residues.data() + r0, off.data(), nq, compBias ? swBias.data() : nullptr, &qs.s);
+        if (rc != SD_OK) return failCtx(ctx.c, rc, "sd_seqset_create (queries)");
+        hits.resize((size_t) nq * par.maxHitsPerQuery);
+        counts.assign(nq, 0);
+        rc = sd_ungapped_prefilter_batch(ctx.c, &par, qs.s, ts.s, tdb->keys.data(), ident.data(), hits.data(), counts.data());
+        if (rc != SD_OK) return failCtx(ctx.c, rc, "sd_ungapped_prefilter_batch");
+        uint64_t c = 0;
+        sd_ungapped_last_cells(ctx.c, &c);
+        cells += c;
+        lap.mark("chunk: bias + device");
+        // QueryMatcher::prefilterHitToBuffer with diagonal 0 (ungappedprefilter.cpp:447-451)
+        char line[64];
+        for (uint32_t i = 0; i < nq; i++) {
+            text.clear();
+            const sd_hit *row = hits.data() + (size_t) i * par.maxHitsPerQuery;
+            for (uint32_t x = 0; x < counts[i]; x++) {
+                const int len = snprintf(line, sizeof(line), "%u\t%d\t0\n", tdb->keys[row[x].seqId], row[x].score);
+                text.append(line, (size_t) len);
+            }
+            totalHits += counts[i];
+            if (!out.write(qdb->keys[c0 + i], text.data(), text.size())) return fail("cannot write " + a.pos[2]);
+        }
+    }
+    if (!out.close(&err)) return fail(err);
+    lap.mark("chunks: text + write");
+    info(a, "%llu ungapped prefilter hits written for %u queries (%llu cells)\n", (unsigned long long) totalHits, qdb->n,
+         (unsigned long long) cells);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 namespace {
 
 int alignPairs(sd_ctx *ctx, const sd_sw_params &par, sd_seqset *qs, sd_seqset *ts, const SeqDb &qdb, const SeqDb &tdb,

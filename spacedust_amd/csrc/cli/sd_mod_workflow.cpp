@@ -103,6 +103,15 @@ int checkWorkflowFlags(const Args &a) {
     return 0;
 }
 
+// --prefilter-mode (M/src/workflow/Search.cpp:337-350): 0 the k-mer prefilter, 1 the exhaustive ungapped scan; what is not
+// implemented is refused by value
+int checkPrefilterMode(const Args &a) {
+    if (int rc = ungappedPrefilterModeCheck(a)) return rc;
+    if (a.integer("--prefilter-mode", 0) == 1 && a.integer("--num-iterations", 1) > 1)
+        return fail("--prefilter-mode 1 with --num-iterations > 1 is not implemented (profile queries in the ungapped prefilter)");
+    return 0;
+}
+
 // DB writers fed by the pipeline's sinks
 struct Sinks {
     const SeqDb *qdb = nullptr, *tdb = nullptr;
@@ -205,6 +214,8 @@ int runSearch(const Args &a, bool withClusters) {
         return fail(withClusters ? "usage: clustersearch <querySetDB> <targetSetDB> <out.tsv> <tmpDir> [options]"
                                  : "usage: search <queryDB> <targetDB> <alignmentDB> <tmpDir> [options]");
     if (int rc = checkWorkflowFlags(a)) return rc;
+    if (int rc = checkPrefilterMode(a)) return rc;
+    const bool ungapped = a.integer("--prefilter-mode", 0) == 1;
     if (a.integer("--num-iterations", 1) > 1) return fail("--num-iterations > 1: run the iterations with the modules (prefilter, align, result2profile)");
     const int rank = (int) a.integer("--rank", envInt("RANK", 0)), world = (int) a.integer("--world-size", envInt("WORLD_SIZE", 1));
     const int device = a.has("--device") ? (int) a.integer("--device", 0) : envInt("LOCAL_RANK", 0);
@@ -235,6 +246,7 @@ int runSearch(const Args &a, bool withClusters) {
         tsP = sameDb ? &qs : &tsOwn;
     }
     par.profileQueries = qdb->profile ? 1 : 0;
+    if (ungapped && qdb->profile) return fail("profile query databases are not implemented in the ungapped prefilter (--prefilter-mode 1)");
     SetDbArrays tv, qv;
     tv.fill(*tdb, tsP);
     qv.fill(*qdb, qsP);
@@ -242,7 +254,10 @@ int runSearch(const Args &a, bool withClusters) {
 
     SearchH S;
     int rc;
-    {
+    if (ungapped) {
+        // --prefilter-mode 1: the scan as the prefilter stage; no k-mer index is read, built or held
+        rc = sd_search_create_ungapped(device, &par, &tv.view, &S.s);
+    } else {
         // TARGET.idx (createindex layout) instead of a rebuild when its parameters match this run
         const int k = par.kmerSize ? par.kmerSize : sd_host_auto_kmer_size(tdb->totalResidues());
         const int thr = par.profileQueries ? 0 : sd_host_kmer_threshold(par.sensitivity, k);
@@ -273,7 +288,8 @@ int runSearch(const Args &a, bool withClusters) {
     uint64_t st[16];
     double tm[16];
     sd_search_stats(S.s, st, tm);
-    info(a, "Index table: k-mer size %llu, k-mer threshold %llu, %llu entries, %llu masked residues (%.2f s host, %.2f s upload)\n",
+    if (ungapped) info(a, "Prefilter mode 1: exhaustive ungapped scan, no index table\n");
+    else info(a, "Index table: k-mer size %llu, k-mer threshold %llu, %llu entries, %llu masked residues (%.2f s host, %.2f s upload)\n",
          (unsigned long long) st[11], (unsigned long long) st[12], (unsigned long long) st[9], (unsigned long long) st[10], tm[0], tm[1]);
 
     // query ranges of this rank: whole query sets (contiguous id ranges), dealt greedily by residue count; a plain search
@@ -925,6 +941,7 @@ int iterativeSearch(const Args &a, const std::string &Q, const std::string &T, c
 }  // namespace
 
 int searchModule(const Args &a) {
+    if (int rc = checkPrefilterMode(a)) return rc;
     if (a.integer("--num-iterations", 1) > 1) {
         if (a.pos.size() != 4) return fail("usage: search <queryDB> <targetDB> <alignmentDB> <tmpDir> [options]");
         if (int rc = checkWorkflowFlags(a)) return rc;
@@ -934,6 +951,7 @@ int searchModule(const Args &a) {
 }
 
 int clustersearchModule(const Args &a) {
+    if (int rc = checkPrefilterMode(a)) return rc;
     if (a.integer("--num-iterations", 1) <= 1) return runSearch(a, true);
     // iterative profile search (BASELINE config 4): the iterations through the modules, then the module chain of
     // R/data/clustersearch.sh:121-151 on the merged alignment DB

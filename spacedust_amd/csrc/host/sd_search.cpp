@@ -162,6 +162,8 @@ struct sd_search {
     sd_seqset *tSeqs = nullptr;
     int k = 6, kmerThr = 0;
     sd_prefilter_params pfPar;
+    bool ungapped = false;          // sd_search_create_ungapped: the prefilter stage is the exhaustive ungapped scan, no k-mer index
+    sd_ungapped_params ugPar;
     sd_sw_params swPar;
     sd_sw_params swParRun;   // swPar with the E-value gate of the running stream (sd_search_stream: predicate pushdown)
     bool targetHasGroups = false;   // sd_seqset_set_groups was applied to tSeqs
@@ -247,13 +249,25 @@ int sd_search_create(int device, const sd_search_params *par, const sd_setdb *ta
     return sd_search_create_indexed(device, par, target, nullptr, out);
 }
 
+static int searchCreate(int device, const sd_search_params *par, const sd_setdb *target, const sd_index_view *view, bool ungapped, sd_search **out);
+
 int sd_search_create_indexed(int device, const sd_search_params *par, const sd_setdb *target, const sd_index_view *view, sd_search **out) {
+    return searchCreate(device, par, target, view, false, out);
+}
+
+int sd_search_create_ungapped(int device, const sd_search_params *par, const sd_setdb *target, sd_search **out) {
+    if (par && par->profileQueries) return SD_EUNSUPPORTED;   // profile queries in this mode are not implemented
+    return searchCreate(device, par, target, nullptr, true, out);
+}
+
+static int searchCreate(int device, const sd_search_params *par, const sd_setdb *target, const sd_index_view *view, bool ungapped, sd_search **out) {
     if (!par || !target || !out || !target->residues || !target->offsets) return SD_EINVAL;
     if (view && (!view->kmerOffsets || !view->entrySeq || !view->entryPos || !view->maskedResidues)) return SD_EINVAL;
     std::unique_ptr<sd_search> s(new sd_search());
     s->par = *par;
     s->T = *target;
     s->device = device;
+    s->ungapped = ungapped;
     memset(s->stats, 0, sizeof(s->stats));
     memset(s->seconds, 0, sizeof(s->seconds));
     const int cpus = hostCpus();
@@ -295,14 +309,14 @@ int sd_search_create_indexed(int device, const sd_search_params *par, const sd_s
     // chunk of 10 000 queries; the host stage the same chunk 0.4 core-seconds of an OpenMP team (bit-identical by construction,
     // tests/test_gpu_pipeline.py::test_device_composition_bias_equals_host)
     const bool devBias = par->deviceBias != 0;
-    if (devBias && par->compBiasCorr && !par->profileQueries) {
+    if (devBias && par->compBiasCorr && !par->profileQueries && !ungapped) {   // (the scan needs the Smith-Waterman bias alone: host stage)
         rc = sd_ctx_create(device, &s->ctxBias);
         if (rc != SD_OK) return rc;
     }
     const uint64_t tRes = target->offsets[target->n];
-    s->k = par->kmerSize ? par->kmerSize : sd_host_auto_kmer_size(tRes);
-    if (s->k != 6 && s->k != 7) return SD_EUNSUPPORTED;
-    s->kmerThr = par->profileQueries ? sd_host_profile_kmer_threshold(par->sensitivity, s->k) : sd_host_kmer_threshold(par->sensitivity, s->k);
+    s->k = ungapped ? 0 : (par->kmerSize ? par->kmerSize : sd_host_auto_kmer_size(tRes));   // (ungapped: no k-mers anywhere; the stats report 0)
+    if (!ungapped && s->k != 6 && s->k != 7) return SD_EUNSUPPORTED;
+    s->kmerThr = ungapped ? 0 : par->profileQueries ? sd_host_profile_kmer_threshold(par->sensitivity, s->k) : sd_host_kmer_threshold(par->sensitivity, s->k);
     const int indexThr = par->profileQueries ? 0 : s->kmerThr;   // profile searches index every k-mer (Prefiltering.cpp:525-527)
     if (view && (view->kmerSize != s->k || view->kmerThr != indexThr)) return SD_EINVAL;
     double t0 = nowSec();
@@ -311,7 +325,9 @@ int sd_search_create_indexed(int device, const sd_search_params *par, const sd_s
     const uint16_t *ePos = nullptr;
     const uint8_t *mres = nullptr;
     const uint64_t *kBase = nullptr;   // block bases of a wide index (>= 2^32 entries)
-    if (view) {
+    if (ungapped) {
+        // no index: the scan reads the target sequences themselves (tSeqs below)
+    } else if (view) {
         kBase = view->kmerBlockBase;
         kOff = view->kmerOffsets;
         eSeq = view->entrySeq;
@@ -351,7 +367,7 @@ int sd_search_create_indexed(int device, const sd_search_params *par, const sd_s
     s->stats[S_K] = (uint64_t) s->k;
     s->stats[S_KMER_THR] = (uint64_t) s->kmerThr;
     t0 = nowSec();
-    if (!s->target) {
+    if (!s->target && !ungapped) {
         const int16_t *s2, *s3;
         const uint16_t *i2, *i3;
         uint32_t z2, z3;
@@ -394,6 +410,12 @@ int sd_search_create_indexed(int device, const sd_search_params *par, const sd_s
     s->pfPar.covThr = (par->covMode == 0 || par->covMode == 2 || par->covMode == 5) ? par->covThr : 0.0f;
     sd_host_matrix(s->host, 2, s->pfPar.ungappedMatrix, nullptr, nullptr);
     s->stats[S_BIN] = s->pfPar.binSize;
+    memset(&s->ugPar, 0, sizeof(s->ugPar));
+    sd_host_matrix(s->host, 0, s->ugPar.matrix, nullptr, nullptr);   // the Smith-Waterman matrix (ungappedprefilter.cpp:536)
+    s->ugPar.minScore = par->minDiagScore;
+    s->ugPar.maxHitsPerQuery = s->pfPar.maxHitsPerQuery;
+    s->ugPar.covMode = par->covMode;
+    s->ugPar.covThr = par->covThr;   // Util::canBeCovered in every coverage mode (ungappedprefilter.cpp:403)
     memset(&s->swPar, 0, sizeof(s->swPar));
     s->swPar.gapOpen = 11;
     s->swPar.gapExtend = 1;
@@ -618,6 +640,12 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
         }
         const double t0 = nowSec();
         o->sw.assign(r1 - r0 + 1, 0);
+        if (s->ungapped) {   // ssw_init's bias is all the scan reads: no diagonal or k-mer bias
+            if (s->par.compBiasCorr) o->rc = sd_host_sw_comp_bias(s->host, 0, Q->residues + r0, o->off.data(), nq, o->sw.data());
+            o->seconds = nowSec() - t0;
+            o->cpu = threadCpuSec() - cpu0;
+            return o;
+        }
         o->dg.assign(r1 - r0 + 1, 0);
         o->km.assign(r1 - r0 + 1, 0);
         if (s->par.compBiasCorr) {
@@ -650,7 +678,15 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
         o->counts.assign(nq, 0);
         o->stats.assign((size_t) nq * 4, 0);
         double t0 = nowSec();
-        if (profile)
+        if (s->ungapped) {
+            // the scan takes the chunk as a sequence set with its Smith-Waterman composition bias (ssw_init's query side)
+            sd_seqset *qs = nullptr;
+            o->rc = sd_seqset_create(pfCtx, Q->residues + r0, b.off.data(), nq, s->par.compBiasCorr ? b.sw.data() : nullptr, &qs);
+            if (o->rc == SD_OK) {
+                o->rc = sd_ungapped_prefilter_batch(pfCtx, &s->ugPar, qs, s->tSeqs, s->T.keys, ident.data(), o->hits.data(), o->counts.data());
+                sd_seqset_destroy(qs);
+            }
+        } else if (profile)
             o->rc = sd_prefilter_profile_batch(pfCtx, s->target, &s->pfPar, nq, Q->residues + r0, b.off.data(), Q->sortedScore + r0 * 20,
                                                Q->sortedIndex + r0 * 20, Q->alnProfile + r0 * 21, ident.data(), o->hits.data(),
                                                o->counts.data(), o->stats.data());
@@ -659,7 +695,7 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
                                        ident.data(), o->hits.data(), o->counts.data(), o->stats.data());
         o->tPrefilter = nowSec() - t0;
         if (o->rc != SD_OK) {
-            o->err = std::string("sd_prefilter_batch: ") + sd_last_error(pfCtx);
+            o->err = std::string(s->ungapped ? "sd_ungapped_prefilter_batch: " : "sd_prefilter_batch: ") + sd_last_error(pfCtx);
             return o;
         }
         for (uint32_t i = 0; i < nq; i++)
@@ -682,7 +718,9 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
                 const sd_hit *row = o->hits.data() + (size_t) q * W;
                 // 0x8000 = no hint: only a pair whose ungapped prefilter score is already near the byte range can have a
                 // diagonal that saturates the byte kernel, the others need not be walked
-                for (uint32_t x = 0; x < o->counts[q]; x++) o->pairDiag[w++] = row[x].score >= 200 ? row[x].diagonal : (uint16_t) 0x8000;
+                // (the ungapped scan reports no diagonal: its hits carry 0)
+                for (uint32_t x = 0; x < o->counts[q]; x++)
+                    o->pairDiag[w++] = (row[x].score >= 200 && !s->ungapped) ? row[x].diagonal : (uint16_t) 0x8000;
             }
         }
         o->tPairs = nowSec() - t0;

@@ -118,11 +118,17 @@ class ClusterSearch:
     def __init__(self, ctx, host, target_db, sensitivity=5.7, max_seqs=300, eval_thr=10.0, cov_mode=2, cov_thr=0.8,
                  aln_len_thr=30, max_gene_gap=3, cluster_size=2, alpha=1.0, p_clu_thr=0.01, p_mh_thr=0.01,
                  filter_self_match=False, bin_size=None, verbose=False, align_ctx=None, k=None, profile_queries=False,
-                 device_bias=None, chunk_queries=0, index=None):
+                 device_bias=None, chunk_queries=0, index=None, prefilter_mode=0, min_ungapped_score=15):
         """ctx / host: the caller's context and host handle (used for the device index and for helper calls such as
         Host.map_profiles); the pipeline object creates its own two contexts on that device -- prefilter and alignments
         run on separate HIP streams so that the prefilter of the next chunk (HBM random-access bound) and the
-        Smith-Waterman of the current one (integer-VALU bound) share the GPU instead of taking turns."""
+        Smith-Waterman of the current one (integer-VALU bound) share the GPU instead of taking turns.
+        prefilter_mode=1 (`--prefilter-mode 1`, sd_search_create_ungapped): the exhaustive ungapped scan is the prefilter stage
+        and no k-mer index is built or held; sensitivity, k, bin_size and index are then not used."""
+        if prefilter_mode not in (0, 1):
+            raise _lib.SdError('prefilter_mode %r: 0 (k-mer) and 1 (ungapped) are implemented' % (prefilter_mode,))
+        if prefilter_mode == 1 and (profile_queries or index is not None):
+            raise _lib.SdError('prefilter_mode 1 takes sequence queries and no k-mer index')
         self.L = _lib.load()
         self.host, self.T = host, target_db
         self.verbose = verbose
@@ -136,13 +142,17 @@ class ClusterSearch:
         p.profileQueries = 1 if profile_queries else 0
         p.chunkQueries = chunk_queries
         p.deviceBias = -1 if device_bias is None else (1 if device_bias else 0)
+        p.minDiagScore = min_ungapped_score
         p.threads = host.threads
         p.alignPriority = int(os.environ.get('SD_ALIGN_PRIO', '1'))
         self.par = p
         self._keep = []
         tv = _setdb_struct(target_db, self._keep)
         h = C.c_void_p()
-        if index is not None:
+        self.prefilter_mode = prefilter_mode
+        if prefilter_mode == 1:
+            rc = self.L.sd_search_create_ungapped(ctx.device_index, C.byref(p), C.byref(tv), C.byref(h))
+        elif index is not None:
             # a target index that exists already (api.HostIndex / api.IndexArrays: built once and shared, or read from a file)
             iv = _lib.IndexView()
             iv.kmerSize, iv.kmerThr = index.k, index.kmer_thr
