@@ -394,7 +394,9 @@ class Context:
 
     def __del__(self):
         try:
-            self.L.sd_ctx_destroy(self.h)
+            h, self.h = self.h, None   # (sets and targets that the collector finalises after their context see it gone)
+            if h:
+                self.L.sd_ctx_destroy(h)
         except Exception:
             pass
 
@@ -418,8 +420,11 @@ class SeqSet:
         self.h = h
 
     def __del__(self):
+        # a set is destroyed before its context (include/spacedust_gpu.h): its buffers go back to the context's pool.  The
+        # cycle collector may finalise the context first (both held by the traceback of a failed test): nothing to return to then
         try:
-            self.ctx.L.sd_seqset_destroy(self.h)
+            if self.ctx.h:
+                self.ctx.L.sd_seqset_destroy(self.h)
         except Exception:
             pass
 
@@ -520,7 +525,8 @@ class Target:
 
     def __del__(self):
         try:
-            self.ctx.L.sd_target_destroy(self.h)
+            if self.ctx.h:   # (as SeqSet.__del__)
+                self.ctx.L.sd_target_destroy(self.h)
         except Exception:
             pass
 

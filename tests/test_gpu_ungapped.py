@@ -118,8 +118,11 @@ def test_capi_lists_follow_the_list_rule(env, synth):
     for min_score in (0, 15, 254):
         for idn in (ident, none, None):
             cases.append(dict(min_score=min_score, max_seqs=ps.n, cov_mode=0, cov_thr=0.0, ident=idn))
-    for cov_mode in (0, 1, 2):
+    for cov_mode in (0, 1, 2, 3, 4, 5):
         cases.append(dict(min_score=15, max_seqs=ps.n, cov_mode=cov_mode, cov_thr=0.8, ident=ident))
+        # the mode both keeps and drops pairs that score above the threshold
+        kept = np.array([ur.covered_mask(0.8, cov_mode, lens[q], lens) for q in range(ps.n)])
+        assert (kept & (full > 15)).sum() > ps.n and (~kept & (full > 15)).sum() > ps.n, cov_mode
     for max_seqs in (1, 7, 40):
         cases.append(dict(min_score=15, max_seqs=max_seqs, cov_mode=0, cov_thr=0.0, ident=ident))
     ties_at_cut = 0

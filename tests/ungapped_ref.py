@@ -66,6 +66,11 @@ def restate_matrix(M, q_res, q_off, q_cb, t_res, t_off):
 def can_be_covered(cov_thr, cov_mode, q_len, t_len):
     """Util::canBeCovered (M/src/commons/Util.cpp:477-494), float arithmetic"""
     c, q, t = np.float32(cov_thr), np.float32(q_len), np.float32(t_len)
+    with np.errstate(divide='ignore', invalid='ignore'):   # (a zero length: inf or nan, as in the reference)
+        return _can_be_covered(c, cov_mode, q, t)
+
+
+def _can_be_covered(c, cov_mode, q, t):
     if cov_mode == 0:
         return bool(q / t >= c and t / q >= c)
     if cov_mode == 1:
@@ -92,6 +97,52 @@ def list_rule(scores, t_keys, q_len, t_lens, min_score=15, max_seqs=300, cov_mod
             hits.append((int(k), int(s)))
     hits.sort(key=lambda h: (-h[1], h[0]))
     return hits[:max_seqs]
+
+
+def expand_pooled(small, pool_id):
+    """scores against targets drawn from a pool: with target t = pool[pool_id[t]], the scores of queries x targets are the
+    columns pool_id of `small` = restate_matrix(queries x pool) ([nQ, nPool] -> [nQ, nT]; one row [nPool] -> [nT])"""
+    return np.asarray(small)[..., np.asarray(pool_id, np.int64)]
+
+
+def covered_mask(cov_thr, cov_mode, q_len, t_lens):
+    """can_be_covered for one query against every target at once, in float32 as the reference computes it (a zero length
+    divides to inf or nan; a comparison with nan is false)"""
+    c, q = np.float32(cov_thr), np.float32(q_len)
+    t = np.asarray(t_lens).astype(np.float32)
+    one = np.float32(1.0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if cov_mode == 0:
+            return (q / t >= c) & (t / q >= c)
+        if cov_mode == 1:
+            return q / t >= c
+        if cov_mode == 2:
+            return t / q >= c
+        if cov_mode == 3:
+            return (t / q >= c) & (t / q <= one)
+        if cov_mode == 4:
+            return (q / t >= c) & (q / t <= one)
+        if cov_mode == 5:
+            return np.minimum(t, q) / np.maximum(t, q) >= c
+    return np.ones(len(t), bool)
+
+
+def list_rule_fast(scores_row, keys, q_len, t_lens, min_score=15, max_seqs=300, cov_mode=0, cov_thr=0.0, identity_key=None):
+    """list_rule for rows of 10^6 targets: the same hits in the same order, as (keys uint32 [n], scores int32 [n]).  The order
+    (score descending, key ascending) is the ascending order of the composite (255 - score) << 32 | key; np.partition finds
+    the max_seqs smallest, a sort orders that head only.  The keys are unique wherever an identity key is given."""
+    s = np.asarray(scores_row).astype(np.int64)
+    k = np.asarray(keys).astype(np.uint64)
+    assert len(s) == len(k) == len(t_lens) and (len(s) == 0 or (0 <= s.min() and s.max() <= 255 and k.max() < (1 << 32)))
+    keep = s > min_score
+    if identity_key is not None:
+        keep |= k == np.uint64(identity_key)
+    keep &= covered_mask(cov_thr, cov_mode, q_len, t_lens)
+    comp = ((255 - s[keep]).astype(np.uint64) << np.uint64(32)) | k[keep]
+    if len(comp) > max_seqs:
+        comp = np.partition(comp, max_seqs - 1)[:max_seqs]
+    comp.sort()
+    return (comp & np.uint64(0xFFFFFFFF)).astype(np.uint32), (255 - (comp >> np.uint64(32)).astype(np.int64)).astype(np.int32)
 
 
 def list_text(hits):
