@@ -293,6 +293,35 @@ int sd_ungapped_score_matrix(sd_ctx *ctx, const int8_t *matrix, const sd_seqset 
 /* cells (sum of query lengths x sum of target lengths) the last sd_ungapped_* call of the context evaluated */
 int sd_ungapped_last_cells(sd_ctx *ctx, uint64_t *cells);
 
+/* ---- rescoring on the diagonal (`rescorediagonal`, `search --alignment-mode 4`) ------------------------------------------
+ * Replaces DistanceCalculator::computeUngappedAlignment (M/src/alignment/DistanceCalculator.h:94-201,276-295) as
+ * doRescorediagonal calls it per prefilter hit (M/src/alignment/rescorediagonal.cpp:235-237), and the identity count of
+ * rescorediagonal.cpp:284-291.  The diagonal of a hit went through an unsigned short, so every hit has the candidates
+ * d16 - 65536 k (k = 1 .. 1 + tLen / 32768) and then d16 + 65536 k (k = 0 .. qLen / 65536); a later candidate replaces the
+ * running one only with a strictly greater score; a hit whose candidates all score 0 keeps the default record.
+ * mode (Parameters::RESCORE_MODE_*): 0 number of equal bytes on the diagonal (case-sensitive), 1 best ungapped local score,
+ * 2 that score with its first and last position.  The letters are compared as letters (B is not D although both score as D),
+ * so both sets must carry the DB's bytes: sd_seqset_set_letters(set, letters) -- `letters` laid out like the residues the set
+ * was created from -- makes them resident beside the residues.  Profile sets: SD_EUNSUPPORTED. */
+typedef struct {
+    int8_t matrix[21 * 21];  /* blosum62 at 2 bit-factor, scoreBias 0 (rescorediagonal.cpp:88): sd_host_matrix(h, 0, ...) */
+    int32_t mode;            /* --rescore-mode 0 / 1 / 2 */
+    uint8_t aa2num[256];     /* letter -> matrix code (sd_host_matrix's aa2num256; SubstitutionMatrix::createAsciiSubMat) */
+} sd_rescore_params;
+typedef struct {
+    int32_t score;           /* LocalAlignment::score */
+    int32_t startPos, endPos;/* along the diagonal; -1 in modes 0 and 1 and in the default record */
+    int32_t diagonalLen;     /* overlap of the two sequences on the chosen diagonal */
+    int32_t distToDiagonal;  /* |diagonal| */
+    int32_t diagonal;        /* signed, as chosen among the candidates; 0 in the default record */
+    int32_t idCnt;           /* mode 2: letters of [startPos, endPos] equal without their case bit; mode 0: score; mode 1: 0 */
+    int32_t pad;
+} sd_rescore_result;
+int sd_seqset_set_letters(sd_seqset *s, const char *letters);
+int sd_rescore_diagonal_batch(sd_ctx *ctx, const sd_rescore_params *par, const sd_seqset *queries, const sd_seqset *targets,
+                              uint32_t nHits, const uint32_t *hitQuery, const uint32_t *hitTarget, const uint16_t *hitDiagonal,
+                              sd_rescore_result *out);
+
 /* ---- Profile queries (`--num-iterations` > 1 feeds profile DBs to prefilter and align) ----
  * sd_host_map_profiles restates Sequence::mapProfile (M/src/commons/Sequence.cpp:241-292) for n profile DB entries
  * (25 bytes per position, Sequence.h:458-471; byteOffsets[n+1] into profileData): per position the query letter,

@@ -46,6 +46,14 @@ class UngappedParams(C.Structure):   # sd_ungapped_params
                 ('covThr', C.c_float)]
 
 
+class RescoreParams(C.Structure):   # sd_rescore_params
+    _fields_ = [('matrix', C.c_int8 * 441), ('mode', C.c_int32), ('aa2num', C.c_uint8 * 256)]
+
+
+RESCORE_DTYPE = np.dtype([('score', '<i4'), ('startPos', '<i4'), ('endPos', '<i4'), ('diagonalLen', '<i4'), ('distToDiagonal', '<i4'),
+                          ('diagonal', '<i4'), ('idCnt', '<i4'), ('pad', '<i4')])   # sd_rescore_result
+
+
 HIT_DTYPE = np.dtype([('seqId', '<u4'), ('score', '<i4'), ('diagonal', '<u2'), ('pad', '<u2')])
 
 
@@ -164,6 +172,8 @@ def load():
         'sd_ungapped_prefilter_batch': (C.c_int, [_vp, C.POINTER(UngappedParams), _vp, _vp, _vp, _vp, _vp, _vp]),
         'sd_ungapped_score_matrix': (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
         'sd_ungapped_last_cells': (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+        'sd_seqset_set_letters': (C.c_int, [_vp, _vp]),
+        'sd_rescore_diagonal_batch': (C.c_int, [_vp, C.POINTER(RescoreParams), _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
         'sd_search_create_ungapped': (C.c_int, [C.c_int, C.POINTER(SearchParams), C.POINTER(SetDbView), C.POINTER(_vp)]),
         'sd_comp_bias_batch': (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp]),
         'sd_prefilter_profile_batch': (C.c_int, [_vp, _vp, C.POINTER(PrefilterParams), C.c_uint32, _vp, _vp, _vp, _vp, _vp,

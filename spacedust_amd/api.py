@@ -376,6 +376,37 @@ class Context:
                 return cidx[:n_out.value], res[:n_out.value], pool[:used.value]
             return res, pool[:used.value]
 
+    def letterset(self, host, seqs):
+        """a SeqSet of ASCII sequences (str or bytes) that also carries their letters (sd_seqset_set_letters): what
+        rescore_diagonal takes"""
+        blobs = [x.encode() if isinstance(x, str) else bytes(x) for x in seqs]
+        off = np.zeros(len(blobs) + 1, np.uint64)
+        np.cumsum(np.fromiter((len(b) for b in blobs), np.uint64, len(blobs)), out=off[1:])
+        blob = b''.join(blobs)
+        res = np.zeros(len(blob), np.uint8)
+        host.L.sd_host_map_sequence(host.h, blob, len(blob), ptr(res))
+        s = SeqSet(self, res, off, None)
+        s.set_letters(blob)
+        return s
+
+    def rescore_diagonal(self, host, queries, targets, hit_q, hit_t, hit_diag, mode=2):
+        """sd_rescore_diagonal_batch: DistanceCalculator::computeUngappedAlignment for every (query, target, 16-bit diagonal) hit.
+        queries / targets: SeqSets with letters (letterset / SeqSet.set_letters); hit_diag: the prefilter row's diagonal (negative
+        values are taken through an unsigned short, as the reference does).  Returns a RESCORE_DTYPE record per hit."""
+        m, _, a2n = host.matrix(0)
+        par = _lib.RescoreParams()
+        par.mode = int(mode)
+        C.memmove(par.matrix, m.ctypes.data, 441)
+        C.memmove(par.aa2num, a2n.ctypes.data, 256)
+        hq = np.ascontiguousarray(hit_q, np.uint32)
+        ht = np.ascontiguousarray(hit_t, np.uint32)
+        hd = np.ascontiguousarray(np.asarray(hit_diag, np.int64) & 0xFFFF, np.uint16)
+        assert len(hq) == len(ht) == len(hd)
+        out = np.zeros(len(hq), _lib.RESCORE_DTYPE)
+        _check(self.h, self.L.sd_rescore_diagonal_batch(self.h, C.byref(par), queries.h, targets.h, len(hq), ptr(hq), ptr(ht), ptr(hd),
+                                                        ptr(out)), 'sd_rescore_diagonal_batch')
+        return out
+
     def set_cigar_pool(self, on=True):
         """sd_sw_set_cigar_pool: the alignment calls return run-length text (Matcher::compressAlignment's output) in the pool;
         a record's text is pool[btOffset : btOffset + (flags >> 8)]"""
@@ -418,6 +449,12 @@ class SeqSet:
             _check(ctx.h, ctx.L.sd_seqset_create(ctx.h, ptr(self.residues), ptr(self.offsets), self.n, ptr(b), C.byref(h)),
                    'sd_seqset_create')
         self.h = h
+
+    def set_letters(self, letters):
+        """sd_seqset_set_letters: the DB's bytes of the same sequences, laid out like the residues"""
+        b = np.frombuffer(bytes(letters), np.uint8) if not isinstance(letters, np.ndarray) else np.ascontiguousarray(letters, np.uint8)
+        assert len(b) == len(self.residues)
+        _check(self.ctx.h, self.ctx.L.sd_seqset_set_letters(self.h, ptr(b) if len(b) else ptr(np.zeros(1, np.uint8))), 'sd_seqset_set_letters')
 
     def __del__(self):
         # a set is destroyed before its context (include/spacedust_gpu.h): its buffers go back to the context's pool.  The

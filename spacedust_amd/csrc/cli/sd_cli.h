@@ -112,6 +112,7 @@ int prefilterModule(const Args &a);
 int ungappedprefilterModule(const Args &a);
 int ungappedPrefilterModeCheck(const Args &a);   // refuses the --prefilter-mode values that are not implemented (2, 3)
 int alignModule(const Args &a);
+int rescorediagonalModule(const Args &a);
 int clusterhitsModule(const Args &a);
 int prefixidModule(const Args &a);
 int besthitbysetModule(const Args &a);

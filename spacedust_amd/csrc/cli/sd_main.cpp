@@ -22,6 +22,7 @@ const Module kModules[] = {
     {"prefilter", prefilterModule, "k-mer prefilter on the GPU: <queryDB> <targetDB> <prefilterDB>"},
     {"ungappedprefilter", ungappedprefilterModule, "exhaustive ungapped prefilter on the GPU (--prefilter-mode 1): <queryDB> <targetDB> <prefilterDB>"},
     {"align", alignModule, "Smith-Waterman alignments on the GPU: <queryDB> <targetDB> <prefilterDB> <alignmentDB>"},
+    {"rescorediagonal", rescorediagonalModule, "ungapped alignment on each hit's diagonal on the GPU (--alignment-mode 4): <queryDB> <targetDB> <prefilterDB> <resultDB>"},
     {"clusterhits", clusterhitsModule, "agglomerative hit clustering on the GPU: <querySetDB> <targetSetDB> <matchesDB> <clustersDB>"},
     {"search", searchModule, "prefilter + align (and the --num-iterations profile loop): <queryDB> <targetDB> <alignmentDB> <tmpDir>"},
     {"clustersearch", clustersearchModule, "the whole --search-mode 0 workflow in one process: <querySetDB> <targetSetDB> <out.tsv> <tmpDir>"},

@@ -938,10 +938,80 @@ int iterativeSearch(const Args &a, const std::string &Q, const std::string &T, c
     return 0;
 }
 
+// the module chain of R/data/clustersearch.sh:121-151 on the alignment DB <tmp>/result
+int clusterChain(const Args &a, const std::string &Q, const std::string &T, const std::string &tmp) {
+    const std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
+    if (int rc = runModule(prefixidModule, "prefixid", {tmp + "/result", tmp + "/result_prefixed"}, common)) return rc;
+    if (int rc = runModule(besthitbysetModule, "besthitbyset", {Q, T, tmp + "/result_prefixed", tmp + "/aggregate"},
+                           with(common, {"--simple-best-hit", "1", "--suboptimal-hits", "0"})))
+        return rc;
+    if (int rc = runModule(mergeresultsbysetModule, "mergeresultsbyset", {Q + "_set_to_member", tmp + "/aggregate", tmp + "/aggregate_merged"}, common))
+        return rc;
+    if (int rc = runModule(combinehitsModule, "combinehits", {Q, T, tmp + "/aggregate_merged", tmp + "/matches", tmp},
+                           with(common, {"--alpha", a.str("--alpha", "1"), "--aggregation-mode", "0", "--filter-self-match",
+                                         a.flag("--filter-self-match", false) ? "1" : "0"})))
+        return rc;
+    std::vector<std::string> ch = with(common, {"--multihit-pval", a.str("--multihit-pval", "0.01"), "--cluster-pval", a.str("--cluster-pval", "0.01"),
+                                                "--max-gene-gap", a.str("--max-gene-gap", "3"), "--cluster-size", a.str("--cluster-size", "2"),
+                                                "--db-output", "1", "--alpha", a.str("--alpha", "1")});
+    if (a.has("--device")) ch = with(ch, {"--device", a.str("--device", "0")});
+    if (int rc = runModule(clusterhitsModule, "clusterhits", {Q, T, tmp + "/matches", tmp + "/clusters"}, ch)) return rc;
+    return runModule(summarizeresultsModule, "summarizeresults", {Q, T, tmp + "/clusters", a.pos[2]}, common);
+}
+
+// `search --alignment-mode 4` (M/src/workflow/Search.cpp:261-319,386-388; M/data/workflow/blastp.sh): the prefilter -- the k-mer one, or
+// the ungapped one under --prefilter-mode 1 -- followed by `rescorediagonal --rescore-mode 2` with the rescorediagonal parameter set
+// (Parameters.cpp:506-523) instead of `align`.  The modules run in this process, the target resident between them.
+int checkUngappedAlign(const Args &a) {
+    if (a.integer("--num-iterations", 1) > 1)
+        return fail("--alignment-mode 4 with --num-iterations > 1: cannot use the ungapped alignment mode with profile databases");
+    if (envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1) return fail("--alignment-mode 4 runs on one rank");
+    return 0;
+}
+
+int ungappedAlignSearch(const Args &a, const std::string &Q, const std::string &T, const std::string &result, const std::string &tmp) {
+    if (int rc = checkUngappedAlign(a)) return rc;
+    mkdir(tmp.c_str(), 0777);
+    const std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
+    const bool ungapped = a.integer("--prefilter-mode", 0) == 1;
+    std::vector<std::string> pref = with(common, {"--max-seqs", a.str("--max-seqs", "300"), "-c", a.str("-c", "0"), "--cov-mode", a.str("--cov-mode", "0"),
+                                                  "--min-ungapped-score", a.str("--min-ungapped-score", "15"), "--comp-bias-corr",
+                                                  a.str("--comp-bias-corr", "1")});
+    if (!ungapped)
+        pref = with(pref, {"-s", a.str("-s", "5.7"), "-k", a.str("-k", "0"), "--mask", a.str("--mask", "1"), "--mask-prob", a.str("--mask-prob", "0.9")});
+    // what each prefilter kind takes beyond that (ungappedprefilter has no index, bins or --add-self-matches)
+    const std::vector<const char *> kmerOnly = {"--device", "--bin-size", "--l2-cache-size", "--chunk-queries", "--add-self-matches"};
+    const std::vector<const char *> ungappedOnly = {"--device", "--chunk-queries"};
+    for (const char *f : ungapped ? ungappedOnly : kmerOnly)
+        if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
+    std::vector<std::string> rescore = with(common, {"--rescore-mode", "2", "-e", a.str("-e", "0.001"), "-c", a.str("-c", "0"), "--cov-mode",
+                                                     a.str("--cov-mode", "0"), "-a", a.str("-a", "0"),
+                                                     "--min-aln-len", a.str("--min-aln-len", "0"), "--seq-id-mode", a.str("--seq-id-mode", "0"),
+                                                     "--sort-results", a.str("--sort-results", "0")});
+    for (const char *f : {"--device", "--add-self-matches", "--filter-hits", "--wrapped-scoring"})
+        if (a.has(f)) rescore = with(rescore, {f, a.str(f, "")});
+    struct ResidentScope {
+        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
+        ~ResidentScope() { resident().clear(); }
+    } residentScope;
+    const std::string prefDb = tmp + "/pref_0";
+    if (ungapped) {
+        if (int rc = runModule(ungappedprefilterModule, "ungappedprefilter", {Q, T, prefDb}, pref)) return rc;
+    } else {
+        if (int rc = runModule(prefilterModule, "prefilter", {Q, T, prefDb}, pref)) return rc;
+    }
+    return runModule(rescorediagonalModule, "rescorediagonal", {Q, T, prefDb, result}, rescore);
+}
+
 }  // namespace
 
 int searchModule(const Args &a) {
     if (int rc = checkPrefilterMode(a)) return rc;
+    if (a.integer("--alignment-mode", 0) == 4) {
+        if (a.pos.size() != 4) return fail("usage: search <queryDB> <targetDB> <alignmentDB> <tmpDir> [options]");
+        if (int rc = checkWorkflowFlags(a)) return rc;
+        return ungappedAlignSearch(a, a.pos[0], a.pos[1], a.pos[2], a.pos[3]);
+    }
     if (a.integer("--num-iterations", 1) > 1) {
         if (a.pos.size() != 4) return fail("usage: search <queryDB> <targetDB> <alignmentDB> <tmpDir> [options]");
         if (int rc = checkWorkflowFlags(a)) return rc;
@@ -952,6 +1022,26 @@ int searchModule(const Args &a) {
 
 int clustersearchModule(const Args &a) {
     if (int rc = checkPrefilterMode(a)) return rc;
+    if (a.integer("--alignment-mode", 2) == 4) {
+        // the ungapped alignment mode through the modules, then the module chain on its alignment DB
+        if (a.pos.size() != 4) return fail("usage: clustersearch <querySetDB> <targetSetDB> <out.tsv> <tmpDir> [options]");
+        if (int rc = checkWorkflowFlags(a)) return rc;
+        if (int rc = checkUngappedAlign(a)) return rc;   // before anything under <tmpDir> is touched
+        const std::string Q = a.pos[0], T = a.pos[1], tmp = a.pos[3];
+        mkdir(tmp.c_str(), 0777);
+        Args s = a;   // the clustersearch workflow's defaults (R/src/workflow/clustersearch.cpp:9-37)
+        auto def = [&](const char *f, const char *v) { if (!s.has(f)) s.opt[f] = v; };
+        def("-s", "5.7");
+        def("--cov-mode", "2");
+        def("-c", "0.8");
+        def("-e", "10");
+        def("--min-aln-len", "30");
+        def("-a", "1");
+        for (const char *db : {"/result", "/result_prefixed", "/aggregate", "/aggregate_merged", "/matches", "/matches_h", "/clusters", "/clusters_h"})
+            sddb::removeDb(tmp + db);
+        if (int rc = ungappedAlignSearch(s, Q, T, tmp + "/result", tmp + "/search")) return rc;
+        return clusterChain(a, Q, T, tmp);
+    }
     if (a.integer("--num-iterations", 1) <= 1) return runSearch(a, true);
     // iterative profile search (BASELINE config 4): the iterations through the modules, then the module chain of
     // R/data/clustersearch.sh:121-151 on the merged alignment DB
@@ -975,23 +1065,7 @@ int clustersearchModule(const Args &a) {
                        envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1;
     if (!files) return iterativeSearch(s, Q, T, tmp + "/result", tmp + "/search", &a.pos[2]);
     if (int rc = iterativeSearch(s, Q, T, tmp + "/result", tmp + "/search")) return rc;
-    const std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
-    if (int rc = runModule(prefixidModule, "prefixid", {tmp + "/result", tmp + "/result_prefixed"}, common)) return rc;
-    if (int rc = runModule(besthitbysetModule, "besthitbyset", {Q, T, tmp + "/result_prefixed", tmp + "/aggregate"},
-                           with(common, {"--simple-best-hit", "1", "--suboptimal-hits", "0"})))
-        return rc;
-    if (int rc = runModule(mergeresultsbysetModule, "mergeresultsbyset", {Q + "_set_to_member", tmp + "/aggregate", tmp + "/aggregate_merged"}, common))
-        return rc;
-    if (int rc = runModule(combinehitsModule, "combinehits", {Q, T, tmp + "/aggregate_merged", tmp + "/matches", tmp},
-                           with(common, {"--alpha", a.str("--alpha", "1"), "--aggregation-mode", "0", "--filter-self-match",
-                                         a.flag("--filter-self-match", false) ? "1" : "0"})))
-        return rc;
-    std::vector<std::string> ch = with(common, {"--multihit-pval", a.str("--multihit-pval", "0.01"), "--cluster-pval", a.str("--cluster-pval", "0.01"),
-                                                "--max-gene-gap", a.str("--max-gene-gap", "3"), "--cluster-size", a.str("--cluster-size", "2"),
-                                                "--db-output", "1", "--alpha", a.str("--alpha", "1")});
-    if (a.has("--device")) ch = with(ch, {"--device", a.str("--device", "0")});
-    if (int rc = runModule(clusterhitsModule, "clusterhits", {Q, T, tmp + "/matches", tmp + "/clusters"}, ch)) return rc;
-    return runModule(summarizeresultsModule, "summarizeresults", {Q, T, tmp + "/clusters", a.pos[2]}, common);
+    return clusterChain(a, Q, T, tmp);
 }
 
 }  // namespace sdcli

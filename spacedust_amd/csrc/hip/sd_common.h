@@ -297,6 +297,8 @@ struct sd_seqset {
     uint32_t *dGroupOf = nullptr, *dGroupKey = nullptr;   // sd_seqset_set_groups: target set and DB key of every sequence
     size_t bGroupOf = 0, bGroupKey = 0;
     uint32_t nGroups = 0;
+    uint8_t *dLet = nullptr;      // sd_seqset_set_letters: the DB's bytes (rescoring compares letters, not matrix codes)
+    size_t bLet = 0;
 };
 
 // the target side of the prefilter, resident in HBM (built by sd_target_create* from host arrays or by sd_target_build on the device)

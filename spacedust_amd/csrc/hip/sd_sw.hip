@@ -2034,6 +2034,7 @@ void sd_seqset_destroy(sd_seqset *s) {
     poolPut(s->ctx, s->dOff, s->bOff);
     poolPut(s->ctx, s->dGroupOf, s->bGroupOf);
     poolPut(s->ctx, s->dGroupKey, s->bGroupKey);
+    poolPut(s->ctx, s->dLet, s->bLet);
     delete s;
 }
 
