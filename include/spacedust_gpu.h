@@ -156,6 +156,30 @@ int sd_sw_align_batch_best_by_group(sd_ctx *ctx, const sd_sw_params *par, const 
                                     const uint8_t *isIdentity, float seqIdThr, int32_t alnLenThr, uint32_t *outIdx, sd_sw_result *out,
                                     uint32_t *nOut, char *btPool, uint64_t btCap, uint64_t *btUsed);
 
+/* ---- alternative alignments (`align --alt-ali N`; Alignment::computeAlternativeAlignment, M/src/alignment/Alignment.cpp:569-601) ----
+ * A seed is an alignment the caller has accepted: query seedQ[s], target seedT[s], target positions [tStart[s], tEnd[s]].  Per seed
+ * the target is copied, positions [tStart, tEnd) of the copy become X (the end is exclusive: the residue at tEnd stays), and up to
+ * maxAlt rounds follow: Matcher::getSWResult on the masked copy with the query profile, coverage mode / threshold and alignment
+ * mode of `par`; a result that passes Alignment::checkCriteria (:548-567: E-value, coverage, and the sequence-identity /
+ * alignment-length thresholds and --seq-id-mode given here) is the seed's next alternative and its [tStart, tEnd) is masked on
+ * top; the first result that fails ends the seed and is not returned.  par->evalThr is taken through a float, as the reference's
+ * function receives it.  par->swMode is 1 or 2 (the masks need start positions; Alignment.cpp:88 forces them too).
+ * isIdentity (nullable): seeds marked there are skipped (count 0), as the reference skips identity pairs.
+ * out[s * maxAlt + r] is alternative r of seed s (r < outCount[s]); backtraces go to btPool as in sd_sw_align_batch,
+ * sd_sw_set_cigar_pool included.  The pool also receives the backtrace of every seed's last, rejected round; N * (qLen + tLen)
+ * bytes per seed always suffice (twice that for run-length text); SD_ENOMEM when it is too small.
+ * The masked copies live in a scratch target set on the device that is rebuilt per round for the seeds still alive; the seeds
+ * are processed in groups whose copies fit a fixed budget (256 MiB; SD_ALT_BUDGET in the environment overrides it, in bytes),
+ * so the workspace ("alt.*" in sd_workspace_report) does not grow with the number of seeds.  Between two rounds the host reads
+ * the number of seeds still alive and nothing else.  Profile query sets are accepted, profile target sets refused. */
+int sd_sw_align_alt_batch(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets, uint32_t nSeeds,
+                          const uint32_t *seedQ, const uint32_t *seedT, const int32_t *tStart, const int32_t *tEnd,
+                          const uint8_t *isIdentity, uint32_t maxAlt, float seqIdThr, int32_t alnLenThr, int32_t seqIdMode,
+                          sd_sw_result *out, uint32_t *outCount, char *btPool, uint64_t btCap, uint64_t *btUsed);
+/* of the context's last sd_sw_align_alt_batch: seed groups, sum over the rounds of the seeds alive in them (= alignments run),
+ * and the bytes the mask kernel wrote into the scratch target set */
+int sd_sw_alt_last_stats(sd_ctx *ctx, uint64_t *groups, uint64_t *seedRounds, uint64_t *bytesCopied);
+
 /* ---- Matcher::compressAlignment on the device (M/src/alignment/Matcher.cpp:166-185) -----------------------------------------------
  * on != 0: the alignment calls of this context (sd_sw_align_batch, _compact, _compact_diag, _best_by_group) fill the pool with the
  * run-length text of every returned backtrace ("57M2I103M"; "0M" first when a backtrace does not begin with a match, as the

@@ -376,6 +376,43 @@ class Context:
                 return cidx[:n_out.value], res[:n_out.value], pool[:used.value]
             return res, pool[:used.value]
 
+    def sw_align_alt(self, par, queries, targets, seed_q, seed_t, t_start, t_end, max_alt, identity=None, seq_id_thr=0.0,
+                     aln_len_thr=0, seq_id_mode=0, bt_cap=None):
+        """sd_sw_align_alt_batch: the alternative alignments of `align --alt-ali max_alt` for seeds (query, target, accepted
+        target interval [t_start, t_end]).  Returns (records [n_seeds, max_alt], counts [n_seeds], pool): records[s, :counts[s]]
+        are seed s's alternatives in round order."""
+        sq = np.ascontiguousarray(seed_q, np.uint32)
+        st = np.ascontiguousarray(seed_t, np.uint32)
+        tb = np.ascontiguousarray(t_start, np.int32)
+        te = np.ascontiguousarray(t_end, np.int32)
+        n = len(sq)
+        assert len(st) == len(tb) == len(te) == n
+        idt = np.ascontiguousarray(identity, np.uint8) if identity is not None else None
+        ql = (queries.offsets[sq.astype(np.int64) + 1] - queries.offsets[sq]).astype(np.int64)
+        tl = (targets.offsets[st.astype(np.int64) + 1] - targets.offsets[st]).astype(np.int64)
+        exact = (2 if getattr(self, '_cigar_pool', False) else 1) * int(max_alt) * int((ql + tl).sum()) + 64
+        if bt_cap is None:
+            bt_cap = min(exact, max(1 << 20, 2 * int((ql + tl).sum()) + 64))
+        res = np.zeros((n, int(max_alt)), _lib.SW_RESULT_DTYPE)
+        cnt = np.zeros(n, np.uint32)
+        while True:
+            pool = np.zeros(bt_cap, np.uint8)
+            used = C.c_uint64()
+            rc = self.L.sd_sw_align_alt_batch(self.h, C.byref(par), queries.h, targets.h, n, ptr(sq), ptr(st), ptr(tb), ptr(te), ptr(idt),
+                                              int(max_alt), float(seq_id_thr), int(aln_len_thr), int(seq_id_mode), ptr(res), ptr(cnt),
+                                              ptr(pool), len(pool), C.byref(used))
+            if rc == _lib.SD_ENOMEM and bt_cap < exact:
+                bt_cap = exact
+                continue
+            _check(self.h, rc, 'sd_sw_align_alt_batch')
+            return res, cnt, pool[:used.value]
+
+    def sw_alt_stats(self):
+        """(seed groups, alignments run, bytes the mask kernel wrote) of the last sw_align_alt"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.L.sd_sw_alt_last_stats(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
     def letterset(self, host, seqs):
         """a SeqSet of ASCII sequences (str or bytes) that also carries their letters (sd_seqset_set_letters): what
         rescore_diagonal takes"""

@@ -39,6 +39,7 @@ struct AlignSetup {
     sd_sw_params par, rpar;      // first pass; the realigner (score-biased matrix, E-value gate off)
     sd_aln_criteria crit;
     int swMode = 0, covMode = 0;
+    int altAli = 0;              // --alt-ali: alternative alignments per accepted hit (Alignment::computeAlternativeAlignment)
     bool realign = false, compBias = true, includeIdentity = false, stopRules = false;
     float realignScoreBias = -0.2f, canCovThr = 0.0f;
 };
@@ -65,6 +66,12 @@ struct AlignChunk {
     std::vector<int8_t> qbias, qaln, qbias2;
     std::vector<sd_sw_result> res, res2, merged, full;
     BtPool pool, pool2;
+    // --alt-ali: the seeds (accepted records), their alternatives, and the combined list
+    std::vector<uint32_t> seedQ, seedT, seedIdx, altCount, finT, finOrder, finCounts;
+    std::vector<int32_t> seedB, seedE;
+    std::vector<uint8_t> seedIdent, finIdent;
+    std::vector<sd_sw_result> altRes, fin;
+    BtPool pool3;
 };
 // aligns the chunk's pairs and applies the criteria / sort / --realign pass.  lap (nullable): the module's SD_DEBUG_TIMING marks.
 // Returns SD_OK or a C-ABI error code (sd_last_error(ctx) says why for device errors; *what names the failing call).

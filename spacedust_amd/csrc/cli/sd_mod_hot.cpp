@@ -496,11 +496,131 @@ struct SeqSetGuard {
     ~SeqSetGuard() { if (s) sd_seqset_destroy(s); }
 };
 
+// --alt-ali (Alignment::computeAlternativeAlignment, Alignment.cpp:399-401,433-435,569-601): the records the chunk's queries have
+// accepted so far are the seeds; sd_sw_align_alt_batch returns up to altAli further alignments per seed, with the pass's own
+// parameters (under --realign the realigner's: score-biased matrix, the coverage threshold, no E-value gate, Alignment.cpp:434).
+// The alternatives join their query's list and the list is ordered by Matcher::compareHits again (:403-405, :437-439): the sort
+// is stable over (seeds in their order, then alternatives in (seed, round) order), which fixes the order of the ties the
+// reference's unstable sort leaves open.
+int altAlignChunk(sd_ctx *ctx, const AlignSetup &s, const SeqDb &qdb, const SeqDb &tdb, const std::vector<uint32_t> &localQ, sd_seqset *qs,
+                  sd_seqset *ts, AlignChunk &c) {
+    const uint32_t nq = (uint32_t) localQ.size();
+    const std::vector<sd_sw_result> &recs = *c.outRecs;
+    const std::vector<uint32_t> &order = *c.outOrder, &counts = *c.outCounts, &recT = *c.outT;
+    const std::vector<uint8_t> &recIdent = *c.outIdent;
+    uint64_t nSeeds = 0;
+    for (uint32_t q = 0; q < nq; q++) nSeeds += counts[q];
+    if (nSeeds == 0) return SD_OK;
+    c.seedQ.resize(nSeeds); c.seedT.resize(nSeeds); c.seedB.resize(nSeeds); c.seedE.resize(nSeeds); c.seedIdent.resize(nSeeds);
+    c.seedIdx.resize(nSeeds);
+    uint64_t w = 0, poolNeed = 64;
+    for (uint32_t q = 0; q < nq; q++)
+        for (uint32_t x = 0; x < counts[q]; x++, w++) {
+            const uint32_t i = order[w];
+            c.seedIdx[w] = i;
+            c.seedQ[w] = q;
+            c.seedT[w] = recT[i];
+            c.seedIdent[w] = recIdent[i];
+            // an identity pair is skipped (its record may carry no positions in a mode without them)
+            c.seedB[w] = recIdent[i] ? 0 : recs[i].tStart;
+            c.seedE[w] = recIdent[i] ? 0 : recs[i].tEnd;
+            poolNeed += (uint64_t) qdb.lens[localQ[q]] + (uint64_t) tdb.lens[recT[i]];
+        }
+    const sd_sw_params &par = s.realign ? s.rpar : s.par;
+    const uint32_t N = (uint32_t) s.altAli;
+    c.altRes.resize(nSeeds * N);
+    c.altCount.assign(nSeeds, 0);
+    // a first guess of two rounds' backtraces per seed; the exact bound is N rounds (a too small pool costs the call again)
+    uint64_t cap = par.swMode == 2 ? std::min<uint64_t>(2, N) * poolNeed : 64, used = 0;
+    for (bool exact = false;;) {
+        c.pool3.reserve(cap);
+        const int rc = sd_sw_align_alt_batch(ctx, &par, qs, ts, (uint32_t) nSeeds, c.seedQ.data(), c.seedT.data(), c.seedB.data(), c.seedE.data(),
+                                             c.seedIdent.data(), N, s.crit.seqIdThr, s.crit.alnLenThr, s.crit.seqIdMode, c.altRes.data(),
+                                             c.altCount.data(), c.pool3.p.get(), c.pool3.cap, &used);
+        if (rc == SD_ENOMEM && !exact) {
+            cap = (uint64_t) N * poolNeed;
+            exact = true;
+            continue;
+        }
+        if (rc != SD_OK) return rc;
+        break;
+    }
+    // the combined records: seeds (their backtraces move behind the alternatives' in pool3), then every seed's alternatives
+    uint64_t nAlt = 0, seedBt = 0;
+    for (uint64_t x = 0; x < nSeeds; x++) {
+        nAlt += c.altCount[x];
+        if (recs[c.seedIdx[x]].btLen > 0) seedBt += (uint64_t) recs[c.seedIdx[x]].btLen;
+    }
+    if (c.pool3.cap < used + seedBt) {
+        BtPool grown;
+        grown.reserve(used + seedBt);
+        memcpy(grown.p.get(), c.pool3.p.get(), used);
+        std::swap(grown, c.pool3);
+    }
+    c.fin.resize(nSeeds + nAlt);
+    c.finT.resize(nSeeds + nAlt);
+    c.finIdent.assign(nSeeds + nAlt, 0);
+    c.finOrder.resize(nSeeds + nAlt);
+    c.finCounts.assign(std::max<uint32_t>(nq, 1), 0);
+    const char *seedPool = c.outPool->data();
+    uint64_t o = 0, x0 = 0;
+    struct Key {
+        double eval;
+        int bits, dbLen;
+        uint32_t dbKey, idx;
+    };
+    std::vector<Key> keys;
+    for (uint32_t q = 0; q < nq; q++) {
+        keys.clear();
+        auto add = [&](const sd_sw_result &r, uint32_t t, uint8_t ident) {
+            c.fin[o] = r;
+            c.finT[o] = t;
+            c.finIdent[o] = ident;
+            Key k;
+            k.eval = r.evalue;
+            k.bits = static_cast<int>(sd_host_bitscore((double) (uint32_t) r.score) + 0.5);
+            k.dbLen = tdb.lens[t];
+            k.dbKey = tdb.keys[t];
+            k.idx = (uint32_t) o++;
+            keys.push_back(k);
+        };
+        for (uint32_t x = 0; x < counts[q]; x++) {
+            sd_sw_result r = recs[c.seedIdx[x0 + x]];
+            if (r.btLen > 0 && seedPool) {
+                memcpy(c.pool3.p.get() + used, seedPool + r.btOffset, (size_t) r.btLen);
+                r.btOffset = used;
+                used += (uint64_t) r.btLen;
+            }
+            add(r, c.seedT[x0 + x], c.seedIdent[x0 + x]);
+        }
+        for (uint32_t x = 0; x < counts[q]; x++)
+            for (uint32_t r = 0; r < c.altCount[x0 + x]; r++) add(c.altRes[(x0 + x) * N + r], c.seedT[x0 + x], 0);
+        std::stable_sort(keys.begin(), keys.end(), [](const Key &a, const Key &b) {   // Matcher::compareHits
+            if (a.eval != b.eval) return a.eval < b.eval;
+            if (a.bits != b.bits) return a.bits > b.bits;
+            if (a.dbLen != b.dbLen) return a.dbLen < b.dbLen;
+            return a.dbKey < b.dbKey;
+        });
+        const uint64_t base = o - keys.size();
+        for (size_t x = 0; x < keys.size(); x++) c.finOrder[base + x] = keys[x].idx;
+        c.finCounts[q] = (uint32_t) keys.size();
+        x0 += counts[q];
+    }
+    c.outRecs = &c.fin;
+    c.outOrder = &c.finOrder;
+    c.outCounts = &c.finCounts;
+    c.outT = &c.finT;
+    c.outIdent = &c.finIdent;
+    c.outPool = &c.pool3;
+    return SD_OK;
+}
+
 }  // namespace
 
 int alignSetupFromArgs(const Args &a, sd_host *host, uint64_t targetResidues, AlignSetup &s) {
     if (a.flag("--wrapped-scoring", false)) return fail("--wrapped-scoring is a nucleotide mode");
-    if (a.integer("--alt-ali", 0) != 0) return fail("--alt-ali > 0 is not supported");
+    s.altAli = (int) std::min<long long>(a.integer("--alt-ali", 0), 4096);
+    if (s.altAli < 0) return fail("--alt-ali must not be negative");
     if (a.integer("--alignment-output-mode", 0) != 0) return fail("--alignment-output-mode 0 only");
     if (a.real("--score-bias", 0.0) != 0.0) return fail("--score-bias 0 only");
     if (a.real("--corr-score-weight", 0.0) != 0.0) return fail("--corr-score-weight 0 only");
@@ -538,6 +658,7 @@ int alignSetupFromArgs(const Args &a, sd_host *host, uint64_t targetResidues, Al
         covThr = 0.0f;
         addBacktrace = true;
     }
+    if (s.altAli > 0) alignmentMode = std::max(alignmentMode, 2);   // start positions for the masks (Alignment.cpp:79-89)
     s.swMode = initSWMode(alignmentMode, (float) a.real("-c", 0.0), seqIdThr);
     memset(&s.par, 0, sizeof(s.par));
     s.par.gapOpen = 11;
@@ -683,6 +804,8 @@ int alignChunkCore(sd_ctx *ctx, sd_host *host, const AlignSetup &s, const SeqDb 
     c.outT = &c.recT;
     c.outIdent = &c.recIdent;
     c.outPool = &c.pool;
+    SeqSetGuard qset2;
+    sd_seqset *rq = qset.s;   // the query set of the pass the output records come from
     if (s.realign && nAcc > 0) {
         // second pass over the accepted records, in their order (Alignment.cpp:408-440)
         c.pq2.resize(nAcc);
@@ -698,8 +821,6 @@ int alignChunkCore(sd_ctx *ctx, sd_host *host, const AlignSetup &s, const SeqDb 
             }
         // the realigner's query profile: composition bias against the score-biased matrix (a profile query carries its
         // scores itself and is reused)
-        SeqSetGuard qset2;
-        sd_seqset *rq = qset.s;
         if (!qdb.profile && s.compBias && s.realignScoreBias != 0.0f) {
             c.qbias2.assign(c.qoff[nq] + 1, 0);
             sd_host_sw_comp_bias(host, 2, c.qres.data(), c.qoff.data(), nq, c.qbias2.data());
@@ -737,6 +858,14 @@ int alignChunkCore(sd_ctx *ctx, sd_host *host, const AlignSetup &s, const SeqDb 
         c.outCounts = &c.counts2;
     }
     if (lap) lap->mark("chunk: accept / sort (+ realign)");
+    if (s.altAli > 0) {
+        rc = altAlignChunk(ctx, s, qdb, tdb, localQ, s.realign ? rq : qset.s, tset, c);
+        if (rc != SD_OK) {
+            *what = "sd_sw_align_alt_batch";
+            return rc;
+        }
+        if (lap) lap->mark("chunk: alternative alignments");
+    }
     return SD_OK;
 }
 

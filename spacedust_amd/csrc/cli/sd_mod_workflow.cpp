@@ -94,7 +94,7 @@ int checkWorkflowFlags(const Args &a) {
     if (a.multi("--seed-sub-mat", "aa", "VTML80.out") != "VTML80.out") return fail("--seed-sub-mat: only VTML80.out is built into this path");
     if (a.integer("--exact-kmer-matching", 0) != 0 || a.integer("--spaced-kmer-mode", 1) != 1 || !a.flag("--diag-score", true))
         return fail("--exact-kmer-matching 1 / --spaced-kmer-mode 0 / --diag-score 0 are not supported");
-    if (a.integer("--alt-ali", 0) != 0 || a.flag("--realign", false)) return fail("--alt-ali / --realign: use the `align` module");
+    if (a.flag("--realign", false)) return fail("--alt-ali / --realign: use the `align` module");
     if (a.real("--min-seq-id", 0.0) != 0.0) return fail("--min-seq-id > 0: use the module-by-module path");
     if (a.integer("--max-accept", INT_MAX) != INT_MAX || a.integer("--max-rejected", INT_MAX) != INT_MAX)
         return fail("--max-accept / --max-rejected: use the `align` module");
@@ -1003,10 +1003,62 @@ int ungappedAlignSearch(const Args &a, const std::string &Q, const std::string &
     return runModule(rescorediagonalModule, "rescorediagonal", {Q, T, prefDb, result}, rescore);
 }
 
+// `search --alt-ali N` (M/src/workflow/Search.cpp hands --alt-ali to the align step of blastp.sh): the prefilter -- the k-mer one,
+// or the ungapped one under --prefilter-mode 1 -- followed by the `align` module with the alternative alignments, in this process
+// with the target resident between them.  The streaming pipeline hands one record per pair from stage to stage and is not used.
+int checkAltAli(const Args &a, bool withClusters) {
+    if (withClusters)
+        return fail("clustersearch --alt-ali: the fused best-hit aggregation is defined on one alignment per (query, target) pair; run "
+                    "`search --alt-ali` or the `align` module");
+    if (a.integer("--alignment-mode", 0) == 4) return fail("--alt-ali with --alignment-mode 4: the ungapped alignment mode has no alternative alignments");
+    if (a.integer("--num-iterations", 1) > 1) return fail("--alt-ali with --num-iterations > 1 is not implemented; run the iterations with the modules");
+    if (envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1) return fail("--alt-ali runs on one rank");
+    return 0;
+}
+
+int altAliSearch(const Args &a, const std::string &Q, const std::string &T, const std::string &result, const std::string &tmp) {
+    mkdir(tmp.c_str(), 0777);
+    const std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
+    const bool ungapped = a.integer("--prefilter-mode", 0) == 1;
+    std::vector<std::string> pref = with(common, {"--max-seqs", a.str("--max-seqs", "300"), "-c", a.str("-c", "0"), "--cov-mode", a.str("--cov-mode", "0"),
+                                                  "--min-ungapped-score", a.str("--min-ungapped-score", "15"), "--comp-bias-corr",
+                                                  a.str("--comp-bias-corr", "1")});
+    if (!ungapped)
+        pref = with(pref, {"-s", a.str("-s", "5.7"), "-k", a.str("-k", "0"), "--mask", a.str("--mask", "1"), "--mask-prob", a.str("--mask-prob", "0.9")});
+    const std::vector<const char *> kmerOnly = {"--device", "--bin-size", "--l2-cache-size", "--chunk-queries", "--add-self-matches"};
+    const std::vector<const char *> ungappedOnly = {"--device", "--chunk-queries"};
+    for (const char *f : ungapped ? ungappedOnly : kmerOnly)
+        if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
+    // the search workflow's alignment mode is 2 (score and coverage, Search.cpp:23)
+    std::vector<std::string> aln = with(common, {"--alt-ali", a.str("--alt-ali", "0"), "--alignment-mode", a.str("--alignment-mode", "2"), "-e",
+                                                 a.str("-e", "0.001"), "-c", a.str("-c", "0"), "--cov-mode", a.str("--cov-mode", "0"), "-a", a.str("-a", "0"),
+                                                 "--min-aln-len", a.str("--min-aln-len", "0"), "--seq-id-mode", a.str("--seq-id-mode", "0"),
+                                                 "--comp-bias-corr", a.str("--comp-bias-corr", "1")});
+    for (const char *f : {"--device", "--add-self-matches"})
+        if (a.has(f)) aln = with(aln, {f, a.str(f, "")});
+    struct ResidentScope {
+        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
+        ~ResidentScope() { resident().clear(); }
+    } residentScope;
+    const std::string prefDb = tmp + "/pref_0";
+    if (ungapped) {
+        if (int rc = runModule(ungappedprefilterModule, "ungappedprefilter", {Q, T, prefDb}, pref)) return rc;
+    } else {
+        if (int rc = runModule(prefilterModule, "prefilter", {Q, T, prefDb}, pref)) return rc;
+    }
+    return runModule(alignModule, "align", {Q, T, prefDb, result}, aln);
+}
+
 }  // namespace
 
 int searchModule(const Args &a) {
     if (int rc = checkPrefilterMode(a)) return rc;
+    if (a.integer("--alt-ali", 0) != 0) {
+        if (a.pos.size() != 4) return fail("usage: search <queryDB> <targetDB> <alignmentDB> <tmpDir> [options]");
+        if (int rc = checkAltAli(a, false)) return rc;
+        if (int rc = checkWorkflowFlags(a)) return rc;
+        return altAliSearch(a, a.pos[0], a.pos[1], a.pos[2], a.pos[3]);
+    }
     if (a.integer("--alignment-mode", 0) == 4) {
         if (a.pos.size() != 4) return fail("usage: search <queryDB> <targetDB> <alignmentDB> <tmpDir> [options]");
         if (int rc = checkWorkflowFlags(a)) return rc;
@@ -1022,6 +1074,7 @@ int searchModule(const Args &a) {
 
 int clustersearchModule(const Args &a) {
     if (int rc = checkPrefilterMode(a)) return rc;
+    if (a.integer("--alt-ali", 0) != 0) return checkAltAli(a, true);
     if (a.integer("--alignment-mode", 2) == 4) {
         // the ungapped alignment mode through the modules, then the module chain on its alignment DB
         if (a.pos.size() != 4) return fail("usage: clustersearch <querySetDB> <targetSetDB> <out.tsv> <tmpDir> [options]");

@@ -34,6 +34,11 @@ struct sd_ctx {
     hipEvent_t evSync = nullptr;   // blocking-sync event: host threads sleep while they wait for the stream (sdStreamSync)
     uint64_t cellsFwd = 0, cellsRev = 0, cellsTb = 0;
     uint64_t cellsUngapped = 0;   // sd_ungapped_last_cells
+    uint64_t altGroups = 0, altSeedRounds = 0, altBytes = 0;   // sd_sw_alt_last_stats
+    // the per-pair records of the last sd_sw_align_batch* call, as they lie on the device (record i belongs to pair i; valid until the
+    // next alignment call on this context): what sd_sw_align_alt_batch judges a round by without a copy through the host
+    const sd_sw_result *alignDevRes = nullptr;
+    size_t alignDevResN = 0;
     bool cigarPool = false;   // sd_sw_set_cigar_pool: the alignment calls return run-length text instead of backtrace letters
     uint64_t d2hRecordBytes = 0, d2hPoolBytes = 0;   // what the alignment calls brought back (sd_sw_download_bytes)
     hipDeviceProp_t prop;

@@ -2113,6 +2113,9 @@ int sd_sw_score_batch(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *que
 
 // compactIdx != nullptr: only the pairs that reached a result worth reporting (identity pairs and pairs that were
 // not stopped at a gate) are returned, out[x] being the record of pair compactIdx[x], x < *nCompact
+// Of the target set this path reads the device side only (n, dRes, dOff, dProf), except for identity pairs, whose targets' host copies
+// (hOff, hRes) it reads as well: sd_sw_align_alt_batch relies on that when it passes a device-only view of its scratch set
+// without identity pairs (sdDeviceSeqView, sd_sw_alt.hip).  ctx->alignDevRes is left pointing at the per-pair records.
 static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
                           uint32_t nPairs, const uint32_t *pairQ, const uint32_t *pairT, const uint8_t *isIdentity,
                           sd_sw_result *out, char *btPool, uint64_t btCap, uint64_t *btUsed, uint32_t *compactIdx,
@@ -2183,6 +2186,8 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
     SD_HIP(ctx, wsGet(ctx, "al.tasks", N, &dTasks));
     SD_HIP(ctx, wsGet(ctx, "al.tb", N, &dTb));
     SD_HIP(ctx, wsGet(ctx, "al.res", N, &dRes));
+    ctx->alignDevRes = dRes;
+    ctx->alignDevResN = N;
     SD_HIP(ctx, wsGet(ctx, "al.scana", N + 1, &dScanA));
     SD_HIP(ctx, wsGet(ctx, "al.scanb", N + 1, &dScanB));
     SD_HIP(ctx, wsGet(ctx, "al.dirbytes", N + 1, &dDirBytes));
