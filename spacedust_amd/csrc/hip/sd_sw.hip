@@ -2347,7 +2347,8 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
         for (int ci = 0; ci < 3; ci++) {
             const uint32_t begin = hb[N_TB_NARROW + ci], cnt = hb[N_TB_NARROW + 1 + ci] - hb[N_TB_NARROW + ci];
             if (cnt == 0) continue;
-            ProfScope ps(ctx, "sw_traceback.lds");
+            static const char *const ldsNames[3] = {"sw_traceback.lds128", "sw_traceback.lds512", "sw_traceback.lds2048"};
+            ProfScope ps(ctx, ldsNames[ci]);
             const int ldsStride = ldsClass[ci] + 1;
             const size_t ldsBytes = (size_t) 2 * 3 * ldsStride * sizeof(int32_t);
             if (queries->dProf)
@@ -2893,7 +2894,7 @@ int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_se
                 return sdFail(ctx, SD_ENOMEM, "traceback scratch allocation failed (%llu bytes)", (unsigned long long) nDir);
             SD_HIP(ctx, hipMemcpyAsync(dT.p, &pending[pos], cnt * sizeof(TbTask), hipMemcpyHostToDevice, ctx->stream));
             {
-                ProfScope ps(ctx, "sw_traceback");
+                ProfScope ps(ctx, cls == 128 ? "sw_traceback.lds128" : (cls == 512 ? "sw_traceback.lds512" : (cls == 2048 ? "sw_traceback.lds2048" : "sw_traceback.global")));
                 const int ldsStride = cls + 1;
                 const size_t ldsBytes = (size_t) 2 * 3 * ldsStride * sizeof(int32_t);
                 if (cls)

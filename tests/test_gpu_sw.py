@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from tbgen import compress_alignment as _compress_alignment
+
 pytestmark = pytest.mark.gpu
 
 
@@ -311,19 +313,6 @@ def test_sw_align_compact_equals_full(gpu, host):
         b = pool_f[int(full['btOffset'][keep[x]]):int(full['btOffset'][keep[x]]) + int(full['btLen'][keep[x]])]
         assert np.array_equal(a, b), x
     assert 100 < len(keep) < len(pq)
-
-
-def _compress_alignment(bt):
-    """Matcher::compressAlignment (M/src/alignment/Matcher.cpp:166-185), letter by letter"""
-    out, state, count = [], 'M', 0
-    for ch in bt:
-        if ch != state:
-            out.append('%d%s' % (count, state))
-            state, count = ch, 1
-        else:
-            count += 1
-    out.append('%d%s' % (count, state))
-    return ''.join(out)
 
 
 def test_sw_run_length_text_from_the_device_equals_compress_alignment(gpu, host):
