@@ -199,6 +199,14 @@ int sd_sw_download_bytes(sd_ctx *ctx, uint64_t *recordBytes, uint64_t *poolBytes
 int sd_selftest_sort_pairs(sd_ctx *ctx, const uint32_t *keys, const uint32_t *vals, uint32_t n, int beginBit, int endBit, uint32_t *outKeys,
                            uint32_t *outVals);
 int sd_selftest_scan(sd_ctx *ctx, const uint32_t *in, uint32_t n, uint64_t *exclusiveSum, uint32_t *runningMax);
+/* sd_selftest_r2p_weights: the weights stage of result2profile alone (csrc/hip/sd_r2p.hip) on nTasks alignments given as cell
+ * matrices, task after task, row-major [nRows][L], row 0 the centre; cell codes 0..19 residue, 20 any residue, 21 gap.  The global
+ * weights are formed as sd_r2p_batch forms them; with a context the alignments go through the staging of sd_r2p_batch_device (the
+ * same function: offsets, strides, scratch sizes, reciprocal table, launch order) and the kernel, with ctx == NULL through the
+ * host implementation, task by task.  freq: sum(L) x 20 weighted residue frequencies, eff: sum(L) effective sequence numbers, in
+ * task order.  SD_EINVAL for L == 0, nRows == 0 or a code above 21. */
+int sd_selftest_r2p_weights(sd_ctx *ctx, uint32_t nTasks, const uint32_t *nRows, const uint32_t *L, const uint8_t *cells, float *freq,
+                            float *eff);
 
 int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
                                uint32_t nPairs, const uint32_t *pairQ, const uint32_t *pairT, const uint8_t *isIdentity,

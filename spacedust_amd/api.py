@@ -156,6 +156,25 @@ def result2profile(q_letters, q_off, edge_off, edge_t, edge_qstart, edge_tstart,
     return out[:-1].tobytes()
 
 
+def r2p_weights(tasks, ctx=None):
+    """sd_selftest_r2p_weights: the weights stage of result2profile alone on alignments given as uint8 cell matrices [nRows, L]
+    (row 0 the centre; 0..19 residue, 20 any, 21 gap) -- on the device through sd_r2p_batch_device's staging with a Context, by
+    the host implementation without.  Returns [(freq float32 [L, 20], eff float32 [L])] per task"""
+    L = _lib.load()
+    mats = [np.ascontiguousarray(m, np.uint8) for m in tasks]
+    assert all(m.ndim == 2 for m in mats)
+    n_rows = np.array([m.shape[0] for m in mats], np.uint32)
+    cols = np.array([m.shape[1] for m in mats], np.uint32)
+    cells = np.concatenate([m.ravel() for m in mats] + [np.zeros(1, np.uint8)])
+    total = int(cols.astype(np.int64).sum())
+    freq = np.zeros((total + 1, 20), np.float32)
+    eff = np.zeros(total + 1, np.float32)
+    h = ctx.h if ctx is not None else None
+    _check(h, L.sd_selftest_r2p_weights(h, len(mats), ptr(n_rows), ptr(cols), ptr(cells), ptr(freq), ptr(eff)), 'sd_selftest_r2p_weights')
+    at = np.concatenate([[0], np.cumsum(cols.astype(np.int64))])
+    return [(freq[at[k]:at[k + 1]].copy(), eff[at[k]:at[k + 1]].copy()) for k in range(len(mats))]
+
+
 class HostIndex:
     def __init__(self, host, residues, offsets, k, kmer_thr, mask, mask_prob):
         self.host = host

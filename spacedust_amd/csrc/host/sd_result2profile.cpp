@@ -786,6 +786,142 @@ static void reciprocalTable(std::vector<float> &table, uint32_t n) {
     }
 }
 
+// a filtered alignment ready for the weights stage (what host stage A leaves per centre)
+struct Prepared {
+    std::vector<char> cells;   // [nRows][stride], kept rows in order
+    std::vector<float> gw;     // global weights, scaled to sum 1
+    uint32_t nRows = 0, L = 0, stride = 0;   // nRows == 0: no task (a centre of length 0)
+};
+
+inline uint32_t cellStride(uint32_t L) { return (L + 3) / 4 * 4; }
+
+struct WeightsStage {   // stage B of a group: the tasks in the order of `prep`, their results by tasks[k].colOff
+    std::vector<R2pTaskH> tasks;
+    std::vector<uint32_t> taskOf;   // index into prep
+    std::unique_ptr<float[]> freq, eff;
+    uint64_t cellBytes = 0, nWeights = 0;
+    double stagingSeconds = 0, deviceSeconds = 0;
+};
+
+// Stage B: the staging arrays and task records of a group of prepared alignments, the reciprocal table, the launch order, the
+// device call.  The only place where the offsets the kernel works with are formed (sd_selftest_r2p_weights runs it as well).
+static int r2pWeightsOnDevice(sd_ctx *ctx, const std::vector<Prepared> &prep, const double *background, WeightsStage &S) {
+    const double t0 = omp_get_wtime();
+    std::vector<R2pTaskH> &tasks = S.tasks;
+    tasks.clear();
+    S.taskOf.clear();
+    uint64_t cellBytes = 0, cmBytes = 0, nWeights = 0, nColumns = 0, scratch = 0;
+    uint32_t maxRows = 1;
+    for (size_t x = 0; x < prep.size(); x++) {
+        const Prepared &P = prep[x];
+        if (P.nRows == 0) continue;
+        R2pTaskH t;
+        t.nRows = P.nRows;
+        t.L = P.L;
+        t.stride = P.stride;
+        t.rowStride = (P.nRows + 63) / 64 * 64;
+        t.cellOff = cellBytes;
+        t.cmOff = cmBytes;
+        t.weightOff = nWeights;
+        t.colOff = nColumns;
+        t.scratchOff = scratch;
+        cellBytes += (uint64_t) P.nRows * P.stride;
+        cmBytes += (uint64_t) t.L * t.rowStride;
+        nWeights += P.nRows;
+        nColumns += t.L;
+        scratch += (uint64_t) (t.L + 1) * 24;
+        maxRows = std::max(maxRows, P.nRows);
+        tasks.push_back(t);
+        S.taskOf.push_back((uint32_t) x);
+    }
+    S.cellBytes = cellBytes;
+    S.nWeights = nWeights;
+    if (tasks.empty()) return SD_OK;
+    // (raw arrays: every byte is written before it is read, and zeroing half a gigabyte per group is time)
+    std::unique_ptr<char[]> cells(new char[cellBytes + 64]);
+    S.freq.reset(new float[nColumns * kResidues + 1]);
+    S.eff.reset(new float[nColumns + 1]);
+    std::vector<float> gw(nWeights + 1), table;
+#pragma omp parallel for schedule(dynamic, 16)
+    for (size_t k = 0; k < tasks.size(); k++) {
+        const Prepared &P = prep[S.taskOf[k]];
+        memcpy(&cells[tasks[k].cellOff], P.cells.data(), P.cells.size());
+        memcpy(&gw[tasks[k].weightOff], P.gw.data(), P.gw.size() * sizeof(float));
+    }
+    const uint32_t rcpN = (maxRows + 1) * 20 + 8;
+    reciprocalTable(table, rcpN);
+    // launch order: the longest alignments first -- the work per alignment grows with the square of its columns, and the
+    // batch is as slow as its last workgroup (the offsets into the staging arrays travel with a task)
+    std::vector<uint32_t> ord(tasks.size());
+    for (size_t k = 0; k < ord.size(); k++) ord[k] = (uint32_t) k;
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
+        if (tasks[x].L != tasks[y].L) return tasks[x].L > tasks[y].L;
+        return tasks[x].nRows > tasks[y].nRows;
+    });
+    std::vector<R2pTaskH> launch(tasks.size());
+    for (size_t k = 0; k < ord.size(); k++) launch[k] = tasks[ord[k]];
+    const double t1 = omp_get_wtime();
+    const int rc = sdR2pColumnWeightsDevice(ctx, (uint32_t) tasks.size(), launch.data(), cells.get(), cellBytes, cmBytes, gw.data(), nWeights,
+                                            nColumns, scratch, table.data(), rcpN, background, S.freq.get(), S.eff.get());
+    S.stagingSeconds = t1 - t0;
+    S.deviceSeconds = omp_get_wtime() - t1;
+    return rc;
+}
+
+extern "C" int sd_selftest_r2p_weights(sd_ctx *ctx, uint32_t nTasks, const uint32_t *nRows, const uint32_t *L, const uint8_t *cells, float *freq,
+                                       float *eff) {
+    if (!nRows || !L || !cells || !freq || !eff) return SD_EINVAL;
+    std::vector<uint64_t> cellAt(nTasks + 1, 0), colAt(nTasks + 1, 0);
+    for (uint32_t k = 0; k < nTasks; k++) {
+        if (nRows[k] == 0 || L[k] == 0) return SD_EINVAL;
+        cellAt[k + 1] = cellAt[k] + (uint64_t) nRows[k] * L[k];
+        colAt[k + 1] = colAt[k] + L[k];
+    }
+    for (uint64_t x = 0; x < cellAt[nTasks]; x++)
+        if (cells[x] > kGap) return SD_EINVAL;
+    sd::SubMat matrix;
+    sd::initSubMat(matrix, sd::MAT_BLOSUM62, 2.0f, -0.2f);
+    const double *background = matrix.pBack;
+    std::vector<Prepared> prep(nTasks);
+#pragma omp parallel
+    {
+        ProfileScratch w;
+        std::vector<char *> row;
+#pragma omp for schedule(dynamic, 1)
+        for (uint32_t k = 0; k < nTasks; k++) {
+            Prepared &P = prep[k];
+            P.nRows = nRows[k];
+            P.L = L[k];
+            P.stride = cellStride(P.L);
+            P.cells.assign((size_t) P.nRows * P.stride, (char) kGap);
+            row.resize(P.nRows);
+            for (uint32_t rr = 0; rr < P.nRows; rr++) {
+                row[rr] = &P.cells[(size_t) rr * P.stride];
+                memcpy(row[rr], cells + cellAt[k] + (uint64_t) rr * P.L, P.L);
+            }
+            P.gw.assign(P.nRows, 0.0f);
+            globalWeights(P.gw.data(), (int) P.L, P.nRows, row.data());
+            scaleToOne(P.gw.data(), (int) P.nRows);
+            if (ctx) continue;
+            w.localWeight.assign(P.nRows, 0.0f);
+            w.frequency.assign((size_t) (P.L + 2) * kResidues, 0.0f);
+            w.effective.assign(P.L + 1, 0.0f);
+            columnWeights(w, background, w.frequency.data(), P.gw.data(), w.effective.data(), (int) P.L, P.nRows, row.data());
+            memcpy(freq + colAt[k] * kResidues, w.frequency.data(), (size_t) P.L * kResidues * sizeof(float));
+            memcpy(eff + colAt[k], w.effective.data(), (size_t) P.L * sizeof(float));
+        }
+    }
+    if (!ctx) return SD_OK;
+    WeightsStage S;
+    const int rc = r2pWeightsOnDevice(ctx, prep, background, S);
+    if (rc != SD_OK) return rc;
+    for (size_t k = 0; k < S.tasks.size(); k++) {   // (every task is staged: task k is prep[k])
+        memcpy(freq + colAt[k] * kResidues, &S.freq[S.tasks[k].colOff * kResidues], (size_t) S.tasks[k].L * kResidues * sizeof(float));
+        memcpy(eff + colAt[k], &S.eff[S.tasks[k].colOff], (size_t) S.tasks[k].L * sizeof(float));
+    }
+    return SD_OK;
+}
+
 static int r2pBatchImpl(sd_ctx *ctx, sd_r2p *r, const sd_r2p_params *par, uint32_t nQ, const uint8_t *qLetters, const uint64_t *qOff,
                         const uint64_t *edgeOff, const uint32_t *edgeT, const int32_t *edgeQStart, const int32_t *edgeTStart,
                         const char *btPool, const uint64_t *btOff, const uint8_t *tResidues, const uint64_t *tOff, char *outProfiles,
@@ -816,12 +952,8 @@ static int r2pBatchImpl(sd_ctx *ctx, sd_r2p *r, const sd_r2p_params *par, uint32
         //   A (host, a thread per centre)  alignment, diversity filter, global weights
         //   B (device)                     position-specific weights, frequencies, effective sequence numbers
         //   C (host, a thread per centre)  pseudo counts, scores, composition bias, masking, record
-        struct Prepared {
-            std::vector<char> cells;   // [nRows][stride], kept rows in order
-            std::vector<float> gw;
-            uint32_t nRows = 0, stride = 0;
-        };
-        const uint64_t budget = 1ull << 30;   // bytes of alignment cells per device call
+        uint64_t budget = 1ull << 30;   // bytes of alignment cells per device call
+        if (const char *e = getenv("SD_R2P_BUDGET")) budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10));   // tests: force groups (1: a centre each)
         uint32_t g0 = 0;
         while (g0 < nQ) {
             // a group: by the UNfiltered size (rows x columns), which bounds the filtered one
@@ -863,7 +995,8 @@ static int r2pBatchImpl(sd_ctx *ctx, sd_r2p *r, const sd_r2p_params *par, uint32
                     if (par->filterMsa) nRows = filter.run(A, nRows, r->scores, fs);
                     Prepared &P = prep[x];
                     P.nRows = (uint32_t) nRows;
-                    P.stride = (uint32_t) ((L + 3) / 4 * 4);
+                    P.L = (uint32_t) L;
+                    P.stride = cellStride((uint32_t) L);
                     P.cells.assign((size_t) nRows * P.stride, (char) kGap);
                     for (size_t rr = 0; rr < nRows; rr++) memcpy(&P.cells[rr * P.stride], A.row[rr], (size_t) L);
                     P.gw.assign(nRows, 0.0f);
@@ -872,70 +1005,21 @@ static int r2pBatchImpl(sd_ctx *ctx, sd_r2p *r, const sd_r2p_params *par, uint32
                 }
             }
             const double tA1 = omp_get_wtime();
-            // staging
-            std::vector<R2pTaskH> tasks;
-            std::vector<uint32_t> taskQ;
-            uint64_t cellBytes = 0, cmBytes = 0, nWeights = 0, nColumns = 0, scratch = 0;
-            uint32_t maxRows = 1;
-            for (uint32_t x = 0; x < nG; x++) {
-                const Prepared &P = prep[x];
-                if (P.nRows == 0) continue;
-                R2pTaskH t;
-                t.nRows = P.nRows;
-                t.L = (uint32_t) (qOff[g0 + x + 1] - qOff[g0 + x]);
-                t.stride = P.stride;
-                t.rowStride = (P.nRows + 63) / 64 * 64;
-                t.cellOff = cellBytes;
-                t.cmOff = cmBytes;
-                t.weightOff = nWeights;
-                t.colOff = nColumns;
-                t.scratchOff = scratch;
-                cellBytes += (uint64_t) P.nRows * P.stride;
-                cmBytes += (uint64_t) t.L * t.rowStride;
-                nWeights += P.nRows;
-                nColumns += t.L;
-                scratch += (uint64_t) (t.L + 1) * 24;
-                maxRows = std::max(maxRows, P.nRows);
-                tasks.push_back(t);
-                taskQ.push_back(g0 + x);
-            }
+            WeightsStage S;
+            const int rc = r2pWeightsOnDevice(ctx, prep, background, S);
+            if (rc != SD_OK) return rc;
+            const std::vector<R2pTaskH> &tasks = S.tasks;
+            const float *freq = S.freq.get(), *eff = S.eff.get();
             if (!tasks.empty()) {
-                // (raw arrays: every byte is written before it is read, and zeroing half a gigabyte per group is time)
-                std::unique_ptr<char[]> cells(new char[cellBytes + 64]);
-                std::unique_ptr<float[]> freq(new float[nColumns * kResidues + 1]), eff(new float[nColumns + 1]);
-                std::vector<float> gw(nWeights + 1), table;
-#pragma omp parallel for schedule(dynamic, 16)
-                for (size_t k = 0; k < tasks.size(); k++) {
-                    const Prepared &P = prep[taskQ[k] - g0];
-                    memcpy(&cells[tasks[k].cellOff], P.cells.data(), P.cells.size());
-                    memcpy(&gw[tasks[k].weightOff], P.gw.data(), P.gw.size() * sizeof(float));
-                }
-                const uint32_t rcpN = (maxRows + 1) * 20 + 8;
-                reciprocalTable(table, rcpN);
-                // launch order: the longest alignments first -- the work per alignment grows with the square of its columns, and the
-                // batch is as slow as its last workgroup (the offsets into the staging arrays travel with a task)
-                std::vector<uint32_t> ord(tasks.size());
-                for (size_t k = 0; k < ord.size(); k++) ord[k] = (uint32_t) k;
-                std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
-                    if (tasks[x].L != tasks[y].L) return tasks[x].L > tasks[y].L;
-                    return tasks[x].nRows > tasks[y].nRows;
-                });
-                std::vector<R2pTaskH> launch(tasks.size());
-                for (size_t k = 0; k < ord.size(); k++) launch[k] = tasks[ord[k]];
-                const double tB0 = omp_get_wtime();
-                const int rc = sdR2pColumnWeightsDevice(ctx, (uint32_t) tasks.size(), launch.data(), cells.get(), cellBytes, cmBytes, gw.data(),
-                                                        nWeights, nColumns, scratch, table.data(), rcpN, background, freq.get(), eff.get());
-                if (rc != SD_OK) return rc;
-                const double tB1 = omp_get_wtime();
                 if (dbg)
                     fprintf(stderr, "[r2p] group of %u centres: %.1f MB cells, %llu rows; build + filter %.2f s, staging %.2f s, device %.2f s\n", nG,
-                            cellBytes / 1e6, (unsigned long long) nWeights, tA1 - tA0, tB0 - tA1, tB1 - tB0);
+                            S.cellBytes / 1e6, (unsigned long long) S.nWeights, tA1 - tA0, S.stagingSeconds, S.deviceSeconds);
 #pragma omp parallel
                 {
                     ProfileScratch w;
 #pragma omp for schedule(dynamic, 8)
                     for (size_t k = 0; k < tasks.size(); k++) {
-                        const uint32_t q = taskQ[k];
+                        const uint32_t q = g0 + S.taskOf[k];
                         const int L = (int) tasks[k].L;
                         w.frequency.assign((size_t) (L + 2) * kResidues, 0.0f);
                         memcpy(w.frequency.data(), &freq[tasks[k].colOff * kResidues], (size_t) L * kResidues * sizeof(float));

@@ -237,7 +237,9 @@ def test_result2profile_sequence_weights_on_the_device(gpu):
     in the reference's summation order) gives the bytes of the host implementation for all 5 898 regression queries -- and, where
     the library travelled, of the reference's own MultipleAlignment / MsaFilter / PSSMCalculator classes run on this box
     (oracle/_ref/libsdref_r2p.so: the approximate reciprocal differs between CPU models, so the comparison is made where the
-    bytes are produced) -- plus the parameter corners and alignments that are deeper than the regression input's"""
+    bytes are produced) -- plus the parameter corners and alignments that are deeper than the regression input's.  The wg=1 corner
+    never reaches the device (global weights are a host computation also with a context; tests/test_gpu_r2p_weights.py asserts that
+    no kernel is launched): its loop compares the host with the host.  The kernel's paths one by one: tests/test_gpu_r2p_weights.py"""
     import sys
     sys.path.insert(0, os.path.dirname(__file__))
     from test_result2profile import _load, _edges
