@@ -281,6 +281,16 @@ int sd_target_sample_check(sd_ctx *ctx, const sd_target *t, const uint32_t *kmer
 int sd_target_download(sd_ctx *ctx, const sd_target *t, uint64_t *nEntries, uint64_t *tableSize, uint8_t *masked, uint64_t *starts,
                        uint32_t *entrySeq, uint16_t *entryPos);
 void sd_target_destroy(sd_target *t);
+/* An upper bound, in bytes, of the device memory that building a target of nSeq sequences / nResidues residues with
+ * sd_target_build takes at its peak (the tables that stay resident -- 2-mer / 3-mer matrices, masked residues, list starts,
+ * entries -- plus the scratch of the build's largest phase: masking, record sort or list-start scan) -- what the target split
+ * (`prefilter --split 0`, --split-mode 2) compares with the free device memory.  It assumes the worst case of one index record
+ * per residue, counts every allocation rounded up to a 2 MiB granule and adds 32 MiB for the runtime's own first-use allocations.
+ * 0 for a k other than 6 or 7. */
+uint64_t sd_target_footprint(int kmerSize, uint64_t nSeq, uint64_t nResidues);
+/* the device memory sd_target_build actually held at the fullest point of each of its phases while it built `t` (the drop of
+ * hipMemGetInfo's free bytes since the call began; 0 for a target made by sd_target_create*) */
+int sd_target_build_peak(const sd_target *t, uint64_t *bytes);
 
 /* Replaces the per-query loop body of Prefiltering::runSplit (Prefiltering.cpp:817-886), i.e.
  * QueryMatcher::matchQuery (QueryMatcher.cpp:85) + the coverage pre-filter, for nQ queries at once.
@@ -440,6 +450,17 @@ int sd_host_ext_matrix(sd_host *h, int wordLen, const int16_t **score, const uin
 int sd_host_kmer_threshold(float sensitivity, int kmerSize);
 /* IndexTable::computeKmerSize (M/src/prefiltering/IndexTable.h:439-449): 6 below 3.35e9 target residues, else 7 */
 int sd_host_auto_kmer_size(uint64_t targetResidues);
+/* The plan of a target split (`prefilter --split N --split-mode 0`; Prefiltering::setupSplit, Prefiltering.cpp:351-361, and
+ * DBReader::decomposeDomainByAminoAcid for every rank, DBReader.cpp:1216-1257).
+ *   entryLengths[nEntries]: the length column of the target DB's index file (sequence length + 2) in the order of
+ *                           DBReader::index, i.e. by key -- the reader's id order whenever the data file is in key order too
+ *   nSplits >= 1; maxSeqs: --max-seqs; kmerSize: -k (0 = automatic); residues: DBReader::getAminoAcidDBSize
+ * dbFrom[nSplits] / dbSize[nSplits]: first entry and number of entries of every split (dbSize 0: the split is skipped,
+ * Prefiltering.cpp:736-738); *listLen: the result list length of one split, max(1, L / N + size_t(4 sqrt(L / N))) with
+ * L = min(maxSeqs, nEntries) for N > 1 and L itself for N = 1; *kmerSizeOut: kmerSize, or for 0 the automatic size of
+ * residues / N.  SD_EINVAL for nSplits = 0 or nSplits larger than the sum of entryLengths (where the reference exits). */
+int sd_host_split_plan(const uint64_t *entryLengths, uint64_t nEntries, uint32_t nSplits, uint64_t maxSeqs, int kmerSize,
+                       uint64_t residues, uint64_t *dbFrom, uint64_t *dbSize, uint64_t *listLen, int *kmerSizeOut);
 unsigned sd_host_bin_size(uint64_t dbSize, uint64_t l2CacheSize); /* l2CacheSize 0 = sysconf of this host */
 /* the (query, target) pair list Alignment::run walks (Alignment.cpp:346-379), from sd_prefilter_batch's row-per-query
  * output; returns the number of pairs (pairQ / pairT NULL: count only) */

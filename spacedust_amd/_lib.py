@@ -147,6 +147,10 @@ def load():
         'sd_host_ext_matrix': (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_uint32)]),
         'sd_host_kmer_threshold': (C.c_int, [C.c_float, C.c_int]),
         'sd_host_auto_kmer_size': (C.c_int, [C.c_uint64]),
+        'sd_host_split_plan': (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_int)]),
+        'sd_target_footprint': (C.c_uint64, [C.c_int, C.c_uint64, C.c_uint64]),
+        'sd_target_build_peak': (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
         'sd_host_bin_size': (C.c_uint, [C.c_uint64, C.c_uint64]),
         'sd_host_pair_list': (C.c_uint64, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
         'sd_host_lgamma_table': (C.c_int, [_vp, C.c_uint32]),

@@ -98,6 +98,19 @@ class Host:
     def bin_size(self, db_size, l2=0):
         return self.L.sd_host_bin_size(db_size, l2)
 
+    def split_plan(self, entry_lengths, n_splits, max_seqs=300, k=0, residues=None):
+        """sd_host_split_plan: the target split of `prefilter --split N --split-mode 0`.  entry_lengths: the length column of the
+        target DB's index (sequence length + 2) in key order; residues defaults to sum(entry_lengths - 2).
+        Returns dict(db_from, db_size [n_splits], list_len, k)."""
+        lens = np.ascontiguousarray(entry_lengths, np.uint64)
+        if residues is None:
+            residues = int(lens.sum()) - 2 * len(lens)
+        db_from, db_size = np.zeros(max(n_splits, 1), np.uint64), np.zeros(max(n_splits, 1), np.uint64)
+        list_len, k_out = C.c_uint64(), C.c_int()
+        _check(None, self.L.sd_host_split_plan(ptr(lens), len(lens), n_splits, int(max_seqs), int(k), int(residues), ptr(db_from), ptr(db_size),
+                                               C.byref(list_len), C.byref(k_out)), 'sd_host_split_plan')
+        return dict(db_from=db_from, db_size=db_size, list_len=int(list_len.value), k=int(k_out.value))
+
     def lgamma_table(self, n):
         out = np.zeros(n, np.float64)
         self.L.sd_host_lgamma_table(ptr(out), n)
@@ -562,6 +575,12 @@ class Target:
         self.build_stats = dict(entries=int(stats[0]), masked_residues=int(stats[1]), passes=int(stats[2]), records=int(stats[3]))
         return self
 
+    def build_peak(self):
+        """sd_target_build_peak: the device bytes sd_target_build held at the fullest point of its phases"""
+        b = C.c_uint64()
+        _check(self.ctx.h, self.ctx.L.sd_target_build_peak(self.h, C.byref(b)), 'sd_target_build_peak')
+        return int(b.value)
+
     def sample_check(self, host, residues, offsets, kmer_thr, runs=24, run_len=400, seed=3, mask=True, mask_prob=0.9):
         """an index too large to download against the host builder on a sample: `runs` runs of `run_len` consecutive sequences are
         masked and indexed on the host (sd_host_index_build of the sample alone: masking and k-mer collection are per sequence);
@@ -622,6 +641,11 @@ class Target:
                 self.ctx.L.sd_target_destroy(self.h)
         except Exception:
             pass
+
+
+def target_footprint(k, n_seq, n_residues):
+    """sd_target_footprint: upper bound, in bytes, of the device memory building and holding a target of that size takes"""
+    return int(_lib.load().sd_target_footprint(int(k), int(n_seq), int(n_residues)))
 
 
 def prefilter_params(host, n_targets, kmer_thr=112, max_hits=300, min_diag=15, bin_size=None, cov_mode=2,

@@ -83,9 +83,147 @@ int deviceOf(const Args &a) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
-int prefilterSetupFromArgs(const Args &a, sd_host *host, const SeqDb &tdb, bool profileQueries, PrefSetup &s) {
+// ---------------------------------------------------------------------------------------------------------------
+// --split / --split-mode / --split-memory-limit (Prefiltering::setupSplit, Prefiltering.cpp:273-377).  The reference decides by host
+// RAM; here the memory that matters is the device's: sd_target_footprint against --split-memory-limit or 0.9 x the free device memory.
+namespace {
+
+// ByteParser::parse (M/src/commons/ByteParser.cpp): digits with an optional B / K / M / G / T suffix, powers of 1024
+bool parseBytes(const std::string &t, uint64_t &out) {
+    if (t.empty()) return false;
+    size_t i = 0;
+    while (i < t.size() && t[i] >= '0' && t[i] <= '9') i++;
+    if (i == 0 || t.size() - i > 1) return false;
+    uint64_t v = strtoull(t.substr(0, i).c_str(), nullptr, 10), mul = 1ull << 20;   // no suffix: megabytes, as ByteParser reads it
+    if (i < t.size()) {
+        switch (t[i]) {
+            case 'b': case 'B': mul = 1; break;
+            case 'k': case 'K': mul = 1ull << 10; break;
+            case 'm': case 'M': mul = 1ull << 20; break;
+            case 'g': case 'G': mul = 1ull << 30; break;
+            case 't': case 'T': mul = 1ull << 40; break;
+            default: return false;
+        }
+    }
+    out = v * mul;
+    return true;
+}
+
+std::string formatBytes(uint64_t b) {   // ByteParser::format: the largest unit that leaves a value >= 1
+    static const char unit[] = {'B', 'K', 'M', 'G', 'T'};
+    int u = 0;
+    uint64_t v = b;
+    while (u < 4 && v >= 1024) {
+        v /= 1024;
+        u++;
+    }
+    return v ? std::to_string(v) + unit[u] : "0";
+}
+
+}  // namespace
+
+int resolveSplit(const Args &a, const sddb::Reader &target, uint64_t residues, uint64_t nQueries, sd_ctx *ctx, bool residentTarget, SplitPlan &p) {
+    const long long split = a.integer("--split", 0), mode = a.integer("--split-mode", 2);
+    if (split < 0) return fail("--split " + std::to_string(split) + ": a number of splits, or 0 to choose it from the device memory");
+    if (mode < 0 || mode > 2) return fail("Invalid split mode: " + std::to_string(mode));
+    const uint64_t nSeq = target.size();
+    const int kArg = (int) a.integer("-k", 0);
+    // DBReader::index is in key order: the plan sums the length column in that order (DBReader.cpp:1243-1250)
+    std::vector<uint64_t> lengths(nSeq);
+    {
+        std::vector<std::pair<uint32_t, uint32_t> > byKey(nSeq);
+        for (uint64_t i = 0; i < nSeq; i++) byKey[i] = std::make_pair(target.key(i), (uint32_t) i);
+        std::sort(byKey.begin(), byKey.end());
+        for (uint64_t i = 0; i < nSeq; i++) lengths[i] = target.entryLength(byKey[i].second);
+    }
+    const uint64_t maxSeqs = (uint64_t) std::max<long long>(0, a.integer("--max-seqs", 300));
+    auto planFor = [&](uint32_t n) -> int {
+        p.from.assign(n, 0);
+        p.size.assign(n, 0);
+        return sd_host_split_plan(lengths.data(), nSeq, n, maxSeqs, kArg, residues, p.from.data(), p.size.data(), &p.listLen, &p.k);
+    };
+    // the largest per-split footprint of an n-way target split (residues of a split: its length column minus the "\n\0" per entry)
+    std::vector<uint64_t> cum(nSeq + 1, 0);
+    for (uint64_t i = 0; i < nSeq; i++) cum[i + 1] = cum[i] + (lengths[i] >= 2 ? lengths[i] - 2 : 0);
+    auto footprintFor = [&](uint32_t n, uint64_t &bytes) -> int {
+        if (int rc = planFor(n)) return rc;
+        bytes = 0;
+        for (uint32_t s = 0; s < n; s++)
+            if (p.size[s]) bytes = std::max(bytes, sd_target_footprint(p.k, p.size[s], cum[p.from[s] + p.size[s]] - cum[p.from[s]]));
+        return 0;
+    };
+    p.n = 1;
+    p.target = false;
+    const bool detect = split == 0 || mode == 2;
+    uint64_t limit = 0, whole = 0, perSplit = 0;
+    bool fits = true;
+    if (detect && !residentTarget) {
+        const std::string lim = a.str("--split-memory-limit", "0");
+        if (lim != "0" && !lim.empty()) {
+            if (!parseBytes(lim, limit)) return fail("--split-memory-limit " + lim + ": a number with an optional B/K/M/G/T suffix");
+        } else {
+            sd_ctx *own = nullptr;
+            if (!ctx) {
+                const int rc = sd_ctx_create(deviceOf(a), &own);
+                if (rc != SD_OK) return fail("no usable HIP device (sd_ctx_create returned " + std::to_string(rc) + "); this path has no CPU fallback");
+            }
+            uint64_t freeB = 0, totalB = 0;
+            const int rc = sd_device_memory(ctx ? ctx : own, &freeB, &totalB);
+            if (own) sd_ctx_destroy(own);
+            if (rc != SD_OK) return fail("sd_device_memory failed (" + std::to_string(rc) + ")");
+            limit = (uint64_t) (0.9 * (double) freeB);   // the reference's factor (Prefiltering.cpp:281,308)
+        }
+        if (footprintFor(1, whole)) return fail("sd_host_split_plan failed");
+        fits = whole <= limit;
+    }
+    if (split > 1 && (uint64_t) split > (mode == 1 || (mode == 2 && fits) ? nQueries : nSeq))   // Prefiltering.cpp:346-349
+        return fail("split was set to " + std::to_string(split) + " but the db to split has only " +
+                    std::to_string(mode == 1 || (mode == 2 && fits) ? nQueries : nSeq) + " sequences. Please run with default paramerters");
+    if (mode == 1 && !fits)   // :282-286
+        return fail("--split-mode was set to query-split (1) but memory limit requires target-split. Please use a device with more memory or run "
+                    "with default --split-mode setting.");
+    if (split == 0) {
+        if (!fits) {
+            // the smallest N whose largest split fits.  No split is smaller than one sequence, so a limit below that footprint ends the
+            // search before it starts; otherwise the loop ends at N = nSeq at the latest (in practice near whole / limit)
+            const int kMin = kArg ? kArg : 6;
+            uint32_t n = 0;
+            if (sd_target_footprint(kMin, 1, 1) <= limit)
+                for (uint32_t c = 2; c <= nSeq; c++) {
+                    uint64_t b = 0;
+                    if (footprintFor(c, b)) return fail("sd_host_split_plan failed");
+                    if (b <= limit) {
+                        n = c;
+                        perSplit = b;
+                        break;
+                    }
+                }
+            if (n == 0) return fail("Cannot fit databases into " + formatBytes(limit) + ". Please use a device with more memory.");
+            p.n = (int) n;
+            p.target = true;
+        }
+    } else {
+        p.n = (int) split;
+        p.target = split > 1 && (mode == 0 || (mode == 2 && !fits));
+        if (p.target && detect && !residentTarget && footprintFor((uint32_t) split, perSplit)) return fail("sd_host_split_plan failed");
+    }
+    // the automatic k-mer size follows the number of splits in either mode (:351-354); the list length shrinks in a target split only
+    if (planFor((uint32_t) p.n)) return fail("split was set to " + std::to_string(p.n) + ": more splits than the target DB has bytes");
+    if (!p.target) {
+        const int k = p.k;
+        planFor(1);
+        p.k = k;
+    }
+    if (p.n > 1) info(a, "%s split mode. Searching through %d splits\n", p.target ? "Target" : "Query", p.n);
+    if (detect && !residentTarget)
+        info(a, "Estimated device memory of the target index: %s per split (limit %s)\n",
+             formatBytes(p.target ? perSplit : whole).c_str(), formatBytes(limit).c_str());
+    return 0;
+}
+
+int prefilterSetupFromArgs(const Args &a, sd_host *host, const SeqDb &tdb, bool profileQueries, PrefSetup &s, int kOverride) {
     // parameters the way Prefiltering's constructor derives them (Prefiltering.cpp:180-215,1005-1065)
-    s.k = (int) a.integer("-k", 0);
+    s.k = kOverride ? kOverride : (int) a.integer("-k", 0);
     if (s.k == 0) s.k = sd_host_auto_kmer_size(tdb.totalResidues());
     if (s.k != 6 && s.k != 7) return fail("-k " + std::to_string(s.k) + ": k-mer sizes 6 and 7 are implemented");
     const float sens = (float) a.real("-s", 4.0);
@@ -114,6 +252,168 @@ int prefilterSetupFromArgs(const Args &a, sd_host *host, const SeqDb &tdb, bool 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// `prefilter --split N --split-mode 0` (Prefiltering::runSplits / runSplit / mergeTargetSplits, Prefiltering.cpp:662-951, 379-479): per
+// non-empty split its own index is built on the device, every query chunk is searched against it with the per-split list length, and
+// the index is destroyed before the next one is built.  A query's entry is the concatenation of its per-split lists, sorted by
+// hit_t::compareHitsByScoreAndId and not cut.  The per-split rows wait in host memory (12 bytes per hit) where the reference keeps them in
+// one temporary DB per split.
+namespace {
+
+// One chunk [c0, c1) of queries against one target that holds the ids [dbFrom, dbFrom + dbSize) of the target DB (the whole DB, or
+// one split of it): identity ids, composition bias, the device call.  hits: row i at i * par.maxHitsPerQuery, ids relative to dbFrom.
+struct QueryChunk {
+    std::vector<sd_hit> hits;
+    std::vector<uint32_t> counts, ident;
+    std::vector<int8_t> diagBias;
+    std::vector<int16_t> kmerBias;
+    std::vector<uint64_t> off;
+    int run(sd_ctx *ctx, sd_host *host, const sd_target *target, const sd_prefilter_params &par, const PrefSetup &PS, const SeqDb &qdb,
+            const SeqDb &tdb, bool sameDb, uint32_t c0, uint32_t c1, uint64_t dbFrom, uint64_t dbSize) {
+        const uint32_t nq = c1 - c0;
+        const uint64_t r0 = qdb.offsets[c0], r1 = qdb.offsets[c1];
+        off.resize((size_t) nq + 1);
+        for (uint32_t i = 0; i <= nq; i++) off[i] = qdb.offsets[c0 + i] - r0;
+        ident.resize(nq);
+        for (uint32_t i = 0; i < nq; i++) {
+            uint64_t id = UINT32_MAX;
+            if (sameDb) id = c0 + i;
+            else if (PS.includeIdentity) {
+                const size_t t = tdb.rd.idOfKey(qdb.keys[c0 + i]);
+                if (t != SIZE_MAX) id = t;
+            }
+            // only the split that holds the query's own target gets the id, relative to dbFrom (Prefiltering.cpp:824-837)
+            ident[i] = id != UINT32_MAX && id >= dbFrom && id < dbFrom + dbSize ? (uint32_t) (id - dbFrom) : UINT32_MAX;
+        }
+        hits.resize((size_t) nq * par.maxHitsPerQuery);
+        counts.assign(nq, 0);
+        if (qdb.profile)
+            return sd_prefilter_profile_batch(ctx, target, &par, nq, qdb.residues.data() + r0, off.data(), qdb.sortedScore.data() + r0 * 20,
+                                              qdb.sortedIndex.data() + r0 * 20, qdb.alnProfile.data() + r0 * 21, ident.data(), hits.data(),
+                                              counts.data(), nullptr);
+        diagBias.assign(r1 - r0 + 1, 0);
+        kmerBias.assign(r1 - r0 + 1, 0);
+        if (PS.compBias) sd_host_comp_bias(host, qdb.residues.data() + r0, off.data(), nq, PS.k, nullptr, diagBias.data(), kmerBias.data());
+        return sd_prefilter_batch(ctx, target, &par, nq, qdb.residues.data() + r0, off.data(), kmerBias.data(), diagBias.data(), ident.data(),
+                                  hits.data(), counts.data(), nullptr);
+    }
+};
+
+struct SplitRow {
+    uint32_t key;
+    int32_t score;
+    int16_t diagonal;
+};
+
+int prefilterTargetSplit(const Args &a, sd_host *host, sd_ctx *ctx, const SeqDb &qdb, const SeqDb &tdb, bool sameDb, const PrefSetup &PS,
+                         const SplitPlan &plan, Lap &lap) {
+    const int k = PS.k;
+    info(a, "Index table k-mer threshold: %d at k-mer size %d\n", PS.kmerThr, k);
+    if (sddb::fileExists(a.pos[1] + ".idx.index")) info(a, "Index file not used: a target split builds the index of every split on the device\n");
+    const int16_t *s2, *s3;
+    const uint16_t *i2, *i3;
+    uint32_t sz2, sz3;
+    sd_host_ext_matrix(host, 2, &s2, &i2, &sz2);
+    sd_host_ext_matrix(host, 3, &s3, &i3, &sz3);
+    double ratios[21 * 21];
+    int8_t self[21];
+    sd_host_index_tables(host, ratios, self);
+    const uint32_t chunk = (uint32_t) std::max<long long>(1, a.integer("--chunk-queries", 16384));
+    const int nSplits = plan.n;
+    std::vector<std::vector<SplitRow> > rows((size_t) nSplits);             // per split: the rows of all queries, query after query
+    std::vector<std::vector<uint32_t> > rowCount((size_t) nSplits);         // per split: rows of every query
+    std::vector<uint8_t> failed(qdb.n, 0);
+    QueryChunk qc;
+    std::vector<uint64_t> tOff;
+    uint64_t notComputed = 0;
+    for (int sp = 0; sp < nSplits; sp++) {
+        info(a, "Process prefiltering step %d of %d\n", sp + 1, nSplits);
+        const uint64_t dbFrom = plan.from[sp], dbSize = plan.size[sp];
+        if (dbSize == 0) continue;   // Prefiltering.cpp:736-738
+        info(a, "Target db start %llu to %llu\n", (unsigned long long) (dbFrom + 1), (unsigned long long) (dbFrom + dbSize));
+        // the split's sequences as a target of their own: ids relative to dbFrom
+        const uint64_t t0 = tdb.offsets[dbFrom];
+        tOff.resize(dbSize + 1);
+        for (uint64_t i = 0; i <= dbSize; i++) tOff[i] = tdb.offsets[dbFrom + i] - t0;
+        TargetH target;   // never resident: destroyed at the end of this split
+        uint64_t st[4] = {0, 0, 0, 0};
+        int rc = sd_target_build(ctx, k, PS.indexThr, PS.mask ? 1 : 0, PS.maskProb, tdb.residues.data() + t0, tOff.data(), (uint32_t) dbSize, ratios, self,
+                                 s2, i2, s3, i3, &target.t, st);
+        if (rc != SD_OK) {
+            if (rc == SD_ENOMEM || strstr(sd_last_error(ctx), "out of memory"))
+                fprintf(stderr, "sdgpu prefilter: the index of split %d of %d did not fit the device memory; raise --split or let --split 0 choose\n",
+                        sp + 1, nSplits);
+            return failCtx(ctx, rc, "sd_target_build");
+        }
+        info(a, "Index statistics\nEntries:          %llu\n", (unsigned long long) st[0]);
+        lap.mark("split: index build");
+        sd_prefilter_params par = PS.par;
+        par.maxHitsPerQuery = (int32_t) std::min<uint64_t>(plan.listLen, dbSize);   // (a list holds no more rows than the split has sequences)
+        // QueryMatcher is constructed with the split's dbSize (Prefiltering.cpp:797-799)
+        if (!a.has("--bin-size")) par.binSize = sd_host_bin_size(dbSize, (uint64_t) a.integer("--l2-cache-size", 0));
+        rowCount[sp].assign(qdb.n, 0);
+        for (uint32_t c0 = 0; c0 < qdb.n; c0 += chunk) {
+            const uint32_t c1 = std::min(qdb.n, c0 + chunk), nq = c1 - c0;
+            rc = qc.run(ctx, host, target.t, par, PS, qdb, tdb, sameDb, c0, c1, dbFrom, dbSize);
+            std::vector<uint32_t> &counts = qc.counts;
+            if (rc != SD_OK) return failCtx(ctx, rc, "sd_prefilter_batch");
+            for (uint32_t i = 0; i < nq; i++) {
+                if (counts[i] == UINT32_MAX) {   // per-query error slot of sd_prefilter_batch: not computed
+                    if (!failed[c0 + i]) {
+                        if (notComputed < 5) fprintf(stderr, "sdgpu prefilter: query %u was not computed: %s\n", qdb.keys[c0 + i], sd_last_error(ctx));
+                        notComputed++;
+                    }
+                    failed[c0 + i] = 1;
+                    counts[i] = 0;
+                }
+                const sd_hit *row = qc.hits.data() + (size_t) i * par.maxHitsPerQuery;
+                // the split's ids become ids of the whole DB, then keys (Prefiltering.cpp:848-850)
+                for (uint32_t x = 0; x < counts[i]; x++)
+                    rows[sp].push_back(SplitRow{tdb.keys[dbFrom + row[x].seqId], row[x].score, (int16_t) row[x].diagonal});
+                rowCount[sp][c0 + i] = counts[i];
+            }
+        }
+        lap.mark("split: query passes");
+    }
+    // mergeTargetSplits: per query the lists of the splits one after the other, sorted, nothing cut
+    std::string err, text;
+    sddb::Writer out;
+    if (!out.open(a.pos[2], sddb::DBTYPE_PREFILTER_RES, &err)) return fail(err);
+    std::vector<size_t> cursor((size_t) nSplits, 0);
+    std::vector<SplitRow> merged;
+    uint64_t totalHits = 0;
+    char line[64];
+    for (uint32_t q = 0; q < qdb.n; q++) {
+        merged.clear();
+        for (int sp = 0; sp < nSplits; sp++) {
+            if (rowCount[sp].empty()) continue;
+            merged.insert(merged.end(), rows[sp].begin() + cursor[sp], rows[sp].begin() + cursor[sp] + rowCount[sp][q]);
+            cursor[sp] += rowCount[sp][q];
+        }
+        if (failed[q]) merged.clear();   // a query one split could not compute is written empty, as in the one-index run
+        std::stable_sort(merged.begin(), merged.end(), [](const SplitRow &x, const SplitRow &y) {   // hit_t::compareHitsByScoreAndId
+            if (abs(x.score) != abs(y.score)) return abs(x.score) > abs(y.score);
+            return x.key < y.key;
+        });
+        text.clear();
+        for (const SplitRow &r : merged) {
+            const int len = snprintf(line, sizeof(line), "%u\t%d\t%d\n", r.key, r.score, (int) r.diagonal);
+            text.append(line, (size_t) len);
+        }
+        totalHits += merged.size();
+        if (!out.write(qdb.keys[q], text.data(), text.size())) return fail("cannot write " + a.pos[2]);
+    }
+    if (!out.close(&err)) return fail(err);
+    lap.mark("merge + write");
+    info(a, "%llu prefilter hits written for %u queries\n", (unsigned long long) totalHits, qdb.n);
+    if (notComputed)
+        return fail(std::to_string(notComputed) + " queries need the reference's double-overflow route (or have >= 2^32 index hits) and were "
+                    "written as empty entries; every other entry is complete");
+    return 0;
+}
+
+}  // namespace
+
 int prefilterModule(const Args &a) {
     if (a.pos.size() != 3) return fail("usage: prefilter <queryDB> <targetDB> <resultDB> [options]");
     if (int rc = checkCommon(a)) return rc;
@@ -126,11 +426,9 @@ int prefilterModule(const Args &a) {
     if (a.integer("--target-search-mode", 0) != 0) return fail("--target-search-mode 1 is not supported");
     if (a.integer("--mask-lower-case", 0) != 0 || a.integer("--mask-n-repeat", 0) != 0)
         return fail("--mask-lower-case / --mask-n-repeat are not supported");
-    if (a.integer("--split", 0) > 1) return fail("--split > 1: the whole target index is resident in HBM here; run with --split 0 or 1");
     if (a.multi("--alph-size", "aa", "21") != "21") return fail("--alph-size aa:21 only");
     if (a.real("--comp-bias-corr-scale", 1.0) != 1.0) return fail("--comp-bias-corr-scale 1 only");
     if (a.has("--taxon-list") && !a.str("--taxon-list", "").empty()) return fail("--taxon-list is not supported");
-    const bool compBias = a.integer("--comp-bias-corr", 1) != 0;
     const int threads = threadsOf(a);
 
     Lap lap("prefilter");
@@ -152,17 +450,33 @@ int prefilterModule(const Args &a) {
     info(a, "Query database size: %u type: %s\nTarget database size: %u type: Aminoacid\n", qdb->n,
          qdb->profile ? "Profile" : "Aminoacid", tdb->n);
 
-    PrefSetup PS;
-    if (int rcS = prefilterSetupFromArgs(a, host.h, *tdb, qdb->profile, PS)) return rcS;
-    const int k = PS.k, kmerThr = PS.kmerThr;
-    const bool mask = PS.mask, includeIdentity = PS.includeIdentity;
-    const double maskProb = PS.maskProb;
-
     CtxH ctx;
     int rc = ctx.open(deviceOf(a));
     if (rc != SD_OK) return fail("no usable HIP device (sd_ctx_create returned " + std::to_string(rc) + "); this path has no CPU fallback");
-
     lap.mark("context");
+
+    // --split: one index for the whole target (today's path, below) or one per target split (prefilterTargetSplit)
+    SplitPlan plan;
+    {
+        bool residentTarget = false;
+        if (resident().enabled) {   // a workflow that holds this DB's index on this device has nothing left to decide
+            char dsuf[24];
+            snprintf(dsuf, sizeof(dsuf), "|%d", deviceOf(a));
+            const std::string pfx = a.pos[1] + "|", suf = dsuf;
+            for (const auto &kv : resident().targets)
+                if (kv.first.compare(0, pfx.size(), pfx) == 0 && kv.first.size() >= suf.size() &&
+                    kv.first.compare(kv.first.size() - suf.size(), suf.size(), suf) == 0)
+                    residentTarget = true;
+        }
+        if (int rcP = resolveSplit(a, tdb->rd, tdb->totalResidues(), qdb->n, ctx.c, residentTarget, plan)) return rcP;
+    }
+    PrefSetup PS;
+    if (int rcS = prefilterSetupFromArgs(a, host.h, *tdb, qdb->profile, PS, plan.k)) return rcS;
+    if (plan.target) return prefilterTargetSplit(a, host.h, ctx.c, *qdb, *tdb, sameDb, PS, plan, lap);
+    const int k = PS.k, kmerThr = PS.kmerThr;
+    const bool mask = PS.mask;
+    const double maskProb = PS.maskProb;
+
     // target side: TARGET.idx when a createindex file with matching parameters lies next to the DB (PrefilteringIndexReader
     // layout, sd_mod_index.cpp), else IndexBuilder::fillDatabase on the device (sd_target_build: mask + lists); resident in HBM afterwards.
     // Profile searches index every k-mer (Prefiltering.cpp:525-527)
@@ -216,7 +530,12 @@ int prefilterModule(const Args &a) {
         uint64_t st[4] = {0, 0, 0, 0};
         rc = sd_target_build(ctx.c, k, indexThr, mask ? 1 : 0, maskProb, tdb->residues.data(), tdb->offsets.data(), tdb->n, ratios, self, s2, i2,
                              s3, i3, &target.t, st);
-        if (rc != SD_OK) return failCtx(ctx.c, rc, "sd_target_build");
+        if (rc != SD_OK) {
+            if (rc == SD_ENOMEM || strstr(sd_last_error(ctx.c), "out of memory"))
+                fprintf(stderr, "sdgpu prefilter: the target index did not fit the device memory; --split 0 chooses a number of target splits "
+                                "that does, --split N --split-mode 0 sets it\n");
+            return failCtx(ctx.c, rc, "sd_target_build");
+        }
         nEntries = st[0];
         maskedRes = st[1];
     } else if (got != 0) {
@@ -264,42 +583,13 @@ int prefilterModule(const Args &a) {
     if (!out.open(a.pos[2], sddb::DBTYPE_PREFILTER_RES, &err)) return fail(err);
 
     const uint32_t chunk = (uint32_t) std::max<long long>(1, a.integer("--chunk-queries", 16384));
-    std::vector<sd_hit> hits;
-    std::vector<uint32_t> counts, ident;
-    std::vector<int8_t> diagBias;
-    std::vector<int16_t> kmerBias;
-    std::vector<uint64_t> off;
+    QueryChunk qc;
     std::string text;
     uint64_t totalHits = 0, notComputed = 0;
     for (uint32_t c0 = 0; c0 < qdb->n; c0 += chunk) {
         const uint32_t c1 = std::min(qdb->n, c0 + chunk), nq = c1 - c0;
-        const uint64_t r0 = qdb->offsets[c0], r1 = qdb->offsets[c1];
-        off.resize((size_t) nq + 1);
-        for (uint32_t i = 0; i <= nq; i++) off[i] = qdb->offsets[c0 + i] - r0;
-        ident.resize(nq);
-        for (uint32_t i = 0; i < nq; i++) {
-            uint32_t id = UINT32_MAX;
-            if (sameDb) id = c0 + i;
-            else if (includeIdentity) {
-                const size_t t = tdb->rd.idOfKey(qdb->keys[c0 + i]);
-                if (t != SIZE_MAX) id = (uint32_t) t;
-            }
-            ident[i] = id;
-        }
-        hits.resize((size_t) nq * par.maxHitsPerQuery);
-        counts.assign(nq, 0);
-        if (qdb->profile) {
-            rc = sd_prefilter_profile_batch(ctx.c, target.t, &par, nq, qdb->residues.data() + r0, off.data(),
-                                            qdb->sortedScore.data() + r0 * 20, qdb->sortedIndex.data() + r0 * 20,
-                                            qdb->alnProfile.data() + r0 * 21, ident.data(), hits.data(), counts.data(), nullptr);
-        } else {
-            diagBias.assign(r1 - r0 + 1, 0);
-            kmerBias.assign(r1 - r0 + 1, 0);
-            if (compBias)
-                sd_host_comp_bias(host.h, qdb->residues.data() + r0, off.data(), nq, k, nullptr, diagBias.data(), kmerBias.data());
-            rc = sd_prefilter_batch(ctx.c, target.t, &par, nq, qdb->residues.data() + r0, off.data(), kmerBias.data(),
-                                    diagBias.data(), ident.data(), hits.data(), counts.data(), nullptr);
-        }
+        rc = qc.run(ctx.c, host.h, target.t, par, PS, *qdb, *tdb, sameDb, c0, c1, 0, tdb->n);
+        std::vector<uint32_t> &counts = qc.counts;
         if (rc != SD_OK) return failCtx(ctx.c, rc, "sd_prefilter_batch");
         lap.mark("chunk: bias + device");
         // QueryMatcher::prefilterHitToBuffer (QueryMatcher.h:118-130): targetKey \t score \t (int16) diagonal
@@ -311,7 +601,7 @@ int prefilterModule(const Args &a) {
                 notComputed++;
                 counts[i] = 0;
             }
-            const sd_hit *row = hits.data() + (size_t) i * par.maxHitsPerQuery;
+            const sd_hit *row = qc.hits.data() + (size_t) i * par.maxHitsPerQuery;
             for (uint32_t x = 0; x < counts[i]; x++) {
                 const int len = snprintf(line, sizeof(line), "%u\t%d\t%d\n", tdb->keys[row[x].seqId], row[x].score,
                                          (int) (int16_t) row[x].diagonal);

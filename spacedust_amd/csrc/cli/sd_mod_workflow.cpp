@@ -858,6 +858,53 @@ std::vector<std::string> with(std::vector<std::string> v, std::initializer_list<
     return v;
 }
 
+// --split / --split-mode / --split-memory-limit of a workflow (none given: nothing is read or decided, `s` stays as it is).
+// The plan is resolved once, here (resolveSplit, sd_mod_hot.cpp), and `s` carries its outcome to the steps:
+//   a target split with N > 1: --split N --split-mode 0 for the prefilter step; targetSplit = true tells the workflow to run the module
+//     chain in this process (the streaming pipeline and the in-memory iterations hold ONE index of the whole target);
+//   otherwise (one split, or query-split semantics: the rows of the unsplit run with k taken from residues / N) the split flags are
+//     dropped and -k carries the k-mer size, so every path runs as it does today.
+int workflowSplit(const Args &a, Args &s, bool &targetSplit) {
+    targetSplit = false;
+    if (!a.has("--split") && !a.has("--split-mode") && !a.has("--split-memory-limit")) return 0;
+    if (a.integer("--prefilter-mode", 0) == 1) return 0;   // the ungapped prefilter has no index to split
+    if (a.pos.size() != 4) return 0;                         // the workflow prints its usage line
+    std::string err;
+    sddb::Reader trd, qrd;
+    if (!trd.open(a.pos[1], sddb::Reader::USE_INDEX, sddb::Reader::NOSORT, &err)) return fail(err);
+    uint64_t nQ = trd.size();
+    if (a.pos[0] != a.pos[1]) {
+        if (!qrd.open(a.pos[0], sddb::Reader::USE_INDEX, sddb::Reader::NOSORT, &err)) return fail(err);
+        nQ = qrd.size();
+    }
+    SplitPlan plan;
+    Args quiet = a;   // the prefilter step prints the split lines
+    quiet.opt["-v"] = "0";
+    if (int rc = resolveSplit(quiet, trd, trd.aminoAcidDbSize(), nQ, nullptr, false, plan)) return rc;
+    s.opt.erase("--split");
+    s.opt.erase("--split-mode");
+    if (plan.target) {
+        if (envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1)
+            return fail("a target split (--split " + std::to_string(plan.n) + ") runs on one rank; several ranks shard the query sets against one resident index");
+        s.opt["--split"] = std::to_string(plan.n);
+        s.opt["--split-mode"] = "0";
+        targetSplit = true;
+        info(a, "Target split into %d splits: the modules run one after the other in this process; the streaming pipeline and the in-memory "
+                "iterations need the whole target index resident and are not used\n", plan.n);
+    } else {
+        s.opt.erase("--split-memory-limit");
+        if (plan.n > 1) s.opt["-k"] = std::to_string(plan.k);
+    }
+    return 0;
+}
+
+// the split flags of a resolved target split for the prefilter step (workflowSplit left them in `a`, or nothing)
+std::vector<std::string> withSplit(const Args &a, std::vector<std::string> pref) {
+    for (const char *f : {"--split", "--split-mode", "--split-memory-limit"})
+        if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
+    return pref;
+}
+
 // `search --num-iterations N` (M/src/workflow/Search.cpp:476-518 builds the per-step parameter strings,
 // M/data/workflow/blastpgp.sh:52-140 runs them): iteration 0 with --realign and the profile E-value, prefilter results of
 // later iterations minus what is aligned already, the last alignment with the user's -e, merged into the result DB
@@ -873,6 +920,7 @@ int iterativeSearch(const Args &a, const std::string &Q, const std::string &T, c
                                                   a.str("--mask-prob", "0.9"), "--comp-bias-corr", a.str("--comp-bias-corr", "1")});
     for (const char *f : {"--device", "--bin-size", "--l2-cache-size", "--chunk-queries"})
         if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
+    pref = withSplit(a, pref);
     std::vector<std::string> aln = with(common, {"-a", "1", "--alignment-mode", a.str("--alignment-mode", "2"), "--min-aln-len", a.str("--min-aln-len", "0"),
                                                  "-c", a.str("-c", "0"), "--cov-mode", a.str("--cov-mode", "0"), "--min-seq-id",
                                                  a.str("--min-seq-id", "0"), "--comp-bias-corr", a.str("--comp-bias-corr", "1"),
@@ -984,6 +1032,7 @@ int ungappedAlignSearch(const Args &a, const std::string &Q, const std::string &
     const std::vector<const char *> ungappedOnly = {"--device", "--chunk-queries"};
     for (const char *f : ungapped ? ungappedOnly : kmerOnly)
         if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
+    if (!ungapped) pref = withSplit(a, pref);
     std::vector<std::string> rescore = with(common, {"--rescore-mode", "2", "-e", a.str("-e", "0.001"), "-c", a.str("-c", "0"), "--cov-mode",
                                                      a.str("--cov-mode", "0"), "-a", a.str("-a", "0"),
                                                      "--min-aln-len", a.str("--min-aln-len", "0"), "--seq-id-mode", a.str("--seq-id-mode", "0"),
@@ -1029,6 +1078,7 @@ int altAliSearch(const Args &a, const std::string &Q, const std::string &T, cons
     const std::vector<const char *> ungappedOnly = {"--device", "--chunk-queries"};
     for (const char *f : ungapped ? ungappedOnly : kmerOnly)
         if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
+    if (!ungapped) pref = withSplit(a, pref);
     // the search workflow's alignment mode is 2 (score and coverage, Search.cpp:23)
     std::vector<std::string> aln = with(common, {"--alt-ali", a.str("--alt-ali", "0"), "--alignment-mode", a.str("--alignment-mode", "2"), "-e",
                                                  a.str("-e", "0.001"), "-c", a.str("-c", "0"), "--cov-mode", a.str("--cov-mode", "0"), "-a", a.str("-a", "0"),
@@ -1051,8 +1101,11 @@ int altAliSearch(const Args &a, const std::string &Q, const std::string &T, cons
 
 }  // namespace
 
-int searchModule(const Args &a) {
-    if (int rc = checkPrefilterMode(a)) return rc;
+int searchModule(const Args &a0) {
+    if (int rc = checkPrefilterMode(a0)) return rc;
+    Args a = a0;
+    bool targetSplit = false;
+    if (int rc = workflowSplit(a0, a, targetSplit)) return rc;
     if (a.integer("--alt-ali", 0) != 0) {
         if (a.pos.size() != 4) return fail("usage: search <queryDB> <targetDB> <alignmentDB> <tmpDir> [options]");
         if (int rc = checkAltAli(a, false)) return rc;
@@ -1069,12 +1122,20 @@ int searchModule(const Args &a) {
         if (int rc = checkWorkflowFlags(a)) return rc;
         return iterativeSearch(a, a.pos[0], a.pos[1], a.pos[2], a.pos[3]);
     }
+    if (targetSplit) {
+        // one pass over a split target: `prefilter --split N` then `align`, the chain altAliSearch runs (with --alt-ali 0)
+        if (int rc = checkWorkflowFlags(a)) return rc;
+        return altAliSearch(a, a.pos[0], a.pos[1], a.pos[2], a.pos[3]);
+    }
     return runSearch(a, false);
 }
 
-int clustersearchModule(const Args &a) {
-    if (int rc = checkPrefilterMode(a)) return rc;
-    if (a.integer("--alt-ali", 0) != 0) return checkAltAli(a, true);
+int clustersearchModule(const Args &a0) {
+    if (int rc = checkPrefilterMode(a0)) return rc;
+    if (a0.integer("--alt-ali", 0) != 0) return checkAltAli(a0, true);
+    Args a = a0;
+    bool targetSplit = false;
+    if (int rc = workflowSplit(a0, a, targetSplit)) return rc;
     if (a.integer("--alignment-mode", 2) == 4) {
         // the ungapped alignment mode through the modules, then the module chain on its alignment DB
         if (a.pos.size() != 4) return fail("usage: clustersearch <querySetDB> <targetSetDB> <out.tsv> <tmpDir> [options]");
@@ -1093,6 +1154,25 @@ int clustersearchModule(const Args &a) {
         for (const char *db : {"/result", "/result_prefixed", "/aggregate", "/aggregate_merged", "/matches", "/matches_h", "/clusters", "/clusters_h"})
             sddb::removeDb(tmp + db);
         if (int rc = ungappedAlignSearch(s, Q, T, tmp + "/result", tmp + "/search")) return rc;
+        return clusterChain(a, Q, T, tmp);
+    }
+    if (a.integer("--num-iterations", 1) <= 1 && targetSplit) {
+        // one pass over a split target through the modules (prefilter --split N, align), then the module chain on its alignment DB
+        if (int rc = checkWorkflowFlags(a)) return rc;
+        const std::string Q = a.pos[0], T = a.pos[1], tmp = a.pos[3];
+        mkdir(tmp.c_str(), 0777);
+        Args s = a;   // the clustersearch workflow's defaults (R/src/workflow/clustersearch.cpp:9-37)
+        auto def = [&](const char *f, const char *v) { if (!s.has(f)) s.opt[f] = v; };
+        def("-s", "5.7");
+        def("--cov-mode", "2");
+        def("-c", "0.8");
+        def("-e", "10");
+        def("--min-aln-len", "30");
+        def("--alignment-mode", "2");
+        def("-a", "1");
+        for (const char *db : {"/result", "/result_prefixed", "/aggregate", "/aggregate_merged", "/matches", "/matches_h", "/clusters", "/clusters_h"})
+            sddb::removeDb(tmp + db);
+        if (int rc = altAliSearch(s, Q, T, tmp + "/result", tmp + "/search")) return rc;
         return clusterChain(a, Q, T, tmp);
     }
     if (a.integer("--num-iterations", 1) <= 1) return runSearch(a, true);
@@ -1115,7 +1195,7 @@ int clustersearchModule(const Args &a) {
     // default: in memory (no DB between the modules of an iteration, no text chain behind them).  The module chain runs when its DBs
     // are wanted (--keep-tmp 1), with SD_ITER_FILES=1, and for several ranks (they shard whole query sets over the module chain's DBs)
     const bool files = a.integer("--keep-tmp", 0) != 0 || (getenv("SD_ITER_FILES") && atoi(getenv("SD_ITER_FILES")) != 0) ||
-                       envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1;
+                       envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1 || targetSplit;
     if (!files) return iterativeSearch(s, Q, T, tmp + "/result", tmp + "/search", &a.pos[2]);
     if (int rc = iterativeSearch(s, Q, T, tmp + "/result", tmp + "/search")) return rc;
     return clusterChain(a, Q, T, tmp);

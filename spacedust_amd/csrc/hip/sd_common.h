@@ -329,6 +329,7 @@ struct sd_target {
     int16_t *dExt2Score = nullptr;
     uint16_t *dExt2Index = nullptr;
     std::vector<uint64_t> hSeqOff;
+    uint64_t buildPeak = 0;          // sd_target_build_peak
 };
 
 int sdFail(sd_ctx *ctx, int code, const char *fmt, ...);

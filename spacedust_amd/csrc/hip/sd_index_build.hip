@@ -578,6 +578,13 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
     t->hSeqOff.assign(seqOffsets, seqOffsets + nSeq + 1);
     const uint64_t total = seqOffsets[nSeq];
     const int span = kmerSize == 6 ? 10 : 11;
+    // sd_target_build_peak: the free device memory is read where a phase holds the most
+    size_t freeAtStart = 0, totalDev = 0;
+    (void) hipMemGetInfo(&freeAtStart, &totalDev);
+    auto notePeak = [&]() {
+        size_t f = 0, tot = 0;
+        if (hipMemGetInfo(&f, &tot) == hipSuccess && f < freeAtStart) t->buildPeak = std::max<uint64_t>(t->buildPeak, freeAtStart - f);
+    };
     {
         static const uint8_t s6[8] = {0, 1, 3, 5, 8, 9, 0, 0}, s7[8] = {0, 1, 3, 5, 6, 9, 10, 0};
         uint32_t pw[8] = {0};
@@ -678,6 +685,7 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
             SD_HIP(ctx, dScale.alloc(sliceRows / TT_SCALE * 64 + 64));
             SD_HIP(ctx, dLr.alloc(IB_ALPH * IB_ALPH));
             SD_HIP(ctx, dN.alloc(1));
+            notePeak();
             SD_HIP(ctx, hipMemcpy(dOrder.p, order.data(), (size_t) nSeq * sizeof(uint32_t), hipMemcpyHostToDevice));
             SD_HIP(ctx, hipMemcpy(dWaveRow.p, waveRow.data(), ((size_t) nWaves + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
             SD_HIP(ctx, hipMemcpy(dLr.p, maskRatios, IB_ALPH * IB_ALPH * sizeof(double), hipMemcpyHostToDevice));
@@ -754,6 +762,7 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
         SD_HIP(ctx, dTileBase.alloc((bufN + IK_TILE - 1) / IK_TILE));
         SD_HIP(ctx, dTot.alloc(1));
         SD_HIP(ctx, dTmp.alloc(sdRadixSortCountsBytes()));   // the radix sort's count matrix (sd_scan_sort.h)
+        notePeak();
         uint32_t bin = 0;
         while (bin < IB_COARSE_BINS) {
             uint32_t e = bin;
@@ -825,6 +834,7 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
         Scoped<uint64_t> dStart, dTot;
         SD_HIP(ctx, dStart.alloc(t->tableSize + 1));
         SD_HIP(ctx, dTot.alloc(1));
+        notePeak();
         int rc = scan32to64(ctx, t->dOffsets, t->tableSize + 1, dStart.p, dTot.p);
         if (rc != SD_OK) return rc;
         uint64_t sum = 0;
@@ -848,6 +858,44 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
     }
     guard.t = nullptr;
     *out = t;
+    return SD_OK;
+}
+
+// The model behind `prefilter --split 0`: every hipMalloc of sd_target_build above, with the data-dependent sizes replaced by
+// their ceilings -- one record per residue, a masking scratch that holds every wavefront at once (the build caps it at an eighth
+// of the device) -- and each allocation rounded up to 2 MiB.  The phases release their scratch, so the peak is the largest of them.
+extern "C" uint64_t sd_target_footprint(int kmerSize, uint64_t nSeq, uint64_t nResidues) {
+    if (kmerSize != 6 && kmerSize != 7) return 0;
+    const uint64_t G = 2ull << 20;
+    auto a = [&](uint64_t bytes) { return (std::max<uint64_t>(bytes, 1) + G - 1) / G * G; };
+    const uint64_t T = kmerSize == 6 ? 64000000ull : 1280000000ull, R = nResidues, S = nSeq;
+    // resident from the start: sequence offsets, 3-mer and 2-mer matrices, the cumulative 3-mer table (+ its min/max pair), masked residues
+    const uint64_t tables = a((S + 1) * 8 + 64) + 2 * a(8000ull * 8000 * 2 + 64) + a(8000ull * 256 * 2) + a(8) + 2 * a(400ull * 400 * 2 + 64) +
+                            a(R + 64);
+    // 1. masking: the residues, the length order, and 64 lanes x (4 + 8 / TT_SCALE) bytes per row; a wavefront's rows are its longest
+    //    sequence rounded up to TT_SCALE; sorted by length, 64 x the rows of a wave are at most the residues of the next full wave, which
+    //    leaves the last two waves (at most 65 535 rows each) and the rounding
+    const uint64_t nWaves = (S + 63) / 64;
+    const uint64_t rows = (R + 63) / 64 + 2 * 65535 + (nWaves + 2) * TT_SCALE;
+    const uint64_t maskPhase = a(R + 64) + a(S * 4) + a((nWaves + 1) * 8) + a(rows * 64 * sizeof(float)) + a((rows / TT_SCALE * 64 + 64) * sizeof(double)) +
+                               a(IB_ALPH * IB_ALPH * 8) + a(8);
+    // 2. records: the entries and counts stay; the sort's two (k-mer, record) buffer pairs and the scans' tiles go
+    const uint64_t entries = a((std::max<uint64_t>(R, 1) + 8) * 8) + a((T + 1) * 4 + 64);
+    const uint64_t bufN = std::min<uint64_t>(1ull << 30, std::max<uint64_t>(R, 1));
+    const uint64_t nWavesR = (S + IB_SEQ_PER_WAVE - 1) / IB_SEQ_PER_WAVE, tiles = (bufN + IK_TILE - 1) / IK_TILE;
+    const uint64_t sortPhase = std::max<uint64_t>(a(IB_COARSE_BINS * 8),
+                                                  2 * a(bufN * 4) + 2 * a(bufN * 8) + a(nWavesR * 4) + a(nWavesR * 8) + a(tiles * 4) + a(tiles * 8) + a(8) +
+                                                      a(sdRadixSortCountsBytes()) + a((std::max(nWavesR, tiles) + IS_TILE - 1) / IS_TILE * 8));
+    // 3. list starts: 64-bit starts of the whole table, the scan's tiles, the wide index's block bases
+    const uint64_t startPhase = a((T + 1) * 8) + a(8) + a((T + IS_TILE) / IS_TILE * 8) + a((((T + 2) >> 16) + 1) * 8);
+    // what the HIP runtime itself takes from the device when the build's kernels first run (code objects, kernel-argument and signal pools)
+    const uint64_t runtime = 32ull << 20;
+    return tables + std::max(maskPhase, entries + std::max(sortPhase, startPhase)) + runtime;
+}
+
+extern "C" int sd_target_build_peak(const sd_target *t, uint64_t *bytes) {
+    if (!t || !bytes) return SD_EINVAL;
+    *bytes = t->buildPeak;
     return SD_OK;
 }
 

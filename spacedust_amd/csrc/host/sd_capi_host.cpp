@@ -1,6 +1,7 @@
 // C-ABI wrappers of the host-side stages (sd_host_* in include/spacedust_gpu.h).
 #include "sd_host.h"
 
+#include <algorithm>
 #include <climits>
 #include <vector>
 #include <omp.h>
@@ -117,6 +118,47 @@ int sd_host_index_build(sd_host *h, const uint8_t *residues, const uint64_t *off
 }
 
 int sd_host_auto_kmer_size(uint64_t targetResidues) { return sd::autoKmerSize(targetResidues); }
+
+int sd_host_split_plan(const uint64_t *entryLengths, uint64_t nEntries, uint32_t nSplits, uint64_t maxSeqs, int kmerSize,
+                       uint64_t residues, uint64_t *dbFrom, uint64_t *dbSize, uint64_t *listLen, int *kmerSizeOut) {
+    if ((!entryLengths && nEntries) || !dbFrom || !dbSize || nSplits == 0) return SD_EINVAL;
+    // DBReader::decomposeDomainByAminoAcid (DBReader.cpp:1216-1257) for every rank of a world of nSplits
+    uint64_t dataSize = 0;   // DBReader::getDataSize: the sum of the index's length column (readIndex, DBReader.cpp:883)
+    for (uint64_t i = 0; i < nEntries; i++) dataSize += entryLengths[i];
+    if (nSplits > dataSize) return SD_EINVAL;   // :1219-1223
+    for (uint32_t r = 0; r < nSplits; r++) dbFrom[r] = dbSize[r] = 0;
+    if (nSplits == 1) {                         // :1225-1229
+        dbSize[0] = nEntries;
+    } else if (nEntries <= nSplits) {           // :1231-1235: one entry per rank while there are entries
+        for (uint32_t r = 0; r < nSplits; r++) {
+            dbFrom[r] = r < nEntries ? r : 0;
+            dbSize[r] = r < nEntries ? 1 : 0;
+        }
+    } else {
+        const uint64_t chunkSize = (uint64_t) ceil((double) dataSize / (double) nSplits);   // :1237
+        uint64_t rank = 0, sum = 0;
+        for (uint64_t i = 0; i < nEntries; i++) {   // :1243-1250: a chunk is closed before the entry after the one that reached chunkSize
+            if (sum >= chunkSize) {
+                sum = 0;
+                rank++;
+                if (rank >= nSplits) return SD_EINVAL;   // only with entries of length 0 after the last chunk (no DB has them)
+            }
+            sum += entryLengths[i];
+            dbSize[rank]++;
+        }
+        for (uint32_t r = 1; r < nSplits; r++) dbFrom[r] = dbFrom[r - 1] + dbSize[r - 1];   // :1252-1256
+    }
+    if (listLen) {   // Prefiltering.cpp:169 and :358-361
+        uint64_t L = std::min<uint64_t>(maxSeqs, nEntries);
+        if (nSplits > 1) {
+            const size_t fourTimesStdDeviation = 4 * sqrt((double) L / (double) nSplits);
+            L = std::max<uint64_t>(1, L / nSplits + fourTimesStdDeviation);
+        }
+        *listLen = L;
+    }
+    if (kmerSizeOut) *kmerSizeOut = kmerSize ? kmerSize : sd::autoKmerSize(residues / nSplits);   // :351-354
+    return SD_OK;
+}
 
 int sd_host_map_profiles(const char *profileData, const uint64_t *byteOffsets, uint32_t n, uint8_t *queryLetters,
                          uint8_t *consensus, int8_t *alnProfile, int16_t *sortedScore, uint8_t *sortedIndex,
