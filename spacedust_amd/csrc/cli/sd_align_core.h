@@ -1,5 +1,5 @@
 // The body of `align` for one chunk of queries without the DB text on either side: pairs in, accepted records in compareHits order
-// out (Alignment::run, M/src/alignment/Alignment.cpp:340-470).  alignModule (sd_mod_hot.cpp) parses a prefilter DB into the pairs and
+// out (Alignment::run, M/src/alignment/Alignment.cpp:340-470).  alignModule (sd_mod_align.cpp) parses a prefilter DB into the pairs and
 // formats the records; the in-memory iterative search (sd_mod_iter.cpp) hands the prefilter rows over as they are and keeps the records.
 #ifndef SD_ALIGN_CORE_H
 #define SD_ALIGN_CORE_H
@@ -24,29 +24,6 @@ struct BtPool {
     }
     const char *data() const { return p.get(); }
 };
-
-// what Prefiltering's constructor derives from the command line (Prefiltering.cpp:180-215,1005-1065)
-struct PrefSetup {
-    int k = 6, kmerThr = 0, indexThr = 0;
-    bool mask = true, includeIdentity = false, compBias = true;
-    double maskProb = 0.9;
-    sd_prefilter_params par;
-};
-// kOverride != 0: the k-mer size a split plan has chosen (the automatic size follows the number of splits)
-int prefilterSetupFromArgs(const Args &a, sd_host *host, const SeqDb &tdb, bool profileQueries, PrefSetup &s, int kOverride = 0);
-
-// --split / --split-mode / --split-memory-limit resolved (Prefiltering::setupSplit, Prefiltering.cpp:273-377) against the device's memory
-struct SplitPlan {
-    int n = 1;                        // number of splits
-    bool target = false;              // a target split with n > 1: one index per split, built, searched and destroyed in turn
-    int k = 0;                        // k-mer size: -k, or the automatic size of residues / n
-    uint64_t listLen = 0;             // result list length of one split (of the whole run when !target)
-    std::vector<uint64_t> from, size; // the target ids of every split (sd_host_split_plan)
-};
-// target: the target DB's reader (any access mode); residues: its residue count; ctx (nullable): a context of the device whose
-// free memory decides when no --split-memory-limit is given (one is created for the question otherwise); residentTarget: the
-// workflow already holds this target's index on the device, so nothing is left to decide.  Prints the reference's split-mode line.
-int resolveSplit(const Args &a, const sddb::Reader &target, uint64_t residues, uint64_t nQueries, sd_ctx *ctx, bool residentTarget, SplitPlan &p);
 
 // what Alignment's constructor derives from the command line (Alignment.cpp:31-57,170-192,296-303)
 struct AlignSetup {

@@ -19,6 +19,8 @@ namespace sdcli {
 
 int fail(const std::string &msg);                       // prints "sdgpu <module>: msg", returns 1
 int failCtx(sd_ctx *ctx, int rc, const char *what);     // with sd_last_error
+// "no usable HIP device (<call> returned <rc>); <consequence>"
+int failNoDevice(int rc, const char *call = "sd_ctx_create", const char *consequence = "this path has no CPU fallback");
 void info(const Args &a, const char *fmt, ...);         // honours -v (>= 3 prints)
 int threadsOf(const Args &a);                           // --threads, default: cgroup quota / hardware threads
 
@@ -105,6 +107,54 @@ struct Resident {
 Resident &resident();
 // the target DB of a module: from the resident cache when it is on, else loaded for this call
 std::shared_ptr<SeqDb> loadTargetDb(const std::string &path, sd_host *host, std::string *err);
+
+// RAII over the C ABI's handles.  own == false: the object belongs to a workflow's resident set (below) and outlives the module
+struct HostH {
+    sd_host *h = nullptr;
+    bool own = true;
+    ~HostH() { if (h && own) sd_host_destroy(h); }
+    int open(int threads) {   // the resident host object of a workflow when that is on, else the module's own
+        if (resident().enabled) {
+            h = resident().host(threads);
+            own = false;
+            return h ? SD_OK : SD_ENOMEM;
+        }
+        return sd_host_create(threads, &h);
+    }
+};
+struct CtxH {
+    sd_ctx *c = nullptr;
+    bool own = true;
+    ~CtxH() { if (c && own) sd_ctx_destroy(c); }
+    int open(int device) {   // the workflow's resident context when that is on, else the module's own
+        if (resident().enabled) {
+            int rc = SD_OK;
+            c = resident().ctx(device, &rc);
+            own = false;
+            return rc;
+        }
+        return sd_ctx_create(device, &c);
+    }
+};
+struct SeqSetH {
+    sd_seqset *s = nullptr;
+    bool own = true;
+    ~SeqSetH() { reset(); }
+    void reset() { if (s && own) sd_seqset_destroy(s); s = nullptr; }
+};
+struct TargetH {
+    sd_target *t = nullptr;
+    bool own = true;
+    ~TargetH() { if (t && own) sd_target_destroy(t); }
+};
+struct IndexH {
+    sd_host_index *ix = nullptr;
+    ~IndexH() { if (ix) sd_host_index_destroy(ix); }
+};
+
+// what the modules refuse (the reference has these paths; this build does not): --compressed 1, another --sub-mat, --gpu 1
+int checkCommon(const Args &a);
+int deviceOf(const Args &a);                            // --device, else LOCAL_RANK, else 0
 
 // modules (each: argv after the module name -> exit code)
 int createindexModule(const Args &a);

@@ -25,6 +25,10 @@ int failCtx(sd_ctx *ctx, int rc, const char *what) {
     return 1;
 }
 
+int failNoDevice(int rc, const char *call, const char *consequence) {
+    return fail(std::string("no usable HIP device (") + call + " returned " + std::to_string(rc) + "); " + consequence);
+}
+
 void info(const Args &a, const char *fmt, ...) {
     g_module = "sdgpu " + a.module;
     if (a.integer("-v", 3) < 3) return;
@@ -58,6 +62,20 @@ int threadsOf(const Args &a) {
         if (t <= 0 || (hw > 0 && t > (long long) hw)) t = hw > 0 ? hw : 1;
     }
     return (int) std::max<long long>(1, t);
+}
+
+int checkCommon(const Args &a) {
+    if (a.integer("--compressed", 0) != 0) return fail("--compressed 1 is not supported");
+    const std::string sm = a.multi("--sub-mat", "aa", "blosum62.out");
+    if (sm != "blosum62.out") return fail("--sub-mat " + sm + ": only blosum62.out is built into this path");
+    if (a.integer("--gpu", 0) != 0) return fail("--gpu 1 selects the reference's CUDA ungapped prefilter (a different algorithm); run without it");
+    return 0;
+}
+
+int deviceOf(const Args &a) {
+    if (a.has("--device")) return (int) a.integer("--device", 0);
+    const char *lr = getenv("LOCAL_RANK");
+    return lr ? atoi(lr) : 0;
 }
 
 Resident &resident() {

@@ -31,15 +31,6 @@ enum { K_VERSION = 0, K_META = 1, K_SCOREMATRIXNAME = 2, K_SCOREMATRIX2MER = 3, 
        K_GENERATOR = 22, K_SPACEDPATTERN = 23 };
 const char *INDEX_VERSION = "16";   // MMSEQS_CURRENT_INDEX_VERSION of the vendored MMseqs2 (read from an index the reference wrote)
 
-struct HostH {
-    sd_host *h = nullptr;
-    ~HostH() { if (h) sd_host_destroy(h); }
-};
-struct IndexH {
-    sd_host_index *ix = nullptr;
-    ~IndexH() { if (ix) sd_host_index_destroy(ix); }
-};
-
 // page aligned entries into one data file; the index file lists (key, offset, length incl. terminator)
 struct IdxWriter {
     FILE *f = nullptr;

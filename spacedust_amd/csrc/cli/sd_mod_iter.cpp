@@ -20,6 +20,7 @@
 // tools/iter3_scale.py checks that chain's DBs against the reference classes and this path's TSV against that chain's.
 #include "sd_align_core.h"
 #include "sd_cli.h"
+#include "sd_pref_core.h"
 
 #include <algorithm>
 #include <atomic>
@@ -93,6 +94,8 @@ struct Worker {
     sd_host *host = nullptr;
     sd_r2p *r2p = nullptr;
     int threads = 1;
+    QueryChunk Q;                 // the prefilter of a chunk; its scratch stays with the worker
+    std::vector<uint8_t> failed;  // per query of the chunk: not computed in an iteration so far
     AlignChunk C;
     std::vector<uint32_t> mark;   // target id -> query stamp (subtractdbs)
     uint32_t stamp = 0;
@@ -131,11 +134,12 @@ int processChunk(const Shared &S, Worker &W, uint32_t g0, uint32_t g1, ChunkOut 
     std::string &pool = out.pool;
     pool.clear();
     std::unique_ptr<SeqDb> pdb;   // the chunk's profiles of the previous iteration (local ids)
-    std::vector<sd_hit> hits;
-    std::vector<uint32_t> counts, identId;
-    std::vector<uint64_t> off((size_t) nq + 1), pfSt((size_t) nq * 4);
-    std::vector<int8_t> diagBias;
-    std::vector<int16_t> kmerBias;
+    QueryChunk &Q = W.Q;
+    const std::vector<sd_hit> &hits = Q.hits;
+    const std::vector<uint32_t> &counts = Q.counts;
+    const std::vector<uint64_t> &off = Q.off;
+    Q.notComputed = 0;
+    W.failed.assign(nq, 0);
     if (W.mark.size() != tdb.n) W.mark.assign(tdb.n, 0);
     AlignChunk &C = W.C;
     for (int step = 0; step < S.numIt; step++) {
@@ -145,45 +149,17 @@ int processChunk(const Shared &S, Worker &W, uint32_t g0, uint32_t g1, ChunkOut 
         const uint32_t base = prof ? 0 : g0;
         const bool sameDbStep = S.sameDb && !prof;   // (a profile DB is never "the same DB" as the target: blastpgp.sh hands the modules its path)
         const PrefSetup &PS = prof ? S.pfProf : S.pfSeq;
-        // ---- prefilter (the loop body of prefilterModule)
+        // ---- prefilter
         double t0 = nowS(), c0 = cpuS();
         const uint64_t r0 = qd.offsets[base], r1 = qd.offsets[base + nq];
-        for (uint32_t i = 0; i <= nq; i++) off[i] = qd.offsets[base + i] - r0;
-        identId.resize(nq);
-        for (uint32_t i = 0; i < nq; i++) {
-            uint32_t id = UINT32_MAX;
-            if (sameDbStep) id = g0 + i;
-            else if (PS.includeIdentity) {
-                const size_t t = tdb.rd.idOfKey(qdb.keys[g0 + i]);
-                if (t != SIZE_MAX) id = (uint32_t) t;
-            }
-            identId[i] = id;
-        }
         const uint32_t Wd = (uint32_t) PS.par.maxHitsPerQuery;
-        hits.resize((size_t) nq * Wd);
-        counts.assign(nq, 0);
-        int rc;
-        if (prof) {
-            rc = sd_prefilter_profile_batch(W.ctx, S.profTarget, &PS.par, nq, qd.residues.data() + r0, off.data(), qd.sortedScore.data() + r0 * 20,
-                                            qd.sortedIndex.data() + r0 * 20, qd.alnProfile.data() + r0 * 21, identId.data(), hits.data(), counts.data(),
-                                            pfSt.data());
-        } else {
-            diagBias.assign(r1 - r0 + 1, 0);
-            kmerBias.assign(r1 - r0 + 1, 0);
-            if (PS.compBias) sd_host_comp_bias(W.host, qd.residues.data() + r0, off.data(), nq, PS.k, nullptr, diagBias.data(), kmerBias.data());
-            rc = sd_prefilter_batch(W.ctx, S.seqTarget, &PS.par, nq, qd.residues.data() + r0, off.data(), kmerBias.data(), diagBias.data(),
-                                    identId.data(), hits.data(), counts.data(), pfSt.data());
-        }
+        int rc = Q.run(W.ctx, W.host, prof ? S.profTarget : S.seqTarget, PS.par, PS, QuerySpan{&qd, base, &qdb, g0, nq}, tdb, sameDbStep, 0, tdb.n,
+                       W.failed.data(), out.pfStats);
         if (rc != SD_OK) return failChunk(out, rc, prof ? "sd_prefilter_profile_batch" : "sd_prefilter_batch", W.ctx);
-        for (uint32_t i = 0; i < nq; i++)
-            if (counts[i] == UINT32_MAX) {   // per-query error slot: not computed (reported, never silent)
-                if (!out.notComputed) out.err = sd_last_error(W.ctx);
-                out.notComputed++;
-                counts[i] = 0;
-            }
-        for (uint32_t i = 0; i < nq; i++)
-            for (int k = 0; k < 4; k++) out.pfStats[k] += pfSt[(size_t) i * 4 + k];
-        out.pfStats[4] += r1 - r0;
+        if (Q.notComputed) {
+            out.notComputed = Q.notComputed;
+            out.err = Q.firstError;
+        }
         out.sec[std::min(step, 7)][IT_PREF] += nowS() - t0;
         out.cpu[std::min(step, 7)][IT_PREF] += cpuS() - c0;
         // ---- the pairs: a query's rows in prefilter order, minus the targets it has aligned already (subtractdbs.cpp:60-90:
@@ -358,24 +334,15 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
                                    const std::vector<std::string> &profFlags, const std::string &eUser, const std::string &eProfile) {
     const int numIt = (int) a.integer("--num-iterations", 1);
     const int threads = threadsOf(a);
-    const int device = a.has("--device") ? (int) a.integer("--device", 0) : (getenv("LOCAL_RANK") ? atoi(getenv("LOCAL_RANK")) : 0);
+    const int device = deviceOf(a);
     const double tStart = nowS();
-    struct HostG {
-        sd_host *h = nullptr;
-        ~HostG() { if (h) sd_host_destroy(h); }
-    } host;
+    HostH host;
     if (sd_host_create(threads, &host.h) != SD_OK) return fail("sd_host_create failed");
     std::string err;
-    const bool sameDb = Q == T;
-    std::unique_ptr<SeqDb> tdb(new SeqDb()), qdbOwn;
-    if (!tdb->load(T, host.h, &err)) return fail(err);
-    if (tdb->profile) return fail("profile target databases are not supported on this path");
-    SeqDb *qdb = tdb.get();
-    if (!sameDb) {
-        qdbOwn.reset(new SeqDb());
-        if (!qdbOwn->load(Q, host.h, &err)) return fail(err);
-        qdb = qdbOwn.get();
-    }
+    DbPair db;   // (loaded for this run alone: not a workflow's resident DB)
+    if (!db.open(Q, T, host.h, false, true, &err)) return fail(err);
+    const bool sameDb = db.sameDb;
+    const SeqDb *const qdb = db.qdb, *const tdb = db.tdb.get();
     if (qdb->profile) return fail("--num-iterations starts from a sequence query DB");
     SetInfo qs, tsOwn;
     if (!qs.load(Q, true, &err)) return fail(err);
@@ -390,7 +357,7 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
     // ---- the modules' parameters, derived by the modules' own setup functions from the modules' own parameter strings
     Shared S;
     S.qdb = qdb;
-    S.tdb = tdb.get();
+    S.tdb = tdb;
     S.sameDb = sameDb;
     S.numIt = numIt;
     S.device = device;
@@ -430,8 +397,7 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
         Worker &W = *workers.back();
         W.threads = perWorker;
         int rc = sd_ctx_create(device, &W.ctx);
-        if (rc != SD_OK)
-            return fail("no usable HIP device (sd_ctx_create returned " + std::to_string(rc) + "); this path has no CPU fallback");
+        if (rc != SD_OK) return failNoDevice(rc);
         if (sd_host_create(perWorker, &W.host) != SD_OK) return fail("sd_host_create failed");
         if (sd_r2p_create(&W.r2p) != SD_OK) return fail("sd_r2p_create failed");
         if (S.profile) sd_profile_enable(W.ctx, 1);
@@ -439,46 +405,29 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
     // ---- the target: both indexes (the sequence search's k-mer threshold; every k-mer for the profile searches,
     // Prefiltering.cpp:525-527) and the sequences, resident for the whole run
     uint64_t indexEntries = 0;
-    struct TargetG {
-        sd_target *a = nullptr, *b = nullptr;
-        sd_seqset *s = nullptr;
-        ~TargetG() {
-            if (s) sd_seqset_destroy(s);
-            if (b) sd_target_destroy(b);
-            if (a) sd_target_destroy(a);
-        }
-    } tg;
+    TargetH seqTarget, profTarget;
+    SeqSetH tset;
     {
-        const int16_t *s2, *s3;
-        const uint16_t *i2, *i3;
-        uint32_t z2, z3;
-        sd_host_ext_matrix(host.h, 2, &s2, &i2, &z2);
-        sd_host_ext_matrix(host.h, 3, &s3, &i3, &z3);
-        double ratios[21 * 21];
-        int8_t self[21];
-        sd_host_index_tables(host.h, ratios, self);
         sd_ctx *c0 = workers[0]->ctx;
-        uint64_t st[4] = {0, 0, 0, 0};
-        int rc = sd_target_build(c0, S.pfSeq.k, S.pfSeq.indexThr, S.pfSeq.mask ? 1 : 0, S.pfSeq.maskProb, tdb->residues.data(), tdb->offsets.data(),
-                                 tdb->n, ratios, self, s2, i2, s3, i3, &tg.a, st);
-        if (rc != SD_OK) return failCtx(c0, rc, "sd_target_build");
+        uint64_t st[2] = {0, 0};
+        if (int rc = buildTarget(host.h, c0, S.pfSeq, tdb->residues.data(), tdb->offsets.data(), tdb->n, &seqTarget.t, st)) return rc;
         indexEntries = st[0];
         info(a, "Index table k-mer threshold: %d at k-mer size %d\nIndex statistics\nEntries:          %llu\n", S.pfSeq.kmerThr, S.pfSeq.k,
              (unsigned long long) st[0]);
         if (numIt > 1) {
-            rc = sd_target_build(c0, S.pfProf.k, S.pfProf.indexThr, S.pfProf.mask ? 1 : 0, S.pfProf.maskProb, tdb->residues.data(), tdb->offsets.data(),
-                                 tdb->n, ratios, self, s2, i2, s3, i3, &tg.b, st);
-            if (rc != SD_OK) return failCtx(c0, rc, "sd_target_build (profile searches)");
+            if (int rc = buildTarget(host.h, c0, S.pfProf, tdb->residues.data(), tdb->offsets.data(), tdb->n, &profTarget.t, st, std::string(),
+                                     "sd_target_build (profile searches)"))
+                return rc;
             indexEntries = std::max<uint64_t>(indexEntries, st[0]);
             info(a, "Index table k-mer threshold: %d at k-mer size %d (profile iterations: every k-mer indexed)\nEntries:          %llu\n",
                  S.pfProf.kmerThr, S.pfProf.k, (unsigned long long) st[0]);
         }
-        rc = sd_seqset_create(c0, tdb->residues.data(), tdb->offsets.data(), tdb->n, nullptr, &tg.s);
+        const int rc = sd_seqset_create(c0, tdb->residues.data(), tdb->offsets.data(), tdb->n, nullptr, &tset.s);
         if (rc != SD_OK) return failCtx(c0, rc, "sd_seqset_create(targets)");
     }
-    S.seqTarget = tg.a;
-    S.profTarget = tg.b;
-    S.tset = tg.s;
+    S.seqTarget = seqTarget.t;
+    S.profTarget = profTarget.t;
+    S.tset = tset.s;
     const double tResident = nowS();
     // ---- how many of the workers the device's free memory allows.  A worker's largest workspace is the prefilter's hit stream: the
     // profile iterations run the lookup path, whose sub-batches hold up to 2^30 hits at ~26 B each (a sub-batch of this chunk size may
@@ -609,10 +558,7 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
     double tAgg = 0, tFinalize = 0;
     uint64_t nEntriesAll = 0, nCluAll = 0, nCluLines = 0, nHitLines = 0;
     double tSearched = 0;
-    struct CtxG {
-        sd_ctx *c = nullptr;
-        ~CtxG() { if (c) sd_ctx_destroy(c); }
-    } finCtx;
+    CtxH finCtx;
     {
         Join join{threadsV, failed, cv};
         if (sd_ctx_create(device, &finCtx.c) != SD_OK) return fail("sd_ctx_create failed");
@@ -900,9 +846,7 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
     if (getenv("SD_DEBUG_TIMING"))
         fprintf(stderr, "[iter] load %.2f s | target resident %.2f s | iterations %.2f s (agg %.2f, finalise %.2f beside) | tail %.2f s | total %.2f s\n",
                 tLoaded - tStart, tResident - tLoaded, tSearched - tResident, tAgg, tFinalize, tEnd - tSearched, tEnd - tStart);
-    if (notComputed)
-        return fail(std::to_string(notComputed) + " queries need the reference's double-overflow route (or have >= 2^32 index hits) and were taken as "
-                    "queries without rows; every other result is complete");
+    if (notComputed) return failNotComputed(notComputed, "taken as queries without rows; every other result is complete");
     return 0;
 }
 

@@ -10,6 +10,7 @@
 // reference's MPI mode merges per-rank result files on the master instead, M/src/prefiltering/Prefiltering.cpp:619-650).
 #include "sd_cli.h"
 #include "sd_align_core.h"
+#include "sd_pref_core.h"
 
 #include <algorithm>
 #include <chrono>
@@ -33,19 +34,6 @@ namespace {
 struct SearchH {
     sd_search *s = nullptr;
     ~SearchH() { if (s) sd_search_destroy(s); }
-};
-struct HostH {
-    sd_host *h = nullptr;
-    bool own = true;   // false: the resident host object of a workflow (sd_cli.h)
-    ~HostH() { if (h && own) sd_host_destroy(h); }
-    int open(int threads) {
-        if (resident().enabled) {
-            h = resident().host(threads);
-            own = false;
-            return h ? SD_OK : SD_ENOMEM;
-        }
-        return sd_host_create(threads, &h);
-    }
 };
 
 int envInt(const char *name, int def) {
@@ -127,14 +115,12 @@ struct Sinks {
     static void onPref(void *u, uint32_t first, uint32_t nQ, const sd_hit *rows, const uint32_t *counts, uint32_t W) {
         Sinks *s = (Sinks *) u;
         if (!s->wantPref || s->failed) return;
-        char line[64];
         std::string &b = s->buf;
         for (uint32_t i = 0; i < nQ; i++) {
             b.clear();
             const sd_hit *row = rows + (size_t) i * W;
             for (uint32_t x = 0; x < counts[i]; x++) {
-                const int len = snprintf(line, sizeof(line), "%u\t%d\t%d\n", s->tdb->keys[row[x].seqId], row[x].score, (int) (int16_t) row[x].diagonal);
-                b.append(line, (size_t) len);
+                appendPrefRow(b, s->tdb->keys[row[x].seqId], row[x].score, row[x].diagonal);
             }
             if (!s->pref.write(s->qdb->keys[first + i], b.data(), b.size())) s->failed = true;
         }
@@ -227,16 +213,10 @@ int runSearch(const Args &a, bool withClusters) {
     HostH host;
     if (sd_host_create(par.threads, &host.h) != SD_OK) return fail("sd_host_create failed");
     std::string err;
-    const bool sameDb = a.pos[0] == a.pos[1];
-    std::unique_ptr<SeqDb> tdb(new SeqDb()), qdbOwn;
-    if (!tdb->load(a.pos[1], host.h, &err)) return fail(err);
-    if (tdb->profile) return fail("profile target databases are not supported on this path");
-    SeqDb *qdb = tdb.get();
-    if (!sameDb) {
-        qdbOwn.reset(new SeqDb());
-        if (!qdbOwn->load(a.pos[0], host.h, &err)) return fail(err);
-        qdb = qdbOwn.get();
-    }
+    DbPair db;   // (loaded for this run alone: not a workflow's resident DB)
+    if (!db.open(a.pos[0], a.pos[1], host.h, false, true, &err)) return fail(err);
+    const bool sameDb = db.sameDb;
+    const SeqDb *const qdb = db.qdb, *const tdb = db.tdb.get();
     SetInfo qs, tsOwn;
     const SetInfo *qsP = nullptr, *tsP = nullptr;
     if (withClusters) {
@@ -283,7 +263,7 @@ int runSearch(const Args &a, bool withClusters) {
             rc = sd_search_create(device, &par, &tv.view, &S.s);
         }
     }
-    if (rc == SD_ENODEVICE) return fail("no usable HIP device (sd_search_create returned -1); this path has no CPU fallback");
+    if (rc == SD_ENODEVICE) return failNoDevice(rc, "sd_search_create");
     if (rc != SD_OK) return fail("sd_search_create failed (" + std::to_string(rc) + ")");
     uint64_t st[16];
     double tm[16];
@@ -334,7 +314,7 @@ int runSearch(const Args &a, bool withClusters) {
     // DB outputs: `search` always writes the alignment DB (and pref_0 under <tmpDir>); clustersearch only with --keep-dbs 1
     Sinks sinks;
     sinks.qdb = qdb;
-    sinks.tdb = tdb.get();
+    sinks.tdb = tdb;
     const bool dbs = !withClusters || a.integer("--keep-dbs", 0) != 0;
     const std::string rankSuffix = world > 1 ? "." + std::to_string(rank) : "";
     if (dbs) {
@@ -552,17 +532,11 @@ int result2profileModule(const Args &a) {
     HostH host;
     if (host.open(threads) != SD_OK) return fail("sd_host_create failed");
     std::string err;
-    const bool sameDb = a.pos[0] == a.pos[1];
-    std::shared_ptr<SeqDb> tdb = loadTargetDb(a.pos[1], host.h, &err);
-    std::unique_ptr<SeqDb> qdbOwn;
-    if (!tdb) return fail(err);
+    DbPair db;
+    if (!db.open(a.pos[0], a.pos[1], host.h, true, false, &err)) return fail(err);
+    const bool sameDb = db.sameDb;
+    const SeqDb *const qdb = db.qdb, *const tdb = db.tdb.get();
     if (tdb->profile) return fail("Only the query OR the target database can be a profile database");
-    SeqDb *qdb = tdb.get();
-    if (!sameDb) {
-        qdbOwn.reset(new SeqDb());
-        if (!qdbOwn->load(a.pos[0], host.h, &err)) return fail(err);
-        qdb = qdbOwn.get();
-    }
     lap.mark("load DBs");
     sddb::Reader aln;
     if (!aln.open(a.pos[2], sddb::Reader::USE_INDEX | sddb::Reader::USE_DATA, sddb::Reader::LINEAR_ACCESS, &err)) return fail(err);
@@ -584,8 +558,8 @@ int result2profileModule(const Args &a) {
             rcCtx = sd_ctx_create(device, &r2pCtx);
         }
         if (rcCtx != SD_OK)
-            return fail("no usable HIP device (sd_ctx_create returned " + std::to_string(rcCtx) + "); result2profile computes the sequence weights on "
-                        "the GPU (--profile-weights-host 1 selects the host implementation)");
+            return failNoDevice(rcCtx, "sd_ctx_create", "result2profile computes the sequence weights on the GPU (--profile-weights-host 1 selects the "
+                                                        "host implementation)");
     }
     std::unique_ptr<sd_ctx, void (*)(sd_ctx *)> ctxGuard(ownCtx ? r2pCtx : nullptr, sd_ctx_destroy);
     lap.mark("r2p object + context");
@@ -859,7 +833,7 @@ std::vector<std::string> with(std::vector<std::string> v, std::initializer_list<
 }
 
 // --split / --split-mode / --split-memory-limit of a workflow (none given: nothing is read or decided, `s` stays as it is).
-// The plan is resolved once, here (resolveSplit, sd_mod_hot.cpp), and `s` carries its outcome to the steps:
+// The plan is resolved once, here (resolveSplit, sd_mod_prefilter.cpp), and `s` carries its outcome to the steps:
 //   a target split with N > 1: --split N --split-mode 0 for the prefilter step; targetSplit = true tells the workflow to run the module
 //     chain in this process (the streaming pipeline and the in-memory iterations hold ONE index of the whole target);
 //   otherwise (one split, or query-split semantics: the rows of the unsplit run with k taken from residues / N) the split flags are

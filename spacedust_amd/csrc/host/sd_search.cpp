@@ -6,6 +6,7 @@
 // Every stage is a call of the C ABI (sd_prefilter_batch, sd_sw_align_batch_compact, sd_agg_*, sd_clusterhits_batch);
 // nothing is computed here.
 #include "sd_host.h"
+#include "sd_target_build.h"
 #include "spacedust_gpu.h"
 
 #include <algorithm>
@@ -157,7 +158,6 @@ struct sd_search {
     sd_ctx *ctxPf2 = nullptr;   // second prefilter lane (same target index, its own workspace and stream)
     sd_ctx *ctxPfMore[2] = {nullptr, nullptr}, *ctxAlMore[2] = {nullptr, nullptr};   // lanes 3 and 4 (SD_PF_LANES / SD_ALIGN_LANES up to 4)
     int alignLanes = 2, pfLanes = 2;
-    sd_host_index *index = nullptr;
     sd_target *target = nullptr;
     sd_seqset *tSeqs = nullptr;
     int k = 6, kmerThr = 0;
@@ -195,7 +195,6 @@ struct sd_search {
     ~sd_search() {
         if (tSeqs) sd_seqset_destroy(tSeqs);
         if (target) sd_target_destroy(target);
-        if (index) sd_host_index_destroy(index);
         if (ctxBias) sd_ctx_destroy(ctxBias);
         for (int x = 0; x < 2; x++) {
             if (ctxPfMore[x]) sd_ctx_destroy(ctxPfMore[x]);
@@ -321,45 +320,20 @@ static int searchCreate(int device, const sd_search_params *par, const sd_setdb 
     if (view && (view->kmerSize != s->k || view->kmerThr != indexThr)) return SD_EINVAL;
     double t0 = nowSec();
     uint64_t nEntries = 0, masked = 0;
-    const uint32_t *kOff = nullptr, *eSeq = nullptr;
-    const uint16_t *ePos = nullptr;
-    const uint8_t *mres = nullptr;
-    const uint64_t *kBase = nullptr;   // block bases of a wide index (>= 2^32 entries)
     if (ungapped) {
         // no index: the scan reads the target sequences themselves (tSeqs below)
-    } else if (view) {
-        kBase = view->kmerBlockBase;
-        kOff = view->kmerOffsets;
-        eSeq = view->entrySeq;
-        ePos = view->entryPos;
-        mres = view->maskedResidues;
+    } else if (view) {   // uploaded below
         nEntries = view->nEntries;
         masked = view->nMaskedResidues;
-    } else if (!getenv("SD_INDEX_HOST")) {
+    } else {
         // the index is built where it is used: masking, k-mer lists and list starts on the device (sd_target_build)
-        const int16_t *s2, *s3;
-        const uint16_t *i2, *i3;
-        uint32_t z2, z3;
-        sd_host_ext_matrix(s->host, 2, &s2, &i2, &z2);
-        sd_host_ext_matrix(s->host, 3, &s3, &i3, &z3);
-        double ratios[21 * 21];
-        int8_t self[21];
-        sd_host_index_tables(s->host, ratios, self);
-        uint64_t st[4] = {0, 0, 0, 0};
-        rc = sd_target_build(s->ctxPf, s->k, indexThr, par->mask ? 1 : 0, par->maskProb, target->residues, target->offsets, target->n, ratios,
-                             self, s2, i2, s3, i3, &s->target, st);
+        uint64_t st[2] = {0, 0};
+        const char *what;
+        rc = sdBuildTarget(s->host, s->ctxPf, s->k, indexThr, par->mask ? 1 : 0, par->maskProb, target->residues, target->offsets, target->n,
+                           &s->target, st, &what);
         if (rc != SD_OK) return rc;
         nEntries = st[0];
         masked = st[1];
-        kOff = nullptr;
-    } else {
-        rc = sd_host_index_build(s->host, target->residues, target->offsets, target->n, s->k, indexThr, par->mask ? 1 : 0, par->maskProb,
-                                 &s->index);
-        if (rc != SD_OK) return rc;
-        uint64_t tableSize = 0;
-        sd_host_index_info(s->index, &tableSize, &nEntries, &masked);
-        sd_host_index_arrays(s->index, &kOff, &eSeq, &ePos, &mres);
-        sd_host_index_block_base(s->index, &kBase, nullptr);
     }
     s->seconds[T_INDEX] = nowSec() - t0;
     s->stats[S_ENTRIES] = nEntries;
@@ -367,19 +341,10 @@ static int searchCreate(int device, const sd_search_params *par, const sd_setdb 
     s->stats[S_K] = (uint64_t) s->k;
     s->stats[S_KMER_THR] = (uint64_t) s->kmerThr;
     t0 = nowSec();
-    if (!s->target && !ungapped) {
-        const int16_t *s2, *s3;
-        const uint16_t *i2, *i3;
-        uint32_t z2, z3;
-        sd_host_ext_matrix(s->host, 2, &s2, &i2, &z2);
-        sd_host_ext_matrix(s->host, 3, &s3, &i3, &z3);
-        rc = sd_target_create_wide(s->ctxPf, s->k, kOff, kBase, eSeq, ePos, nEntries, mres, target->offsets, target->n, s2, i2, s3, i3,
-                                   &s->target);
+    if (view && !ungapped) {
+        rc = sdUploadTarget(s->host, s->ctxPf, s->k, view->kmerOffsets, view->kmerBlockBase, view->entrySeq, view->entryPos, nEntries,
+                            view->maskedResidues, target->offsets, target->n, &s->target);
         if (rc != SD_OK) return rc;
-    }
-    if (s->index) {   // the host copy is not needed once the target is resident
-        sd_host_index_destroy(s->index);
-        s->index = nullptr;
     }
     rc = sd_seqset_create(s->ctxAl, target->residues, target->offsets, target->n, nullptr, &s->tSeqs);
     if (rc != SD_OK) return rc;

@@ -352,16 +352,26 @@ def test_iterative_profile_search_config4(work):
         assert sorted_md5(tsv, drop_first_column=True) == 'ca3dd1ba9c0f89b9a7cf0726a1bab2ce'
 
 
-def test_iterative_search_in_memory_equals_the_module_chain(work):
+ITER3 = ['--filter-self-match', '--num-iterations', '3', '--threads', '8', '-v', '0']
+
+
+@pytest.fixture(scope='module')
+def iter3_chain_tsv(work):
+    """the TSV of `clustersearch --num-iterations 3` run as the module chain over DB files (--keep-tmp 1)"""
+    g = work / 'genome'
+    sdgpu('clustersearch', g, g, work / 'itf.tsv', work / 'tmpitf', *ITER3, '--keep-tmp', '1')
+    return open(work / 'itf.tsv').read()
+
+
+def test_iterative_search_in_memory_equals_the_module_chain(work, iter3_chain_tsv):
     """`clustersearch --num-iterations 3` without --keep-tmp runs the iterations in memory (csrc/cli/sd_mod_iter.cpp: chunks of queries
     through prefilter -> subtract -> align -> merge -> result2profile of all iterations, several chunks at a time, one aggregation): the
     TSV is the module chain's, byte for byte -- whatever the number of workers and wherever the chunks are cut -- and no DB is left
     between the modules.  Also with two different set DBs (query != target: no identity pairs, the query's own sequence is an ordinary
     target of the profile iterations)."""
     g = work / 'genome'
-    common = ['--filter-self-match', '--num-iterations', '3', '--threads', '8', '-v', '0']
-    sdgpu('clustersearch', g, g, work / 'itf.tsv', work / 'tmpitf', *common, '--keep-tmp', '1')
-    want = open(work / 'itf.tsv').read()
+    common = ITER3
+    want = iter3_chain_tsv
     assert want.count('\n#') > 100
     for tag, env in (('a', {}), ('b', {'SD_ITER_WORKERS': '1', 'SD_ITER_CHUNK': '5898'}), ('c', {'SD_ITER_WORKERS': '4', 'SD_ITER_CHUNK': '611'})):
         p = subprocess.run([SDGPU, 'clustersearch', str(g), str(g), str(work / ('itm_%s.tsv' % tag)), str(work / ('tmpitm_' + tag))] + common,
@@ -416,3 +426,66 @@ def test_literal_config1_two_set_dbs(work):
     clu = [l for l in tsv if l.startswith('#')]
     assert (sum(1 for l in tsv if l.startswith('>')), len(clu), sum(1 for l in clu if float(l.split('\t')[3]) < 1e-20)) == (176, 61, 1)
     assert len(tsv) == 237 and sorted_md5(tsv, drop_first_column=True) == '521fe66c5fd4b93b0b3363bd149f9bd7'
+
+
+# ---- chunk boundaries of the shared prefilter chunk runner (QueryChunk, csrc/cli/sd_pref_core.cpp): 5 898 queries in chunks of 1 000 are
+# five full chunks and a ragged one of 898; offsets rebased to the chunk, identity ids across chunks
+
+def test_prefilter_in_chunks_reproduces_the_reference_db(work):
+    g = work / 'genome'
+    sdgpu('prefilter', g, g, work / 'pref_chunked', *PREFILTER_PAR, '--chunk-queries', '1000')
+    lines = flat(work, 'pref_chunked')
+    assert (len(lines), sorted_md5(lines)) == (98957, '8109a70bdea70ee10e0dbd27ba6b7e37')
+
+
+def test_target_split_in_chunks_golden_rows(work):
+    """the golden rows of tests/golden/split_vectors.npz (the reference's classes on this input: 3 splits, --max-seqs 30), as
+    test_gpu_split.py::test_golden_rows expects them of the unchunked run"""
+    import numpy as np
+    from dbutil import GOLD, read_db
+    from test_gpu_split import PREF, rows_of
+    gold = np.load(os.path.join(GOLD, 'split_vectors.npz'))
+    g = work / 'genome'
+    p = sdgpu('prefilter', g, g, work / 'split3_chunked', '--split', str(int(gold['n_splits'])), '--split-mode', '0', '--max-seqs',
+              str(int(gold['max_seqs'])), '--chunk-queries', '1000', *PREF)
+    assert 'Target split mode. Searching through 3 splits' in p.stdout
+    got = read_db(str(work / 'split3_chunked'))
+    for i, q in enumerate(gold['queries']):
+        a, b = int(gold['merged_off'][i]), int(gold['merged_off'][i + 1])
+        want = list(zip(gold['merged_key'][a:b].tolist(), gold['merged_score'][a:b].tolist(), gold['merged_diag'][a:b].tolist()))
+        assert rows_of(got[int(q)]) == want, int(q)
+
+
+def test_two_way_target_split_in_chunks_equals_unsplit_runs(work):
+    """--split 2 --split-mode 0 --chunk-queries 1000: every query's entry is the merge of the unsplit (unchunked) module's lists on the
+    two physically split target DBs, as test_gpu_split.py expects of the unchunked 2-way split"""
+    from dbutil import read_db
+    from test_gpu_split import PREF, rows_of, merge, sub_dbs
+    g = work / 'genome'
+    db = read_db(str(g))
+    genome = (db, [len(db[k]) + 1 for k in sorted(db)])
+    paths, list_len = sub_dbs(work, genome, 2, 30)
+    assert list_len == 30 and all(paths)
+    per_split = []
+    for s, path in enumerate(paths):
+        sdgpu('prefilter', g, path, work / ('phys2_%d' % s), '-k', '6', '--max-seqs', str(list_len), '--add-self-matches', '1', *PREF)
+        per_split.append(read_db(str(work / ('phys2_%d' % s))))
+    p = sdgpu('prefilter', g, g, work / 'split2_chunked', '--split', '2', '--split-mode', '0', '--max-seqs', '30', '-k', '6', '--chunk-queries',
+              '1000', *PREF)
+    assert 'Target split mode. Searching through 2 splits' in p.stdout
+    got = read_db(str(work / 'split2_chunked'))
+    assert sorted(got) == list(range(5898))
+    longer = 0
+    for q in range(5898):
+        want = merge([rows_of(d[q]) for d in per_split])
+        assert rows_of(got[q]) == want, q
+        longer += len(want) > 30
+    assert longer > 0
+
+
+def test_iterative_search_in_memory_in_small_chunks(work, iter3_chain_tsv):
+    """--iter-chunk-queries 500: the two query sets (4 319 and 1 579 proteins) in nine and four chunks; the module chain's TSV"""
+    g = work / 'genome'
+    p = sdgpu('clustersearch', g, g, work / 'itm_500.tsv', work / 'tmpitm_500', *ITER3, '-v', '3', '--iter-chunk-queries', '500')
+    assert 'chunks of <= 500 queries' in p.stdout
+    assert open(work / 'itm_500.tsv').read() == iter3_chain_tsv
