@@ -1526,7 +1526,7 @@ k_bound_apply(uint32_t nPairs, SwTask *__restrict__ tasks, const uint64_t *__res
 }
 
 // ---- tasks of one query two by two (shared-profile kernels) --------------------------------------------------------
-// key = class (5 bits) | query (17 bits) | target-length bucket (10 bits): one stable sort puts the tasks of a
+// key = class (6 bits) | query (17 bits) | target-length bucket (9 bits): one stable sort puts the tasks of a
 // (class, query) run together, longest target first; inside a run of a packed class consecutive tasks form pairs, an
 // odd last task stays alone.  Invalid tasks sort last (all ones).
 constexpr uint32_t PAIR_NONE = 0xFFFFFFFFu;

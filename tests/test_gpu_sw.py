@@ -277,7 +277,10 @@ def test_sw_packed_kernel_equals_int32_kernel(gpu, host, monkeypatch, pairs):
     ss = gpu.seqset(residues, offsets, sw_bias)
     par = gpu.sw_params(mat, db)
     ident = (pq == pt)
+    gpu.profile()
     a, pa = gpu.sw_align(par, ss, ss, pq, pt, identity=ident)
+    scopes = set(gpu.profile_report())
+    gpu.profile(False)
     monkeypatch.setenv('SD_SW_INT32', '1')
     b, pb = gpu.sw_align(par, ss, ss, pq, pt, identity=ident)
     for f in ('score', 'qStart', 'qEnd', 'tStart', 'tEnd', 'identical', 'btLen', 'flags', 'evalue'):
@@ -289,6 +292,9 @@ def test_sw_packed_kernel_equals_int32_kernel(gpu, host, monkeypatch, pairs):
         assert np.array_equal(pa, pb)
         assert lens[pq].min() <= 160 and lens[pq].max() > 768 and lens[pt].min() < 32   # the aligned row classes, targets below 32 residues
         assert int((a['score'] > 0).sum()) > len(pq) // 2
+    # what the lengths only suggest: the packed call launched the 128-row kernel, most aligned row classes and a wide one
+    assert 'sw_score_pk.rt4x32' in scopes and sum(k.startswith('sw_score_pk.a_seg') for k in scopes) >= 15, sorted(scopes)
+    assert any(k.startswith('sw_score_pk.w_') for k in scopes), sorted(scopes)
 
 
 def test_sw_align_compact_equals_full(gpu, host):
