@@ -473,6 +473,13 @@ int sd_host_lgamma_table(double *out, uint32_t n);
 int sd_host_cluster_pvalues(uint32_t nHits, const uint32_t *qPos, const uint32_t *tPos, const uint8_t *strands, const double *pval,
                             uint32_t querySetSize, double alpha, const double *lGamma, uint32_t lGammaLen, double *pCluster,
                             double *pMultihit, uint32_t *order);
+/* One clusterhits entry through the reference's dense K x K loop on the host (csrc/host/sd_chdense.cpp): what
+ * sd_clusterhits_batch runs for an entry that repeats a query position, where the result depends on the order std::sort
+ * leaves equal positions in.  Outputs as sd_clusterhits_batch's for a batch of this one entry. */
+int sd_host_clusterhits_dense(uint32_t nHits, const uint32_t *qPos, const uint32_t *tPos, const uint8_t *strands, const double *pval,
+                              uint32_t querySetSize, const sd_ch_params *par, const double *lGamma, uint32_t lGammaLen,
+                              uint32_t *clusterOfHit, uint32_t *rankInCluster, uint32_t *nClusters, double *pCO, double *pMH,
+                              uint32_t *clusterSizeOut);
 double sd_host_evalue(uint64_t dbResidues, double score, double qLen);
 double sd_host_bitscore(double score);
 /* A double after one hand-off between two reference modules: printed as "%.3E" (Matcher.cpp:288, besthitbyset.cpp:129,

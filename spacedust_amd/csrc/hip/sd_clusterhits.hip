@@ -12,7 +12,7 @@
 //          merge i2 into i1 (always, even below sMin), then test score >= sMin          (:395,412-453)
 //          dmin[i1] = first arg-max_j of the new row;  for j != i1,i2:
 //          dmin[j]  = D[j][i1] > D[j][dmin[j]] ? i1 : dmin[j]   (stale entries persist)   (:439-449)
-// Per merge this is O(K) box tests spread over the workgroup and a few O(cluster) list merges; HBM traffic
+// Per merge this is O(K) box tests spread over the workgroup and one O(1) list join; HBM traffic
 // is the K*(4+4+1) input bytes plus K*4 output bytes per pair (algorithmic), the scratch stays in L2.
 // The double-precision P-values of the emitted clusters (exp/pow/log) are evaluated on the host with the
 // reference's own expressions (sd_clusterhits_batch below) so their text form matches digit for digit.
@@ -77,32 +77,16 @@ __device__ double chPairScore(const ChView &v, uint32_t a, uint32_t b) {
     const int spanI = (int) (iMax - iMin + 1), spanJ = (int) (jMax - jMin + 1);
     const int span = spanI > spanJ ? spanI : spanJ;
     // conserved neighbour pairs of the union in ascending query position (findConservedPairs, :104-117).  Whether two
-    // members count depends on that pair alone (chConserved), so when one node's members all come before the other's -- the
-    // usual case: a collinear cluster growing at its ends -- the union's count is the two nodes' own counts plus the one
-    // pair at the seam, and the lists need not be walked (a self pair of K = 3 000 collinear hits was 2.4 s of list walks)
-    {
-        const uint32_t ta = v.tail[a], hb = v.head[b], tb = v.tail[b], ha = v.head[a];
-        if (v.rank[ta] < v.rank[hb]) return chScoreKSM(v, k, span, (int) (v.mcnt[a] + v.mcnt[b] + chConserved(v, ta, hb)));
-        if (v.rank[tb] < v.rank[ha]) return chScoreKSM(v, k, span, (int) (v.mcnt[a] + v.mcnt[b] + chConserved(v, tb, ha)));
-    }
-    uint32_t pa = v.head[a], pb = v.head[b];
-    int m = 0;
-    bool first = true, prevS = false;
-    uint32_t prevT = 0;
-    while (pa != NIL || pb != NIL) {
-        uint32_t pick;
-        if (pb == NIL || (pa != NIL && v.rank[pa] < v.rank[pb])) { pick = pa; pa = v.next[pa]; }
-        else { pick = pb; pb = v.next[pb]; }
-        const uint8_t st = v.strand[pick];
-        const bool sEq = ((st & 1) != 0) == ((st & 2) != 0);
-        const uint32_t tp = v.tPos[pick];
-        if (!first) {
-            const bool sameOrder = tp > prevT;
-            if ((prevS == sameOrder) && (sEq == sameOrder)) m++;
-        }
-        prevT = tp; prevS = sEq; first = false;
-    }
-    return chScoreKSM(v, k, span, m);
+    // members count depends on that pair alone (chConserved), so when one node's members all come before the other's the
+    // union's count is the two nodes' own counts plus the one pair at the seam, and the lists need not be walked (a self pair
+    // of K = 3 000 collinear hits was 2.4 s of list walks).
+    // INVARIANT: that is every pair that gets here.  The query positions of an entry on the device are distinct
+    // (sd_clusterhits_batch sends entries that repeat one to the host's dense path), and the unsigned gap above is <= d
+    // (d + the largest position < 2^32, checked on the host) only where iMin1 >= iMax2 or iMin2 >= iMax1 without wrapping:
+    // one query range lies wholly before the other, so if a's tail is not before b's head, b's tail is before a's head.
+    const uint32_t ta = v.tail[a], hb = v.head[b], tb = v.tail[b], ha = v.head[a];
+    if (v.rank[ta] < v.rank[hb]) return chScoreKSM(v, k, span, (int) (v.mcnt[a] + v.mcnt[b] + chConserved(v, ta, hb)));
+    return chScoreKSM(v, k, span, (int) (v.mcnt[a] + v.mcnt[b] + chConserved(v, tb, ha)));
 }
 
 // block-wide arg-max: larger value wins, ties -> smaller index.  256 threads.
@@ -153,7 +137,7 @@ clusterhits_kernel(const ChPair *__restrict__ pairs, uint32_t nPairs, const uint
         if (t == 0) mergesOut[p] = 0;
         return;
     }
-    // rank by (qPos, index); singleton nodes
+    // rank by qPos (distinct within an entry, see chPairScore; the index only keeps the ranks a permutation); singleton nodes
     for (uint32_t h = t; h < K; h += 256) {
         const uint32_t q = v.qPos[h];
         uint32_t r = 0;
@@ -211,34 +195,17 @@ clusterhits_kernel(const ChPair *__restrict__ pairs, uint32_t nPairs, const uint
         const uint32_t i1 = sI1, i2 = sI2;
         const double maxScore = sMax;
         if (maxScore == 0.0) break;
-        // merge i2 into i1: rank-sorted list merge, box union
+        // merge i2 into i1: the lists joined end to end, box union
         if (t == 0) {
             const uint32_t h1 = v.head[i1], t1 = v.tail[i1], h2 = v.head[i2], t2 = v.tail[i2];
             if (v.rank[t1] < v.rank[h2]) {          // i2's members all behind i1's: append
                 v.next[t1] = h2;
                 v.tail[i1] = t2;
                 v.mcnt[i1] += v.mcnt[i2] + chConserved(v, t1, h2);
-            } else if (v.rank[t2] < v.rank[h1]) {   // all in front: prepend
+            } else {                                // all in front (the invariant of chPairScore: the score was not 0): prepend
                 v.next[t2] = h1;
                 v.head[i1] = h2;
                 v.mcnt[i1] += v.mcnt[i2] + chConserved(v, t2, h1);
-            } else {                                // interleaved: rank-sorted merge, the count taken along the way
-                uint32_t pa = h1, pb = h2, hd = NIL, tl = NIL, m = 0;
-                while (pa != NIL || pb != NIL) {
-                    uint32_t pick;
-                    if (pb == NIL || (pa != NIL && v.rank[pa] < v.rank[pb])) { pick = pa; pa = v.next[pa]; }
-                    else { pick = pb; pb = v.next[pb]; }
-                    if (hd == NIL) hd = pick;
-                    else {
-                        v.next[tl] = pick;
-                        m += chConserved(v, tl, pick);
-                    }
-                    tl = pick;
-                }
-                v.next[tl] = NIL;
-                v.head[i1] = hd;
-                v.tail[i1] = tl;
-                v.mcnt[i1] = m;
             }
             v.head[i2] = NIL;
             v.size[i1] += v.size[i2];
@@ -313,8 +280,28 @@ extern "C" int sd_clusterhits_batch(sd_ctx *ctx, const sd_ch_params *par, uint32
     // every table index used on the device is < span + 2 <= max position + 3
     uint32_t maxPos = 0;
     for (uint64_t x = 0; x < total; x++) maxPos = std::max(maxPos, std::max(qPos[x], tPos[x]));
-    if ((uint64_t) maxPos + 3 > lGammaLen || (uint64_t) maxK + 2 > lGammaLen || par->maxGeneGap + 3 > lGammaLen)
-        return sdFail(ctx, SD_EINVAL, "logGamma table too short: %u entries, need %llu", lGammaLen, (unsigned long long) std::max<uint64_t>(maxPos + 3, maxK + 2));
+    if ((uint64_t) maxPos + 3 > lGammaLen || (uint64_t) maxK + 2 > lGammaLen || (uint64_t) par->maxGeneGap + 3 > lGammaLen)
+        return sdFail(ctx, SD_EINVAL, "logGamma table too short: %u entries, need %llu", lGammaLen,
+                      (unsigned long long) std::max<uint64_t>(std::max<uint64_t>((uint64_t) maxPos + 3, (uint64_t) maxK + 2), (uint64_t) par->maxGeneGap + 3));
+    // the kernel reads the unsigned box gap `<= d` as "one range wholly before the other" (chPairScore): a wrapped difference
+    // is at least 2^32 - maxPos, so that holds while d + maxPos < 2^32
+    if ((uint64_t) par->maxGeneGap + maxPos >= (1ull << 32))
+        return sdFail(ctx, SD_EINVAL, "max gene gap %u + largest gene position %u reach 2^32", par->maxGeneGap, maxPos);
+    // Entries that repeat a query position leave the device empty and run on the host's dense path (csrc/host/sd_chdense.cpp):
+    // there the reference's result depends on where std::sort leaves equal positions.  One pass, a stamp per position.
+    std::vector<uint8_t> dense(nPairs, 0);
+    {
+        std::vector<uint32_t> stamp((size_t) maxPos + 1, 0);
+        for (uint32_t p = 0; p < nPairs; p++) {
+            if (hp[p].K <= 1) continue;
+            const uint64_t end = hitOff[p + 1];
+            for (uint64_t x = hitOff[p]; x < end; x++) {
+                if (stamp[qPos[x]] == p + 1) { dense[p] = 1; break; }
+                stamp[qPos[x]] = p + 1;
+            }
+            if (dense[p]) hp[p].K = 0;
+        }
+    }
     hs.reset(new HostScope(ctx, "ch.device"));
     struct { ChPair *p; } dPairs;
     struct { uint32_t *p; } dQ, dT, dScratchU, dNode, dMerges;
@@ -374,6 +361,7 @@ extern "C" int sd_clusterhits_batch(sd_ctx *ctx, const sd_ch_params *par, uint32
     SD_HIP(ctx, sdStreamSync(ctx));
     hs.reset(new HostScope(ctx, "ch.finalise"));
     // ---- emission (:456-485): nodes in index order, size >= cls, pCO / pMH thresholds
+    uint32_t badEntry = UINT32_MAX;
 #pragma omp parallel
     {
         std::vector<uint32_t> start, items;
@@ -381,6 +369,17 @@ extern "C" int sd_clusterhits_batch(sd_ctx *ctx, const sd_ch_params *par, uint32
 #pragma omp for schedule(dynamic, 1)
         for (uint32_t p = 0; p < nPairs; p++) {
             const uint64_t off = hitOff[p];
+            if (dense[p]) {
+                nClusters[p] = sd::chDenseEntry(lGamma, (uint32_t) (hitOff[p + 1] - off), qPos + off, tPos + off, strands + off, pval + off,
+                                                (int) Nq[p], par->maxGeneGap, par->clusterSize, par->alpha, par->pCluThr, par->pMHThr,
+                                                clusterOfHit + off, rankInCluster + off, pCO + off, pMH + off, clusterSizeOut + off);
+                if (nClusters[p] == UINT32_MAX) {
+                    nClusters[p] = 0;
+#pragma omp critical
+                    badEntry = std::min(badEntry, p);
+                }
+                continue;
+            }
             const uint32_t K = hp[p].K;
             for (uint32_t h = 0; h < K; h++) {
                 clusterOfHit[off + h] = UINT32_MAX;
@@ -433,5 +432,7 @@ extern "C" int sd_clusterhits_batch(sd_ctx *ctx, const sd_ch_params *par, uint32
             nClusters[p] = nClu;
         }
     }
+    if (badEntry != UINT32_MAX)
+        return sdFail(ctx, SD_EINVAL, "entry %u: hits that share both gene positions put more hits than genes into a cluster", badEntry);
     return SD_OK;
 }

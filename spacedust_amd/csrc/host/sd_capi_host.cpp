@@ -310,6 +310,23 @@ int sd_host_cluster_pvalues(uint32_t nHits, const uint32_t *qPos, const uint32_t
     return SD_OK;
 }
 
+int sd_host_clusterhits_dense(uint32_t nHits, const uint32_t *qPos, const uint32_t *tPos, const uint8_t *strands, const double *pval,
+                               uint32_t querySetSize, const sd_ch_params *par, const double *lGamma, uint32_t lGammaLen,
+                               uint32_t *clusterOfHit, uint32_t *rankInCluster, uint32_t *nClusters, double *pCO, double *pMH,
+                               uint32_t *clusterSizeOut) {
+    if (!par || !lGamma || !nClusters || (nHits && (!qPos || !tPos || !strands || !pval || !clusterOfHit || !rankInCluster || !pCO || !pMH ||
+                                                     !clusterSizeOut)))
+        return SD_EINVAL;
+    uint32_t hi = 0;
+    for (uint32_t x = 0; x < nHits; x++) hi = std::max(hi, std::max(qPos[x], tPos[x]));
+    // the table covers span + 1, hits + 1 and the threshold's d + 2
+    if ((uint64_t) hi + 3 > lGammaLen || (uint64_t) nHits + 2 > lGammaLen || (uint64_t) par->maxGeneGap + 3 > lGammaLen) return SD_EINVAL;
+    *nClusters = sd::chDenseEntry(lGamma, nHits, qPos, tPos, strands, pval, (int) querySetSize, par->maxGeneGap, par->clusterSize,
+                                  par->alpha, par->pCluThr, par->pMHThr, clusterOfHit, rankInCluster, pCO, pMH, clusterSizeOut);
+    if (*nClusters == UINT32_MAX) return SD_EINVAL;   // more hits than genes in a cluster: the reference has no result
+    return SD_OK;
+}
+
 int sd_host_lgamma_table(double *out, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) out[i] = chLogGamma(i * 1.0);
     return SD_OK;

@@ -13,7 +13,8 @@
 // multiply-adds are written as std::fma here (k * ln q0 onto the placement term; m * ln 2 off the tail term) -- the result
 // no longer depends on the compiler's contraction mode -- and r^i / i! keeps the library calls pow and exp.  Pinned bit for
 // bit against the reference's compiled functions (oracle/_ref/libsdref_ch.so): tests/test_oracle_clusterhits_ref.py (host,
-// sd_host_cluster_pvalues) and tests/test_gpu_clusterhits.py (through the device path).
+// sd_host_cluster_pvalues) and tests/test_gpu_clusterhits.py (through the device path); the edges of chMultihitPval and the
+// score form the dense path uses (sd_chdense.cpp) against the reference's rows in tests/test_ch_classes.py.
 #include "sd_host.h"
 
 #include <algorithm>
@@ -70,6 +71,20 @@ double logOrdering(const double *lnFact, const ClusterShape &c) {
 double chClusterPval(const double *lnFact, std::vector<ClusterHit> &members) {
     if (members.empty()) return 1.0;
     const ClusterShape shape = measure(members);
+    return std::exp(0.5 * logPlacement(lnFact, shape) + 0.5 * logOrdering(lnFact, shape));
+}
+
+// halving is exact, so whichever way a compiler contracts the reference's `-0.5 * a - 0.5 * b` the value is -(a + b) / 2
+// rounded once: the score and the P-value above are the same sum
+double chMatchScoreOfShape(const double *lnFact, int k, int span, int m) {
+    ClusterShape shape;
+    shape.hits = k; shape.span = span; shape.conserved = m;
+    return -(0.5 * logPlacement(lnFact, shape) + 0.5 * logOrdering(lnFact, shape));
+}
+
+double chClusterPvalOfShape(const double *lnFact, int k, int span, int m) {
+    ClusterShape shape;
+    shape.hits = k; shape.span = span; shape.conserved = m;
     return std::exp(0.5 * logPlacement(lnFact, shape) + 0.5 * logOrdering(lnFact, shape));
 }
 

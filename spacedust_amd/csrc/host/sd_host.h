@@ -180,6 +180,17 @@ struct ClusterHit {
 // exp(-clusterMatchScore): sorts `cluster` by query position like the reference's findConservedPairs does
 double chClusterPval(const double *lgammaTable, std::vector<ClusterHit> &cluster);
 double chMultihitPval(const double *lgammaTable, const std::vector<ClusterHit> &cluster, int Nq, double alpha);
+// the same from a cluster's shape: k hits over `span` genes, m conserved neighbour pairs.  chMatchScoreOfShape is
+// clusterMatchScore (:120-134), chClusterPvalOfShape its exp(-score)
+double chMatchScoreOfShape(const double *lgammaTable, int k, int span, int m);
+double chClusterPvalOfShape(const double *lgammaTable, int k, int span, int m);
+// One (query set, target set) entry through the reference's dense K x K loop, literally (sd_chdense.cpp): the path of
+// entries that repeat a query position, where the order std::sort leaves equal positions in decides the result.
+// Outputs as sd_clusterhits_batch's, relative to the entry; returns the number of clusters, or UINT32_MAX for an entry whose
+// hits share both positions so often that the reference reads in front of its logGamma table (k hits over fewer than k - 1 genes).
+uint32_t chDenseEntry(const double *lgammaTable, uint32_t K, const uint32_t *qPos, const uint32_t *tPos, const uint8_t *strands,
+                      const double *pval, int Nq, uint32_t maxGeneGap, uint32_t clusterSize, double alpha, float pCluThr,
+                      float pMHThr, uint32_t *clusterOf, uint32_t *rank, double *pCO, double *pMH, uint32_t *size);
 
 }  // namespace sd
 

@@ -68,6 +68,71 @@ def test_module_by_module_reproduces_reference_dbs(work):
     assert sorted_md5(tsv, drop_first_column=True) == 'abb28ee37bc130a5f09a9f767ef00ccf'
 
 
+def _matches_db(work):
+    """the matches DB of test_module_by_module_reproduces_reference_dbs (built here when that test did not run before)"""
+    g = work / 'genome'
+    if not os.path.exists(work / 'matches.index'):
+        sdgpu('prefilter', g, g, work / 'pref_0', *PREFILTER_PAR)
+        sdgpu('align', g, g, work / 'pref_0', work / 'result', *ALIGN_PAR)
+        sdgpu('prefixid', work / 'result', work / 'result_prefixed', '--threads', '8', '-v', '3')
+        sdgpu('besthitbyset', g, g, work / 'result_prefixed', work / 'aggregate', '--simple-best-hit', '1', '--suboptimal-hits', '0',
+              '--threads', '8', '--compressed', '0', '-v', '3')
+        sdgpu('mergeresultsbyset', str(g) + '_set_to_member', work / 'aggregate', work / 'aggregate_merged', '--threads', '8', '-v', '3')
+        sdgpu('combinehits', g, g, work / 'aggregate_merged', work / 'matches', work / 'tmp', '--alpha', '1', '--aggregation-mode', '0',
+              '--filter-self-match', '1', '--threads', '8', '--compressed', '0', '-v', '3')
+    return work / 'matches'
+
+
+def test_clusterhits_module_with_other_flags(work):
+    """`sdgpu clusterhits` away from the workflow's flags (--max-gene-gap 1 --cluster-size 3 --alpha 0.01, a loose
+    --cluster-pval, a strict --multihit-pval) on the matches DB: every cluster record and header, entry by entry, against the
+    reference's own compiled clusterhits code where oracle/_ref holds it, else against the oracle's dense restatement"""
+    import numpy as np
+    from dbutil import read_db
+    from oracle.pyoracle import Oracle, RefClusterHits, oracle_clusterhits, ref_ch_available
+    flags = dict(d=1, cls=3, alpha=0.01, p_clu=0.5, p_mh=1e-6)
+    m = _matches_db(work)
+    g = work / 'genome'
+    sdgpu('clusterhits', g, g, m, work / 'clusters_other', '--multihit-pval', '1e-6', '--cluster-pval', '0.5', '--max-gene-gap', '1',
+          '--cluster-size', '3', '--cluster-use-weight', '0', '--db-output', '1', '--alpha', '0.01', '--threads', '8', '--compressed', '0', '-v', '3')
+    pos, strand = {}, {}
+    for line in open(str(g) + '.lookup'):
+        key, name, _ = line.rstrip('\n').split('\t')
+        _, p, st, en = name.rsplit('_', 3)   # accession_index_start_end
+        pos[int(key)], strand[int(key)] = int(p), int(int(st) < int(en))
+    ref = RefClusterHits() if ref_ch_available() else None
+    orc = None if ref else Oracle(4)
+    body, head = read_db(str(m)), read_db(str(m) + '_h')
+    want_body, want_head, entries = [], [], 0
+    for key in sorted(body):
+        lines = body[key].decode().splitlines(keepends=True)
+        if len(lines) <= 1:
+            continue
+        q_set, t_set, nq = head[key].decode().split('\t')[:3]
+        cols = [l.split() for l in lines]
+        q = np.array([pos[int(c[0])] for c in cols], np.uint32)
+        t = np.array([pos[int(c[1])] for c in cols], np.uint32)
+        s = np.array([strand[int(c[0])] | (strand[int(c[1])] << 1) for c in cols], np.uint8)
+        p = np.array([float(c[2]) for c in cols])
+        assert len(np.unique(q)) == len(q)   # one hit per query protein: the workflow's matches never repeat a query position
+        if ref:
+            cof, rank, sizes, pco, pmh = ref.entry(q, t, s, p, int(nq), **flags)
+            members = [np.nonzero(cof == c)[0][np.argsort(rank[cof == c])] for c in range(len(sizes))]
+        else:
+            cof, mo, sizes, pco, pmh, _ = oracle_clusterhits(orc, q, t, s, p, int(nq), **flags)
+            ends = np.cumsum(sizes)
+            members = [mo[e - n:e] for e, n in zip(ends, sizes)]
+        for c, mem in enumerate(members):
+            want_body.append(''.join(lines[h] for h in mem))
+            want_head.append('%s\t%s\t%.3E\t%.3E\t%d\n' % (q_set, t_set, pco[c], pmh[c], sizes[c]))
+        entries += 1
+    got_body, got_head = read_db(str(work / 'clusters_other')), read_db(str(work / 'clusters_other') + '_h')
+    assert [got_body[k].decode() for k in sorted(got_body)] == want_body
+    assert [got_head[k].decode() for k in sorted(got_head)] == want_head
+    # both genome pairs of the example; 21 + 12 clusters by the reference's compiled code (108 with the workflow's flags)
+    assert entries == 2 and len(want_body) == 33 and all(b.count('\n') >= 3 for b in want_body)
+
+
 def test_align_on_the_reference_prefilter_db(work):
     """`align` alone on the prefilter DB of the real reference classes (fixture), read from split data files"""
     pref = flat_lines_from_gz('config1_pref.tsv.gz')
