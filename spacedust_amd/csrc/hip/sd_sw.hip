@@ -7,11 +7,14 @@
 //     E'(q)   = max(E[q]-ge, Hpre(q)-go, 0)               E is opened from Hpre, NOT from G
 //     Fl'     = max(Fl-ge, Hpre(q)-go, 0)  (reset to 0 where q % segLen == 0),  Ff' = max(Ff-ge, G(q)-go, 0)
 // (M/src/alignment/StripedSmithWaterman.cpp:713-871 byte kernel, :1013-1149 word kernel).
+// Fl is carried by the int32 kernel of this file (sw_score_kernel: every call with go < ge, SD_SW_INT32=1, tasks beyond the
+// int16 range, and sd_sw_score_batch) only.  The packed kernels of sd_sw_pk.h, which run everything else, evaluate
+// Hpre = max(0, G[c-1][q-1] + P, E[q]) without it: for go >= ge, G is the same in every cell (see there).
 //
 // Mapping to CDNA4: integer DP, no MFMA.  A task (one pair, one pass) is owned by a 32-lane half
 // wavefront; lane l holds RT consecutive query rows in VGPRs and the half-wave sweeps the target as a
-// systolic array (lane l works on column k-l at step k), handing (G, Ff, Fl, residue) of its last row to
-// lane l+1 each step.  The per-task query profile (int8 [21][32*RT]) lives in LDS and is the only
+// systolic array (lane l works on column k-l at step k), handing (G, Ff, residue -- and Fl in the int32 kernel) of its
+// last row to lane l+1 each step.  The per-task query profile (int8 [21][32*RT]) lives in LDS and is the only
 // indexed operand; every lane reads only its own RT bytes of the row selected by its current target
 // residue.  HBM traffic is the two residue streams (algorithmic bytes qLen + tLen per task), so the
 // kernel is VALU bound; bench.py reports it in GCUPS.
@@ -929,7 +932,7 @@ int runScoreTasks(sd_ctx *ctx, std::vector<SwTask> &tasks, const sd_seqset *q, c
 // and receives the finished result records + a dense backtrace pool.
 // ---------------------------------------------------------------------------------------------
 // score-pass task classes (the pair sort carries the class in six bits: fewer than 64)
-//   0          packed-int16 kernel, <= 128 rows (general form: per-row segment masks)
+//   0          packed-int16 kernel, <= 128 rows (general form)
 //   1 .. 20    aligned packed kernel (sw_score_pk_aligned_kernel): RT = ceil(n / 32) = 5 .. 24, i.e. 129 .. 768 rows in steps
 //              of 32 -- a task pays for the rows of its class, and the reference's 32 SIMD segments are the 32 lanes
 //   21 .. 23   2 / 3 / more strips of 512 rows (general form)
@@ -2214,7 +2217,9 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
 
     // ---- pass 1: forward, byte-kernel lane structure
     hs.reset(new HostScope(ctx, "align.fwd32"));
-    // the packed-int16 kernel's recurrence needs go >= ge (see sd_sw_pk.h); SD_SW_INT32=1 forces the int32 kernel
+    // the packed-int16 kernels need go >= ge twice over (see sd_sw_pk.h): for their F update, and for leaving out the lane-structure
+    // chain Fl, which changes no G only then.  This is the one place that admits them -- the class keys of all three passes are made
+    // with usePk, and runScoreTasks (sd_sw_score_batch, the host path) launches the int32 kernel only.  SD_SW_INT32=1 forces the int32 kernel
     const int usePk = (go >= ge && go < 1024 && ge >= 0 && getenv("SD_SW_INT32") == nullptr) ? 1 : 0;
     uint32_t nValid = 0;
     hipLaunchKernelGGL(k_make_fwd, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dPQ, dPT, dIdent, queries->dOff, targets->dOff,

@@ -6,7 +6,7 @@
 //     DP register, pair B in the high 16 bits, so each v_pk_* instruction advances two cells;
 //   * lane l owns RT consecutive query rows of both pairs and walks the target one column per step,
 //     one column behind lane l-1 (systolic anti-diagonal): the only traffic between lanes is the
-//     (H, F_first, F_lazy, residue) hand-off, done with DPP wave_shr:1 moves -- no LDS, no bpermute;
+//     (H, F, residue) hand-off, done with DPP wave_shr:1 moves -- no LDS, no bpermute;
 //   * the int8 query profiles (21 residues + 1 neutral row) sit in LDS, read as RT/4 dwords per pair and
 //     step; profile bytes are sign-extended and added to the diagonal in one SDWA v_add_u16 per cell;
 //   * target residues are fetched 32 columns at a time (coalesced) and fed to lane 0 with v_readlane.
@@ -14,6 +14,15 @@
 // recurrence (see sw_score_kernel) is evaluated with unsigned saturating subtractions, which supply every
 // max(...,0) of the original for free, and with F_first' = max(F_first - ge, Hpre - go), which equals
 // max(F_first - ge, G - go) whenever go >= ge (G - go = max(Hpre - go, F_first - go) <= the former).
+// The reference's second vertical chain, the lane-structure F_lazy (a gap that may only have started inside the
+// same SIMD segment; sw_score_kernel carries it), is NOT evaluated here: Hpre = max(h, E).  F_lazy feeds Hpre
+// only and results are read from G = max(Hpre, F_first) only.  F_lazy <= F_first in every cell (the same
+// openings, fewer of them), so it never raises G directly; what it adds to Hpre can only matter through a gap
+// opened from it -- a vertical gap followed at once by a horizontal one, or by a second vertical one -- and for
+// go >= ge the path with the two gaps in the other order costs the same, stays inside the matrix and runs through
+// E and then F_first.  So G, and with it every score and end position, is the same in every cell, whatever the
+// segment length (tests/test_sw_fl_equivalence.py).  This needs go >= ge like the F update above:
+// alignBatchImpl (sd_sw.hip, usePk) sends every other call to the int32 kernel, and nothing else launches these.
 // The column maximum carries the row in its low five bits (g*32 + 31-r, saturating): exact while g < 1024,
 // and a saturated result (1023) is above every byte-kernel overflow threshold, so such pairs are rerun by
 // the caller with the int32 kernel exactly like the reference reruns them with its word kernel.
@@ -32,7 +41,7 @@ struct SwTask {
     int32_t tL;        // target columns scanned
     int32_t qStep;     // +1 forward, -1 reverse pass
     int32_t tStep;
-    int32_t segLen;    // ceil(n / lanes) of the reference kernel being reproduced
+    int32_t segLen;    // ceil(n / lanes) of the reference kernel being reproduced (read by the int32 kernel only)
     uint32_t slot;     // output slot
     uint64_t boundOff; // offset (in uint2 units) into the strip boundary workspace (multi-strip tasks only)
 };
@@ -172,14 +181,12 @@ sw_score_pk_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint
 
     for (int strip = 0; strip < nStrips; strip++) {
         const int q0 = strip * ROWS + l * RT;
-        // ---- query profiles of this strip (SmithWaterman::createQueryProfile, :163-187) and the lazy-F reset rows
-        uint32_t mask[RTP];
+        // ---- query profiles of this strip (SmithWaterman::createQueryProfile, :163-187)
         if (strip > 0) __syncthreads();   // the previous strip's profile reads are done
 #pragma unroll
         for (int x = 0; x < (SHARED ? 1 : 2); x++) {
             const SwTask &T = x ? B : A;
             uint32_t *pw = &prof[SHARED ? grp : 2 * grp + x][0][0] + l * WORDS;
-            int seg = T.segLen > 0 ? q0 % T.segLen : 0;
 #pragma unroll
             for (int w = 0; w < WORDS; w++) {
                 int res[4], cb[4];
@@ -198,12 +205,6 @@ sw_score_pk_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint
                         cb[b] = qBias[idx];
                         pidx[b] = idx * 21;
                     }
-                    const bool reset = valid[b] && seg == 0;
-                    seg = (seg + 1 == T.segLen) ? 0 : seg + 1;
-                    const uint32_t m = reset ? 0u : 0xFFFFu;
-                    if (SHARED) mask[4 * w + b] = m | (m << 16);
-                    else if (x == 0) mask[4 * w + b] = m;
-                    else mask[4 * w + b] |= m << 16;
                 }
                 if (qProf) {   // profile query: the position's own row
                     for (int a = 0; a < 21; a++) {
@@ -237,7 +238,7 @@ sw_score_pk_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint
             H[r] = 0;
             E[r] = 0;
         }
-        uint32_t outG = 0, outFf = 0, outFl = 0, prevInG = 0;
+        uint32_t outG = 0, outFf = 0, prevInG = 0;
         uint32_t curT = PK_NEUTRAL | (PK_NEUTRAL << 8);
         uint32_t bestv = 0, bestcm = 0, bestcol = 0;          // packed tracking (!WIDE)
         uint32_t bestA = 0, bestB = 0, bcolA = 0, bcolB = 0;   // per task (WIDE)
@@ -253,45 +254,41 @@ sw_score_pk_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint
             if (col < B.tL) b = tRes[(int64_t) B.tOff + (int64_t) col * B.tStep];
             return a | (b << 8);
         };
-        auto loadBound = [&](int c0) -> uint4 {
+        auto loadBound = [&](int c0) -> uint2 {   // (G, Ff) of the previous strip's last row: the first 8 bytes of a 16-byte element
             const int col = c0 + l;
-            uint4 v = make_uint4(0, 0, 0, 0);
+            uint2 v = make_uint2(0, 0);
             if (readBound && col < pairTL) {
                 const unsigned long long lo = __hip_atomic_load((unsigned long long *) &bnd[col], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long hi = __hip_atomic_load((unsigned long long *) &bnd[col] + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                v.x = (uint32_t) lo; v.y = (uint32_t) (lo >> 32); v.z = (uint32_t) hi;
+                v.x = (uint32_t) lo; v.y = (uint32_t) (lo >> 32);
             }
             return v;
         };
         if (readBound) __threadfence();   // boundary values of the previous strip must be visible
 
         uint32_t chunk = loadChunk(0);
-        uint4 bchunk = loadBound(0);
+        uint2 bchunk = loadBound(0);
         for (int k0 = 0; k0 < steps; k0 += LW) {
             const uint32_t chunkNext = loadChunk(k0 + LW);
-            uint4 bnext = make_uint4(0, 0, 0, 0);
+            uint2 bnext = make_uint2(0, 0);
             if (readBound) bnext = loadBound(k0 + LW);
             const int iEnd = min(LW, steps - k0);
 #pragma unroll 1
             for (int i = 0; i < iEnd; i++) {
                 // ---- hand-off from lane l-1; lane 0 of each half wavefront takes the target residues (and the
                 //      previous strip's boundary) instead
-                uint32_t inT = dppShr1(curT), inG = dppShr1(outG), inFf = dppShr1(outFf), inFl = dppShr1(outFl);
+                uint32_t inT = dppShr1(curT), inG = dppShr1(outG), inFf = dppShr1(outFf);
                 inT = writeLane<0>(readLane(chunk, i), inT);
                 if (NGRP == 2) inT = writeLane<32>(readLane(chunk, 32 + i), inT);
                 if (readBound) {
                     inG = writeLane<0>(readLane(bchunk.x, i), inG);
                     inFf = writeLane<0>(readLane(bchunk.y, i), inFf);
-                    inFl = writeLane<0>(readLane(bchunk.z, i), inFl);
                     if (NGRP == 2) {
                         inG = writeLane<32>(readLane(bchunk.x, 32 + i), inG);
                         inFf = writeLane<32>(readLane(bchunk.y, 32 + i), inFf);
-                        inFl = writeLane<32>(readLane(bchunk.z, 32 + i), inFl);
                     }
                 } else if (NGRP == 2) {
                     inG = writeLane<32>(0, inG);
                     inFf = writeLane<32>(0, inFf);
-                    inFl = writeLane<32>(0, inFl);
                 }
                 curT = inT;
                 const uint32_t *pa = profA + (curT & 0xFFu) * PSTRIDE;
@@ -304,15 +301,13 @@ sw_score_pk_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint
                                 h[4 * w + 3]);
                 }
                 prevInG = inG;
-                uint32_t Fl = inFl, Ff = inFf, cm = 0, cmA = 0, cmB = 0;
+                uint32_t Ff = inFf, cm = 0, cmA = 0, cmB = 0;
 #pragma unroll
                 for (int r = 0; r < RT; r++) {
-                    Fl &= mask[r];
-                    const uint32_t hpre = pkMax(pkMax(h[r], E[r]), Fl);
+                    const uint32_t hpre = pkMax(h[r], E[r]);
                     const uint32_t g = pkMax(hpre, Ff);
                     const uint32_t open = pkSubSat(hpre, goP);
                     E[r] = pkMax(pkSubSat(E[r], geP), open);
-                    Fl = pkMax(pkSubSat(Fl, geP), open);
                     Ff = pkMax(pkSubSat(Ff, geP), open);
                     H[r] = g;
                     if (WIDE) {
@@ -324,14 +319,11 @@ sw_score_pk_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint
                 }
                 outG = H[RT - 1];
                 outFf = Ff;
-                outFl = Fl;
                 if (MULTI && !lastStrip && l == LW - 1) {
                     const int c = k0 + i - (LW - 1);
                     if (c >= 0 && c < pairTL) {
                         const unsigned long long lo = (unsigned long long) outG | ((unsigned long long) outFf << 32);
                         __hip_atomic_store((unsigned long long *) &bnd[c], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store((unsigned long long *) &bnd[c] + 1, (unsigned long long) outFl, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
                     }
                 }
                 // ---- column maximum: a strictly larger value takes over (first column wins, smallest row inside)
@@ -395,13 +387,13 @@ sw_score_pk_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint
     }
 }
 
-// ---- aligned form: the lanes ARE the reference's SIMD segments ---------------------------------------------------------
+// ---- aligned form: RT = ceil(n / 32) rows per lane, one strip ---------------------------------------------------------------
 // A byte-structure task (segLen = ceil(n / 32), StripedSmithWaterman.cpp:639-915) with n in (32 (RT - 1), 32 RT] has
-// segLen == RT: on a 32-lane group with RT rows per lane the reference's 32 segments are exactly the lanes.  The lazy-F
-// chain of the lane structure, Fl, then restarts at row 0 of every lane in every column: no per-row reset masks, no Fl
-// hand-off, and the first / last row of a lane drop the Fl instructions they do not need.  The class of a task is its RT
-// (5 .. 24: 129 .. 768 rows), so a task pays for at most 31 padding rows and queries beyond 384 rows keep the 32-lane
-// ramp.  Also here, against the per-column overhead of the general kernel (sw_score_pk_kernel):
+// segLen == RT: on a 32-lane group with RT rows per lane the reference's 32 segments are exactly the lanes.  While the kernels
+// carried the lane-structure chain Fl, that was what made this form cheaper per row (no reset masks, no Fl hand-off); with Fl
+// gone from both forms (see the head of this file) results no longer depend on the segment length, and what remains is the
+// layout: the class of a task is its RT (5 .. 24: 129 .. 768 rows), so a task pays for at most 31 padding rows and queries
+// beyond 384 rows keep the 32-lane ramp.  Against the per-column overhead of the general kernel (sw_score_pk_kernel):
 //   * the residue stream carries LDS byte offsets of the profile rows (res * row stride, 16 bits per task), so a lane's
 //     profile address is one SDWA add per task;
 //   * the profile words of column k + 1 are requested before the cells of column k are computed (the residue a lane sees
@@ -430,7 +422,7 @@ __device__ __forceinline__ uint32_t addWord1(uint32_t base, uint32_t packed) {  
     return r;
 }
 
-// Two 32-lane groups of a task pair each per wavefront; a lane is one segment (RT = segLen).
+// Two 32-lane groups of a task pair each per wavefront; a lane holds RT = ceil(n / 32) rows.
 // SHARED: false = every task has its own profile; true = ALL four tasks of the wavefront have the same query (the caller pads a
 // query's run of pairs to whole wavefronts): one profile per wavefront, a quarter of the LDS, which is what lets the memory-bound
 // prefilter workgroups of the other streams live on the same CUs.  Removed variants, each measured no faster (DESIGN.md §4.1,
@@ -613,16 +605,13 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
             addProfile4(pac[w], pbc[w], d0, H[4 * w], H[4 * w + 1], H[4 * w + 2], h[4 * w], h[4 * w + 1], h[4 * w + 2], h[4 * w + 3]);
         }
         prevInG = inG;
-        uint32_t Fl = 0, Ff = inFf, cm = 0;
+        uint32_t Ff = inFf, cm = 0;
 #pragma unroll
         for (int r = 0; r < RT; r++) {
-            uint32_t hpre = pkMax(h[r], E[r]);
-            if (r != 0) hpre = pkMax(hpre, Fl);   // row 0 starts the segment: no vertical gap of the lane structure enters
+            const uint32_t hpre = pkMax(h[r], E[r]);
             const uint32_t g = pkMax(hpre, Ff);
             const uint32_t open = pkSubSat(hpre, goP);
             E[r] = pkMax(pkSubSat(E[r], geP), open);
-            if (r == 0) Fl = open;
-            else if (r + 1 != RT) Fl = pkMax(pkSubSat(Fl, geP), open);
             Ff = pkMax(pkSubSat(Ff, geP), open);
             H[r] = g;
             const uint32_t code = pkRowCode(g, 31 - r);
