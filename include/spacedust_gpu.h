@@ -192,6 +192,20 @@ int sd_sw_alt_last_stats(sd_ctx *ctx, uint64_t *groups, uint64_t *seedRounds, ui
 int sd_sw_set_cigar_pool(sd_ctx *ctx, int on);
 int sd_sw_download_bytes(sd_ctx *ctx, uint64_t *recordBytes, uint64_t *poolBytes);
 
+/* ---- word-structure passes only where the narrow score pass cannot answer ----------------------------------------------------------
+ * on != 0: in the alignment calls of this context (sd_sw_align_batch, _compact, _compact_diag, _best_by_group) a pair whose byte
+ * score saturates (score + bias >= 255) is rerun on the wide packed kernels only when the first pass reported 1023, the value its
+ * row-coded column maximum saturates to, or when the prefilter's diagonal already proves a score of 1023 and the pair skipped the
+ * first pass.  Below 1023 the first pass's (score, tEnd, qEnd) is what the rerun would compute (both packed kernels evaluate the
+ * same cells and choose the end cell by the same rule), so it is final, and the pair's start-position task runs in the narrow
+ * classes.  Records, flags (bit 0 still marks every pair whose byte score saturates) and backtraces are the same bytes either way;
+ * fewer cells are evaluated and counted (sd_sw_last_cells).  Calls on the int32 kernel (gap open < gap extend, SD_SW_INT32=1) and
+ * pairs with more than 65 535 target columns are not affected.  Off by default; the streaming search (sd_search_*) and the
+ * in-memory iterations switch it on for their own contexts (SD_SW_NARROW_FINAL=0 in the environment keeps it off there).
+ * With profiling enabled the calls add three counters to the profile: stat.sw_word_pairs (pairs with flag bit 0),
+ * stat.sw_word_wide (of these: rerun wide) and stat.sw_word_narrow_final (first pass final), as sums in the `ms` field. */
+int sd_sw_set_narrow_final(sd_ctx *ctx, int on);
+
 /* ---- self-test entry points of the library's own device primitives (csrc/hip/sd_scan_sort.h), for tests/ ----------------------
  * sd_selftest_sort_pairs: stable sort of (key, value) pairs by the key bits [beginBit, endBit) -- what the alignment task order and
  * the prefilter's fall-back paths use.  sd_selftest_scan: exclusive sums of n 32-bit values into 64-bit offsets (n + 1 outputs: the

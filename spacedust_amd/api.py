@@ -482,6 +482,11 @@ class Context:
         _check(self.h, self.L.sd_sw_set_cigar_pool(self.h, 1 if on else 0), 'sd_sw_set_cigar_pool')
         self._cigar_pool = bool(on)
 
+    def set_narrow_final(self, on=True):
+        """sd_sw_set_narrow_final: a pair whose byte score saturates is rerun on the wide kernels only when the narrow forward
+        pass reports 1023 (or the pair skipped that pass); same records, fewer launches and cells"""
+        _check(self.h, self.L.sd_sw_set_narrow_final(self.h, 1 if on else 0), 'sd_sw_set_narrow_final')
+
     def sw_download_bytes(self):
         a, b = C.c_uint64(), C.c_uint64()
         self.L.sd_sw_download_bytes(self.h, C.byref(a), C.byref(b))

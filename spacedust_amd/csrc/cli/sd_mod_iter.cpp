@@ -101,6 +101,7 @@ struct Worker {
     uint32_t stamp = 0;
     ~Worker() {
         if (r2p) sd_r2p_destroy(r2p);
+        if (ctx) sd_sw_set_narrow_final(ctx, 0);
         if (ctx) sd_ctx_destroy(ctx);
         if (host) sd_host_destroy(host);
     }
@@ -401,6 +402,8 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
         if (sd_host_create(perWorker, &W.host) != SD_OK) return fail("sd_host_create failed");
         if (sd_r2p_create(&W.r2p) != SD_OK) return fail("sd_r2p_create failed");
         if (S.profile) sd_profile_enable(W.ctx, 1);
+        // word-structure reruns only where the narrow score pass cannot answer (same records; SD_SW_NARROW_FINAL=0: every saturating pair)
+        sd_sw_set_narrow_final(W.ctx, (getenv("SD_SW_NARROW_FINAL") && atoi(getenv("SD_SW_NARROW_FINAL")) == 0) ? 0 : 1);
     }
     // ---- the target: both indexes (the sequence search's k-mer threshold; every k-mer for the profile searches,
     // Prefiltering.cpp:525-527) and the sequences, resident for the whole run

@@ -35,6 +35,7 @@
 namespace {
 
 using sdpk::SwTask;
+using sdpk::NARROW_EXACT;
 
 template <int RT>
 __global__ void __launch_bounds__(64)
@@ -1023,12 +1024,15 @@ __device__ __forceinline__ bool devHasCoverage(float covThr, int covMode, float 
 // prefilter's diagonal at hand, k_pre_word walks that diagonal with the alignment's own scoring (matrix row + composition bias,
 // or the profile row) and marks the pairs whose bound already reaches 255 - bias; they skip pass 1 and go straight to pass 2.
 // On proteome-scale searches that is most true homologs, i.e. the longest-running tasks of pass 1.
+// sd_sw_set_narrow_final (narrowFinal): the bound is NARROW_EXACT instead.  The packed kernels of pass 1 do not saturate at 255: they
+// evaluate the cells the rerun evaluates and choose the end cell by its rule, so below NARROW_EXACT their (score, tEnd, qEnd) is the
+// rerun's and pass 1 is the cheaper way to it; a pair skips pass 1 only when it is certain to need the wide kernel all the same.
 __global__ void __launch_bounds__(256)
 k_pre_word(uint32_t nPairs, const uint32_t *__restrict__ pairQ, const uint32_t *__restrict__ pairT, const uint16_t *__restrict__ pairDiag,
            const uint32_t *__restrict__ fwdKeys, const uint64_t *__restrict__ qOff, const uint64_t *__restrict__ tOff,
            const uint8_t *__restrict__ qRes, const int8_t *__restrict__ qBias, const uint8_t *__restrict__ tRes, const int8_t *__restrict__ mat,
            const int8_t *__restrict__ qProf, const int32_t *__restrict__ minBias, int matMin, uint8_t *__restrict__ preWord,
-           uint32_t *__restrict__ pass1Keys) {
+           uint32_t *__restrict__ pass1Keys, int narrowFinal) {
     __shared__ int8_t smat[441];
     for (int x = threadIdx.x; x < 441; x += blockDim.x) smat[x] = mat[x];
     __syncthreads();
@@ -1043,7 +1047,7 @@ k_pre_word(uint32_t nPairs, const uint32_t *__restrict__ pairQ, const uint32_t *
             const int d = (int) (int16_t) pairDiag[i];
             int q0 = d >= 0 ? d : 0, t0 = d >= 0 ? 0 : -d;
             const int n = min(qL - q0, tL - t0);
-            const int need = 255 - (abs(matMin) + abs(minBias[pairQ[i]]));
+            const int need = narrowFinal ? NARROW_EXACT : 255 - (abs(matMin) + abs(minBias[pairQ[i]]));
             int run = 0, best = 0;
             for (int x = 0; x < n && best < need; x++) {
                 const int qr = qRes[qo + q0 + x], tr = tRes[to + t0 + x];
@@ -1101,22 +1105,32 @@ __global__ void __launch_bounds__(256)
 k_gate_word(uint32_t nPairs, const uint32_t *__restrict__ pairQ, const int32_t *__restrict__ out32,
             const int32_t *__restrict__ minBias, int matMin, SwTask *__restrict__ tasks, uint32_t *__restrict__ keys,
             uint32_t *__restrict__ vals, uint8_t *__restrict__ word, const uint32_t *__restrict__ fwdKeys, int usePk, int wideRowLimit,
-            const uint8_t *__restrict__ preWord /* nullable: pairs that skipped pass 1 because their byte score saturates for certain */) {
+            const uint8_t *__restrict__ preWord /* nullable: pairs that skipped pass 1 because their byte score saturates for certain */,
+            uint8_t *__restrict__ wide /* nullable (sd_sw_set_narrow_final, packed calls): of the word pairs, those that pass 1 does not
+                                          answer -- it was skipped, it reports the saturated row code, or it ran on the int32 kernel */,
+            unsigned long long *__restrict__ wordCount /* with wide: {word pairs, of them wide} are added here */) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nPairs) return;
-    vals[i] = i;
-    bool w = false;
-    if (fwdKeys[i] != KEY_INVALID) {
-        const int mb = minBias[pairQ[i]];
-        const int bias = abs(matMin) + abs(mb);
-        w = (preWord && preWord[i]) || out32[3 * i] + bias >= 255;
+    bool w = false, rerun = false;
+    if (i < nPairs) {
+        vals[i] = i;
+        if (fwdKeys[i] != KEY_INVALID) {
+            const int mb = minBias[pairQ[i]];
+            const int bias = abs(matMin) + abs(mb);
+            const bool pre = preWord && preWord[i];
+            w = pre || out32[3 * i] + bias >= 255;
+            rerun = w && (!wide || pre || out32[3 * i] >= NARROW_EXACT || tasks[i].tL > 65535);
+        }
+        word[i] = w ? 1 : 0;
+        if (wide) wide[i] = rerun ? 1 : 0;
+        if (w) tasks[i].segLen = max(1, (tasks[i].n + 15) / 16);
+        keys[i] = rerun ? scoreKey(tasks[i].n, tasks[i].tL, usePk ? SCORE_PK_WIDE : SCORE_INT32, wideRowLimit) : KEY_INVALID;
     }
-    word[i] = w ? 1 : 0;
-    if (w) {
-        tasks[i].segLen = max(1, (tasks[i].n + 15) / 16);
-        keys[i] = scoreKey(tasks[i].n, tasks[i].tL, usePk ? SCORE_PK_WIDE : SCORE_INT32, wideRowLimit);
-    } else {
-        keys[i] = KEY_INVALID;
+    if (wide) {   // (no thread has returned: the ballots see the whole wavefront)
+        const int nw = __popcll(__ballot(w)), nr = __popcll(__ballot(rerun));
+        if ((threadIdx.x & (warpSize - 1)) == 0 && nw) {
+            atomicAdd(&wordCount[0], (unsigned long long) nw);
+            if (nr) atomicAdd(&wordCount[1], (unsigned long long) nr);
+        }
     }
 }
 
@@ -1126,13 +1140,17 @@ k_gate_rev(uint32_t nPairs, DevGateParams gp, const uint32_t *__restrict__ pairQ
            const uint64_t *__restrict__ qOff, const uint64_t *__restrict__ tOff, const int32_t *__restrict__ out32,
            const int32_t *__restrict__ out16, const uint8_t *__restrict__ word, const uint32_t *__restrict__ fwdKeys,
            SwTask *__restrict__ tasks, uint32_t *__restrict__ keys, uint32_t *__restrict__ vals,
-           sd_sw_result *__restrict__ res, int usePk) {
+           sd_sw_result *__restrict__ res, int usePk,
+           const uint8_t *__restrict__ wide /* nullable (k_gate_word): the word pairs that were rerun; null: all of them */) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nPairs) return;
     vals[i] = i;
     keys[i] = KEY_INVALID;
     if (fwdKeys[i] == KEY_INVALID) return;
-    const int32_t *src = word[i] ? &out16[3 * i] : &out32[3 * i];
+    // a word pair that was not rerun: pass 1's result is the rerun's, and its start-position task stays in the narrow classes whatever
+    // wideRowLimit is -- no cell of a reverse pass exceeds the forward score, which is below NARROW_EXACT
+    const bool rerun = wide ? wide[i] != 0 : word[i] != 0;
+    const int32_t *src = rerun ? &out16[3 * i] : &out32[3 * i];
     sd_sw_result r = res[i];
     r.score = src[0];
     r.tEnd = src[1];
@@ -1158,7 +1176,7 @@ k_gate_rev(uint32_t nPairs, DevGateParams gp, const uint32_t *__restrict__ pairQ
     tk.segLen = max(1, (tk.n + lanes - 1) / lanes);
     tk.slot = i; tk.boundOff = 0;
     tasks[i] = tk;
-    keys[i] = scoreKey(tk.n, tk.tL, !usePk ? SCORE_INT32 : (word[i] ? SCORE_PK_WIDE : SCORE_PK), gp.wideRowLimit);
+    keys[i] = scoreKey(tk.n, tk.tL, !usePk ? SCORE_INT32 : (rerun ? SCORE_PK_WIDE : SCORE_PK), gp.wideRowLimit);
 }
 
 // traceback task classes: N_TB_NARROW register-band classes by query rows, then three LDS-band classes by band width
@@ -2226,7 +2244,9 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
                        dTasks, dFwdKeys, dVals, dRes, usePk);
     // pairs whose byte score saturates for certain (k_pre_word) skip this pass
     uint32_t *dPass1Keys = dFwdKeys;
-    uint8_t *dPreWord = nullptr;
+    uint8_t *dPreWord = nullptr, *dWide = nullptr;
+    const bool narrowFinal = ctx->narrowFinal && usePk;   // sd_sw_set_narrow_final
+    if (narrowFinal) SD_HIP(ctx, wsGet(ctx, "al.wide", N, &dWide));
     if (pairDiag && usePk) {
         uint16_t *dDiag = nullptr;
         SD_HIP(ctx, wsGet(ctx, "al.diag", N, &dDiag));
@@ -2236,7 +2256,8 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
         hipLaunchKernelGGL(k_pre_word, dim3(grid), dim3(256), 0, ctx->stream, nPairs, (const uint32_t *) dPQ, (const uint32_t *) dPT,
                            (const uint16_t *) dDiag, (const uint32_t *) dFwdKeys, (const uint64_t *) queries->dOff, (const uint64_t *) targets->dOff,
                            (const uint8_t *) queries->dRes, (const int8_t *) queries->dBias, (const uint8_t *) targets->dRes, (const int8_t *) dMat,
-                           (const int8_t *) queries->dProf, (const int32_t *) dMinBias, queries->dProf ? 0 : matMin, dPreWord, dPass1Keys);
+                           (const int8_t *) queries->dProf, (const int32_t *) dMinBias, queries->dProf ? 0 : matMin, dPreWord, dPass1Keys,
+                           narrowFinal ? 1 : 0);
     }
     hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dPass1Keys, dCells + 0);
     const uint32_t *dShare = queries->n >= (1u << PAIR_QUERY_BITS) ? nullptr : dPQ;   // forward passes scan whole queries: pair by query
@@ -2246,7 +2267,7 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
     // ---- pass 2: saturated pairs again with the word kernel's 16-lane structure
     hs.reset(new HostScope(ctx, "align.fwd16"));
     hipLaunchKernelGGL(k_gate_word, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dPQ, dOut32, dMinBias, queries->dProf ? 0 : matMin, dTasks, dKeys,
-                       dVals, dWord, dFwdKeys, usePk, gp.wideRowLimit, (const uint8_t *) dPreWord);
+                       dVals, dWord, dFwdKeys, usePk, gp.wideRowLimit, (const uint8_t *) dPreWord, dWide, dCells + 2);
     hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dKeys, dCells + 0);
     rc = devRunScore(ctx, nPairs, dKeys, dVals, dKeysS, dOrder, dBounds, dTasks, dScanA, dScanB, queries, targets, dMat, go, ge,
                      dOut16, &nValid, dShare);
@@ -2254,7 +2275,7 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
     // ---- gates + pass 3: start positions
     hs.reset(new HostScope(ctx, "align.rev"));
     hipLaunchKernelGGL(k_gate_rev, dim3(grid), dim3(256), 0, ctx->stream, nPairs, gp, dPQ, dPT, queries->dOff, targets->dOff, dOut32,
-                       dOut16, dWord, dFwdKeys, dTasks, dRevKeys, dVals, dRes, usePk);
+                       dOut16, dWord, dFwdKeys, dTasks, dRevKeys, dVals, dRes, usePk, (const uint8_t *) dWide);
     hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dRevKeys, dCells + 1);
     rc = devRunScore(ctx, nPairs, dRevKeys, dVals, dKeysS, dOrder, dBounds, dTasks, dScanA, dScanB, queries, targets, dMat, go, ge,
                      dOutRev, &nValid, nullptr);   // start-position tasks scan per-pair prefixes: no shared profile
@@ -2474,6 +2495,15 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
     if (hErr[0] == 2) return sdFail(ctx, SD_EHIP, "Trace back error");
     ctx->cellsFwd = hCells[0];
     ctx->cellsRev = hCells[1];
+    if (narrowFinal && ctx->profiling) {   // counters beside the kernel times (sums in `ms`): what the switch did to this call's word pairs
+        const double add[3] = {(double) hCells[2], (double) hCells[3], (double) (hCells[2] - hCells[3])};
+        static const char *const names[3] = {"stat.sw_word_pairs", "stat.sw_word_wide", "stat.sw_word_narrow_final"};
+        for (int x = 0; x < 3; x++) {
+            sd_profile_entry &pe = ctx->profile[names[x]];
+            pe.ms += add[x];
+            pe.launches += 1;
+        }
+    }
     // identity pairs need pool space too (scoreIdentical backtraces are written by the host below)
     uint64_t identBytes = 0;
     if (isIdentity && btPool)
@@ -2608,6 +2638,12 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
 int sd_sw_set_cigar_pool(sd_ctx *ctx, int on) {
     if (!ctx) return SD_EINVAL;
     ctx->cigarPool = on != 0;
+    return SD_OK;
+}
+
+int sd_sw_set_narrow_final(sd_ctx *ctx, int on) {
+    if (!ctx) return SD_EINVAL;
+    ctx->narrowFinal = on != 0;
     return SD_OK;
 }
 

@@ -68,6 +68,8 @@ __device__ __forceinline__ uint32_t pkAshr(uint32_t a, int s) {
     return __builtin_bit_cast(uint32_t, (s16x2) (__builtin_bit_cast(s16x2, a) >> (s16x2) ((short) s)));
 }
 // g*32 + code in both halves, saturating to int16
+// (NARROW_EXACT: what a saturated row code reports, 32767 >> 5; a narrow kernel's result below it is exact)
+constexpr int NARROW_EXACT = 1023;
 __device__ __forceinline__ uint32_t pkRowCode(uint32_t g, int code) {
     uint32_t r;
     asm("v_pk_mad_i16 %0, %1, 32, %2 op_sel_hi:[1,0,0] clamp" : "=v"(r) : "v"(g), "s"(code));

@@ -523,6 +523,20 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
                 if (c) sd_sw_set_cigar_pool(c, 0);
         }
     } cigarMode(s, s->cigarOnDevice);
+    // The lanes rerun a pair whose byte score saturates on the wide score kernels only where the narrow pass cannot answer: a narrow
+    // forward score below 1023 is already the rerun's result (sd_sw_set_narrow_final; same records).  SD_SW_NARROW_FINAL=0: every
+    // such pair is rerun, as a direct caller's context does.
+    struct NarrowFinalMode {
+        sd_ctx *al[4];
+        explicit NarrowFinalMode(sd_search *s_, bool on) : al{s_->ctxAl, s_->ctxAl2, s_->ctxAlMore[0], s_->ctxAlMore[1]} {
+            for (sd_ctx *c : al)
+                if (c) sd_sw_set_narrow_final(c, on ? 1 : 0);
+        }
+        ~NarrowFinalMode() {
+            for (sd_ctx *c : al)
+                if (c) sd_sw_set_narrow_final(c, 0);
+        }
+    } narrowFinalMode(s, !(getenv("SD_SW_NARROW_FINAL") && atoi(getenv("SD_SW_NARROW_FINAL")) == 0));
     std::vector<uint32_t> qSetSize(Q->nSets, 0);
     if (aggregate)
         for (uint32_t i = 0; i < Q->n; i++)
