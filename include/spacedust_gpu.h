@@ -213,6 +213,12 @@ int sd_sw_set_narrow_final(sd_ctx *ctx, int on);
 int sd_selftest_sort_pairs(sd_ctx *ctx, const uint32_t *keys, const uint32_t *vals, uint32_t n, int beginBit, int endBit, uint32_t *outKeys,
                            uint32_t *outVals);
 int sd_selftest_scan(sd_ctx *ctx, const uint32_t *in, uint32_t n, uint64_t *exclusiveSum, uint32_t *runningMax);
+/* sd_selftest_score_class: the class of the Smith-Waterman score-class table (csrc/hip/sd_sw.hip) that a task of n rows and tL columns
+ * falls into, and the profile scope of the kernel that runs it, for tasks paired by query (shared != 0) or alone.  kernel: what the
+ * gates ask for -- 0 the packed kernels, 1 the packed kernels with the wide row code (beyond wideRowLimit in both dimensions: the
+ * int32 kernel), 2 the int32 kernel.  The table and the index function are the ones the device code uses; no context, no GPU. */
+int sd_selftest_score_class(int kernel /* 0 packed, 1 packed wide, 2 int32 */, int32_t n, int32_t tL, int shared, int32_t wideRowLimit,
+                            uint32_t *klass, char *scope, size_t cap);
 /* sd_selftest_r2p_weights: the weights stage of result2profile alone (csrc/hip/sd_r2p.hip) on nTasks alignments given as cell
  * matrices, task after task, row-major [nRows][L], row 0 the centre; cell codes 0..19 residue, 20 any residue, 21 gap.  The global
  * weights are formed as sd_r2p_batch forms them; with a context the alignments go through the staging of sd_r2p_batch_device (the

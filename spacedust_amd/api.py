@@ -122,6 +122,16 @@ class Host:
     def bitscore(self, score):
         return self.L.sd_host_bitscore(float(score))
 
+    def score_class(self, kernel, n, tl, shared, wide_row_limit):
+        """sd_selftest_score_class: (class, profile scope) of a Smith-Waterman score task of n rows and tl columns on kernel
+        0 (packed), 1 (packed, wide row code) or 2 (int32), from the library's class table; needs no GPU"""
+        klass = C.c_uint32()
+        if not hasattr(self, '_scope_buf'):
+            self._scope_buf = C.create_string_buffer(48)
+        _check(None, self.L.sd_selftest_score_class(kernel, n, tl, int(shared), wide_row_limit, C.byref(klass), self._scope_buf, 48),
+               'sd_selftest_score_class')
+        return klass.value, self._scope_buf.value.decode()
+
 
 def uncompress_cigar(c):
     """Matcher::uncompressAlignment (Matcher.cpp:187-201)"""

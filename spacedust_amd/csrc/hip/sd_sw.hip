@@ -785,6 +785,11 @@ sw_traceback_narrow_kernel(TbTask *__restrict__ tasks, uint32_t nTasks, const ui
     res[2 * id + 1] = ids;
 }
 
+// ---- score kernels: one launcher signature for all three families (n: entries of dOrder; dBound: strip hand-over space of the
+// multi-strip classes, unused by the others)
+using ScoreLaunch = void (*)(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, uint32_t n, const sd_seqset *q, const sd_seqset *t,
+                             const int8_t *dMat, int go, int ge, int32_t *dOut, uint2 *dBound);
+
 template <int RT, int LW, bool MULTI, bool WIDE, bool SHARED>
 void launchScorePk(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, uint32_t n, const sd_seqset *q,
                    const sd_seqset *t, const int8_t *dMat, int go, int ge, int32_t *dOut, uint2 *dBound) {
@@ -797,7 +802,7 @@ void launchScorePk(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, ui
 
 template <int RT, bool SHARED>
 void launchScorePkAligned(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, uint32_t n, const sd_seqset *q, const sd_seqset *t,
-                          const int8_t *dMat, int go, int ge, int32_t *dOut) {
+                          const int8_t *dMat, int go, int ge, int32_t *dOut, uint2 * /* dBound: one strip */) {
     if (n == 0) return;
     constexpr uint32_t perWave = 4;   // two 32-lane groups of a task pair each
     dim3 grid((n + perWave - 1) / perWave), block(64);
@@ -805,22 +810,7 @@ void launchScorePkAligned(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOr
                        dMat, go, ge, dOut, dOrder, (const int8_t *) q->dProf);
 }
 
-int rtClass(int n) {
-    if (n <= 128) return 4;
-    if (n <= 256) return 8;
-    if (n <= 512) return 16;
-    return 32;
-}
-
-template <int RT>
-void launchScore(sd_ctx *ctx, const SwTask *dTasks, uint32_t n, const sd_seqset *q, const sd_seqset *t,
-                 const int8_t *dMat, int go, int ge, int32_t *dOut, uint2 *dBound) {
-    if (n == 0) return;
-    dim3 grid((n + 1) / 2), block(64);
-    hipLaunchKernelGGL(sw_score_kernel<RT>, grid, block, 0, ctx->stream, dTasks, n, q->dRes, q->dBias, t->dRes, dMat,
-                       go, ge, dOut, dBound, (const uint32_t *) nullptr, (const int8_t *) q->dProf);
-}
-
+// dOrder nullable: the tasks in their own order
 template <int RT>
 void launchScoreIdx(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, uint32_t n, const sd_seqset *q,
                     const sd_seqset *t, const int8_t *dMat, int go, int ge, int32_t *dOut, uint2 *dBound) {
@@ -828,6 +818,120 @@ void launchScoreIdx(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, u
     dim3 grid((n + 1) / 2), block(64);
     hipLaunchKernelGGL(sw_score_kernel<RT>, grid, block, 0, ctx->stream, dTasks, n, q->dRes, q->dBias, t->dRes, dMat,
                        go, ge, dOut, dBound, dOrder, (const int8_t *) q->dProf);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The score-class table: a class is a row limit of one of three forms, and per form of pairing (tasks of one query two by two --
+// shared -- or every task alone) the kernel instantiation that runs it and the profile scope that names that kernel.  Everything
+// that has to know a class reads it here: the class of a task (scoreClassOf, checked against the limits below for every row count),
+// the strip hand-over space (k_bound_need), the launches (devRunScore, runScoreTasks) and sd_selftest_score_class.
+//   narrow    pass 1 and the start positions of its results: <= 128 rows on the general packed kernel, 129 .. 768 rows in steps of 32
+//             on the aligned one (RT = ceil(n / 32) = 5 .. 24: a task pays for the rows of its class, and the reference's 32 SIMD
+//             segments are the 32 lanes), then 2 / 3 / more strips of 512 rows.  Unshared tasks (two profiles per pair in LDS) beyond
+//             384 rows keep their class of 32 rows and run on the general kernel of 512 / 640 / 768 rows
+//   wide      the general packed kernel with the wide row code: word-kernel reruns and their start positions
+//   int32     every call the packed kernels do not take (usePk), and word tasks beyond wideRowLimit
+// The pair sort carries the class in six bits: fewer than 64 classes.
+enum ScoreKernel { SCORE_PK = 0, SCORE_PK_WIDE = 1, SCORE_INT32 = 2 };
+constexpr int SCORE_ROWS_ANY = 0x7FFFFFFF;
+constexpr int I32_STRIP_ROWS = 1024;   // sw_score_kernel<32>: a task of more rows hands its last row from strip to strip
+struct ScoreSide { const char *scope; ScoreLaunch launch; };
+struct ScoreClass {
+    ScoreKernel form;
+    int rows;        // the class holds the tasks of its form with more rows than the class before it and at most this many
+    int boundNeed;   // strip hand-over space, uint2 per target column: the packed kernels hand over 16 bytes, the int32 kernel 8
+    ScoreSide shared, unshared;
+};
+constexpr ScoreClass SCORE_CLASSES[] = {
+    {SCORE_PK, 128, 0, {"sw_score_pk.rt4x32", launchScorePk<4, 32, false, false, true>}, {"sw_score_pk.rt4x32", launchScorePk<4, 32, false, false, false>}},
+    {SCORE_PK, 160, 0, {"sw_score_pk.a_seg5", launchScorePkAligned<5, true>}, {"sw_score_pk.a_seg5", launchScorePkAligned<5, false>}},
+    {SCORE_PK, 192, 0, {"sw_score_pk.a_seg6", launchScorePkAligned<6, true>}, {"sw_score_pk.a_seg6", launchScorePkAligned<6, false>}},
+    {SCORE_PK, 224, 0, {"sw_score_pk.a_seg7", launchScorePkAligned<7, true>}, {"sw_score_pk.a_seg7", launchScorePkAligned<7, false>}},
+    {SCORE_PK, 256, 0, {"sw_score_pk.a_seg8", launchScorePkAligned<8, true>}, {"sw_score_pk.a_seg8", launchScorePkAligned<8, false>}},
+    {SCORE_PK, 288, 0, {"sw_score_pk.a_seg9", launchScorePkAligned<9, true>}, {"sw_score_pk.a_seg9", launchScorePkAligned<9, false>}},
+    {SCORE_PK, 320, 0, {"sw_score_pk.a_seg10", launchScorePkAligned<10, true>}, {"sw_score_pk.a_seg10", launchScorePkAligned<10, false>}},
+    {SCORE_PK, 352, 0, {"sw_score_pk.a_seg11", launchScorePkAligned<11, true>}, {"sw_score_pk.a_seg11", launchScorePkAligned<11, false>}},
+    {SCORE_PK, 384, 0, {"sw_score_pk.a_seg12", launchScorePkAligned<12, true>}, {"sw_score_pk.a_seg12", launchScorePkAligned<12, false>}},
+    {SCORE_PK, 416, 0, {"sw_score_pk.a_seg13", launchScorePkAligned<13, true>}, {"sw_score_pk.rt8x64", launchScorePk<8, 64, false, false, false>}},
+    {SCORE_PK, 448, 0, {"sw_score_pk.a_seg14", launchScorePkAligned<14, true>}, {"sw_score_pk.rt8x64", launchScorePk<8, 64, false, false, false>}},
+    {SCORE_PK, 480, 0, {"sw_score_pk.a_seg15", launchScorePkAligned<15, true>}, {"sw_score_pk.rt8x64", launchScorePk<8, 64, false, false, false>}},
+    {SCORE_PK, 512, 0, {"sw_score_pk.a_seg16", launchScorePkAligned<16, true>}, {"sw_score_pk.rt8x64", launchScorePk<8, 64, false, false, false>}},
+    {SCORE_PK, 544, 0, {"sw_score_pk.a_seg17", launchScorePkAligned<17, true>}, {"sw_score_pk.rt10x64", launchScorePk<10, 64, false, false, false>}},
+    {SCORE_PK, 576, 0, {"sw_score_pk.a_seg18", launchScorePkAligned<18, true>}, {"sw_score_pk.rt10x64", launchScorePk<10, 64, false, false, false>}},
+    {SCORE_PK, 608, 0, {"sw_score_pk.a_seg19", launchScorePkAligned<19, true>}, {"sw_score_pk.rt10x64", launchScorePk<10, 64, false, false, false>}},
+    {SCORE_PK, 640, 0, {"sw_score_pk.a_seg20", launchScorePkAligned<20, true>}, {"sw_score_pk.rt10x64", launchScorePk<10, 64, false, false, false>}},
+    {SCORE_PK, 672, 0, {"sw_score_pk.a_seg21", launchScorePkAligned<21, true>}, {"sw_score_pk.rt12x64", launchScorePk<12, 64, false, false, false>}},
+    {SCORE_PK, 704, 0, {"sw_score_pk.a_seg22", launchScorePkAligned<22, true>}, {"sw_score_pk.rt12x64", launchScorePk<12, 64, false, false, false>}},
+    {SCORE_PK, 736, 0, {"sw_score_pk.a_seg23", launchScorePkAligned<23, true>}, {"sw_score_pk.rt12x64", launchScorePk<12, 64, false, false, false>}},
+    {SCORE_PK, 768, 0, {"sw_score_pk.a_seg24", launchScorePkAligned<24, true>}, {"sw_score_pk.rt12x64", launchScorePk<12, 64, false, false, false>}},
+    {SCORE_PK, 1024, 2, {"sw_score_pk.rt8x64s2", launchScorePk<8, 64, true, false, true>}, {"sw_score_pk.rt8x64s2", launchScorePk<8, 64, true, false, false>}},
+    {SCORE_PK, 1536, 2, {"sw_score_pk.rt8x64s3", launchScorePk<8, 64, true, false, true>}, {"sw_score_pk.rt8x64s3", launchScorePk<8, 64, true, false, false>}},
+    {SCORE_PK, SCORE_ROWS_ANY, 2, {"sw_score_pk.rt8x64sN", launchScorePk<8, 64, true, false, true>}, {"sw_score_pk.rt8x64sN", launchScorePk<8, 64, true, false, false>}},
+    {SCORE_PK_WIDE, 128, 0, {"sw_score_pk.w_rt4x32", launchScorePk<4, 32, false, true, true>}, {"sw_score_pk.w_rt4x32", launchScorePk<4, 32, false, true, false>}},
+    {SCORE_PK_WIDE, 192, 0, {"sw_score_pk.w_rt6x32", launchScorePk<6, 32, false, true, true>}, {"sw_score_pk.w_rt6x32", launchScorePk<6, 32, false, true, false>}},
+    {SCORE_PK_WIDE, 224, 0, {"sw_score_pk.w_rt7x32", launchScorePk<7, 32, false, true, true>}, {"sw_score_pk.w_rt7x32", launchScorePk<7, 32, false, true, false>}},
+    {SCORE_PK_WIDE, 256, 0, {"sw_score_pk.w_rt8x32", launchScorePk<8, 32, false, true, true>}, {"sw_score_pk.w_rt8x32", launchScorePk<8, 32, false, true, false>}},
+    {SCORE_PK_WIDE, 288, 0, {"sw_score_pk.w_rt9x32", launchScorePk<9, 32, false, true, true>}, {"sw_score_pk.w_rt9x32", launchScorePk<9, 32, false, true, false>}},
+    {SCORE_PK_WIDE, 320, 0, {"sw_score_pk.w_rt10x32", launchScorePk<10, 32, false, true, true>}, {"sw_score_pk.w_rt10x32", launchScorePk<10, 32, false, true, false>}},
+    {SCORE_PK_WIDE, 352, 0, {"sw_score_pk.w_rt11x32", launchScorePk<11, 32, false, true, true>}, {"sw_score_pk.w_rt11x32", launchScorePk<11, 32, false, true, false>}},
+    {SCORE_PK_WIDE, 384, 0, {"sw_score_pk.w_rt12x32", launchScorePk<12, 32, false, true, true>}, {"sw_score_pk.w_rt12x32", launchScorePk<12, 32, false, true, false>}},
+    {SCORE_PK_WIDE, 512, 0, {"sw_score_pk.w_rt8x64", launchScorePk<8, 64, false, true, true>}, {"sw_score_pk.w_rt8x64", launchScorePk<8, 64, false, true, false>}},
+    {SCORE_PK_WIDE, 640, 0, {"sw_score_pk.w_rt10x64", launchScorePk<10, 64, false, true, true>}, {"sw_score_pk.w_rt10x64", launchScorePk<10, 64, false, true, false>}},
+    {SCORE_PK_WIDE, 768, 0, {"sw_score_pk.w_rt12x64", launchScorePk<12, 64, false, true, true>}, {"sw_score_pk.w_rt12x64", launchScorePk<12, 64, false, true, false>}},
+    {SCORE_PK_WIDE, 1024, 2, {"sw_score_pk.w_rt8x64s2", launchScorePk<8, 64, true, true, true>}, {"sw_score_pk.w_rt8x64s2", launchScorePk<8, 64, true, true, false>}},
+    {SCORE_PK_WIDE, 1536, 2, {"sw_score_pk.w_rt8x64s3", launchScorePk<8, 64, true, true, true>}, {"sw_score_pk.w_rt8x64s3", launchScorePk<8, 64, true, true, false>}},
+    {SCORE_PK_WIDE, SCORE_ROWS_ANY, 2, {"sw_score_pk.w_rt8x64sN", launchScorePk<8, 64, true, true, true>}, {"sw_score_pk.w_rt8x64sN", launchScorePk<8, 64, true, true, false>}},
+    // (tasks of the int32 classes are never paired; of the last class only those of more than I32_STRIP_ROWS rows hand over)
+    {SCORE_INT32, 128, 0, {"sw_score.rt4", launchScoreIdx<4>}, {"sw_score.rt4", launchScoreIdx<4>}},
+    {SCORE_INT32, 256, 0, {"sw_score.rt8", launchScoreIdx<8>}, {"sw_score.rt8", launchScoreIdx<8>}},
+    {SCORE_INT32, 512, 0, {"sw_score.rt16", launchScoreIdx<16>}, {"sw_score.rt16", launchScoreIdx<16>}},
+    {SCORE_INT32, SCORE_ROWS_ANY, 1, {"sw_score.rt32", launchScoreIdx<32>}, {"sw_score.rt32", launchScoreIdx<32>}},
+};
+constexpr uint32_t N_SCORE_CLASSES = sizeof(SCORE_CLASSES) / sizeof(SCORE_CLASSES[0]);
+static_assert(N_SCORE_CLASSES < 63, "class boundaries are found by one 64-lane wavefront; six class bits in the pair key");
+constexpr uint32_t firstScoreClass(ScoreKernel form) {
+    uint32_t ci = 0;
+    while (SCORE_CLASSES[ci].form != form) ci++;
+    return ci;
+}
+constexpr uint32_t FIRST_WIDE_CLASS = firstScoreClass(SCORE_PK_WIDE), FIRST_INT32_CLASS = firstScoreClass(SCORE_INT32);
+constexpr uint32_t KEY_INVALID = N_SCORE_CLASSES * 1024u;   // sorts after every class
+// the classes whose tasks need `need` uint2 of hand-over space per column, one bit each (device code reads the table through constants)
+constexpr uint64_t scoreBoundMask(int need) {
+    uint64_t m = 0;
+    for (uint32_t ci = 0; ci < N_SCORE_CLASSES; ci++) m |= (uint64_t) (SCORE_CLASSES[ci].boundNeed == need) << ci;
+    return m;
+}
+// the class of a task in closed form (the gate kernels run it per pair).
+// wideRowLimit: int16 cells hold a score for certain while min(n, tL) * (largest entry of this call's query profiles) <= 32 767
+// (no saturation of the reference's word kernel to reproduce, no wrap); longer pairs take the int32 kernel
+constexpr __host__ __device__ uint32_t scoreClassOf(int n, int tL, int kernel, int wideRowLimit) {
+    if (kernel == SCORE_PK_WIDE && (n < tL ? n : tL) > wideRowLimit) kernel = SCORE_INT32;
+    if (kernel == SCORE_INT32 || tL > 65535) return FIRST_INT32_CLASS + (n <= 128 ? 0 : (n <= 256 ? 1 : (n <= 512 ? 2 : 3)));
+    const int strips = (n + 511) / 512 < 4 ? (n + 511) / 512 : 4;   // beyond 768 rows: 2, 3, more
+    if (kernel == SCORE_PK_WIDE) {
+        if (n <= 192) return FIRST_WIDE_CLASS + (n <= 128 ? 0 : 1);
+        if (n <= 384) return FIRST_WIDE_CLASS + 2 + (n - 193) / 32;   // 224, 256, 288, 320, 352, 384 rows
+        if (n <= 768) return FIRST_WIDE_CLASS + (n <= 512 ? 8 : (n <= 640 ? 9 : 10));
+        return FIRST_WIDE_CLASS + 11 + strips - 2;
+    }
+    if (n <= 128) return 0;
+    if (n <= 768) return (n + 31) / 32 - 4;   // RT = 5 .. 24
+    return 21 + strips - 2;
+}
+constexpr bool scoreClassesAreTheTables() {
+    for (int form = SCORE_PK; form <= SCORE_INT32; form++)
+        for (int n = 1; n <= 2049; n++) {
+            const uint32_t ci = scoreClassOf(n, 1, form, SCORE_ROWS_ANY);
+            if (ci >= N_SCORE_CLASSES || SCORE_CLASSES[ci].form != form || n > SCORE_CLASSES[ci].rows) return false;
+            if (ci > 0 && SCORE_CLASSES[ci - 1].form == form && n <= SCORE_CLASSES[ci - 1].rows) return false;
+        }
+    return true;
+}
+static_assert(scoreClassesAreTheTables(), "scoreClassOf: n lies in (rows of the class before, rows of its class] for every n, in every form");
+static_assert(SCORE_CLASSES[N_SCORE_CLASSES - 1].form == SCORE_INT32 && SCORE_CLASSES[FIRST_INT32_CLASS - 1].form == SCORE_PK_WIDE, "forms in order");
+__device__ __forceinline__ uint32_t scoreKey(int n, int tL, int kernel, int wideRowLimit = 800) {
+    return scoreClassOf(n, tL, kernel, wideRowLimit) * 1024u + (uint32_t) (1023 - min(tL >> 4, 1023));
 }
 
 // run a list of score tasks (any mix of sizes); results land in hOut[3*slot..]
@@ -839,16 +943,15 @@ int runScoreTasks(sd_ctx *ctx, std::vector<SwTask> &tasks, const sd_seqset *q, c
     if (tasks.empty()) return SD_OK;
     HostScope hsAll(ctx, "score.total");
     const size_t n = tasks.size();
-    constexpr int NB = 4 * 1024;
+    constexpr int N_I32 = N_SCORE_CLASSES - FIRST_INT32_CLASS, NB = N_I32 * 1024;
     auto keyOf = [](const SwTask &t) {
-        const int c = rtClass(t.n);
-        const int ci = c == 4 ? 0 : (c == 8 ? 1 : (c == 16 ? 2 : 3));
-        return (uint32_t) ci * 1024u + (uint32_t) (1023 - std::min(t.tL >> 4, 1023));
+        const uint32_t ci = scoreClassOf(t.n, t.tL, SCORE_INT32, 0) - FIRST_INT32_CLASS;
+        return ci * 1024u + (uint32_t) (1023 - std::min(t.tL >> 4, 1023));
     };
     SwTask *sorted = nullptr;
     SD_HIP(ctx, pinGet(ctx, (std::string("sw.tasks.") + tag).c_str(), n, &sorted));
     uint64_t boundTotal = 0, cellSum = 0;
-    size_t classBegin[5] = {0, 0, 0, 0, 0};
+    size_t classBegin[N_I32 + 1] = {};
     {
         int T = 1;
 #pragma omp parallel
@@ -878,7 +981,7 @@ int runScoreTasks(sd_ctx *ctx, std::vector<SwTask> &tasks, const sd_seqset *q, c
                 run += c;
             }
         }
-        classBegin[4] = run;
+        classBegin[N_I32] = run;
 #pragma omp parallel num_threads(T)
         {
             const int th = omp_get_thread_num();
@@ -888,8 +991,8 @@ int runScoreTasks(sd_ctx *ctx, std::vector<SwTask> &tasks, const sd_seqset *q, c
         }
     }
     *cells += cellSum;
-    for (size_t i = classBegin[3]; i < classBegin[4]; i++) {   // multi-strip tasks exist in class 32 only
-        if (sorted[i].n > 1024) {
+    for (size_t i = classBegin[N_I32 - 1]; i < classBegin[N_I32]; i++) {   // multi-strip tasks exist in the last class only
+        if (sorted[i].n > I32_STRIP_ROWS) {
             sorted[i].boundOff = boundTotal;
             boundTotal += (uint64_t) sorted[i].tL;
         }
@@ -904,19 +1007,12 @@ int runScoreTasks(sd_ctx *ctx, std::vector<SwTask> &tasks, const sd_seqset *q, c
     SD_HIP(ctx, pinGet(ctx, "sw.hout", (size_t) nSlots * 3, &hPin));
     SD_HIP(ctx, hipMemcpyAsync(dTasks, sorted, n * sizeof(SwTask), hipMemcpyHostToDevice, ctx->stream));
     SD_HIP(ctx, hipMemsetAsync(dOut, 0, (size_t) nSlots * 3 * sizeof(int32_t), ctx->stream));
-    static const int classes[4] = {4, 8, 16, 32};
-    for (int ci = 0; ci < 4; ci++) {
+    for (int ci = 0; ci < N_I32; ci++) {
         const size_t begin = classBegin[ci], end = classBegin[ci + 1];
         if (end == begin) continue;
-        const uint32_t cnt = (uint32_t) (end - begin);
         {
             ProfScope ps(ctx, "sw_score");
-            switch (classes[ci]) {
-                case 4: launchScore<4>(ctx, dTasks + begin, cnt, q, t, dMat, go, ge, dOut, dBound); break;
-                case 8: launchScore<8>(ctx, dTasks + begin, cnt, q, t, dMat, go, ge, dOut, dBound); break;
-                case 16: launchScore<16>(ctx, dTasks + begin, cnt, q, t, dMat, go, ge, dOut, dBound); break;
-                default: launchScore<32>(ctx, dTasks + begin, cnt, q, t, dMat, go, ge, dOut, dBound); break;
-            }
+            SCORE_CLASSES[FIRST_INT32_CLASS + ci].unshared.launch(ctx, dTasks + begin, nullptr, (uint32_t) (end - begin), q, t, dMat, go, ge, dOut, dBound);
         }
         SD_HIP(ctx, hipGetLastError());
     }
@@ -932,48 +1028,6 @@ int runScoreTasks(sd_ctx *ctx, std::vector<SwTask> &tasks, const sd_seqset *q, c
 // the ordering of tasks all happen on the GPU; the host only launches, reads six class boundaries per pass
 // and receives the finished result records + a dense backtrace pool.
 // ---------------------------------------------------------------------------------------------
-// score-pass task classes (the pair sort carries the class in six bits: fewer than 64)
-//   0          packed-int16 kernel, <= 128 rows (general form)
-//   1 .. 20    aligned packed kernel (sw_score_pk_aligned_kernel): RT = ceil(n / 32) = 5 .. 24, i.e. 129 .. 768 rows in steps
-//              of 32 -- a task pays for the rows of its class, and the reference's 32 SIMD segments are the 32 lanes
-//   21 .. 23   2 / 3 / more strips of 512 rows (general form)
-//   24 .. 37   the general packed kernel with the wide row code (word-kernel reruns; rows: <=128, <=192, <=224, <=256,
-//              <=288, <=320, <=352, <=384, <=512, <=640, <=768, then 2 / 3 / more strips)
-//   38 .. 41   int32 kernel (rows: <=128, <=256, <=512, more)
-constexpr uint32_t N_NARROW_CLASSES = 24;
-constexpr uint32_t FIRST_NARROW_MULTI = 21;
-constexpr uint32_t N_PK_CLASSES = 14;     // classes of the wide form
-constexpr uint32_t FIRST_MULTI_PK = 11;   // (wide form) classes of more than one strip
-constexpr uint32_t FIRST_WIDE_CLASS = N_NARROW_CLASSES;
-constexpr uint32_t FIRST_INT32_CLASS = FIRST_WIDE_CLASS + N_PK_CLASSES;
-constexpr uint32_t N_SCORE_CLASSES = FIRST_INT32_CLASS + 4;
-static_assert(N_SCORE_CLASSES < 63, "class boundaries are found by one 64-lane wavefront; six class bits in the pair key");
-enum ScoreKernel { SCORE_PK = 0, SCORE_PK_WIDE = 1, SCORE_INT32 = 2 };
-constexpr uint32_t KEY_INVALID = N_SCORE_CLASSES * 1024u;   // sorts after every class
-__host__ __device__ __forceinline__ bool scoreClassIsMulti(uint32_t ci) {   // packed classes of more than one strip
-    return (ci >= FIRST_NARROW_MULTI && ci < FIRST_WIDE_CLASS) || (ci >= FIRST_WIDE_CLASS + FIRST_MULTI_PK && ci < FIRST_INT32_CLASS);
-}
-// wideRowLimit: int16 cells hold a score for certain while min(n, tL) * (largest entry of this call's query profiles) <= 32 767
-// (no saturation of the reference's word kernel to reproduce, no wrap); longer pairs take the int32 kernel
-__device__ __forceinline__ uint32_t scoreKey(int n, int tL, int kernel, int wideRowLimit = 800) {
-    int ci;
-    if (kernel == SCORE_PK_WIDE && min(n, tL) > wideRowLimit) kernel = SCORE_INT32;
-    if (kernel == SCORE_INT32 || tL > 65535) {
-        ci = FIRST_INT32_CLASS + (n <= 128 ? 0 : (n <= 256 ? 1 : (n <= 512 ? 2 : 3)));
-    } else if (kernel == SCORE_PK_WIDE) {
-        if (n <= 192) ci = n <= 128 ? 0 : 1;
-        else if (n <= 384) ci = 2 + (n - 193) / 32;                      // 224, 256, 288, 320, 352, 384 rows -> 2..7
-        else if (n <= 768) ci = n <= 512 ? 8 : (n <= 640 ? 9 : 10);
-        else ci = min((int) FIRST_MULTI_PK + (n + 511) / 512 - 2, 13);   // 2 strips -> 11, 3 strips -> 12, more -> 13
-        ci += FIRST_WIDE_CLASS;
-    } else {
-        if (n <= 128) ci = 0;
-        else if (n <= 768) ci = (n + 31) / 32 - 4;                       // RT = 5 .. 24 -> 1 .. 20
-        else ci = min((int) FIRST_NARROW_MULTI + (n + 511) / 512 - 2, (int) FIRST_WIDE_CLASS - 1);
-    }
-    return (uint32_t) ci * 1024u + (uint32_t) (1023 - min(tL >> 4, 1023));
-}
-
 struct DevGateParams {
     int go, ge, matMin, swMode, covMode, wideRowLimit;
     float covThr;
@@ -1184,40 +1238,72 @@ k_gate_rev(uint32_t nPairs, DevGateParams gp, const uint32_t *__restrict__ pairQ
 // The register-band kernel keeps a task's direction codes (16 B per row), query / bias / target slices in LDS, and
 // it is latency bound, so its throughput is its occupancy: classes by query rows keep the LDS request close to what
 // the tasks need (a band <= 14 means |tLen - qLen| <= 13, so qCap + 16 target columns always suffice).
+// TB_CLASSES is that table for the device (tbKey, tbDirBytes) and the host (the launches of both orchestrations).
+// cap: query rows of a register-band class; band cells per row of an LDS-band class, whose widest band is cap - 1; 0: the global class
+struct TbClass { int cap; const char *scope; };
 constexpr int N_TB_NARROW = 9;
-__constant__ int c_tbNarrowQ[N_TB_NARROW] = {128, 192, 256, 320, 384, 512, 640, 768, 1024};
-static const int TB_NARROW_Q[N_TB_NARROW] = {128, 192, 256, 320, 384, 512, 640, 768, 1024};
-__device__ __forceinline__ bool tbNarrow(int band, int qLen, int tLen) { return band * 2 + 3 <= 32 && qLen <= 1024 && tLen <= 1024 + 13; }
+constexpr TbClass TB_CLASSES[] = {
+    {128, "sw_traceback.narrow128"}, {192, "sw_traceback.narrow192"}, {256, "sw_traceback.narrow256"},
+    {320, "sw_traceback.narrow320"}, {384, "sw_traceback.narrow384"}, {512, "sw_traceback.narrow512"},
+    {640, "sw_traceback.narrow640"}, {768, "sw_traceback.narrow768"}, {1024, "sw_traceback.narrow1024"},
+    {128, "sw_traceback.lds128"},    {512, "sw_traceback.lds512"},    {2048, "sw_traceback.lds2048"},
+    {0, "sw_traceback.global"},
+};
+constexpr uint32_t N_TB_CLASSES = sizeof(TB_CLASSES) / sizeof(TB_CLASSES[0]), TB_GLOBAL = N_TB_CLASSES - 1;
+constexpr uint32_t TBKEY_INVALID = N_TB_CLASSES * 4096u;
+constexpr int TB_NARROW_ROWS = TB_CLASSES[N_TB_NARROW - 1].cap;
+static_assert(TB_CLASSES[N_TB_NARROW].cap < TB_CLASSES[N_TB_NARROW - 1].cap && TB_CLASSES[TB_GLOBAL].cap == 0, "nine register-band classes first, the global class last");
+__host__ __device__ __forceinline__ bool tbNarrow(int band, int qLen, int tLen) { return band * 2 + 3 <= 32 && qLen <= TB_NARROW_ROWS && tLen <= TB_NARROW_ROWS + 13; }
+// the class of a task that is not a register-band task
+__host__ __device__ __forceinline__ uint32_t tbBandClass(int band) {
+    uint32_t ci = N_TB_NARROW;
+    while (ci < TB_GLOBAL && band * 2 + 3 > TB_CLASSES[ci].cap - 1) ci++;
+    return ci;
+}
 __device__ __forceinline__ uint32_t tbKey(int band, int qLen, int tLen) {
-    const int w = band * 2 + 3;
-    int ci;
     if (tbNarrow(band, qLen, tLen)) {
-        ci = 0;
-        while (qLen > c_tbNarrowQ[ci]) ci++;
-    } else {
-        ci = N_TB_NARROW + (w <= 127 ? 0 : (w <= 511 ? 1 : (w <= 2047 ? 2 : 3)));
-    }
-    if (ci < N_TB_NARROW) {
+        uint32_t ci = 0;
+        while (qLen > TB_CLASSES[ci].cap) ci++;
         // register-band kernel: the two tasks of a wavefront run in lock step through max(attempts) x max(rows).  Tasks with the
         // same number of bands the kernel can try (initial band 1: 1, 2, 4, 8; 2-3: three; 4-7: two; 8-14: one) sit together,
         // most attempts first, longest query first inside
         const int tries = band <= 1 ? 4 : (band <= 3 ? 3 : (band <= 7 ? 2 : 1));
-        return (uint32_t) ci * 4096u + (uint32_t) (4 - tries) * 1024u + (uint32_t) (1023 - min(max(qLen - 1, 0), 1023));
+        return ci * 4096u + (uint32_t) (4 - tries) * 1024u + (uint32_t) (1023 - min(max(qLen - 1, 0), 1023));
     }
     const unsigned long long work = (unsigned long long) ((2 * band + 1 + 31) / 32) * (unsigned long long) qLen;
-    return (uint32_t) ci * 4096u + (uint32_t) (4095 - (int) min(work >> 3, 4095ull));
+    return tbBandClass(band) * 4096u + (uint32_t) (4095 - (int) min(work >> 3, 4095ull));
 }
-constexpr uint32_t N_TB_CLASSES = N_TB_NARROW + 4;   // + the global-band class (w > 2047)
-constexpr uint32_t TBKEY_INVALID = N_TB_CLASSES * 4096u;
 // global direction scratch (LDS-band kernel only), sized for the widest band of the task's class because the
 // kernel keeps doubling the band inside its class
 __device__ __forceinline__ uint64_t tbDirBytes(int band, int qLen, int tLen) {
     if (tbNarrow(band, qLen, tLen)) return 0ull;
-    const int w = band * 2 + 3;
-    if (w > 2047)   // global-band class: one attempt per round at exactly this band, band arrays in front of the directions
-        return (tbGlobalIntBytes(band) + (uint64_t) (w - 2) * (uint64_t) qLen + 31) & ~15ull;
-    const int wMax = w <= 127 ? 127 : (w <= 511 ? 511 : 2047);
-    return ((uint64_t) (wMax - 2) * (uint64_t) qLen + 31) & ~15ull;   // multiples of 16: every task's region stays aligned
+    const uint32_t ci = tbBandClass(band);
+    if (ci == TB_GLOBAL)   // one attempt per round at exactly this band, band arrays in front of the directions
+        return (tbGlobalIntBytes(band) + (uint64_t) (band * 2 + 1) * (uint64_t) qLen + 31) & ~15ull;
+    return ((uint64_t) (TB_CLASSES[ci].cap - 3) * (uint64_t) qLen + 31) & ~15ull;   // multiples of 16: every task's region stays aligned
+}
+// the launches of a traceback class, one function per kernel family; PROF follows the query set.  order nullable
+void launchTbNarrow(sd_ctx *ctx, const sd_seqset *q, const sd_seqset *t, const int8_t *dMat, int go, int ge, const TbClass &cls, TbTask *dTb,
+                    uint32_t cnt, char *dBt, int32_t *dTbRes, const uint32_t *order) {
+    const int qCap = cls.cap, tCap = qCap + 16;
+    const size_t ldsBytes = 2 * ((size_t) 16 * qCap + 2 * (size_t) qCap + tCap);
+    auto *kernel = q->dProf ? sw_traceback_narrow_kernel<true> : sw_traceback_narrow_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((cnt + 1) / 2), dim3(64), ldsBytes, ctx->stream, dTb, cnt, q->dRes, q->dBias, t->dRes, dMat, go, ge, qCap,
+                       tCap, dBt, dTbRes, order, (const int8_t *) q->dProf);
+}
+// an LDS-band class or the global class (band arrays in global scratch, one attempt per round), and the walk through the directions
+void launchTbBand(sd_ctx *ctx, const sd_seqset *q, const sd_seqset *t, const int8_t *dMat, int go, int ge, const TbClass &cls,
+                  int maxWidthLoop, TbTask *dTb, uint32_t cnt, int8_t *dDir, char *dBt, int32_t *dTbRes, const uint32_t *order) {
+    const bool global = cls.cap == 0;
+    const int ldsStride = global ? INT_MAX : cls.cap + 1;
+    const size_t ldsBytes = global ? 0 : (size_t) 2 * 3 * ldsStride * sizeof(int32_t);
+    auto *band = global ? (q->dProf ? sw_traceback_kernel<true, true> : sw_traceback_kernel<false, true>)
+                        : (q->dProf ? sw_traceback_kernel<true, false> : sw_traceback_kernel<false, false>);
+    hipLaunchKernelGGL(band, dim3((cnt + 1) / 2), dim3(64), ldsBytes, ctx->stream, dTb, cnt, q->dRes, q->dBias, t->dRes, dMat, go, ge, ldsStride,
+                       dDir, dBt, dTbRes, order, maxWidthLoop, (const int8_t *) q->dProf);
+    auto *walk = global ? sw_traceback_walk_kernel<true> : sw_traceback_walk_kernel<false>;
+    hipLaunchKernelGGL(walk, dim3((cnt + 256 / TBW_LANES - 1) / (256 / TBW_LANES)), dim3(256), 0, ctx->stream, dTb, cnt, q->dRes, t->dRes, dDir,
+                       dBt, dTbRes, order);
 }
 
 // start positions (:475-476), second coverage gate (:483-489) and traceback tasks
@@ -1534,8 +1620,9 @@ k_bound_need(uint32_t nPairs, const SwTask *__restrict__ tasks, const uint32_t *
     uint64_t v = 0;
     if (keys[i] != KEY_INVALID) {
         const uint32_t ci = keys[i] >> 10;
-        if (scoreClassIsMulti(ci)) v = 2ull * (uint64_t) tasks[i].tL;
-        else if (ci == N_SCORE_CLASSES - 1 && tasks[i].n > 1024) v = (uint64_t) tasks[i].tL;
+        constexpr uint64_t TWO = scoreBoundMask(2), ONE = scoreBoundMask(1);   // (the classes of SCORE_CLASSES with that boundNeed)
+        if ((TWO >> ci) & 1) v = 2ull * (uint64_t) tasks[i].tL;
+        else if (((ONE >> ci) & 1) && tasks[i].n > I32_STRIP_ROWS) v = (uint64_t) tasks[i].tL;
     }
     need[i] = v;
 }
@@ -1609,11 +1696,27 @@ __global__ void k_pair_bounds(const uint32_t *__restrict__ keyS, uint32_t n, con
     b[c] = (uint32_t) pairIdx[lo];
 }
 
-// sort (keys,vals) -> order, read the class boundaries, launch one score kernel per RT class
-int devRunScore(sd_ctx *ctx, uint32_t nPairs, const uint32_t *dKeys, const uint32_t *dVals, uint32_t *dKeysSorted,
-                uint32_t *dOrder, uint32_t *dBounds, SwTask *dTasks, uint64_t *dScanA, uint64_t *dScanB,
-                const sd_seqset *q, const sd_seqset *t, const int8_t *dMat, int go, int ge, int32_t *dOut,
-                uint32_t *nValid, const uint32_t *dPairQ /* non-null: every task scans its whole query, pair them up */) {
+// the workspace of one alignBatchImpl call (alignWsInit)
+struct AlignWs {
+    size_t N;
+    unsigned grid;
+    int8_t *dMat;
+    uint32_t *dPQ, *dPT, *dKeys, *dVals, *dKeysS, *dOrder, *dBounds, *dFwdKeys, *dRevKeys;
+    uint8_t *dIdent, *dWord;
+    int32_t *dMinBias, *dOut32, *dOut16, *dOutRev, *dTbRes;
+    int *dErr;
+    SwTask *dTasks;
+    TbTask *dTb;
+    sd_sw_result *dRes;
+    uint64_t *dScanA, *dScanB, *dDirBytes, *dDirOff, *dBtBytes, *dBtOff, *dBtLen, *dDense;
+    unsigned long long *dCells;
+    char *dBt;   // backtrace scratch of the traceback tasks (sized after k_gate_tb)
+};
+
+// sort (keys,vals) -> order, read the class boundaries, launch the kernel of every class that has a task (SCORE_CLASSES)
+int devRunScore(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs, const uint32_t *dKeys, const sd_seqset *q, const sd_seqset *t, int go, int ge,
+                int32_t *dOut, const uint32_t *dPairQ /* non-null: every task scans its whole query, pair them up */) {
+    const uint32_t *dOrder = w.dOrder;
     const unsigned grid = (nPairs + 255) / 256;
     int rc = SD_OK;
     uint32_t *dOrder2 = nullptr, *dPairBounds = nullptr;
@@ -1633,111 +1736,48 @@ int devRunScore(sd_ctx *ctx, uint32_t nPairs, const uint32_t *dKeys, const uint3
         SD_HIP(ctx, hipMemsetAsync(dOrder2, 0xFF, order2Cap * sizeof(uint32_t), ctx->stream));   // empty pairs: PAIR_NONE
         SD_HIP(ctx, wsGet(ctx, "sp.bounds", 64, &dPairBounds));
         hipLaunchKernelGGL(k_pair_keys, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeys, dPairQ, dKey2);
-        rc = devSortPairs(ctx, dKey2, dKeysSorted, dVals, dVals2, nPairs, 32);
+        rc = devSortPairs(ctx, dKey2, w.dKeysS, w.dVals, dVals2, nPairs, 32);
         if (rc != SD_OK) return rc;
         dOrder = dVals2;
-        hipLaunchKernelGGL(k_pair_heads, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeysSorted, dHead);
+        hipLaunchKernelGGL(k_pair_heads, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dHead);
         rc = devInclusiveMax(ctx, dHead, dRunStart, nPairs);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, dKeysSorted, dRunStart, dLeader);
+        hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dRunStart, dLeader);
         rc = devExclusiveScan(ctx, (const uint8_t *) dLeader, dPairIdx, (size_t) nPairs + 1);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_pair_emit, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeysSorted, dVals2, dRunStart, dPairIdx, dOrder2);
-        hipLaunchKernelGGL(k_pair_bounds, dim3(1), dim3(64), 0, ctx->stream, dKeysSorted, nPairs, dPairIdx, dPairBounds,
+        hipLaunchKernelGGL(k_pair_emit, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dVals2, dRunStart, dPairIdx, dOrder2);
+        hipLaunchKernelGGL(k_pair_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, dPairIdx, dPairBounds,
                            (int) FIRST_INT32_CLASS + 1);
-        hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, dKeysSorted, nPairs, 1u << 26, dBounds, (int) N_SCORE_CLASSES + 1);
+        hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, 1u << 26, w.dBounds, (int) N_SCORE_CLASSES + 1);
     } else {
-        rc = devSortPairs(ctx, dKeys, dKeysSorted, dVals, dOrder, nPairs, 16);
+        rc = devSortPairs(ctx, dKeys, w.dKeysS, w.dVals, w.dOrder, nPairs, 16);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, dKeysSorted, nPairs, 1024u, dBounds, (int) N_SCORE_CLASSES + 1);
+        hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, 1024u, w.dBounds, (int) N_SCORE_CLASSES + 1);
     }
     // strip hand-off workspace for queries longer than one 1024-row strip
-    hipLaunchKernelGGL(k_bound_need, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dKeys, dScanA);
-    SD_HIP(ctx, hipMemsetAsync(dScanA + nPairs, 0, sizeof(uint64_t), ctx->stream));
-    rc = devExclusiveScan(ctx, dScanA, dScanB, (size_t) nPairs + 1);
+    hipLaunchKernelGGL(k_bound_need, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, dKeys, w.dScanA);
+    SD_HIP(ctx, hipMemsetAsync(w.dScanA + nPairs, 0, sizeof(uint64_t), ctx->stream));
+    rc = devExclusiveScan(ctx, w.dScanA, w.dScanB, (size_t) nPairs + 1);
     if (rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_bound_apply, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dScanB);
+    hipLaunchKernelGGL(k_bound_apply, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, w.dScanB);
     uint32_t hb[N_SCORE_CLASSES + 1], hpb[FIRST_INT32_CLASS + 1];
     uint64_t boundTotal = 0;
     if (dPairQ) SD_HIP(ctx, sdD2H(ctx, hpb, dPairBounds, sizeof(hpb)));
-    SD_HIP(ctx, sdD2H(ctx, hb, dBounds, sizeof(hb)));
-    SD_HIP(ctx, sdD2H(ctx, &boundTotal, dScanB + nPairs, sizeof(uint64_t)));
+    SD_HIP(ctx, sdD2H(ctx, hb, w.dBounds, sizeof(hb)));
+    SD_HIP(ctx, sdD2H(ctx, &boundTotal, w.dScanB + nPairs, sizeof(uint64_t)));
     SD_HIP(ctx, sdStreamSync(ctx));
-    *nValid = hb[N_SCORE_CLASSES];
     uint2 *dBound = nullptr;
     SD_HIP(ctx, wsGet(ctx, "sw.bound", std::max<uint64_t>(boundTotal, 1), &dBound));
     for (uint32_t ci = 0; ci < N_SCORE_CLASSES; ci++) {
         const uint32_t begin = hb[ci], cnt = hb[ci + 1] - hb[ci];
         if (cnt == 0) continue;
-        static const char *const pkNames[N_PK_CLASSES] = {"rt4x32", "rt6x32", "rt7x32", "rt8x32", "rt9x32", "rt10x32", "rt11x32", "rt12x32",
-                                                          "rt8x64", "rt10x64", "rt12x64", "rt8x64s2", "rt8x64s3", "rt8x64sN"};
-        static const char *const i32Names[4] = {"sw_score.rt4", "sw_score.rt8", "sw_score.rt16", "sw_score.rt32"};
         const bool shared = dPairQ != nullptr && ci < FIRST_INT32_CLASS;
-        const int alignedRT = (ci >= 1 && ci < FIRST_NARROW_MULTI) ? (int) ci + 4 : 0;
-        // start-position tasks (two profiles per pair in LDS) beyond 384 rows use the general kernels
-        const bool aligned = alignedRT > 0 && (alignedRT <= 12 || shared);
-        // the general kernel by rows: class 0, the multi-strip classes, and the aligned classes when they are not taken
-        int generalIdx = 0;
-        if (ci >= FIRST_NARROW_MULTI && ci < FIRST_WIDE_CLASS) generalIdx = (int) FIRST_MULTI_PK + (int) (ci - FIRST_NARROW_MULTI);
-        else if (alignedRT) generalIdx = alignedRT <= 6 ? 1 : (alignedRT <= 12 ? alignedRT - 5 : (alignedRT <= 16 ? 8 : (alignedRT <= 20 ? 9 : 10)));
-        char name[48];
-        if (aligned) snprintf(name, sizeof(name), "sw_score_pk.a_seg%d", alignedRT);
-        else if (ci < FIRST_WIDE_CLASS) snprintf(name, sizeof(name), "sw_score_pk.%s", pkNames[generalIdx]);
-        else if (ci < FIRST_INT32_CLASS) snprintf(name, sizeof(name), "sw_score_pk.w_%s", pkNames[ci - FIRST_WIDE_CLASS]);
-        else snprintf(name, sizeof(name), "%s", i32Names[ci - FIRST_INT32_CLASS]);
-        ProfScope ps(ctx, name);
-        const uint32_t *ord = dOrder + begin;
-        uint32_t nOrd = cnt;
-        if (shared) {   // explicit pairs: two entries per pair of the class
-            ord = dOrder2 + 2 * (size_t) hpb[ci];
-            nOrd = 2 * (hpb[ci + 1] - hpb[ci]);
-        }
-#define SD_PK(RT, LW, MULTI, WIDE)                                                                                          \
-    do {                                                                                                                   \
-        if (shared) launchScorePk<RT, LW, MULTI, WIDE, true>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut, dBound);     \
-        else launchScorePk<RT, LW, MULTI, WIDE, false>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut, dBound);           \
-    } while (0)
-#define SD_PKA(RT)                                                                                       \
-    case RT:                                                                                             \
-        if (shared) launchScorePkAligned<RT, true>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);    \
-        else launchScorePkAligned<RT, false>(ctx, dTasks, ord, nOrd, q, t, dMat, go, ge, dOut);          \
-        break;
-#define SD_PK_CLASS(WIDE, IDX)                                                \
-        switch (IDX) {                                                        \
-            case 0: SD_PK(4, 32, false, WIDE); break;                         \
-            case 1: SD_PK(6, 32, false, WIDE); break;                         \
-            case 2: SD_PK(7, 32, false, WIDE); break;                         \
-            case 3: SD_PK(8, 32, false, WIDE); break;                         \
-            case 4: SD_PK(9, 32, false, WIDE); break;                         \
-            case 5: SD_PK(10, 32, false, WIDE); break;                        \
-            case 6: SD_PK(11, 32, false, WIDE); break;                        \
-            case 7: SD_PK(12, 32, false, WIDE); break;                        \
-            case 8: SD_PK(8, 64, false, WIDE); break;                         \
-            case 9: SD_PK(10, 64, false, WIDE); break;                        \
-            case 10: SD_PK(12, 64, false, WIDE); break;                       \
-            default: SD_PK(8, 64, true, WIDE); break;                         \
-        }
-        if (aligned) {
-            switch (alignedRT) {
-                SD_PKA(5) SD_PKA(6) SD_PKA(7) SD_PKA(8) SD_PKA(9) SD_PKA(10) SD_PKA(11) SD_PKA(12) SD_PKA(13) SD_PKA(14)
-                SD_PKA(15) SD_PKA(16) SD_PKA(17) SD_PKA(18) SD_PKA(19) SD_PKA(20) SD_PKA(21) SD_PKA(22) SD_PKA(23) SD_PKA(24)
-                default: break;
-            }
-        } else if (ci < FIRST_WIDE_CLASS) {
-            SD_PK_CLASS(false, generalIdx)
-        } else if (ci < FIRST_INT32_CLASS) {
-            SD_PK_CLASS(true, (int) (ci - FIRST_WIDE_CLASS))
-        } else {
-            switch (ci - FIRST_INT32_CLASS) {
-                case 0: launchScoreIdx<4>(ctx, dTasks, ord, cnt, q, t, dMat, go, ge, dOut, dBound); break;
-                case 1: launchScoreIdx<8>(ctx, dTasks, ord, cnt, q, t, dMat, go, ge, dOut, dBound); break;
-                case 2: launchScoreIdx<16>(ctx, dTasks, ord, cnt, q, t, dMat, go, ge, dOut, dBound); break;
-                default: launchScoreIdx<32>(ctx, dTasks, ord, cnt, q, t, dMat, go, ge, dOut, dBound); break;
-            }
-        }
-#undef SD_PKA
-#undef SD_PK_CLASS
-#undef SD_PK
+        const ScoreSide &side = shared ? SCORE_CLASSES[ci].shared : SCORE_CLASSES[ci].unshared;
+        ProfScope ps(ctx, side.scope);
+        if (shared)   // explicit pairs: two entries per pair of the class
+            side.launch(ctx, w.dTasks, dOrder2 + 2 * (size_t) hpb[ci], 2 * (hpb[ci + 1] - hpb[ci]), q, t, w.dMat, go, ge, dOut, dBound);
+        else
+            side.launch(ctx, w.dTasks, dOrder + begin, cnt, q, t, w.dMat, go, ge, dOut, dBound);
     }
     SD_HIP(ctx, hipGetLastError());
     return SD_OK;
@@ -2088,6 +2128,42 @@ int sd_sw_last_cells(sd_ctx *ctx, uint64_t *f, uint64_t *r, uint64_t *t) {
     return SD_OK;
 }
 
+// forward task of a pair: the whole query against the whole target in `lanes` segments (32: byte structure, 16: word structure)
+static SwTask fwdTask(const sd_seqset *queries, const sd_seqset *targets, uint32_t q, uint32_t t, uint32_t slot, int lanes) {
+    SwTask tk;
+    tk.qOff = queries->hOff[q]; tk.tOff = targets->hOff[t];
+    tk.n = (int) (queries->hOff[q + 1] - tk.qOff); tk.tL = (int) (targets->hOff[t + 1] - tk.tOff); tk.qStep = 1; tk.tStep = 1;
+    tk.segLen = std::max(1, (tk.n + lanes - 1) / lanes);
+    tk.slot = slot; tk.boundOff = 0;
+    return tk;
+}
+
+// scoreIdentical (StripedSmithWaterman.cpp:1675-1710), host side, O(L): the record of identity pair i but for its backtrace (btLen
+// letters 'M', which the caller puts into its pool)
+static int scoreIdentical(sd_ctx *ctx, const sd_sw_params *par, const sd::Evaluer &ev, const sd_seqset *queries, const sd_seqset *targets,
+                          uint32_t i, uint32_t pq, uint32_t pt, sd_sw_result &r) {
+    const int L = (int) (targets->hOff[pt + 1] - targets->hOff[pt]);
+    const int qL = (int) (queries->hOff[pq + 1] - queries->hOff[pq]);
+    if (qL != L) return sdFail(ctx, SD_EINVAL, "scoreIdentical has different lengths for pair %u", i);
+    const uint8_t *q = queries->hRes.data() + queries->hOff[pq];
+    const int8_t *cb = queries->hBias.data() + queries->hOff[pq];
+    const uint8_t *t = targets->hRes.data() + targets->hOff[pt];
+    short score = 0;
+    if (queries->dProf) {   // profile_word_linear[target letter][position] (:1700-1703, :1293-1298)
+        const int8_t *pr = queries->hProf.data() + queries->hOff[pq] * 21;
+        for (int p = 0; p < L; p++) score += (short) pr[(size_t) p * 21 + t[p]];
+    } else {
+        for (int p = 0; p < L; p++) score += (short) (par->matrix[t[p] * 21 + q[p]] + cb[p]);
+    }
+    r.score = (int32_t) (uint32_t) (int) score;
+    r.qStart = par->swMode == 0 ? -1 : 0;
+    r.tStart = par->swMode == 0 ? -1 : 0;
+    r.qEnd = L - 1; r.tEnd = L - 1; r.identical = L; r.btLen = L; r.flags = 0;
+    r.evalue = sd::computeEvalue(ev, (double) (uint32_t) r.score, qL);
+    r.btOffset = 0;
+    return SD_OK;
+}
+
 int sd_sw_score_batch(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
                       uint32_t nPairs, const uint32_t *pairQ, const uint32_t *pairT, int lanes, int reverse,
                       const int32_t *qEnd, const int32_t *tEnd, int32_t *out) {
@@ -2099,18 +2175,12 @@ int sd_sw_score_batch(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *que
     std::vector<SwTask> tasks;
     tasks.reserve(nPairs);
     for (uint32_t i = 0; i < nPairs; i++) {
-        const uint64_t qo = queries->hOff[pairQ[i]], to = targets->hOff[pairT[i]];
-        const int qL = (int) (queries->hOff[pairQ[i] + 1] - qo), tL = (int) (targets->hOff[pairT[i] + 1] - to);
-        SwTask tk;
-        if (!reverse) {
-            tk.qOff = qo; tk.tOff = to; tk.n = qL; tk.tL = tL; tk.qStep = 1; tk.tStep = 1;
-        } else {
-            if (qEnd[i] < 0 || tEnd[i] < 0 || qEnd[i] >= qL || tEnd[i] >= tL) return sdFail(ctx, SD_EINVAL, "bad end position for pair %u", i);
-            tk.qOff = qo + qEnd[i]; tk.tOff = to + tEnd[i]; tk.n = qEnd[i] + 1; tk.tL = tEnd[i] + 1; tk.qStep = -1; tk.tStep = -1;
+        SwTask tk = fwdTask(queries, targets, pairQ[i], pairT[i], i, lanes);
+        if (reverse) {
+            if (qEnd[i] < 0 || tEnd[i] < 0 || qEnd[i] >= tk.n || tEnd[i] >= tk.tL) return sdFail(ctx, SD_EINVAL, "bad end position for pair %u", i);
+            tk.qOff += qEnd[i]; tk.tOff += tEnd[i]; tk.n = qEnd[i] + 1; tk.tL = tEnd[i] + 1; tk.qStep = -1; tk.tStep = -1;
+            tk.segLen = std::max(1, (tk.n + lanes - 1) / lanes);
         }
-        tk.segLen = std::max(1, (tk.n + lanes - 1) / lanes);
-        tk.slot = i;
-        tk.boundOff = 0;
         if (tk.n > 0 && tk.tL > 0) tasks.push_back(tk);
     }
     std::vector<int32_t> h;
@@ -2132,166 +2202,88 @@ int sd_sw_score_batch(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *que
     return SD_OK;
 }
 
-// compactIdx != nullptr: only the pairs that reached a result worth reporting (identity pairs and pairs that were
-// not stopped at a gate) are returned, out[x] being the record of pair compactIdx[x], x < *nCompact
-// Of the target set this path reads the device side only (n, dRes, dOff, dProf), except for identity pairs, whose targets' host copies
-// (hOff, hRes) it reads as well: sd_sw_align_alt_batch relies on that when it passes a device-only view of its scratch set
-// without identity pairs (sdDeviceSeqView, sd_sw_alt.hip).  ctx->alignDevRes is left pointing at the per-pair records.
-static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
-                          uint32_t nPairs, const uint32_t *pairQ, const uint32_t *pairT, const uint8_t *isIdentity,
-                          sd_sw_result *out, char *btPool, uint64_t btCap, uint64_t *btUsed, uint32_t *compactIdx,
-                          uint32_t *nCompact, const uint16_t *pairDiag = nullptr /* the prefilter's diagonal of every pair (nullable) */,
-                          const float *bestBy = nullptr /* non-null: {seqIdThr, alnLenThr}: sd_sw_align_batch_best_by_group */) {
-    if (!ctx || !par || !queries || !targets || !out) return SD_EINVAL;
-    if (compactIdx && (!nCompact || par->swMode != 2)) return sdFail(ctx, SD_EINVAL, "the compact variants need swMode 2 (records with backtraces)");
-    (void) hipSetDevice(ctx->device);
-    sdD2HReset(ctx);   // (reads an earlier, failed call left pending)
-    if (btUsed) *btUsed = 0;
-    if (nCompact) *nCompact = 0;
-    if (nPairs == 0) return SD_OK;
-    const int go = par->gapOpen, ge = par->gapExtend;
-    ctx->cellsFwd = ctx->cellsRev = ctx->cellsTb = 0;
-    sd::Evaluer ev;
-    sd::initEvaluer(ev, par->dbResidues);
-    int matMin = 0;
-    for (int i = 0; i < 441; i++) matMin = std::min(matMin, (int) par->matrix[i]);
-    for (uint32_t i = 0; i < nPairs; i++)
-        if (pairQ[i] >= queries->n || pairT[i] >= targets->n) return sdFail(ctx, SD_EINVAL, "pair %u out of range", i);
-    if (targets->dProf) return sdFail(ctx, SD_EUNSUPPORTED, "profile targets are not implemented (profile queries are)");
-    std::unique_ptr<HostScope> hs(new HostScope(ctx, "align.upload"));
-    DevGateParams gp;
-    gp.go = go; gp.ge = ge; gp.matMin = matMin; gp.swMode = par->swMode; gp.covMode = par->covMode; gp.covThr = par->covThr;
-    {   // the int16 kernels are exact while no cell can exceed 32 767: rows x the largest entry of a query profile of this call
-        int matMax = 0;
-        for (int x = 0; x < 441; x++) matMax = std::max(matMax, (int) par->matrix[x]);
-        const int maxEntry = std::max(1, queries->dProf ? queries->maxEntryAdd : matMax + queries->maxEntryAdd);
-        gp.wideRowLimit = 32767 / maxEntry;
-    }
-    gp.evalThr = par->evalThr;
-    gp.lambda = ev.lambda; gp.K = ev.K; gp.aI = ev.aI; gp.bI = ev.bI; gp.alphaI = ev.alphaI; gp.betaI = ev.betaI;
-    gp.aJ = ev.aJ; gp.bJ = ev.bJ; gp.alphaJ = ev.alphaJ; gp.betaJ = ev.betaJ; gp.sigma = ev.sigma; gp.tau = ev.tau;
-    gp.viThr = ev.viThr; gp.vjThr = ev.vjThr; gp.cThr = ev.cThr; gp.dbResidues = ev.dbResidues;
+// ---- alignBatchImpl: the arguments of a call, its workspace, and its stages in the order they run
+struct AlignCall {
+    const sd_sw_params *par;
+    const sd_seqset *queries, *targets;
+    uint32_t nPairs;
+    const uint32_t *pairQ, *pairT;
+    const uint8_t *isIdentity;
+    sd_sw_result *out;
+    char *btPool;
+    uint64_t btCap, *btUsed;
+    uint32_t *compactIdx, *nCompact;
+    const uint16_t *pairDiag;   // the prefilter's diagonal of every pair (nullable)
+    const float *bestBy;        // non-null: {seqIdThr, alnLenThr}: sd_sw_align_batch_best_by_group
+};
+// what downloadRecords brought back (pinned buffers of the context)
+struct AlignRecords {
+    uint32_t nRec, *hIdx;   // hIdx: compact mode, the pair of every record
+    sd_sw_result *hRes;
+    char *hPool;
+    uint64_t poolBytes;
+    bool cigarPool;
+};
 
-    const size_t N = nPairs;
-    const unsigned grid = (unsigned) ((N + 255) / 256);
-    int8_t *dMat = nullptr;
-    uint32_t *dPQ = nullptr, *dPT = nullptr, *dKeys = nullptr, *dVals = nullptr, *dKeysS = nullptr, *dOrder = nullptr,
-             *dBounds = nullptr, *dFwdKeys = nullptr, *dRevKeys = nullptr;
-    uint8_t *dIdent = nullptr, *dWord = nullptr;
-    int32_t *dMinBias = nullptr, *dOut32 = nullptr, *dOut16 = nullptr, *dOutRev = nullptr, *dTbRes = nullptr;
-    int *dErr = nullptr;
-    SwTask *dTasks = nullptr;
-    TbTask *dTb = nullptr;
-    sd_sw_result *dRes = nullptr;
-    uint64_t *dScanA = nullptr, *dScanB = nullptr, *dDirBytes = nullptr, *dDirOff = nullptr, *dBtBytes = nullptr,
-             *dBtOff = nullptr, *dBtLen = nullptr, *dDense = nullptr;
-    unsigned long long *dCells = nullptr;
-    SD_HIP(ctx, wsGet(ctx, "al.mat", 448, &dMat));
-    SD_HIP(ctx, wsGet(ctx, "al.pq", N, &dPQ));
-    SD_HIP(ctx, wsGet(ctx, "al.pt", N, &dPT));
-    SD_HIP(ctx, wsGet(ctx, "al.ident", N, &dIdent));
-    SD_HIP(ctx, wsGet(ctx, "al.word", N, &dWord));
-    SD_HIP(ctx, wsGet(ctx, "al.keys", N, &dKeys));
-    SD_HIP(ctx, wsGet(ctx, "al.vals", N, &dVals));
-    SD_HIP(ctx, wsGet(ctx, "al.keyss", N, &dKeysS));
-    SD_HIP(ctx, wsGet(ctx, "al.order", N, &dOrder));
-    SD_HIP(ctx, wsGet(ctx, "al.fwdkeys", N, &dFwdKeys));
-    SD_HIP(ctx, wsGet(ctx, "al.revkeys", N, &dRevKeys));
-    SD_HIP(ctx, wsGet(ctx, "al.bounds", 64, &dBounds));
-    SD_HIP(ctx, wsGet(ctx, "al.minbias", queries->n, &dMinBias));
-    SD_HIP(ctx, wsGet(ctx, "al.out32", N * 3, &dOut32));
-    SD_HIP(ctx, wsGet(ctx, "al.out16", N * 3, &dOut16));
-    SD_HIP(ctx, wsGet(ctx, "al.outrev", N * 3, &dOutRev));
-    SD_HIP(ctx, wsGet(ctx, "al.tbres", N * 2, &dTbRes));
-    SD_HIP(ctx, wsGet(ctx, "al.err", 4, &dErr));
-    SD_HIP(ctx, wsGet(ctx, "al.tasks", N, &dTasks));
-    SD_HIP(ctx, wsGet(ctx, "al.tb", N, &dTb));
-    SD_HIP(ctx, wsGet(ctx, "al.res", N, &dRes));
-    ctx->alignDevRes = dRes;
+static int alignWsInit(sd_ctx *ctx, const AlignCall &a, AlignWs &w) {
+    const sd_seqset *queries = a.queries;
+    const size_t N = w.N = a.nPairs;
+    w.grid = (unsigned) ((N + 255) / 256);
+    SD_HIP(ctx, wsGet(ctx, "al.mat", 448, &w.dMat));
+    SD_HIP(ctx, wsGet(ctx, "al.pq", N, &w.dPQ));
+    SD_HIP(ctx, wsGet(ctx, "al.pt", N, &w.dPT));
+    SD_HIP(ctx, wsGet(ctx, "al.ident", N, &w.dIdent));
+    SD_HIP(ctx, wsGet(ctx, "al.word", N, &w.dWord));
+    SD_HIP(ctx, wsGet(ctx, "al.keys", N, &w.dKeys));
+    SD_HIP(ctx, wsGet(ctx, "al.vals", N, &w.dVals));
+    SD_HIP(ctx, wsGet(ctx, "al.keyss", N, &w.dKeysS));
+    SD_HIP(ctx, wsGet(ctx, "al.order", N, &w.dOrder));
+    SD_HIP(ctx, wsGet(ctx, "al.fwdkeys", N, &w.dFwdKeys));
+    SD_HIP(ctx, wsGet(ctx, "al.revkeys", N, &w.dRevKeys));
+    SD_HIP(ctx, wsGet(ctx, "al.bounds", 64, &w.dBounds));
+    SD_HIP(ctx, wsGet(ctx, "al.minbias", queries->n, &w.dMinBias));
+    SD_HIP(ctx, wsGet(ctx, "al.out32", N * 3, &w.dOut32));
+    SD_HIP(ctx, wsGet(ctx, "al.out16", N * 3, &w.dOut16));
+    SD_HIP(ctx, wsGet(ctx, "al.outrev", N * 3, &w.dOutRev));
+    SD_HIP(ctx, wsGet(ctx, "al.tbres", N * 2, &w.dTbRes));
+    SD_HIP(ctx, wsGet(ctx, "al.err", 4, &w.dErr));
+    SD_HIP(ctx, wsGet(ctx, "al.tasks", N, &w.dTasks));
+    SD_HIP(ctx, wsGet(ctx, "al.tb", N, &w.dTb));
+    SD_HIP(ctx, wsGet(ctx, "al.res", N, &w.dRes));
+    ctx->alignDevRes = w.dRes;
     ctx->alignDevResN = N;
-    SD_HIP(ctx, wsGet(ctx, "al.scana", N + 1, &dScanA));
-    SD_HIP(ctx, wsGet(ctx, "al.scanb", N + 1, &dScanB));
-    SD_HIP(ctx, wsGet(ctx, "al.dirbytes", N + 1, &dDirBytes));
-    SD_HIP(ctx, wsGet(ctx, "al.diroff", N + 1, &dDirOff));
-    SD_HIP(ctx, wsGet(ctx, "al.btbytes", N + 1, &dBtBytes));
-    SD_HIP(ctx, wsGet(ctx, "al.btoff", N + 1, &dBtOff));
-    SD_HIP(ctx, wsGet(ctx, "al.btlen", N + 1, &dBtLen));
-    SD_HIP(ctx, wsGet(ctx, "al.dense", N + 1, &dDense));
-    SD_HIP(ctx, wsGet(ctx, "al.cells", 4, &dCells));
-    SD_HIP(ctx, hipMemcpyAsync(dMat, par->matrix, 441, hipMemcpyHostToDevice, ctx->stream));
-    SD_HIP(ctx, hipMemcpyAsync(dPQ, pairQ, N * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    SD_HIP(ctx, hipMemcpyAsync(dPT, pairT, N * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (isIdentity) SD_HIP(ctx, hipMemcpyAsync(dIdent, isIdentity, N, hipMemcpyHostToDevice, ctx->stream));
-    else SD_HIP(ctx, hipMemsetAsync(dIdent, 0, N, ctx->stream));
+    SD_HIP(ctx, wsGet(ctx, "al.scana", N + 1, &w.dScanA));
+    SD_HIP(ctx, wsGet(ctx, "al.scanb", N + 1, &w.dScanB));
+    SD_HIP(ctx, wsGet(ctx, "al.dirbytes", N + 1, &w.dDirBytes));
+    SD_HIP(ctx, wsGet(ctx, "al.diroff", N + 1, &w.dDirOff));
+    SD_HIP(ctx, wsGet(ctx, "al.btbytes", N + 1, &w.dBtBytes));
+    SD_HIP(ctx, wsGet(ctx, "al.btoff", N + 1, &w.dBtOff));
+    SD_HIP(ctx, wsGet(ctx, "al.btlen", N + 1, &w.dBtLen));
+    SD_HIP(ctx, wsGet(ctx, "al.dense", N + 1, &w.dDense));
+    SD_HIP(ctx, wsGet(ctx, "al.cells", 4, &w.dCells));
+    SD_HIP(ctx, hipMemcpyAsync(w.dMat, a.par->matrix, 441, hipMemcpyHostToDevice, ctx->stream));
+    SD_HIP(ctx, hipMemcpyAsync(w.dPQ, a.pairQ, N * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    SD_HIP(ctx, hipMemcpyAsync(w.dPT, a.pairT, N * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (a.isIdentity) SD_HIP(ctx, hipMemcpyAsync(w.dIdent, a.isIdentity, N, hipMemcpyHostToDevice, ctx->stream));
+    else SD_HIP(ctx, hipMemsetAsync(w.dIdent, 0, N, ctx->stream));
     // byte-kernel bias (ssw_init, :1276-1287): |min(matrix)| + |min(0, composition bias)| for sequences, |min(0, profile)| for profiles
-    SD_HIP(ctx, hipMemcpyAsync(dMinBias, queries->dProf ? queries->hProfBias.data() : queries->hMinBias.data(),
+    SD_HIP(ctx, hipMemcpyAsync(w.dMinBias, queries->dProf ? queries->hProfBias.data() : queries->hMinBias.data(),
                                queries->n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dErr, 0, 4 * sizeof(int), ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dCells, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dOut32, 0, N * 3 * sizeof(int32_t), ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dOut16, 0, N * 3 * sizeof(int32_t), ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dOutRev, 0, N * 3 * sizeof(int32_t), ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dBtLen, 0, (N + 1) * sizeof(uint64_t), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(w.dErr, 0, 4 * sizeof(int), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(w.dCells, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(w.dOut32, 0, N * 3 * sizeof(int32_t), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(w.dOut16, 0, N * 3 * sizeof(int32_t), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(w.dOutRev, 0, N * 3 * sizeof(int32_t), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(w.dBtLen, 0, (N + 1) * sizeof(uint64_t), ctx->stream));
+    return SD_OK;
+}
 
-    // ---- pass 1: forward, byte-kernel lane structure
-    hs.reset(new HostScope(ctx, "align.fwd32"));
-    // the packed-int16 kernels need go >= ge twice over (see sd_sw_pk.h): for their F update, and for leaving out the lane-structure
-    // chain Fl, which changes no G only then.  This is the one place that admits them -- the class keys of all three passes are made
-    // with usePk, and runScoreTasks (sd_sw_score_batch, the host path) launches the int32 kernel only.  SD_SW_INT32=1 forces the int32 kernel
-    const int usePk = (go >= ge && go < 1024 && ge >= 0 && getenv("SD_SW_INT32") == nullptr) ? 1 : 0;
-    uint32_t nValid = 0;
-    hipLaunchKernelGGL(k_make_fwd, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dPQ, dPT, dIdent, queries->dOff, targets->dOff,
-                       dTasks, dFwdKeys, dVals, dRes, usePk);
-    // pairs whose byte score saturates for certain (k_pre_word) skip this pass
-    uint32_t *dPass1Keys = dFwdKeys;
-    uint8_t *dPreWord = nullptr, *dWide = nullptr;
-    const bool narrowFinal = ctx->narrowFinal && usePk;   // sd_sw_set_narrow_final
-    if (narrowFinal) SD_HIP(ctx, wsGet(ctx, "al.wide", N, &dWide));
-    if (pairDiag && usePk) {
-        uint16_t *dDiag = nullptr;
-        SD_HIP(ctx, wsGet(ctx, "al.diag", N, &dDiag));
-        SD_HIP(ctx, wsGet(ctx, "al.preword", N, &dPreWord));
-        SD_HIP(ctx, wsGet(ctx, "al.pass1keys", N, &dPass1Keys));
-        SD_HIP(ctx, hipMemcpyAsync(dDiag, pairDiag, N * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_pre_word, dim3(grid), dim3(256), 0, ctx->stream, nPairs, (const uint32_t *) dPQ, (const uint32_t *) dPT,
-                           (const uint16_t *) dDiag, (const uint32_t *) dFwdKeys, (const uint64_t *) queries->dOff, (const uint64_t *) targets->dOff,
-                           (const uint8_t *) queries->dRes, (const int8_t *) queries->dBias, (const uint8_t *) targets->dRes, (const int8_t *) dMat,
-                           (const int8_t *) queries->dProf, (const int32_t *) dMinBias, queries->dProf ? 0 : matMin, dPreWord, dPass1Keys,
-                           narrowFinal ? 1 : 0);
-    }
-    hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dPass1Keys, dCells + 0);
-    const uint32_t *dShare = queries->n >= (1u << PAIR_QUERY_BITS) ? nullptr : dPQ;   // forward passes scan whole queries: pair by query
-    int rc = devRunScore(ctx, nPairs, dPass1Keys, dVals, dKeysS, dOrder, dBounds, dTasks, dScanA, dScanB, queries, targets, dMat, go,
-                         ge, dOut32, &nValid, dShare);
-    if (rc != SD_OK) return rc;
-    // ---- pass 2: saturated pairs again with the word kernel's 16-lane structure
-    hs.reset(new HostScope(ctx, "align.fwd16"));
-    hipLaunchKernelGGL(k_gate_word, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dPQ, dOut32, dMinBias, queries->dProf ? 0 : matMin, dTasks, dKeys,
-                       dVals, dWord, dFwdKeys, usePk, gp.wideRowLimit, (const uint8_t *) dPreWord, dWide, dCells + 2);
-    hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dKeys, dCells + 0);
-    rc = devRunScore(ctx, nPairs, dKeys, dVals, dKeysS, dOrder, dBounds, dTasks, dScanA, dScanB, queries, targets, dMat, go, ge,
-                     dOut16, &nValid, dShare);
-    if (rc != SD_OK) return rc;
-    // ---- gates + pass 3: start positions
-    hs.reset(new HostScope(ctx, "align.rev"));
-    hipLaunchKernelGGL(k_gate_rev, dim3(grid), dim3(256), 0, ctx->stream, nPairs, gp, dPQ, dPT, queries->dOff, targets->dOff, dOut32,
-                       dOut16, dWord, dFwdKeys, dTasks, dRevKeys, dVals, dRes, usePk, (const uint8_t *) dWide);
-    hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dTasks, dRevKeys, dCells + 1);
-    rc = devRunScore(ctx, nPairs, dRevKeys, dVals, dKeysS, dOrder, dBounds, dTasks, dScanA, dScanB, queries, targets, dMat, go, ge,
-                     dOutRev, &nValid, nullptr);   // start-position tasks scan per-pair prefixes: no shared profile
-    if (rc != SD_OK) return rc;
-    // ---- pass 4: banded traceback, band doubling on the device
-    hs.reset(new HostScope(ctx, "align.traceback"));
-    hipLaunchKernelGGL(k_gate_tb, dim3(grid), dim3(256), 0, ctx->stream, nPairs, gp, dPQ, dPT, queries->dOff, targets->dOff, dOutRev,
-                       dRevKeys, dTb, dKeys, dVals, dDirBytes, dBtBytes, dRes, dErr);
-    SD_HIP(ctx, hipMemsetAsync(dBtBytes + N, 0, sizeof(uint64_t), ctx->stream));
-    rc = devExclusiveScan(ctx, dBtBytes, dBtOff, N + 1);
-    if (rc != SD_OK) return rc;
-    uint64_t btScratch = 0;
-    SD_HIP(ctx, sdD2H(ctx, &btScratch, dBtOff + N, sizeof(uint64_t)));
-    SD_HIP(ctx, sdStreamSync(ctx));
-    char *dBt = nullptr;
-    SD_HIP(ctx, wsGet(ctx, "tb.bt", btScratch + 64, &dBt));
+// pass 4: banded traceback, band doubling on the device, in slices of what the direction scratch holds at a time
+static int runTracebackRounds(sd_ctx *ctx, const AlignCall &a, const AlignWs &w) {
+    const sd_seqset *queries = a.queries, *targets = a.targets;
+    const uint32_t nPairs = a.nPairs;
+    const size_t N = w.N;
+    const int go = a.par->gapOpen, ge = a.par->gapExtend;
     // direction scratch of the LDS-band kernel (1 B per band cell, sized for the widest band of the task's class): a
     // quarter of the device memory at most (288 GB HBM: 72 GB), the rest belongs to the index and the prefilter workspace
     uint64_t SCRATCH_BUDGET = 16ull << 30;
@@ -2305,27 +2297,23 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
     }
     uint32_t *dKeysRound = nullptr;
     SD_HIP(ctx, wsGet(ctx, "tb.keysRound", N + 1, &dKeysRound));
-    bool tbPending = false, budgetRaised = false;
+    bool budgetRaised = false;
     for (int round = 0; round < 4096; round++) {   // band doublings, and slices of what the direction scratch holds at a time
-        tbPending = true;
-        SD_HIP(ctx, hipMemsetAsync(dDirBytes + N, 0, sizeof(uint64_t), ctx->stream));
-        rc = devExclusiveScan(ctx, dDirBytes, dDirOff, N + 1);
+        SD_HIP(ctx, hipMemsetAsync(w.dDirBytes + N, 0, sizeof(uint64_t), ctx->stream));
+        int rc = devExclusiveScan(ctx, w.dDirBytes, w.dDirOff, N + 1);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_tb_round, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeys, dDirOff, dDirBytes, SCRATCH_BUDGET, dKeysRound);
-        hipLaunchKernelGGL(k_tb_offsets, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeysRound, dDirOff, dBtOff, dTb);
-        rc = devSortPairs(ctx, dKeysRound, dKeysS, dVals, dOrder, nPairs, 16);
+        hipLaunchKernelGGL(k_tb_round, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, w.dKeys, w.dDirOff, w.dDirBytes, SCRATCH_BUDGET, dKeysRound);
+        hipLaunchKernelGGL(k_tb_offsets, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, dKeysRound, w.dDirOff, w.dBtOff, w.dTb);
+        rc = devSortPairs(ctx, dKeysRound, w.dKeysS, w.dVals, w.dOrder, nPairs, 16);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, dKeysS, nPairs, 4096u, dBounds, (int) N_TB_CLASSES + 1);
+        hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, 4096u, w.dBounds, (int) N_TB_CLASSES + 1);
         uint32_t hb[N_TB_CLASSES + 1];
         uint64_t dirTotal = 0;
-        SD_HIP(ctx, sdD2H(ctx, hb, dBounds, sizeof(hb)));
-        SD_HIP(ctx, sdD2H(ctx, &dirTotal, dDirOff + N, sizeof(uint64_t)));
+        SD_HIP(ctx, sdD2H(ctx, hb, w.dBounds, sizeof(hb)));
+        SD_HIP(ctx, sdD2H(ctx, &dirTotal, w.dDirOff + N, sizeof(uint64_t)));
         SD_HIP(ctx, sdStreamSync(ctx));
         if (hb[N_TB_CLASSES] == 0) {
-            if (dirTotal == 0) {   // nothing left
-                tbPending = false;
-                break;
-            }
+            if (dirTotal == 0) return SD_OK;   // nothing left
             // tasks are pending but not even the first fits the budget (a global-band task of a long protein, or a budget halved
             // after an allocation failure): the budget grows to what a single task needs -- or the call fails, never a silent exit
             if (SCRATCH_BUDGET >= dirTotal) return sdFail(ctx, SD_EHIP, "traceback: pending tasks but an empty round (budget %llu, pending %llu bytes)",
@@ -2351,145 +2339,104 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
             SCRATCH_BUDGET /= 2;   // another lane took the memory meanwhile: smaller slices
             continue;
         }
-        for (int ci = 0; ci < N_TB_NARROW; ci++) {
+        for (uint32_t ci = 0; ci < N_TB_CLASSES; ci++) {
             const uint32_t begin = hb[ci], cnt = hb[ci + 1] - hb[ci];
             if (cnt == 0) continue;
-            static const char *const tbNames[N_TB_NARROW] = {"sw_traceback.narrow128", "sw_traceback.narrow192", "sw_traceback.narrow256",
-                                                             "sw_traceback.narrow320", "sw_traceback.narrow384", "sw_traceback.narrow512",
-                                                             "sw_traceback.narrow640", "sw_traceback.narrow768", "sw_traceback.narrow1024"};
-            ProfScope ps(ctx, tbNames[ci]);
-            const int qCap = TB_NARROW_Q[ci], tCap = qCap + 16;
-            const size_t ldsBytes = 2 * ((size_t) 16 * qCap + 2 * (size_t) qCap + tCap);
-            if (queries->dProf)
-                hipLaunchKernelGGL(sw_traceback_narrow_kernel<true>, dim3((cnt + 1) / 2), dim3(64), ldsBytes, ctx->stream, dTb, cnt,
-                                   queries->dRes, queries->dBias, targets->dRes, dMat, go, ge, qCap, tCap, dBt, dTbRes, dOrder + begin,
-                                   (const int8_t *) queries->dProf);
-            else
-                hipLaunchKernelGGL(sw_traceback_narrow_kernel<false>, dim3((cnt + 1) / 2), dim3(64), ldsBytes, ctx->stream, dTb, cnt,
-                                   queries->dRes, queries->dBias, targets->dRes, dMat, go, ge, qCap, tCap, dBt, dTbRes, dOrder + begin,
-                                   (const int8_t *) nullptr);
-        }
-        static const int ldsClass[3] = {128, 512, 2048};
-        for (int ci = 0; ci < 3; ci++) {
-            const uint32_t begin = hb[N_TB_NARROW + ci], cnt = hb[N_TB_NARROW + 1 + ci] - hb[N_TB_NARROW + ci];
-            if (cnt == 0) continue;
-            static const char *const ldsNames[3] = {"sw_traceback.lds128", "sw_traceback.lds512", "sw_traceback.lds2048"};
-            ProfScope ps(ctx, ldsNames[ci]);
-            const int ldsStride = ldsClass[ci] + 1;
-            const size_t ldsBytes = (size_t) 2 * 3 * ldsStride * sizeof(int32_t);
-            if (queries->dProf)
-                hipLaunchKernelGGL(sw_traceback_kernel<true>, dim3((cnt + 1) / 2), dim3(64), ldsBytes, ctx->stream, dTb, cnt, queries->dRes,
-                                   queries->dBias, targets->dRes, dMat, go, ge, ldsStride, dDir, dBt, dTbRes, dOrder + begin,
-                                   ldsClass[ci] - 1, (const int8_t *) queries->dProf);
-            else
-                hipLaunchKernelGGL(sw_traceback_kernel<false>, dim3((cnt + 1) / 2), dim3(64), ldsBytes, ctx->stream, dTb, cnt, queries->dRes,
-                                   queries->dBias, targets->dRes, dMat, go, ge, ldsStride, dDir, dBt, dTbRes, dOrder + begin,
-                                   ldsClass[ci] - 1, (const int8_t *) nullptr);
-            hipLaunchKernelGGL(sw_traceback_walk_kernel<false>, dim3((cnt + 256 / TBW_LANES - 1) / (256 / TBW_LANES)), dim3(256), 0, ctx->stream, dTb, cnt, queries->dRes,
-                               targets->dRes, dDir, dBt, dTbRes, dOrder + begin);
-        }
-        {   // bands beyond the LDS classes: band arrays in global scratch, one attempt per round
-            const uint32_t begin = hb[N_TB_NARROW + 3], cnt = hb[N_TB_NARROW + 4] - hb[N_TB_NARROW + 3];
-            if (cnt) {
-                ProfScope ps(ctx, "sw_traceback.global");
-                if (queries->dProf)
-                    hipLaunchKernelGGL((sw_traceback_kernel<true, true>), dim3((cnt + 1) / 2), dim3(64), 0, ctx->stream, dTb, cnt, queries->dRes,
-                                       queries->dBias, targets->dRes, dMat, go, ge, INT_MAX, dDir, dBt, dTbRes, dOrder + begin, 0,
-                                       (const int8_t *) queries->dProf);
-                else
-                    hipLaunchKernelGGL((sw_traceback_kernel<false, true>), dim3((cnt + 1) / 2), dim3(64), 0, ctx->stream, dTb, cnt, queries->dRes,
-                                       queries->dBias, targets->dRes, dMat, go, ge, INT_MAX, dDir, dBt, dTbRes, dOrder + begin, 0,
-                                       (const int8_t *) nullptr);
-                hipLaunchKernelGGL(sw_traceback_walk_kernel<true>, dim3((cnt + 256 / TBW_LANES - 1) / (256 / TBW_LANES)), dim3(256), 0, ctx->stream, dTb, cnt, queries->dRes,
-                                   targets->dRes, dDir, dBt, dTbRes, dOrder + begin);
-            }
+            const TbClass &cls = TB_CLASSES[ci];
+            ProfScope ps(ctx, cls.scope);
+            if (ci < N_TB_NARROW) launchTbNarrow(ctx, queries, targets, w.dMat, go, ge, cls, w.dTb, cnt, w.dBt, w.dTbRes, w.dOrder + begin);
+            else launchTbBand(ctx, queries, targets, w.dMat, go, ge, cls, std::max(0, cls.cap - 1), w.dTb, cnt, dDir, w.dBt, w.dTbRes, w.dOrder + begin);
         }
         SD_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_tb_collect, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeys, dVals, dTb, dTbRes, dDirBytes, dBtLen,
-                           dRes, dErr, 4 * 65536, dKeysRound);
+        hipLaunchKernelGGL(k_tb_collect, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, w.dKeys, w.dVals, w.dTb, w.dTbRes, w.dDirBytes, w.dBtLen,
+                           w.dRes, w.dErr, 4 * 65536, dKeysRound);
     }
-    if (tbPending) return sdFail(ctx, SD_EHIP, "traceback: tasks still pending after 4096 rounds");
-    if (getenv("SD_DEBUG_TB")) {   // band statistics of the finished tasks
-        std::vector<TbTask> hT(nPairs);
-        std::vector<uint64_t> hL(nPairs);
-        SD_HIP(ctx, hipMemcpy(hT.data(), dTb, (size_t) nPairs * sizeof(TbTask), hipMemcpyDeviceToHost));
-        SD_HIP(ctx, hipMemcpy(hL.data(), dBtLen, (size_t) nPairs * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        uint64_t nDone = 0, init6 = 0, init6final6 = 0, init6final14 = 0, final14 = 0;
-        for (uint32_t i = 0; i < nPairs; i++) {
-            if (hL[i] == 0) continue;
-            nDone++;
-            const int ib = abs(hT[i].tLen - hT[i].qLen) + 1, fb = hT[i].band;
-            if (ib <= 6) { init6++; if (fb <= 6) init6final6++; else if (fb <= 14) init6final14++; }
-            if (fb <= 14) final14++;
-        }
-        {
-            static const int lim[8] = {1, 2, 3, 4, 6, 8, 14, 1 << 30};
-            uint64_t hi[8] = {0}, hf[8] = {0}, rowsF[8] = {0};
-            for (uint32_t i = 0; i < nPairs; i++) {
-                if (hL[i] == 0) continue;
-                const int ib = abs(hT[i].tLen - hT[i].qLen) + 1, fb = hT[i].band;
-                int a = 0, b = 0;
-                while (ib > lim[a]) a++;
-                while (fb > lim[b]) b++;
-                hi[a]++;
-                hf[b]++;
-                rowsF[b] += (uint64_t) hT[i].qLen;
-            }
-            fprintf(stderr, "[tb] band <=1 <=2 <=3 <=4 <=6 <=8 <=14 >14: initial");
-            for (int x = 0; x < 8; x++) fprintf(stderr, " %llu", (unsigned long long) hi[x]);
-            fprintf(stderr, " | final");
-            for (int x = 0; x < 8; x++) fprintf(stderr, " %llu", (unsigned long long) hf[x]);
-            fprintf(stderr, " | rows by final");
-            for (int x = 0; x < 8; x++) fprintf(stderr, " %llu", (unsigned long long) rowsF[x]);
-            fprintf(stderr, "\n");
-        }
-        fprintf(stderr, "[tb] done %llu: final band<=14 %llu; initial<=6 %llu of which final<=6 %llu, final 7..14 %llu\n",
-                (unsigned long long) nDone, (unsigned long long) final14, (unsigned long long) init6, (unsigned long long) init6final6,
-                (unsigned long long) init6final14);
+    return sdFail(ctx, SD_EHIP, "traceback: tasks still pending after 4096 rounds");
+}
+
+// SD_DEBUG_TB: band statistics of the finished tasks
+static int printTracebackStats(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs) {
+    std::vector<TbTask> hT(nPairs);
+    std::vector<uint64_t> hL(nPairs);
+    SD_HIP(ctx, hipMemcpy(hT.data(), w.dTb, (size_t) nPairs * sizeof(TbTask), hipMemcpyDeviceToHost));
+    SD_HIP(ctx, hipMemcpy(hL.data(), w.dBtLen, (size_t) nPairs * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t nDone = 0, init6 = 0, init6final6 = 0, init6final14 = 0, final14 = 0;
+    static const int lim[8] = {1, 2, 3, 4, 6, 8, 14, 1 << 30};
+    uint64_t hi[8] = {0}, hf[8] = {0}, rowsF[8] = {0};
+    for (uint32_t i = 0; i < nPairs; i++) {
+        if (hL[i] == 0) continue;
+        nDone++;
+        const int ib = abs(hT[i].tLen - hT[i].qLen) + 1, fb = hT[i].band;
+        if (ib <= 6) { init6++; if (fb <= 6) init6final6++; else if (fb <= 14) init6final14++; }
+        if (fb <= 14) final14++;
+        int x = 0, y = 0;
+        while (ib > lim[x]) x++;
+        while (fb > lim[y]) y++;
+        hi[x]++;
+        hf[y]++;
+        rowsF[y] += (uint64_t) hT[i].qLen;
     }
-    // ---- besthitbyset on the device: only identity pairs and the first accepted alignment of every (query, target set) cell keep
-    // their record and their backtrace (a table of queries x target sets; beyond 2^27 cells the call returns everything)
-    if (bestBy && compactIdx && targets->dGroupOf && targets->nGroups > 0 && (uint64_t) queries->n * targets->nGroups <= (1ull << 27)) {
-        BestByGroup B;
-        B.groupOf = targets->dGroupOf;
-        B.groupKey = targets->dGroupKey;
-        B.nGroups = targets->nGroups;
-        B.seqIdThr = bestBy[0];
-        B.alnLenThr = (int) bestBy[1];
-        B.covThr = par->covThr;
-        B.covMode = par->covMode;
-        B.evalThr = par->evalThr;
-        B.evalExact = (getenv("SD_BEST_EXACT") && atof(getenv("SD_BEST_EXACT")) == 0.0) ? 0.0 : BB_EVAL_EXACT;
-        unsigned long long *dTable = nullptr;
-        const size_t cellsN = (size_t) queries->n * targets->nGroups;
-        SD_HIP(ctx, wsGet(ctx, "al.besttable", cellsN, &dTable));
-        SD_HIP(ctx, hipMemsetAsync(dTable, 0, cellsN * sizeof(unsigned long long), ctx->stream));
-        ProfScope ps(ctx, "align_best_by_group");
-        hipLaunchKernelGGL(k_best_mark, dim3(grid), dim3(256), 0, ctx->stream, nPairs, (const sd_sw_result *) dRes, (const uint8_t *) dIdent,
-                           (const uint32_t *) dPQ, (const uint32_t *) dPT, (const uint64_t *) queries->dOff, (const uint64_t *) targets->dOff, B, dTable);
-        hipLaunchKernelGGL(k_best_keep, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dRes, (const uint8_t *) dIdent, (const uint32_t *) dPQ,
-                           (const uint32_t *) dPT, (const uint64_t *) queries->dOff, (const uint64_t *) targets->dOff, B,
-                           (const unsigned long long *) dTable, dBtLen);
+    const uint64_t *const hist[3] = {hi, hf, rowsF};
+    static const char *const head[3] = {"[tb] band <=1 <=2 <=3 <=4 <=6 <=8 <=14 >14: initial", " | final", " | rows by final"};
+    for (int h = 0; h < 3; h++) {
+        fprintf(stderr, "%s", head[h]);
+        for (int x = 0; x < 8; x++) fprintf(stderr, " %llu", (unsigned long long) hist[h][x]);
     }
-    // ---- dense backtrace pool + results back to the host
-    hs.reset(new HostScope(ctx, "align.download"));
+    fprintf(stderr, "\n");
+    fprintf(stderr, "[tb] done %llu: final band<=14 %llu; initial<=6 %llu of which final<=6 %llu, final 7..14 %llu\n",
+            (unsigned long long) nDone, (unsigned long long) final14, (unsigned long long) init6, (unsigned long long) init6final6,
+            (unsigned long long) init6final14);
+    return SD_OK;
+}
+
+// besthitbyset on the device: only identity pairs and the first accepted alignment of every (query, target set) cell keep
+// their record and their backtrace (a table of queries x target sets)
+static int markBestByGroup(sd_ctx *ctx, const AlignCall &a, const AlignWs &w) {
+    const sd_seqset *queries = a.queries, *targets = a.targets;
+    BestByGroup B;
+    B.groupOf = targets->dGroupOf;
+    B.groupKey = targets->dGroupKey;
+    B.nGroups = targets->nGroups;
+    B.seqIdThr = a.bestBy[0];
+    B.alnLenThr = (int) a.bestBy[1];
+    B.covThr = a.par->covThr;
+    B.covMode = a.par->covMode;
+    B.evalThr = a.par->evalThr;
+    B.evalExact = (getenv("SD_BEST_EXACT") && atof(getenv("SD_BEST_EXACT")) == 0.0) ? 0.0 : BB_EVAL_EXACT;
+    unsigned long long *dTable = nullptr;
+    const size_t cellsN = (size_t) queries->n * targets->nGroups;
+    SD_HIP(ctx, wsGet(ctx, "al.besttable", cellsN, &dTable));
+    SD_HIP(ctx, hipMemsetAsync(dTable, 0, cellsN * sizeof(unsigned long long), ctx->stream));
+    ProfScope ps(ctx, "align_best_by_group");
+    hipLaunchKernelGGL(k_best_mark, dim3(w.grid), dim3(256), 0, ctx->stream, a.nPairs, (const sd_sw_result *) w.dRes, (const uint8_t *) w.dIdent,
+                       (const uint32_t *) w.dPQ, (const uint32_t *) w.dPT, (const uint64_t *) queries->dOff, (const uint64_t *) targets->dOff, B, dTable);
+    hipLaunchKernelGGL(k_best_keep, dim3(w.grid), dim3(256), 0, ctx->stream, a.nPairs, w.dRes, (const uint8_t *) w.dIdent, (const uint32_t *) w.dPQ,
+                       (const uint32_t *) w.dPT, (const uint64_t *) queries->dOff, (const uint64_t *) targets->dOff, B,
+                       (const unsigned long long *) dTable, w.dBtLen);
+    return SD_OK;
+}
+
+// dense backtrace pool + records back to the host: all records, or (compact mode) only identity pairs and pairs that passed every gate
+static int downloadRecords(sd_ctx *ctx, const AlignCall &a, const AlignWs &w, bool narrowFinal, AlignRecords &rec) {
+    const uint32_t nPairs = a.nPairs;
+    const size_t N = w.N;
     // (sd_sw_set_cigar_pool: the pool holds run-length text, its offsets are a scan of the text lengths)
-    const bool cigarPool = ctx->cigarPool && btPool != nullptr;
+    const bool cigarPool = rec.cigarPool = ctx->cigarPool && a.btPool != nullptr;
     uint64_t *dCigLen = nullptr;
     if (cigarPool) {
         SD_HIP(ctx, wsGet(ctx, "al.ciglen", N + 1, &dCigLen));
         SD_HIP(ctx, hipMemsetAsync(dCigLen + nPairs, 0, (N + 1 - nPairs) * sizeof(uint64_t), ctx->stream));
-        hipLaunchKernelGGL(k_bt_cigar<false>, dim3((nPairs + 3) / 4), dim3(256), 0, ctx->stream, nPairs, (const uint64_t *) dBtLen,
-                           (const uint64_t *) nullptr, (const TbTask *) dTb, (const char *) dBt, (char *) nullptr, dCigLen, (sd_sw_result *) nullptr);
+        hipLaunchKernelGGL(k_bt_cigar<false>, dim3((nPairs + 3) / 4), dim3(256), 0, ctx->stream, nPairs, (const uint64_t *) w.dBtLen,
+                           (const uint64_t *) nullptr, (const TbTask *) w.dTb, (const char *) w.dBt, (char *) nullptr, dCigLen, (sd_sw_result *) nullptr);
     }
-    rc = devExclusiveScan(ctx, cigarPool ? dCigLen : dBtLen, dDense, N + 1);
+    const int rc = devExclusiveScan(ctx, cigarPool ? dCigLen : w.dBtLen, w.dDense, N + 1);
     if (rc != SD_OK) return rc;
-    uint64_t poolBytes = 0;
+    uint64_t &poolBytes = rec.poolBytes = 0;
     int hErr[4] = {0, 0, 0, 0};
     unsigned long long hCells[4] = {0, 0, 0, 0};
-    SD_HIP(ctx, sdD2H(ctx, &poolBytes, dDense + N, sizeof(uint64_t)));
-    SD_HIP(ctx, sdD2H(ctx, hErr, dErr, sizeof(hErr)));
-    SD_HIP(ctx, sdD2H(ctx, hCells, dCells, sizeof(hCells)));
+    SD_HIP(ctx, sdD2H(ctx, &poolBytes, w.dDense + N, sizeof(uint64_t)));
+    SD_HIP(ctx, sdD2H(ctx, hErr, w.dErr, sizeof(hErr)));
+    SD_HIP(ctx, sdD2H(ctx, hCells, w.dCells, sizeof(hCells)));
     SD_HIP(ctx, sdStreamSync(ctx));
     if (hErr[0] == 1) return sdFail(ctx, SD_EMISMATCH, "Score of forward/backward SW differ (fatal in the reference, StripedSmithWaterman.cpp:466-473)");
     if (hErr[0] == 2) return sdFail(ctx, SD_EHIP, "Trace back error");
@@ -2504,26 +2451,25 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
             pe.launches += 1;
         }
     }
-    // identity pairs need pool space too (scoreIdentical backtraces are written by the host below)
+    // identity pairs need pool space too (scoreIdentical backtraces are written by the host: finishRecordsOnHost)
     uint64_t identBytes = 0;
-    if (isIdentity && btPool)
+    if (a.isIdentity && a.btPool)
         for (uint32_t i = 0; i < nPairs; i++)
-            if (isIdentity[i]) identBytes += cigarPool ? 8 : targets->hOff[pairT[i] + 1] - targets->hOff[pairT[i]];
-    if (poolBytes > 0 && btPool == nullptr) return sdFail(ctx, SD_EINVAL, "swMode 2 needs a backtrace pool");
-    if (poolBytes + identBytes > btCap && btPool) return sdFail(ctx, SD_ENOMEM, "backtrace pool too small");
+            if (a.isIdentity[i]) identBytes += cigarPool ? 8 : a.targets->hOff[a.pairT[i] + 1] - a.targets->hOff[a.pairT[i]];
+    if (poolBytes > 0 && a.btPool == nullptr) return sdFail(ctx, SD_EINVAL, "swMode 2 needs a backtrace pool");
+    if (poolBytes + identBytes > a.btCap && a.btPool) return sdFail(ctx, SD_ENOMEM, "backtrace pool too small");
     char *dPool = nullptr;
     SD_HIP(ctx, wsGet(ctx, "al.pool", poolBytes + 64, &dPool));
     if (poolBytes > 0 && cigarPool)
-        hipLaunchKernelGGL(k_bt_cigar<true>, dim3((nPairs + 3) / 4), dim3(256), 0, ctx->stream, nPairs, (const uint64_t *) dBtLen,
-                           (const uint64_t *) dDense, (const TbTask *) dTb, (const char *) dBt, dPool, (uint64_t *) nullptr, dRes);
+        hipLaunchKernelGGL(k_bt_cigar<true>, dim3((nPairs + 3) / 4), dim3(256), 0, ctx->stream, nPairs, (const uint64_t *) w.dBtLen,
+                           (const uint64_t *) w.dDense, (const TbTask *) w.dTb, (const char *) w.dBt, dPool, (uint64_t *) nullptr, w.dRes);
     else if (poolBytes > 0)
-        hipLaunchKernelGGL(k_bt_pack, dim3((nPairs + 3) / 4), dim3(256), 0, ctx->stream, nPairs, dBtLen, dDense, dTb, dBt, dPool,
-                           (uint64_t) 0, dRes);
-    // records to bring back: all of them, or (compact mode) only identity pairs and pairs that passed every gate
-    uint32_t nRec = nPairs;
-    sd_sw_result *dRecSrc = dRes;
-    uint32_t *hIdx = nullptr;
-    if (compactIdx) {
+        hipLaunchKernelGGL(k_bt_pack, dim3((nPairs + 3) / 4), dim3(256), 0, ctx->stream, nPairs, w.dBtLen, w.dDense, w.dTb, w.dBt, dPool,
+                           (uint64_t) 0, w.dRes);
+    uint32_t &nRec = rec.nRec = nPairs;
+    sd_sw_result *dRecSrc = w.dRes;
+    rec.hIdx = nullptr;
+    if (a.compactIdx) {
         uint8_t *dAcc = nullptr;
         uint64_t *dAccPos = nullptr;
         sd_sw_result *dResC = nullptr;
@@ -2532,45 +2478,51 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
         SD_HIP(ctx, wsGet(ctx, "al.accpos", N + 1, &dAccPos));
         SD_HIP(ctx, wsGet(ctx, "al.resc", N, &dResC));
         SD_HIP(ctx, wsGet(ctx, "al.idxc", N, &dIdxC));
-        hipLaunchKernelGGL(k_accept, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dRes, dIdent, dAcc);
+        hipLaunchKernelGGL(k_accept, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, w.dRes, w.dIdent, dAcc);
         SD_HIP(ctx, hipMemsetAsync(dAcc + N, 0, 1, ctx->stream));
-        {
-            const int rcS = devExclusiveScan(ctx, (const uint8_t *) dAcc, dAccPos, N + 1);
-            if (rcS != SD_OK) return rcS;
-        }
-        hipLaunchKernelGGL(k_accept_compact, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dRes, dAcc, dAccPos, dResC, dIdxC);
+        const int rcS = devExclusiveScan(ctx, (const uint8_t *) dAcc, dAccPos, N + 1);
+        if (rcS != SD_OK) return rcS;
+        hipLaunchKernelGGL(k_accept_compact, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, w.dRes, dAcc, dAccPos, dResC, dIdxC);
         uint64_t nAcc = 0;
         SD_HIP(ctx, sdD2H(ctx, &nAcc, dAccPos + N, sizeof(uint64_t)));
         SD_HIP(ctx, sdStreamSync(ctx));
         nRec = (uint32_t) nAcc;
         dRecSrc = dResC;
-        SD_HIP(ctx, pinGet(ctx, "al.hidx", std::max<uint32_t>(nRec, 1), &hIdx));
-        SD_HIP(ctx, hipMemcpyAsync(hIdx, dIdxC, (size_t) nRec * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        SD_HIP(ctx, pinGet(ctx, "al.hidx", std::max<uint32_t>(nRec, 1), &rec.hIdx));
+        SD_HIP(ctx, hipMemcpyAsync(rec.hIdx, dIdxC, (size_t) nRec * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    sd_sw_result *hRes = nullptr;
-    char *hPool = nullptr;
-    SD_HIP(ctx, pinGet(ctx, "al.hres", std::max<uint32_t>(nRec, 1), &hRes));
-    SD_HIP(ctx, pinGet(ctx, "al.hpool", poolBytes + 64, &hPool));
-    SD_HIP(ctx, hipMemcpyAsync(hRes, dRecSrc, (size_t) nRec * sizeof(sd_sw_result), hipMemcpyDeviceToHost, ctx->stream));
-    if (poolBytes > 0) SD_HIP(ctx, hipMemcpyAsync(hPool, dPool, poolBytes, hipMemcpyDeviceToHost, ctx->stream));
+    SD_HIP(ctx, pinGet(ctx, "al.hres", std::max<uint32_t>(nRec, 1), &rec.hRes));
+    SD_HIP(ctx, pinGet(ctx, "al.hpool", poolBytes + 64, &rec.hPool));
+    SD_HIP(ctx, hipMemcpyAsync(rec.hRes, dRecSrc, (size_t) nRec * sizeof(sd_sw_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (poolBytes > 0) SD_HIP(ctx, hipMemcpyAsync(rec.hPool, dPool, poolBytes, hipMemcpyDeviceToHost, ctx->stream));
     SD_HIP(ctx, sdStreamSync(ctx));
-    hs.reset(new HostScope(ctx, "align.finish"));
+    return SD_OK;
+}
+
+// the pool into the caller's, exact E-values (the device value only served the gate), the rare results the device let through
+// because they sat within 1e-9 of the E-value threshold, and identity pairs
+static int finishRecordsOnHost(sd_ctx *ctx, const AlignCall &a, const sd::Evaluer &ev, const AlignRecords &rec) {
+    const sd_sw_params *par = a.par;
+    const sd_seqset *queries = a.queries;
+    const uint8_t *isIdentity = a.isIdentity;
+    const uint32_t *pairQ = a.pairQ, *hIdx = rec.hIdx;
+    const uint32_t nRec = rec.nRec;
+    char *btPool = a.btPool;
+    const uint64_t poolBytes = rec.poolBytes;
     {
         const int nth = std::max(1, std::min(omp_get_max_threads(), 64));
         const size_t blk = (poolBytes + nth - 1) / nth;
 #pragma omp parallel for schedule(static) num_threads(nth)
         for (int t = 0; t < nth; t++) {
-            const size_t a = std::min<size_t>(poolBytes, (size_t) t * blk), b = std::min<size_t>(poolBytes, a + blk);
-            if (b > a) memcpy(btPool + a, hPool + a, b - a);
+            const size_t lo = std::min<size_t>(poolBytes, (size_t) t * blk), hi = std::min<size_t>(poolBytes, lo + blk);
+            if (hi > lo) memcpy(btPool + lo, rec.hPool + lo, hi - lo);
         }
     }
     uint64_t btPos = poolBytes;
-    // exact E-values (the device value only served the gate), identity pairs, and the rare results the device
-    // let through because they sat within 1e-9 of the E-value threshold
 #pragma omp parallel for schedule(static)
     for (uint32_t x = 0; x < nRec; x++) {
         const uint32_t i = hIdx ? hIdx[x] : x;
-        sd_sw_result r = hRes[x];
+        sd_sw_result r = rec.hRes[x];
         if (!(isIdentity && isIdentity[i])) {
             const int qL = (int) (queries->hOff[pairQ[i] + 1] - queries->hOff[pairQ[i]]);
             if (r.tEnd != -1 && qL > 0) {
@@ -2585,36 +2537,19 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
                 r.evalue = 0.0;
             }
         }
-        out[x] = r;
-        if (compactIdx) compactIdx[x] = i;
+        a.out[x] = r;
+        if (a.compactIdx) a.compactIdx[x] = i;
     }
-    if (nCompact) *nCompact = nRec;
+    if (a.nCompact) *a.nCompact = nRec;
     if (isIdentity) {
         for (uint32_t x = 0; x < nRec; x++) {
             const uint32_t i = hIdx ? hIdx[x] : x;
             if (!isIdentity[i]) continue;
-            // scoreIdentical (StripedSmithWaterman.cpp:1675-1710), host side, O(L)
-            const int L = (int) (targets->hOff[pairT[i] + 1] - targets->hOff[pairT[i]]);
-            const int qL = (int) (queries->hOff[pairQ[i] + 1] - queries->hOff[pairQ[i]]);
-            if (qL != L) return sdFail(ctx, SD_EINVAL, "scoreIdentical has different lengths for pair %u", i);
-            const uint8_t *q = queries->hRes.data() + queries->hOff[pairQ[i]];
-            const int8_t *cb = queries->hBias.data() + queries->hOff[pairQ[i]];
-            const uint8_t *t = targets->hRes.data() + targets->hOff[pairT[i]];
-            short score = 0;
-            if (queries->dProf) {   // profile_word_linear[target letter][position] (:1700-1703, :1293-1298)
-                const int8_t *pr = queries->hProf.data() + queries->hOff[pairQ[i]] * 21;
-                for (int p = 0; p < L; p++) score += (short) pr[(size_t) p * 21 + t[p]];
-            } else {
-                for (int p = 0; p < L; p++) score += (short) (par->matrix[t[p] * 21 + q[p]] + cb[p]);
-            }
-            sd_sw_result &r = out[x];
-            r.score = (int32_t) (uint32_t) (int) score;
-            r.qStart = par->swMode == 0 ? -1 : 0;
-            r.tStart = par->swMode == 0 ? -1 : 0;
-            r.qEnd = L - 1; r.tEnd = L - 1; r.identical = L; r.btLen = L; r.flags = 0;
-            r.evalue = sd::computeEvalue(ev, (double) (uint32_t) r.score, qL);
-            r.btOffset = 0;
-            if (btPool && cigarPool) {   // "<L>M"
+            sd_sw_result &r = a.out[x];
+            const int rc = scoreIdentical(ctx, par, ev, queries, a.targets, i, pairQ[i], a.pairT[i], r);
+            if (rc != SD_OK) return rc;
+            const int L = r.btLen;
+            if (btPool && rec.cigarPool) {   // "<L>M"
                 char txt[16];
                 const int nTxt = snprintf(txt, sizeof(txt), "%dM", L);
                 memcpy(btPool + btPos, txt, (size_t) nTxt);
@@ -2628,11 +2563,127 @@ static int alignBatchImpl(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
             }
         }
     }
-    if (btUsed) *btUsed = btPos;
-    ctx->d2hRecordBytes += (uint64_t) nRec * (sizeof(sd_sw_result) + (compactIdx ? sizeof(uint32_t) : 0));
+    if (a.btUsed) *a.btUsed = btPos;
+    ctx->d2hRecordBytes += (uint64_t) nRec * (sizeof(sd_sw_result) + (a.compactIdx ? sizeof(uint32_t) : 0));
     ctx->d2hPoolBytes += poolBytes;
-    hs.reset();
     return SD_OK;
+}
+
+// compactIdx != nullptr: only the pairs that reached a result worth reporting (identity pairs and pairs that were
+// not stopped at a gate) are returned, out[x] being the record of pair compactIdx[x], x < *nCompact
+// Of the target set this path reads the device side only (n, dRes, dOff, dProf), except for identity pairs, whose targets' host copies
+// (hOff, hRes) it reads as well: sd_sw_align_alt_batch relies on that when it passes a device-only view of its scratch set
+// without identity pairs (sdDeviceSeqView, sd_sw_alt.hip).  ctx->alignDevRes is left pointing at the per-pair records.
+static int alignBatchImpl(sd_ctx *ctx, const AlignCall &a) {
+    const sd_sw_params *par = a.par;
+    const sd_seqset *queries = a.queries, *targets = a.targets;
+    const uint32_t nPairs = a.nPairs;
+    if (!ctx || !par || !queries || !targets || !a.out) return SD_EINVAL;
+    if (a.compactIdx && (!a.nCompact || par->swMode != 2)) return sdFail(ctx, SD_EINVAL, "the compact variants need swMode 2 (records with backtraces)");
+    (void) hipSetDevice(ctx->device);
+    sdD2HReset(ctx);   // (reads an earlier, failed call left pending)
+    if (a.btUsed) *a.btUsed = 0;
+    if (a.nCompact) *a.nCompact = 0;
+    if (nPairs == 0) return SD_OK;
+    const int go = par->gapOpen, ge = par->gapExtend;
+    ctx->cellsFwd = ctx->cellsRev = ctx->cellsTb = 0;
+    sd::Evaluer ev;
+    sd::initEvaluer(ev, par->dbResidues);
+    int matMin = 0;
+    for (int i = 0; i < 441; i++) matMin = std::min(matMin, (int) par->matrix[i]);
+    for (uint32_t i = 0; i < nPairs; i++)
+        if (a.pairQ[i] >= queries->n || a.pairT[i] >= targets->n) return sdFail(ctx, SD_EINVAL, "pair %u out of range", i);
+    if (targets->dProf) return sdFail(ctx, SD_EUNSUPPORTED, "profile targets are not implemented (profile queries are)");
+    std::unique_ptr<HostScope> hs(new HostScope(ctx, "align.upload"));
+    DevGateParams gp;
+    gp.go = go; gp.ge = ge; gp.matMin = matMin; gp.swMode = par->swMode; gp.covMode = par->covMode; gp.covThr = par->covThr;
+    {   // the int16 kernels are exact while no cell can exceed 32 767: rows x the largest entry of a query profile of this call
+        int matMax = 0;
+        for (int x = 0; x < 441; x++) matMax = std::max(matMax, (int) par->matrix[x]);
+        const int maxEntry = std::max(1, queries->dProf ? queries->maxEntryAdd : matMax + queries->maxEntryAdd);
+        gp.wideRowLimit = 32767 / maxEntry;
+    }
+    gp.evalThr = par->evalThr;
+    gp.lambda = ev.lambda; gp.K = ev.K; gp.aI = ev.aI; gp.bI = ev.bI; gp.alphaI = ev.alphaI; gp.betaI = ev.betaI;
+    gp.aJ = ev.aJ; gp.bJ = ev.bJ; gp.alphaJ = ev.alphaJ; gp.betaJ = ev.betaJ; gp.sigma = ev.sigma; gp.tau = ev.tau;
+    gp.viThr = ev.viThr; gp.vjThr = ev.vjThr; gp.cThr = ev.cThr; gp.dbResidues = ev.dbResidues;
+    AlignWs w = {};
+    int rc = alignWsInit(ctx, a, w);
+    if (rc != SD_OK) return rc;
+    const size_t N = w.N;
+    const unsigned grid = w.grid;
+
+    // ---- pass 1: forward, byte-kernel lane structure
+    hs.reset(new HostScope(ctx, "align.fwd32"));
+    // the packed-int16 kernels need go >= ge twice over (see sd_sw_pk.h): for their F update, and for leaving out the lane-structure
+    // chain Fl, which changes no G only then.  This is the one place that admits them -- the class keys of all three passes are made
+    // with usePk, and runScoreTasks (sd_sw_score_batch, the host path) launches the int32 kernel only.  SD_SW_INT32=1 forces the int32 kernel
+    const int usePk = (go >= ge && go < 1024 && ge >= 0 && getenv("SD_SW_INT32") == nullptr) ? 1 : 0;
+    hipLaunchKernelGGL(k_make_fwd, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dPQ, w.dPT, w.dIdent, queries->dOff, targets->dOff,
+                       w.dTasks, w.dFwdKeys, w.dVals, w.dRes, usePk);
+    // pairs whose byte score saturates for certain (k_pre_word) skip this pass
+    uint32_t *dPass1Keys = w.dFwdKeys;
+    uint8_t *dPreWord = nullptr, *dWide = nullptr;
+    const bool narrowFinal = ctx->narrowFinal && usePk;   // sd_sw_set_narrow_final
+    if (narrowFinal) SD_HIP(ctx, wsGet(ctx, "al.wide", N, &dWide));
+    if (a.pairDiag && usePk) {
+        uint16_t *dDiag = nullptr;
+        SD_HIP(ctx, wsGet(ctx, "al.diag", N, &dDiag));
+        SD_HIP(ctx, wsGet(ctx, "al.preword", N, &dPreWord));
+        SD_HIP(ctx, wsGet(ctx, "al.pass1keys", N, &dPass1Keys));
+        SD_HIP(ctx, hipMemcpyAsync(dDiag, a.pairDiag, N * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_pre_word, dim3(grid), dim3(256), 0, ctx->stream, nPairs, (const uint32_t *) w.dPQ, (const uint32_t *) w.dPT,
+                           (const uint16_t *) dDiag, (const uint32_t *) w.dFwdKeys, (const uint64_t *) queries->dOff, (const uint64_t *) targets->dOff,
+                           (const uint8_t *) queries->dRes, (const int8_t *) queries->dBias, (const uint8_t *) targets->dRes, (const int8_t *) w.dMat,
+                           (const int8_t *) queries->dProf, (const int32_t *) w.dMinBias, queries->dProf ? 0 : matMin, dPreWord, dPass1Keys,
+                           narrowFinal ? 1 : 0);
+    }
+    hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, dPass1Keys, w.dCells + 0);
+    const uint32_t *dShare = queries->n >= (1u << PAIR_QUERY_BITS) ? nullptr : w.dPQ;   // forward passes scan whole queries: pair by query
+    rc = devRunScore(ctx, w, nPairs, dPass1Keys, queries, targets, go, ge, w.dOut32, dShare);
+    if (rc != SD_OK) return rc;
+    // ---- pass 2: saturated pairs again with the word kernel's 16-lane structure
+    hs.reset(new HostScope(ctx, "align.fwd16"));
+    hipLaunchKernelGGL(k_gate_word, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dPQ, w.dOut32, w.dMinBias, queries->dProf ? 0 : matMin, w.dTasks, w.dKeys,
+                       w.dVals, w.dWord, w.dFwdKeys, usePk, gp.wideRowLimit, (const uint8_t *) dPreWord, dWide, w.dCells + 2);
+    hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, w.dKeys, w.dCells + 0);
+    rc = devRunScore(ctx, w, nPairs, w.dKeys, queries, targets, go, ge, w.dOut16, dShare);
+    if (rc != SD_OK) return rc;
+    // ---- gates + pass 3: start positions
+    hs.reset(new HostScope(ctx, "align.rev"));
+    hipLaunchKernelGGL(k_gate_rev, dim3(grid), dim3(256), 0, ctx->stream, nPairs, gp, w.dPQ, w.dPT, queries->dOff, targets->dOff, w.dOut32,
+                       w.dOut16, w.dWord, w.dFwdKeys, w.dTasks, w.dRevKeys, w.dVals, w.dRes, usePk, (const uint8_t *) dWide);
+    hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, w.dRevKeys, w.dCells + 1);
+    rc = devRunScore(ctx, w, nPairs, w.dRevKeys, queries, targets, go, ge, w.dOutRev, nullptr);   // start-position tasks scan per-pair prefixes: no shared profile
+    if (rc != SD_OK) return rc;
+    // ---- pass 4: banded traceback, band doubling on the device
+    hs.reset(new HostScope(ctx, "align.traceback"));
+    hipLaunchKernelGGL(k_gate_tb, dim3(grid), dim3(256), 0, ctx->stream, nPairs, gp, w.dPQ, w.dPT, queries->dOff, targets->dOff, w.dOutRev,
+                       w.dRevKeys, w.dTb, w.dKeys, w.dVals, w.dDirBytes, w.dBtBytes, w.dRes, w.dErr);
+    SD_HIP(ctx, hipMemsetAsync(w.dBtBytes + N, 0, sizeof(uint64_t), ctx->stream));
+    rc = devExclusiveScan(ctx, w.dBtBytes, w.dBtOff, N + 1);
+    if (rc != SD_OK) return rc;
+    uint64_t btScratch = 0;
+    SD_HIP(ctx, sdD2H(ctx, &btScratch, w.dBtOff + N, sizeof(uint64_t)));
+    SD_HIP(ctx, sdStreamSync(ctx));
+    SD_HIP(ctx, wsGet(ctx, "tb.bt", btScratch + 64, &w.dBt));
+    rc = runTracebackRounds(ctx, a, w);
+    if (rc != SD_OK) return rc;
+    if (getenv("SD_DEBUG_TB")) {
+        rc = printTracebackStats(ctx, w, nPairs);
+        if (rc != SD_OK) return rc;
+    }
+    // (beyond 2^27 cells of queries x target sets the call returns everything)
+    if (a.bestBy && a.compactIdx && targets->dGroupOf && targets->nGroups > 0 && (uint64_t) queries->n * targets->nGroups <= (1ull << 27)) {
+        rc = markBestByGroup(ctx, a, w);
+        if (rc != SD_OK) return rc;
+    }
+    hs.reset(new HostScope(ctx, "align.download"));
+    AlignRecords rec;
+    rc = downloadRecords(ctx, a, w, narrowFinal, rec);
+    if (rc != SD_OK) return rc;
+    hs.reset(new HostScope(ctx, "align.finish"));
+    return finishRecordsOnHost(ctx, a, ev, rec);
 }
 
 int sd_sw_set_cigar_pool(sd_ctx *ctx, int on) {
@@ -2657,7 +2708,7 @@ int sd_sw_download_bytes(sd_ctx *ctx, uint64_t *recordBytes, uint64_t *poolBytes
 int sd_sw_align_batch(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
                       uint32_t nPairs, const uint32_t *pairQ, const uint32_t *pairT, const uint8_t *isIdentity,
                       sd_sw_result *out, char *btPool, uint64_t btCap, uint64_t *btUsed) {
-    return alignBatchImpl(ctx, par, queries, targets, nPairs, pairQ, pairT, isIdentity, out, btPool, btCap, btUsed, nullptr, nullptr);
+    return alignBatchImpl(ctx, {par, queries, targets, nPairs, pairQ, pairT, isIdentity, out, btPool, btCap, btUsed, nullptr, nullptr, nullptr, nullptr});
 }
 
 int sd_sw_align_batch_compact(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
@@ -2665,7 +2716,7 @@ int sd_sw_align_batch_compact(sd_ctx *ctx, const sd_sw_params *par, const sd_seq
                               uint32_t *outIdx, sd_sw_result *out, uint32_t *nOut, char *btPool, uint64_t btCap,
                               uint64_t *btUsed) {
     if (!outIdx || !nOut) return SD_EINVAL;
-    return alignBatchImpl(ctx, par, queries, targets, nPairs, pairQ, pairT, isIdentity, out, btPool, btCap, btUsed, outIdx, nOut);
+    return alignBatchImpl(ctx, {par, queries, targets, nPairs, pairQ, pairT, isIdentity, out, btPool, btCap, btUsed, outIdx, nOut, nullptr, nullptr});
 }
 
 int sd_sw_align_batch_compact_diag(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
@@ -2673,7 +2724,7 @@ int sd_sw_align_batch_compact_diag(sd_ctx *ctx, const sd_sw_params *par, const s
                                    const uint8_t *isIdentity, uint32_t *outIdx, sd_sw_result *out, uint32_t *nOut, char *btPool,
                                    uint64_t btCap, uint64_t *btUsed) {
     if (!outIdx || !nOut) return SD_EINVAL;
-    return alignBatchImpl(ctx, par, queries, targets, nPairs, pairQ, pairT, isIdentity, out, btPool, btCap, btUsed, outIdx, nOut, pairDiag);
+    return alignBatchImpl(ctx, {par, queries, targets, nPairs, pairQ, pairT, isIdentity, out, btPool, btCap, btUsed, outIdx, nOut, pairDiag, nullptr});
 }
 
 int sd_selftest_sort_pairs(sd_ctx *ctx, const uint32_t *keys, const uint32_t *vals, uint32_t n, int beginBit, int endBit, uint32_t *outKeys,
@@ -2720,6 +2771,15 @@ int sd_selftest_scan(sd_ctx *ctx, const uint32_t *in, uint32_t n, uint64_t *excl
     return SD_OK;
 }
 
+int sd_selftest_score_class(int kernel, int32_t n, int32_t tL, int shared, int32_t wideRowLimit, uint32_t *klass, char *scope, size_t cap) {
+    if (kernel < SCORE_PK || kernel > SCORE_INT32 || n < 1 || tL < 1 || !klass || (cap && !scope)) return SD_EINVAL;
+    const uint32_t ci = scoreClassOf(n, tL, kernel, wideRowLimit);
+    const ScoreSide &side = shared && ci < FIRST_INT32_CLASS ? SCORE_CLASSES[ci].shared : SCORE_CLASSES[ci].unshared;   // (devRunScore)
+    *klass = ci;
+    if (cap) snprintf(scope, cap, "%s", side.scope);
+    return SD_OK;
+}
+
 int sd_sw_align_batch_best_by_group(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
                                     uint32_t nPairs, const uint32_t *pairQ, const uint32_t *pairT, const uint16_t *pairDiag,
                                     const uint8_t *isIdentity, float seqIdThr, int32_t alnLenThr, uint32_t *outIdx, sd_sw_result *out,
@@ -2727,7 +2787,7 @@ int sd_sw_align_batch_best_by_group(sd_ctx *ctx, const sd_sw_params *par, const 
     if (!outIdx || !nOut || !targets) return SD_EINVAL;
     if (!targets->dGroupOf) return sdFail(ctx, SD_EINVAL, "sd_sw_align_batch_best_by_group: the target set has no groups (sd_seqset_set_groups)");
     const float bb[2] = {seqIdThr, (float) alnLenThr};
-    return alignBatchImpl(ctx, par, queries, targets, nPairs, pairQ, pairT, isIdentity, out, btPool, btCap, btUsed, outIdx, nOut, pairDiag, bb);
+    return alignBatchImpl(ctx, {par, queries, targets, nPairs, pairQ, pairT, isIdentity, out, btPool, btCap, btUsed, outIdx, nOut, pairDiag, bb});
 }
 
 int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
@@ -2758,40 +2818,22 @@ int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_se
         r.score = 0; r.qStart = -1; r.qEnd = -1; r.tStart = -1; r.tEnd = -1; r.identical = 0; r.btLen = 0; r.flags = 0;
         r.evalue = 0.0; r.btOffset = 0;
     }
-    // ---- identity pairs: scoreIdentical (StripedSmithWaterman.cpp:1675-1710), host side, O(L)
+    // ---- identity pairs
     for (uint32_t i = 0; i < nPairs; i++) {
         if (!(isIdentity && isIdentity[i])) continue;
-        const int L = tLv[i];
-        if (qLv[i] != L) return sdFail(ctx, SD_EINVAL, "scoreIdentical has different lengths for pair %u", i);
-        const uint8_t *q = queries->hRes.data() + queries->hOff[pairQ[i]];
-        const int8_t *cb = queries->hBias.data() + queries->hOff[pairQ[i]];
-        const uint8_t *t = targets->hRes.data() + targets->hOff[pairT[i]];
-        short score = 0;
-        for (int p = 0; p < L; p++) score += (short) (par->matrix[t[p] * 21 + q[p]] + cb[p]);
         sd_sw_result &r = out[i];
-        r.score = (int32_t) (uint32_t) (int) score;
-        r.qStart = par->swMode == 0 ? -1 : 0;
-        r.tStart = par->swMode == 0 ? -1 : 0;
-        r.qEnd = L - 1; r.tEnd = L - 1; r.identical = L; r.btLen = L;
-        r.evalue = sd::computeEvalue(ev, (double) (uint32_t) r.score, qLv[i]);
+        const int rcI = scoreIdentical(ctx, par, ev, queries, targets, i, pairQ[i], pairT[i], r);
+        if (rcI != SD_OK) return rcI;
         if (btPool) {
-            if (btPos + (uint64_t) L > btCap) return sdFail(ctx, SD_ENOMEM, "backtrace pool too small");
-            memset(btPool + btPos, 'M', L);
+            if (btPos + (uint64_t) r.btLen > btCap) return sdFail(ctx, SD_ENOMEM, "backtrace pool too small");
+            memset(btPool + btPos, 'M', r.btLen);
             r.btOffset = btPos;
-            btPos += L;
+            btPos += r.btLen;
         }
     }
     hs.reset(new HostScope(ctx, "align.fwd32"));
     // ---- pass 1: forward, byte-kernel lane structure (32 lanes)
     std::vector<SwTask> tasks;
-    auto fwdTask = [&](uint32_t i, int lanes) {
-        SwTask tk;
-        tk.qOff = queries->hOff[pairQ[i]]; tk.tOff = targets->hOff[pairT[i]];
-        tk.n = qLv[i]; tk.tL = tLv[i]; tk.qStep = 1; tk.tStep = 1;
-        tk.segLen = std::max(1, (tk.n + lanes - 1) / lanes);
-        tk.slot = i; tk.boundOff = 0;
-        return tk;
-    };
     {
         // every pair gets a slot-ordered task; identity / empty pairs are dropped with a parallel compaction
         std::vector<uint32_t> keepIdx(nPairs);
@@ -2800,7 +2842,7 @@ int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_se
             if (!(isIdentity && isIdentity[i]) && qLv[i] > 0 && tLv[i] > 0) keepIdx[nKeep++] = i;
         tasks.resize(nKeep);
 #pragma omp parallel for schedule(static)
-        for (uint32_t x = 0; x < nKeep; x++) tasks[x] = fwdTask(keepIdx[x], 32);
+        for (uint32_t x = 0; x < nKeep; x++) tasks[x] = fwdTask(queries, targets, pairQ[keepIdx[x]], pairT[keepIdx[x]], keepIdx[x], 32);
     }
     std::vector<int32_t> h;
     int rc = runScoreTasks(ctx, tasks, queries, targets, dMat.p, go, ge, h, nPairs, &ctx->cellsFwd, "f32");
@@ -2815,7 +2857,7 @@ int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_se
         const int bias = std::abs(matMin) + std::abs(queries->hMinBias[pairQ[i]]);
         if (h[3 * i] + bias >= 255) {
             word[i] = 1;
-            tasks2.push_back(fwdTask(i, 16));
+            tasks2.push_back(fwdTask(queries, targets, pairQ[i], pairT[i], i, 16));
         }
     }
     std::vector<int32_t> h2;
@@ -2890,19 +2932,17 @@ int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_se
     // ---- pass 4: banded traceback in chunks that fit the scratch budget
     if (!tb.empty() && btPool == nullptr) return sdFail(ctx, SD_EINVAL, "swMode 2 needs a backtrace pool");
     const uint64_t SCRATCH_BUDGET = 8ull << 30;
-    auto widthClass = [](int band) { int w = band * 2 + 3; return w <= 127 ? 128 : (w <= 511 ? 512 : (w <= 2047 ? 2048 : 0)); };   // 0: global-band class
     std::vector<TbTask> pending = tb;
     while (!pending.empty()) {
         for (size_t x = 0; x < pending.size(); x++)
             if (pending[x].band > 4 * 65536) return sdFail(ctx, SD_EHIP, "Trace back error (pair %u)", pending[x].slot);
         {   // order: LDS width class, then work (row chunks x rows) descending -- stable counting sort
             auto keyOf = [&](const TbTask &t) {
-                const int c = widthClass(t.band);
-                const int ci = c == 128 ? 0 : (c == 512 ? 1 : (c == 2048 ? 2 : 3));
+                const uint32_t ci = tbBandClass(t.band) - N_TB_NARROW;
                 const uint64_t work = (uint64_t) ((2 * t.band + 1 + 31) / 32) * (uint64_t) t.qLen;
-                return (uint32_t) ci * 4096u + (uint32_t) (4095 - std::min<uint64_t>(work >> 3, 4095));
+                return ci * 4096u + (uint32_t) (4095 - std::min<uint64_t>(work >> 3, 4095));
             };
-            std::vector<uint32_t> cnt(4 * 4096 + 1, 0);
+            std::vector<uint32_t> cnt((N_TB_CLASSES - N_TB_NARROW) * 4096 + 1, 0);
             for (size_t i = 0; i < pending.size(); i++) cnt[keyOf(pending[i]) + 1]++;
             for (size_t i = 1; i < cnt.size(); i++) cnt[i] += cnt[i - 1];
             std::vector<TbTask> sortedTb(pending.size());
@@ -2914,11 +2954,11 @@ int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_se
         while (pos < pending.size()) {
             uint64_t nDir = 0, nBt = 0;
             size_t end = pos;
-            const int cls = widthClass(pending[pos].band);
-            while (end < pending.size() && widthClass(pending[end].band) == cls) {
+            const uint32_t cls = tbBandClass(pending[pos].band);
+            while (end < pending.size() && tbBandClass(pending[end].band) == cls) {
                 TbTask &t = pending[end];
                 const uint64_t width_d = (uint64_t) t.band * 2 + 1;
-                const uint64_t ad = ((cls ? 0 : tbGlobalIntBytes(t.band)) + width_d * (uint64_t) t.qLen + 31) & ~15ull, ab = (uint64_t) t.qLen + t.tLen + 2;
+                const uint64_t ad = ((cls != TB_GLOBAL ? 0 : tbGlobalIntBytes(t.band)) + width_d * (uint64_t) t.qLen + 31) & ~15ull, ab = (uint64_t) t.qLen + t.tLen + 2;
                 if (end > pos && (nDir + ad) > SCRATCH_BUDGET) break;
                 t.intOff = 0; t.dirOff = nDir; t.btOff = nBt;
                 nDir += ad; nBt += ab;
@@ -2935,23 +2975,8 @@ int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_se
                 return sdFail(ctx, SD_ENOMEM, "traceback scratch allocation failed (%llu bytes)", (unsigned long long) nDir);
             SD_HIP(ctx, hipMemcpyAsync(dT.p, &pending[pos], cnt * sizeof(TbTask), hipMemcpyHostToDevice, ctx->stream));
             {
-                ProfScope ps(ctx, cls == 128 ? "sw_traceback.lds128" : (cls == 512 ? "sw_traceback.lds512" : (cls == 2048 ? "sw_traceback.lds2048" : "sw_traceback.global")));
-                const int ldsStride = cls + 1;
-                const size_t ldsBytes = (size_t) 2 * 3 * ldsStride * sizeof(int32_t);
-                if (cls)
-                    hipLaunchKernelGGL(sw_traceback_kernel<false>, dim3((cnt + 1) / 2), dim3(64), ldsBytes, ctx->stream, dT.p, cnt,
-                                       queries->dRes, queries->dBias, targets->dRes, dMat.p, go, ge, ldsStride, dDir.p, dBt.p, dRes.p,
-                                       (const uint32_t *) nullptr, 0, (const int8_t *) nullptr);
-                else
-                    hipLaunchKernelGGL((sw_traceback_kernel<false, true>), dim3((cnt + 1) / 2), dim3(64), 0, ctx->stream, dT.p, cnt,
-                                       queries->dRes, queries->dBias, targets->dRes, dMat.p, go, ge, INT_MAX, dDir.p, dBt.p, dRes.p,
-                                       (const uint32_t *) nullptr, 0, (const int8_t *) nullptr);
-                if (cls)
-                    hipLaunchKernelGGL(sw_traceback_walk_kernel<false>, dim3((cnt + 256 / TBW_LANES - 1) / (256 / TBW_LANES)), dim3(256), 0, ctx->stream, dT.p, cnt, queries->dRes,
-                                       targets->dRes, dDir.p, dBt.p, dRes.p, (const uint32_t *) nullptr);
-                else
-                    hipLaunchKernelGGL(sw_traceback_walk_kernel<true>, dim3((cnt + 256 / TBW_LANES - 1) / (256 / TBW_LANES)), dim3(256), 0, ctx->stream, dT.p, cnt, queries->dRes,
-                                       targets->dRes, dDir.p, dBt.p, dRes.p, (const uint32_t *) nullptr);
+                ProfScope ps(ctx, TB_CLASSES[cls].scope);
+                launchTbBand(ctx, queries, targets, dMat.p, go, ge, TB_CLASSES[cls], 0, dT.p, cnt, dDir.p, dBt.p, dRes.p, nullptr);
             }
             SD_HIP(ctx, hipGetLastError());
             TbTask *back = nullptr;

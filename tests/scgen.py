@@ -1,4 +1,4 @@
-"""Constructed pairs for the Smith-Waterman score passes (sd_sw.hip: scoreKey / devRunScore, sd_sw_pk.h), shared by the CPU and
+"""Constructed pairs for the Smith-Waterman score passes (sd_sw.hip: the SCORE_CLASSES table, scoreClassOf / devRunScore; sd_sw_pk.h), shared by the CPU and
 GPU tests and by tools/make_golden_score_classes.py, plus a restatement of the class table: which kernel instantiation and
 which profile scope a task of a pass runs in.
 
@@ -60,7 +60,7 @@ I32_NAMES = ('rt4', 'rt8', 'rt16', 'rt32')
 
 
 def klass(pass_, n, shared, wide_row_limit, packed=True, word=False, tl=65535):
-    """(task class, profile scope) of a score task of n rows and tl columns (scoreKey and the naming of devRunScore).  pass_: 'fwd' (the
+    """(task class, profile scope) of a score task of n rows and tl columns (scoreClassOf and the scopes of SCORE_CLASSES in sd_sw.hip; written by hand, never derived from that table).  pass_: 'fwd' (the
     forward byte pass), 'word' (the rerun of a saturated pair with the word structure) or 'start' (start positions: of a
     rerun pair when word is set).  shared: tasks paired by query (forward and rerun passes of a query set below 2^17
     sequences).  packed: False when the int32 kernel is forced or the gap costs demand it.  The unshared classes of 385 .. 768
@@ -110,7 +110,7 @@ def instantiation(scope_name, shared):
 
 
 def instantiations():
-    """the 63 kernels that devRunScore instantiates"""
+    """the 63 kernels that the SCORE_CLASSES table of sd_sw.hip instantiates"""
     out = [('a_seg%d' % rt, True) for rt in range(5, 25)] + [('a_seg%d' % rt, False) for rt in range(5, 13)]
     out += [('rt4x32', True), ('rt4x32', False), ('rt8x64', False), ('rt10x64', False), ('rt12x64', False), ('rt8x64multi', True),
             ('rt8x64multi', False)]

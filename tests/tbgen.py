@@ -1,5 +1,5 @@
 """Constructed pairs with a known band history for the banded traceback (sd_sw.hip), shared by the CPU and GPU tests and by
-tools/make_golden_tb_classes.py, plus a restatement of which traceback task class a band reaches (tbKey / widthClass).
+tools/make_golden_tb_classes.py, plus a restatement of which traceback task class a band reaches (tbKey / tbBandClass over TB_CLASSES).
 
 Three random segments A, B, C and independent random inserts X, Y:
   doubling  q = A X B C, t = A B Y C, |X| = |Y| = g: a square rectangle (first band 1) whose optimal path leaves the main

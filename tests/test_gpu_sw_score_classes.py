@@ -1,4 +1,4 @@
-"""GPU: every instantiation of the Smith-Waterman score kernels (sd_sw_pk.h, devRunScore in sd_sw.hip) in every pass that
+"""GPU: every instantiation of the Smith-Waterman score kernels (sd_sw_pk.h, SCORE_CLASSES / devRunScore in sd_sw.hip) in every pass that
 reaches it, on the constructed pairs of tests/scgen.py, through the device orchestration (Context.sw_align).  Every record is
 compared exactly with the rows that the REAL reference produced (tests/golden/score_classes.npz, alignment modes 0, 1, 2),
 and the launch counts of the sw_score* profile scopes equal what the restated class table derives from those rows: one

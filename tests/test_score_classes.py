@@ -1,7 +1,8 @@
 """CPU: the constructed score-class pairs (tests/scgen.py) against the rows that the REAL reference produced for them in
 alignment modes 0, 1 and 2 (tests/golden/score_classes.npz, tools/make_golden_score_classes.py): the oracle equals every
 row, every pair has the shape it was built for, and the restated class table puts the tasks that follow from the
-reference's rows into every one of the 63 score kernels that devRunScore instantiates.
+reference's rows into every one of the 63 score kernels that the SCORE_CLASSES table of sd_sw.hip instantiates, and
+the library's table (sd_selftest_score_class) equals the restatement for every row count.
 tests/test_gpu_sw_score_classes.py runs the same pairs through the kernels."""
 from collections import Counter
 
@@ -224,6 +225,28 @@ def test_reach_every_instantiation(gold, rows):
         fam |= set(t[3] for t in prow.tasks(k, 2))
     assert fam >= {('a_seg10', True), ('a_seg10', False), ('rt4x32', True), ('rt8x64', False), ('rt8x64multi', True), ('rt8x64multi', False),
                    ('w_rt10x32', True), ('w_rt8x64', False), ('w_rt8x64multi', True)}
+
+
+def test_library_table_equals_the_restatement(host):
+    """sd_selftest_score_class reads the table and the index function that the gate kernels and devRunScore use: for every pass,
+    both pairings, the packed and the int32 kernels, every row count up to 2 600 and one far beyond, the column counts around
+    wideRowLimit and around 65 535, the library's (class, scope) is klass()'s"""
+    checked = 0
+    for W in (258, 2340):
+        for pass_, word in (('fwd', False), ('word', False), ('start', False), ('start', True)):
+            wide = pass_ == 'word' or word
+            for packed in (True, False):
+                kernel = 2 if not packed else 1 if wide else 0
+                for shared in (True, False):
+                    lib_shared = shared and pass_ != 'start'      # (start-position tasks are never paired: alignBatchImpl)
+                    for tl in (1, W, W + 1, 65535, 65536):
+                        for n in list(range(1, 2601)) + [60000]:
+                            want = scgen.klass(pass_, n, shared, W, packed=packed, word=word, tl=tl)
+                            got = host.score_class(kernel, n, tl, lib_shared, W)
+                            if got != want:
+                                raise AssertionError((pass_, word, packed, shared, W, tl, n, got, want))
+                            checked += 1
+    assert checked == 2 * 4 * 2 * 2 * 5 * 2601
 
 
 def test_scope_restates_the_class_limits():
