@@ -205,6 +205,15 @@ int sd_sw_download_bytes(sd_ctx *ctx, uint64_t *recordBytes, uint64_t *poolBytes
  * With profiling enabled the calls add three counters to the profile: stat.sw_word_pairs (pairs with flag bit 0),
  * stat.sw_word_wide (of these: rerun wide) and stat.sw_word_narrow_final (first pass final), as sums in the `ms` field. */
 int sd_sw_set_narrow_final(sd_ctx *ctx, int on);
+/* on != 0: in the alignment calls of this context the start-position pass runs the narrow tasks of a query of 129 .. 768 residues
+ * as suffixes of ONE int8 profile of the whole reversed query (a task begins at profile row qLen - 1 - qEnd), four tasks of a query
+ * per wavefront, instead of building a profile of the reversed prefix per task.  Every cell and the end-cell rule are the same, so
+ * records, flags and backtraces are the same bytes; sd_sw_last_cells still counts (qEnd + 1) x (tEnd + 1) per task.  Not affected:
+ * queries of up to 128 or more than 768 residues, tasks of the wide and int32 kernels, calls on the int32 kernel, and query sets of
+ * 2^17 sequences or more (tasks are not paired by query there).  Off by default; the streaming search (sd_search_*) and the
+ * in-memory iterations switch it on for their own contexts (SD_SW_SHARED_START=0 in the environment keeps it off there).  With
+ * profiling enabled these launches appear in scopes of their own, sw_score_pk.s_seg5 .. s_seg24. */
+int sd_sw_set_shared_start(sd_ctx *ctx, int on);
 
 /* ---- self-test entry points of the library's own device primitives (csrc/hip/sd_scan_sort.h), for tests/ ----------------------
  * sd_selftest_sort_pairs: stable sort of (key, value) pairs by the key bits [beginBit, endBit) -- what the alignment task order and
@@ -216,8 +225,9 @@ int sd_selftest_scan(sd_ctx *ctx, const uint32_t *in, uint32_t n, uint64_t *excl
 /* sd_selftest_score_class: the class of the Smith-Waterman score-class table (csrc/hip/sd_sw.hip) that a task of n rows and tL columns
  * falls into, and the profile scope of the kernel that runs it, for tasks paired by query (shared != 0) or alone.  kernel: what the
  * gates ask for -- 0 the packed kernels, 1 the packed kernels with the wide row code (beyond wideRowLimit in both dimensions: the
- * int32 kernel), 2 the int32 kernel.  The table and the index function are the ones the device code uses; no context, no GPU. */
-int sd_selftest_score_class(int kernel /* 0 packed, 1 packed wide, 2 int32 */, int32_t n, int32_t tL, int shared, int32_t wideRowLimit,
+ * int32 kernel), 2 the int32 kernel, 3 the start-row form (sd_sw_set_shared_start; n is then the query's length, and outside
+ * 129 .. 768 rows the answer is kernel 0's).  The table and the index function are the ones the device code uses; no context, no GPU. */
+int sd_selftest_score_class(int kernel /* 0 packed, 1 packed wide, 2 int32, 3 packed start-row */, int32_t n, int32_t tL, int shared, int32_t wideRowLimit,
                             uint32_t *klass, char *scope, size_t cap);
 /* sd_selftest_r2p_weights: the weights stage of result2profile alone (csrc/hip/sd_r2p.hip) on nTasks alignments given as cell
  * matrices, task after task, row-major [nRows][L], row 0 the centre; cell codes 0..19 residue, 20 any residue, 21 gap.  The global

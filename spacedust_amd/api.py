@@ -497,6 +497,11 @@ class Context:
         pass reports 1023 (or the pair skipped that pass); same records, fewer launches and cells"""
         _check(self.h, self.L.sd_sw_set_narrow_final(self.h, 1 if on else 0), 'sd_sw_set_narrow_final')
 
+    def set_shared_start(self, on=True):
+        """sd_sw_set_shared_start: the narrow start-position tasks of a query of 129 .. 768 residues run as suffixes of one profile
+        of the whole reversed query (scopes sw_score_pk.s_seg*); same records"""
+        _check(self.h, self.L.sd_sw_set_shared_start(self.h, 1 if on else 0), 'sd_sw_set_shared_start')
+
     def sw_download_bytes(self):
         a, b = C.c_uint64(), C.c_uint64()
         self.L.sd_sw_download_bytes(self.h, C.byref(a), C.byref(b))

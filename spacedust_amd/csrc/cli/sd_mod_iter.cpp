@@ -102,6 +102,7 @@ struct Worker {
     ~Worker() {
         if (r2p) sd_r2p_destroy(r2p);
         if (ctx) sd_sw_set_narrow_final(ctx, 0);
+        if (ctx) sd_sw_set_shared_start(ctx, 0);
         if (ctx) sd_ctx_destroy(ctx);
         if (host) sd_host_destroy(host);
     }
@@ -404,6 +405,8 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
         if (S.profile) sd_profile_enable(W.ctx, 1);
         // word-structure reruns only where the narrow score pass cannot answer (same records; SD_SW_NARROW_FINAL=0: every saturating pair)
         sd_sw_set_narrow_final(W.ctx, (getenv("SD_SW_NARROW_FINAL") && atoi(getenv("SD_SW_NARROW_FINAL")) == 0) ? 0 : 1);
+        // narrow start-position tasks of one query share the query's profile (same records; SD_SW_SHARED_START=0: a profile per task)
+        sd_sw_set_shared_start(W.ctx, (getenv("SD_SW_SHARED_START") && atoi(getenv("SD_SW_SHARED_START")) == 0) ? 0 : 1);
     }
     // ---- the target: both indexes (the sequence search's k-mer threshold; every k-mer for the profile searches,
     // Prefiltering.cpp:525-527) and the sequences, resident for the whole run

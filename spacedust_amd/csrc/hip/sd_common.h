@@ -40,6 +40,7 @@ struct sd_ctx {
     const sd_sw_result *alignDevRes = nullptr;
     size_t alignDevResN = 0;
     bool cigarPool = false;   // sd_sw_set_cigar_pool: the alignment calls return run-length text instead of backtrace letters
+    bool sharedStart = false; // sd_sw_set_shared_start: narrow start-position tasks of a query of 129 .. 768 rows share the query's one profile
     bool narrowFinal = false; // sd_sw_set_narrow_final: a narrow forward score below 1023 is final, only the other saturating pairs rerun wide
     uint64_t d2hRecordBytes = 0, d2hPoolBytes = 0;  // what the alignment calls brought back (sd_sw_download_bytes)
     hipDeviceProp_t prop;

@@ -800,13 +800,13 @@ void launchScorePk(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, ui
                        t->dRes, dMat, go, ge, dOut, dBound, dOrder, (const int8_t *) q->dProf);
 }
 
-template <int RT, bool SHARED>
+template <int RT, bool SHARED, bool START = false>
 void launchScorePkAligned(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, uint32_t n, const sd_seqset *q, const sd_seqset *t,
                           const int8_t *dMat, int go, int ge, int32_t *dOut, uint2 * /* dBound: one strip */) {
     if (n == 0) return;
     constexpr uint32_t perWave = 4;   // two 32-lane groups of a task pair each
     dim3 grid((n + perWave - 1) / perWave), block(64);
-    hipLaunchKernelGGL((sdpk::sw_score_pk_aligned_kernel<RT, SHARED>), grid, block, 0, ctx->stream, dTasks, n, q->dRes, q->dBias, t->dRes,
+    hipLaunchKernelGGL((sdpk::sw_score_pk_aligned_kernel<RT, SHARED, START>), grid, block, 0, ctx->stream, dTasks, n, q->dRes, q->dBias, t->dRes,
                        dMat, go, ge, dOut, dOrder, (const int8_t *) q->dProf);
 }
 
@@ -831,8 +831,12 @@ void launchScoreIdx(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, u
 //             384 rows keep their class of 32 rows and run on the general kernel of 512 / 640 / 768 rows
 //   wide      the general packed kernel with the wide row code: word-kernel reruns and their start positions
 //   int32     every call the packed kernels do not take (usePk), and word tasks beyond wideRowLimit
+//   start     sd_sw_set_shared_start: the narrow start-position tasks of a query of 129 .. 768 rows, on the start-row form of the
+//             aligned kernel.  The class is the QUERY's (n = its length: the profile of the whole reversed query serves every task
+//             of the query, k_gate_rev), always paired by query, so there is one side.  The forms before it keep their indices
 // The pair sort carries the class in six bits: fewer than 64 classes.
-enum ScoreKernel { SCORE_PK = 0, SCORE_PK_WIDE = 1, SCORE_INT32 = 2 };
+enum ScoreKernel { SCORE_PK = 0, SCORE_PK_WIDE = 1, SCORE_INT32 = 2, SCORE_PK_START = 3 };
+constexpr int START_ROWS_MIN = 129, START_ROWS_MAX = 768;
 constexpr int SCORE_ROWS_ANY = 0x7FFFFFFF;
 constexpr int I32_STRIP_ROWS = 1024;   // sw_score_kernel<32>: a task of more rows hands its last row from strip to strip
 struct ScoreSide { const char *scope; ScoreLaunch launch; };
@@ -886,6 +890,27 @@ constexpr ScoreClass SCORE_CLASSES[] = {
     {SCORE_INT32, 256, 0, {"sw_score.rt8", launchScoreIdx<8>}, {"sw_score.rt8", launchScoreIdx<8>}},
     {SCORE_INT32, 512, 0, {"sw_score.rt16", launchScoreIdx<16>}, {"sw_score.rt16", launchScoreIdx<16>}},
     {SCORE_INT32, SCORE_ROWS_ANY, 1, {"sw_score.rt32", launchScoreIdx<32>}, {"sw_score.rt32", launchScoreIdx<32>}},
+    // (whole queries of START_ROWS_MIN .. START_ROWS_MAX rows, RT = 5 .. 24; launched with explicit pairs only)
+    {SCORE_PK_START, 160, 0, {"sw_score_pk.s_seg5", launchScorePkAligned<5, true, true>}, {"sw_score_pk.s_seg5", launchScorePkAligned<5, true, true>}},
+    {SCORE_PK_START, 192, 0, {"sw_score_pk.s_seg6", launchScorePkAligned<6, true, true>}, {"sw_score_pk.s_seg6", launchScorePkAligned<6, true, true>}},
+    {SCORE_PK_START, 224, 0, {"sw_score_pk.s_seg7", launchScorePkAligned<7, true, true>}, {"sw_score_pk.s_seg7", launchScorePkAligned<7, true, true>}},
+    {SCORE_PK_START, 256, 0, {"sw_score_pk.s_seg8", launchScorePkAligned<8, true, true>}, {"sw_score_pk.s_seg8", launchScorePkAligned<8, true, true>}},
+    {SCORE_PK_START, 288, 0, {"sw_score_pk.s_seg9", launchScorePkAligned<9, true, true>}, {"sw_score_pk.s_seg9", launchScorePkAligned<9, true, true>}},
+    {SCORE_PK_START, 320, 0, {"sw_score_pk.s_seg10", launchScorePkAligned<10, true, true>}, {"sw_score_pk.s_seg10", launchScorePkAligned<10, true, true>}},
+    {SCORE_PK_START, 352, 0, {"sw_score_pk.s_seg11", launchScorePkAligned<11, true, true>}, {"sw_score_pk.s_seg11", launchScorePkAligned<11, true, true>}},
+    {SCORE_PK_START, 384, 0, {"sw_score_pk.s_seg12", launchScorePkAligned<12, true, true>}, {"sw_score_pk.s_seg12", launchScorePkAligned<12, true, true>}},
+    {SCORE_PK_START, 416, 0, {"sw_score_pk.s_seg13", launchScorePkAligned<13, true, true>}, {"sw_score_pk.s_seg13", launchScorePkAligned<13, true, true>}},
+    {SCORE_PK_START, 448, 0, {"sw_score_pk.s_seg14", launchScorePkAligned<14, true, true>}, {"sw_score_pk.s_seg14", launchScorePkAligned<14, true, true>}},
+    {SCORE_PK_START, 480, 0, {"sw_score_pk.s_seg15", launchScorePkAligned<15, true, true>}, {"sw_score_pk.s_seg15", launchScorePkAligned<15, true, true>}},
+    {SCORE_PK_START, 512, 0, {"sw_score_pk.s_seg16", launchScorePkAligned<16, true, true>}, {"sw_score_pk.s_seg16", launchScorePkAligned<16, true, true>}},
+    {SCORE_PK_START, 544, 0, {"sw_score_pk.s_seg17", launchScorePkAligned<17, true, true>}, {"sw_score_pk.s_seg17", launchScorePkAligned<17, true, true>}},
+    {SCORE_PK_START, 576, 0, {"sw_score_pk.s_seg18", launchScorePkAligned<18, true, true>}, {"sw_score_pk.s_seg18", launchScorePkAligned<18, true, true>}},
+    {SCORE_PK_START, 608, 0, {"sw_score_pk.s_seg19", launchScorePkAligned<19, true, true>}, {"sw_score_pk.s_seg19", launchScorePkAligned<19, true, true>}},
+    {SCORE_PK_START, 640, 0, {"sw_score_pk.s_seg20", launchScorePkAligned<20, true, true>}, {"sw_score_pk.s_seg20", launchScorePkAligned<20, true, true>}},
+    {SCORE_PK_START, 672, 0, {"sw_score_pk.s_seg21", launchScorePkAligned<21, true, true>}, {"sw_score_pk.s_seg21", launchScorePkAligned<21, true, true>}},
+    {SCORE_PK_START, 704, 0, {"sw_score_pk.s_seg22", launchScorePkAligned<22, true, true>}, {"sw_score_pk.s_seg22", launchScorePkAligned<22, true, true>}},
+    {SCORE_PK_START, 736, 0, {"sw_score_pk.s_seg23", launchScorePkAligned<23, true, true>}, {"sw_score_pk.s_seg23", launchScorePkAligned<23, true, true>}},
+    {SCORE_PK_START, 768, 0, {"sw_score_pk.s_seg24", launchScorePkAligned<24, true, true>}, {"sw_score_pk.s_seg24", launchScorePkAligned<24, true, true>}},
 };
 constexpr uint32_t N_SCORE_CLASSES = sizeof(SCORE_CLASSES) / sizeof(SCORE_CLASSES[0]);
 static_assert(N_SCORE_CLASSES < 63, "class boundaries are found by one 64-lane wavefront; six class bits in the pair key");
@@ -895,6 +920,7 @@ constexpr uint32_t firstScoreClass(ScoreKernel form) {
     return ci;
 }
 constexpr uint32_t FIRST_WIDE_CLASS = firstScoreClass(SCORE_PK_WIDE), FIRST_INT32_CLASS = firstScoreClass(SCORE_INT32);
+constexpr uint32_t FIRST_START_CLASS = firstScoreClass(SCORE_PK_START);
 constexpr uint32_t KEY_INVALID = N_SCORE_CLASSES * 1024u;   // sorts after every class
 // the classes whose tasks need `need` uint2 of hand-over space per column, one bit each (device code reads the table through constants)
 constexpr uint64_t scoreBoundMask(int need) {
@@ -906,6 +932,10 @@ constexpr uint64_t scoreBoundMask(int need) {
 // wideRowLimit: int16 cells hold a score for certain while min(n, tL) * (largest entry of this call's query profiles) <= 32 767
 // (no saturation of the reference's word kernel to reproduce, no wrap); longer pairs take the int32 kernel
 constexpr __host__ __device__ uint32_t scoreClassOf(int n, int tL, int kernel, int wideRowLimit) {
+    if (kernel == SCORE_PK_START) {   // (outside its rows, or beyond 16-bit columns: the narrow form's class)
+        if (n >= START_ROWS_MIN && n <= START_ROWS_MAX && tL <= 65535) return FIRST_START_CLASS + (n + 31) / 32 - 5;
+        kernel = SCORE_PK;
+    }
     if (kernel == SCORE_PK_WIDE && (n < tL ? n : tL) > wideRowLimit) kernel = SCORE_INT32;
     if (kernel == SCORE_INT32 || tL > 65535) return FIRST_INT32_CLASS + (n <= 128 ? 0 : (n <= 256 ? 1 : (n <= 512 ? 2 : 3)));
     const int strips = (n + 511) / 512 < 4 ? (n + 511) / 512 : 4;   // beyond 768 rows: 2, 3, more
@@ -926,10 +956,20 @@ constexpr bool scoreClassesAreTheTables() {
             if (ci >= N_SCORE_CLASSES || SCORE_CLASSES[ci].form != form || n > SCORE_CLASSES[ci].rows) return false;
             if (ci > 0 && SCORE_CLASSES[ci - 1].form == form && n <= SCORE_CLASSES[ci - 1].rows) return false;
         }
+    for (int n = 1; n <= 2049; n++) {   // the start form: its own classes inside its rows, the narrow form's outside
+        const uint32_t ci = scoreClassOf(n, 1, SCORE_PK_START, SCORE_ROWS_ANY);
+        if (n < START_ROWS_MIN || n > START_ROWS_MAX) {
+            if (ci != scoreClassOf(n, 1, SCORE_PK, SCORE_ROWS_ANY)) return false;
+            continue;
+        }
+        if (ci >= N_SCORE_CLASSES || SCORE_CLASSES[ci].form != SCORE_PK_START || n > SCORE_CLASSES[ci].rows) return false;
+        if (SCORE_CLASSES[ci - 1].form == SCORE_PK_START && n <= SCORE_CLASSES[ci - 1].rows) return false;
+    }
     return true;
 }
 static_assert(scoreClassesAreTheTables(), "scoreClassOf: n lies in (rows of the class before, rows of its class] for every n, in every form");
-static_assert(SCORE_CLASSES[N_SCORE_CLASSES - 1].form == SCORE_INT32 && SCORE_CLASSES[FIRST_INT32_CLASS - 1].form == SCORE_PK_WIDE, "forms in order");
+static_assert(SCORE_CLASSES[N_SCORE_CLASSES - 1].form == SCORE_PK_START && SCORE_CLASSES[FIRST_START_CLASS - 1].form == SCORE_INT32 &&
+              SCORE_CLASSES[FIRST_INT32_CLASS - 1].form == SCORE_PK_WIDE, "forms in order");
 __device__ __forceinline__ uint32_t scoreKey(int n, int tL, int kernel, int wideRowLimit = 800) {
     return scoreClassOf(n, tL, kernel, wideRowLimit) * 1024u + (uint32_t) (1023 - min(tL >> 4, 1023));
 }
@@ -943,7 +983,7 @@ int runScoreTasks(sd_ctx *ctx, std::vector<SwTask> &tasks, const sd_seqset *q, c
     if (tasks.empty()) return SD_OK;
     HostScope hsAll(ctx, "score.total");
     const size_t n = tasks.size();
-    constexpr int N_I32 = N_SCORE_CLASSES - FIRST_INT32_CLASS, NB = N_I32 * 1024;
+    constexpr int N_I32 = FIRST_START_CLASS - FIRST_INT32_CLASS, NB = N_I32 * 1024;
     auto keyOf = [](const SwTask &t) {
         const uint32_t ci = scoreClassOf(t.n, t.tL, SCORE_INT32, 0) - FIRST_INT32_CLASS;
         return ci * 1024u + (uint32_t) (1023 - std::min(t.tL >> 4, 1023));
@@ -1195,7 +1235,8 @@ k_gate_rev(uint32_t nPairs, DevGateParams gp, const uint32_t *__restrict__ pairQ
            const int32_t *__restrict__ out16, const uint8_t *__restrict__ word, const uint32_t *__restrict__ fwdKeys,
            SwTask *__restrict__ tasks, uint32_t *__restrict__ keys, uint32_t *__restrict__ vals,
            sd_sw_result *__restrict__ res, int usePk,
-           const uint8_t *__restrict__ wide /* nullable (k_gate_word): the word pairs that were rerun; null: all of them */) {
+           const uint8_t *__restrict__ wide /* nullable (k_gate_word): the word pairs that were rerun; null: all of them */,
+           int sharedStart /* sd_sw_set_shared_start, packed calls whose tasks are paired by query */) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nPairs) return;
     vals[i] = i;
@@ -1229,8 +1270,13 @@ k_gate_rev(uint32_t nPairs, DevGateParams gp, const uint32_t *__restrict__ pairQ
     const int lanes = word[i] ? 16 : 32;
     tk.segLen = max(1, (tk.n + lanes - 1) / lanes);
     tk.slot = i; tk.boundOff = 0;
+    // a narrow task of a query in the start form's rows: the class is the query's, the task carries the profile row it begins at
+    // (segLen is free: only the int32 kernel reads it as a segment length).  tk.n stays the task's rows (k_cells, k_gate_tb)
+    const bool start = sharedStart && usePk && !rerun && scoreClassOf(qL, tk.tL, SCORE_PK_START, 0) >= FIRST_START_CLASS;
+    if (start) tk.segLen = qL - 1 - r.qEnd;
     tasks[i] = tk;
-    keys[i] = scoreKey(tk.n, tk.tL, !usePk ? SCORE_INT32 : (rerun ? SCORE_PK_WIDE : SCORE_PK), gp.wideRowLimit);
+    keys[i] = start ? scoreKey(qL, tk.tL, SCORE_PK_START)
+                    : scoreKey(tk.n, tk.tL, !usePk ? SCORE_INT32 : (rerun ? SCORE_PK_WIDE : SCORE_PK), gp.wideRowLimit);
 }
 
 // traceback task classes: N_TB_NARROW register-band classes by query rows, then three LDS-band classes by band width
@@ -1639,13 +1685,21 @@ k_bound_apply(uint32_t nPairs, SwTask *__restrict__ tasks, const uint64_t *__res
 // odd last task stays alone.  Invalid tasks sort last (all ones).
 constexpr uint32_t PAIR_NONE = 0xFFFFFFFFu;
 constexpr int PAIR_QUERY_BITS = 17;
+// The classes whose tasks are paired.  Forward passes: every packed class.  The start-position pass (startOnly): the start
+// form's classes alone -- its other tasks scan per-pair prefixes, have no profile to share and keep the plain order.
+__host__ __device__ __forceinline__ bool pairedClass(uint32_t ci, int startOnly) {
+    return startOnly ? ci >= FIRST_START_CLASS && ci < N_SCORE_CLASSES : ci < FIRST_INT32_CLASS;
+}
 __global__ void __launch_bounds__(256)
-k_pair_keys(uint32_t n, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ pairQ, uint32_t *__restrict__ key2) {
+k_pair_keys(uint32_t n, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ pairQ, uint32_t *__restrict__ key2, int startOnly) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t k = keys[i];
     // class (6 bits) | query (17 bits) | target length code (9 bits): invalid entries sort behind the last class
-    key2[i] = k == KEY_INVALID ? 0xFFFFFFFFu : ((k >> 10) << 26) | (pairQ[i] << 9) | ((k & 1023u) >> 1);
+    uint32_t v = k == KEY_INVALID ? 0xFFFFFFFFu : ((k >> 10) << 26) | (pairQ[i] << 9) | ((k & 1023u) >> 1);
+    // startOnly, unpaired classes: class | the ten bits of the target length code, i.e. the order of the plain sort of `keys`
+    if (startOnly && k != KEY_INVALID && !pairedClass(k >> 10, startOnly)) v = ((k >> 10) << 26) | ((k & 1023u) << 16);
+    key2[i] = v;
 }
 __global__ void __launch_bounds__(256)
 k_pair_heads(uint32_t n, const uint32_t *__restrict__ keyS, uint32_t *__restrict__ headPos) {
@@ -1658,11 +1712,12 @@ k_pair_heads(uint32_t n, const uint32_t *__restrict__ keyS, uint32_t *__restrict
 // one EMPTY pair when the run holds an odd number of pairs, so that every wavefront of four tasks (two pairs) stays inside one
 // query (sw_score_pk_aligned_kernel<.., SHARED = true>: one profile per wavefront)
 __global__ void __launch_bounds__(256)
-k_pair_leaders(uint32_t n, const uint32_t *__restrict__ keyS, const uint32_t *__restrict__ runStart, uint8_t *__restrict__ leader) {
+k_pair_leaders(uint32_t n, const uint32_t *__restrict__ keyS, const uint32_t *__restrict__ runStart, uint8_t *__restrict__ leader,
+               int startOnly) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p > n) return;
     uint8_t v = 0;
-    if (p < n && (keyS[p] >> 26) < FIRST_INT32_CLASS) {
+    if (p < n && pairedClass(keyS[p] >> 26, startOnly)) {
         const uint32_t o = p - runStart[p];
         v = (o & 1u) == 0 ? 1 : 0;
         const bool lastOfRun = p + 1 >= n || (keyS[p + 1] >> 9) != (keyS[p] >> 9);
@@ -1673,15 +1728,15 @@ k_pair_leaders(uint32_t n, const uint32_t *__restrict__ keyS, const uint32_t *__
 }
 __global__ void __launch_bounds__(256)
 k_pair_emit(uint32_t n, const uint32_t *__restrict__ keyS, const uint32_t *__restrict__ vals, const uint32_t *__restrict__ runStartOf,
-            const uint64_t *__restrict__ pairIdx, uint32_t *__restrict__ order2) {
+            const uint64_t *__restrict__ pairIdx, uint32_t *__restrict__ order2, int startOnly) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n || (keyS[p] >> 26) >= FIRST_INT32_CLASS || ((p - runStartOf[p]) & 1u)) return;   // the first task of every pair (packed classes) writes it
+    if (p >= n || !pairedClass(keyS[p] >> 26, startOnly) || ((p - runStartOf[p]) & 1u)) return;   // the first task of every pair (paired classes) writes it
     const uint64_t w = pairIdx[p];
     order2[2 * w] = vals[p];
     const bool mate = p + 1 < n && (keyS[p + 1] >> 9) == (keyS[p] >> 9);
     order2[2 * w + 1] = mate ? vals[p + 1] : PAIR_NONE;
 }
-// pair-index boundaries of the packed classes: b[c] = number of pairs of classes < c
+// pair-index boundaries of the classes: b[c] = number of pairs of classes < c
 __global__ void k_pair_bounds(const uint32_t *__restrict__ keyS, uint32_t n, const uint64_t *__restrict__ pairIdx,
                               uint32_t *__restrict__ b, int nb) {
     const int c = threadIdx.x;
@@ -1715,7 +1770,8 @@ struct AlignWs {
 
 // sort (keys,vals) -> order, read the class boundaries, launch the kernel of every class that has a task (SCORE_CLASSES)
 int devRunScore(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs, const uint32_t *dKeys, const sd_seqset *q, const sd_seqset *t, int go, int ge,
-                int32_t *dOut, const uint32_t *dPairQ /* non-null: every task scans its whole query, pair them up */) {
+                int32_t *dOut, const uint32_t *dPairQ /* non-null: pair the tasks of the paired classes by query */,
+                int startOnly = 0 /* pairedClass: the start-position pass pairs the start form's classes only */) {
     const uint32_t *dOrder = w.dOrder;
     const unsigned grid = (nPairs + 255) / 256;
     int rc = SD_OK;
@@ -1735,19 +1791,19 @@ int devRunScore(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs, const uint32_t *
         SD_HIP(ctx, wsGet(ctx, "sp.order2", order2Cap, &dOrder2));
         SD_HIP(ctx, hipMemsetAsync(dOrder2, 0xFF, order2Cap * sizeof(uint32_t), ctx->stream));   // empty pairs: PAIR_NONE
         SD_HIP(ctx, wsGet(ctx, "sp.bounds", 64, &dPairBounds));
-        hipLaunchKernelGGL(k_pair_keys, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeys, dPairQ, dKey2);
+        hipLaunchKernelGGL(k_pair_keys, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeys, dPairQ, dKey2, startOnly);
         rc = devSortPairs(ctx, dKey2, w.dKeysS, w.dVals, dVals2, nPairs, 32);
         if (rc != SD_OK) return rc;
         dOrder = dVals2;
         hipLaunchKernelGGL(k_pair_heads, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dHead);
         rc = devInclusiveMax(ctx, dHead, dRunStart, nPairs);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dRunStart, dLeader);
+        hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dRunStart, dLeader, startOnly);
         rc = devExclusiveScan(ctx, (const uint8_t *) dLeader, dPairIdx, (size_t) nPairs + 1);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_pair_emit, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dVals2, dRunStart, dPairIdx, dOrder2);
+        hipLaunchKernelGGL(k_pair_emit, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dVals2, dRunStart, dPairIdx, dOrder2, startOnly);
         hipLaunchKernelGGL(k_pair_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, dPairIdx, dPairBounds,
-                           (int) FIRST_INT32_CLASS + 1);
+                           (int) N_SCORE_CLASSES + 1);
         hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, 1u << 26, w.dBounds, (int) N_SCORE_CLASSES + 1);
     } else {
         rc = devSortPairs(ctx, dKeys, w.dKeysS, w.dVals, w.dOrder, nPairs, 16);
@@ -1760,7 +1816,7 @@ int devRunScore(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs, const uint32_t *
     rc = devExclusiveScan(ctx, w.dScanA, w.dScanB, (size_t) nPairs + 1);
     if (rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_bound_apply, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, w.dScanB);
-    uint32_t hb[N_SCORE_CLASSES + 1], hpb[FIRST_INT32_CLASS + 1];
+    uint32_t hb[N_SCORE_CLASSES + 1], hpb[N_SCORE_CLASSES + 1];
     uint64_t boundTotal = 0;
     if (dPairQ) SD_HIP(ctx, sdD2H(ctx, hpb, dPairBounds, sizeof(hpb)));
     SD_HIP(ctx, sdD2H(ctx, hb, w.dBounds, sizeof(hb)));
@@ -1771,7 +1827,7 @@ int devRunScore(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs, const uint32_t *
     for (uint32_t ci = 0; ci < N_SCORE_CLASSES; ci++) {
         const uint32_t begin = hb[ci], cnt = hb[ci + 1] - hb[ci];
         if (cnt == 0) continue;
-        const bool shared = dPairQ != nullptr && ci < FIRST_INT32_CLASS;
+        const bool shared = dPairQ != nullptr && pairedClass(ci, startOnly);
         const ScoreSide &side = shared ? SCORE_CLASSES[ci].shared : SCORE_CLASSES[ci].unshared;
         ProfScope ps(ctx, side.scope);
         if (shared)   // explicit pairs: two entries per pair of the class
@@ -2651,10 +2707,15 @@ static int alignBatchImpl(sd_ctx *ctx, const AlignCall &a) {
     if (rc != SD_OK) return rc;
     // ---- gates + pass 3: start positions
     hs.reset(new HostScope(ctx, "align.rev"));
+    // Start-position tasks scan per-pair prefixes of the reversed query.  sd_sw_set_shared_start: the narrow ones of a query of
+    // 129 .. 768 rows run as suffixes of the profile of the whole reversed query, four tasks of one query per wavefront, paired by
+    // the same sort that orders the others (k_pair_keys): still one sort and one boundary read-back in this pass.  Every other
+    // task builds its own profile, as all of them do with the switch off
+    const bool sharedStart = ctx->sharedStart && usePk && dShare != nullptr;
     hipLaunchKernelGGL(k_gate_rev, dim3(grid), dim3(256), 0, ctx->stream, nPairs, gp, w.dPQ, w.dPT, queries->dOff, targets->dOff, w.dOut32,
-                       w.dOut16, w.dWord, w.dFwdKeys, w.dTasks, w.dRevKeys, w.dVals, w.dRes, usePk, (const uint8_t *) dWide);
+                       w.dOut16, w.dWord, w.dFwdKeys, w.dTasks, w.dRevKeys, w.dVals, w.dRes, usePk, (const uint8_t *) dWide, sharedStart ? 1 : 0);
     hipLaunchKernelGGL(k_cells, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, w.dRevKeys, w.dCells + 1);
-    rc = devRunScore(ctx, w, nPairs, w.dRevKeys, queries, targets, go, ge, w.dOutRev, nullptr);   // start-position tasks scan per-pair prefixes: no shared profile
+    rc = devRunScore(ctx, w, nPairs, w.dRevKeys, queries, targets, go, ge, w.dOutRev, sharedStart ? dShare : nullptr, 1);
     if (rc != SD_OK) return rc;
     // ---- pass 4: banded traceback, band doubling on the device
     hs.reset(new HostScope(ctx, "align.traceback"));
@@ -2695,6 +2756,12 @@ int sd_sw_set_cigar_pool(sd_ctx *ctx, int on) {
 int sd_sw_set_narrow_final(sd_ctx *ctx, int on) {
     if (!ctx) return SD_EINVAL;
     ctx->narrowFinal = on != 0;
+    return SD_OK;
+}
+
+int sd_sw_set_shared_start(sd_ctx *ctx, int on) {
+    if (!ctx) return SD_EINVAL;
+    ctx->sharedStart = on != 0;
     return SD_OK;
 }
 
@@ -2772,9 +2839,9 @@ int sd_selftest_scan(sd_ctx *ctx, const uint32_t *in, uint32_t n, uint64_t *excl
 }
 
 int sd_selftest_score_class(int kernel, int32_t n, int32_t tL, int shared, int32_t wideRowLimit, uint32_t *klass, char *scope, size_t cap) {
-    if (kernel < SCORE_PK || kernel > SCORE_INT32 || n < 1 || tL < 1 || !klass || (cap && !scope)) return SD_EINVAL;
+    if (kernel < SCORE_PK || kernel > SCORE_PK_START || n < 1 || tL < 1 || !klass || (cap && !scope)) return SD_EINVAL;
     const uint32_t ci = scoreClassOf(n, tL, kernel, wideRowLimit);
-    const ScoreSide &side = shared && ci < FIRST_INT32_CLASS ? SCORE_CLASSES[ci].shared : SCORE_CLASSES[ci].unshared;   // (devRunScore)
+    const ScoreSide &side = shared && (ci < FIRST_INT32_CLASS || ci >= FIRST_START_CLASS) ? SCORE_CLASSES[ci].shared : SCORE_CLASSES[ci].unshared;   // (devRunScore)
     *klass = ci;
     if (cap) snprintf(scope, cap, "%s", side.scope);
     return SD_OK;

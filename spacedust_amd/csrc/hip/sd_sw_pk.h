@@ -41,7 +41,8 @@ struct SwTask {
     int32_t tL;        // target columns scanned
     int32_t qStep;     // +1 forward, -1 reverse pass
     int32_t tStep;
-    int32_t segLen;    // ceil(n / lanes) of the reference kernel being reproduced (read by the int32 kernel only)
+    int32_t segLen;    // int32 kernel: ceil(n / lanes) of the reference kernel being reproduced.  Start-row form of the aligned
+                       // kernel: j0, the row of the wavefront's profile at which this task's rows begin.  Nothing else reads it
     uint32_t slot;     // output slot
     uint64_t boundOff; // offset (in uint2 units) into the strip boundary workspace (multi-strip tasks only)
 };
@@ -430,7 +431,17 @@ __device__ __forceinline__ uint32_t addWord1(uint32_t base, uint32_t packed) {  
 // prefilter workgroups of the other streams live on the same CUs.  Removed variants, each measured no faster (DESIGN.md §4.1,
 // profiles/r05_experiments.txt): 16-lane groups of two segments per lane, one profile per task pair, two wavefronts per
 // workgroup sharing the profile, and quads of one query chained through one wavefront.
-template <int RT, bool SHARED>
+// START (start-position pass, with SHARED): the four tasks scan suffixes of one profile.  A start-position task is the reversed
+// query cut at qEnd against the reversed target cut at tEnd; its rows are rows j0 = qLen - 1 - qEnd .. qLen - 1 of the profile of
+// the WHOLE reversed query, which the wavefront builds once (the first task names it: qOff - j0 * qStep, n + j0 rows).  Task row
+// i sits in profile row j0 + i, so its chain begins in lane s = j0 / RT instead of lane 0:
+//   * what lane s - 1 hands to lane s (G, Ff) is zeroed, per 16-bit half (the two tasks of a register have their own s);
+//   * in lane s the profile bytes of the rows before j0 are replaced by the neutral byte: those rows stay 0 in H, E and Ff, so
+//     row j0 sees the zero boundary row of its own matrix;
+//   * lanes before s compute cells of no task: they are left out of the final reduce;
+//   * the reported row is the profile row - j0.  Columns, the row code and the tie rule are those of the other forms.
+// The target still enters at lane 0, so a task pays s extra ramp steps out of the 31 that every launch pays anyway.
+template <int RT, bool SHARED, bool START = false>
 __global__ void __launch_bounds__(64)
 sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint8_t *__restrict__ qRes,
                            const int8_t *__restrict__ qBias, const uint8_t *__restrict__ tRes, const int8_t *__restrict__ mat,
@@ -444,6 +455,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     constexpr int NT = 2 * NGRP;           // tasks per wavefront: a task pair per group of LW lanes
     constexpr uint32_t ROWB = PSTRIDE * 4; // bytes per residue row
     static_assert(22 * ROWB < 65536, "row offsets travel in 16 bits");
+    static_assert(SHARED || !START, "the start-row form has one profile per wavefront");
     __shared__ uint32_t prof[SHARED ? 1 : NT][22][PSTRIDE];
     __shared__ int8_t smat[441];
     for (int i = threadIdx.x; i < 441; i += 64) smat[i] = mat[i];
@@ -460,7 +472,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
         if (tid != 0xFFFFFFFFu) {
             tk[x] = tasks[tid];
         } else {
-            tk[x].n = 0; tk[x].tL = 0; tk[x].qOff = 0; tk[x].tOff = 0; tk[x].qStep = 1; tk[x].tStep = 1; tk[x].segLen = 1;
+            tk[x].n = 0; tk[x].tL = 0; tk[x].qOff = 0; tk[x].tOff = 0; tk[x].qStep = 1; tk[x].tStep = 1; tk[x].segLen = START ? 0 : 1;
             tk[x].slot = 0; tk[x].boundOff = 0;
         }
     }
@@ -491,6 +503,9 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
         // (SHARED: each group writes a share of the residue rows of the one profile; the first task of the wavefront is a real
         // one -- a run is padded at its end -- and names the query for all of them)
         const SwTask &T = SHARED ? tk[0] : (x ? B : A);
+        // (START: the whole query, of which the task scans the rows from j0 on)
+        const int64_t pOff = START ? (int64_t) T.qOff - (int64_t) T.segLen * T.qStep : (int64_t) T.qOff;
+        const int pN = START ? T.n + T.segLen : T.n;
         uint32_t *pw = &prof[SHARED ? 0 : 2 * grp + x][0][0] + l * WORDS;
 #pragma unroll
         for (int w = 0; w < WORDS; w++) {
@@ -500,12 +515,12 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
 #pragma unroll
             for (int b = 0; b < 4; b++) {
                 const int qi = q0 + 4 * w + b;
-                valid[b] = (4 * w + b < RT) && qi < T.n;
+                valid[b] = (4 * w + b < RT) && qi < pN;
                 res[b] = 20;
                 cb[b] = 0;
                 pidx[b] = 0;
                 if (valid[b]) {
-                    const int64_t idx = (int64_t) T.qOff + (int64_t) qi * T.qStep;
+                    const int64_t idx = pOff + (int64_t) qi * T.qStep;
                     res[b] = qRes[idx];
                     cb[b] = qBias[idx];
                     pidx[b] = idx * 21;
@@ -551,6 +566,20 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     }
     uint32_t outG = 0, outFf = 0, prevInG = 0;
     uint32_t bestcm = 0, bestcol = 0;
+    // START: the lane a task's chain begins in, the hand-off mask of this lane (a zero half where a chain begins here) and the
+    // profile bytes this lane keeps (all of them except, in the first lane of a chain, those of the rows before j0)
+    const int sA = START ? A.segLen / RT : 0, sB = START ? B.segLen / RT : 0;
+    uint32_t handMask = 0xFFFFFFFFu, keepA[WORDS], keepB[WORDS];
+    const uint32_t neutralWord = 0xC0C0C0C0u;
+    if (START) {
+        handMask = (l == sA ? 0u : 0x0000FFFFu) | (l == sB ? 0u : 0xFFFF0000u);
+#pragma unroll
+        for (int w = 0; w < WORDS; w++) {
+            const int dropA = min(max(A.segLen - sA * RT - 4 * w, 0), 4), dropB = min(max(B.segLen - sB * RT - 4 * w, 0), 4);
+            keepA[w] = l != sA ? 0xFFFFFFFFu : (dropA == 4 ? 0u : 0xFFFFFFFFu << (8 * dropA));
+            keepB[w] = l != sB ? 0xFFFFFFFFu : (dropB == 4 ? 0u : 0xFFFFFFFFu << (8 * dropB));
+        }
+    }
     constexpr uint32_t NEUT = (uint32_t) PK_NEUTRAL * ROWB;
     auto loadChunk = [&](int c0) -> uint32_t {   // row offsets (bytes) of the residues of one column per lane, task A | task B << 16
         const int col = c0 + l;   // lane l holds column c0 + l
@@ -598,13 +627,20 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
         }
         // ---- hand-off from lane l - 1 (nothing enters the first lane of a group)
         uint32_t inG = dppShr1(outG), inFf = dppShr1(outFf);
-        inG = writeLane<32>(0, inG);
-        inFf = writeLane<32>(0, inFf);
+        if (START) {   // (nothing enters the lane a chain begins in; what enters the lanes before it belongs to no task)
+            inG &= handMask;
+            inFf &= handMask;
+        } else {
+            inG = writeLane<32>(0, inG);
+            inFf = writeLane<32>(0, inFf);
+        }
         uint32_t h[RTP];
 #pragma unroll
         for (int w = 0; w < WORDS; w++) {
             const uint32_t d0 = (w == 0) ? prevInG : H[4 * w - 1];
-            addProfile4(pac[w], pbc[w], d0, H[4 * w], H[4 * w + 1], H[4 * w + 2], h[4 * w], h[4 * w + 1], h[4 * w + 2], h[4 * w + 3]);
+            const uint32_t qa = START ? bfiAsm(keepA[w], pac[w], neutralWord) : pac[w];
+            const uint32_t qb = START ? bfiAsm(keepB[w], pbc[w], neutralWord) : pbc[w];
+            addProfile4(qa, qb, d0, H[4 * w], H[4 * w + 1], H[4 * w + 2], h[4 * w], h[4 * w + 1], h[4 * w + 2], h[4 * w + 3]);
         }
         prevInG = inG;
         uint32_t Ff = inFf, cm = 0;
@@ -638,10 +674,12 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     unsigned long long keyA = 0, keyB = 0;
     {
         const uint32_t vA = (bestcm & 0xFFFFu) >> 5, vB = bestcm >> 21;
-        const uint32_t rowA = (uint32_t) (q0 + 31 - (int) (bestcm & 31u)), rowB = (uint32_t) (q0 + 31 - (int) ((bestcm >> 16) & 31u));
+        // (START: rows in the task's own coordinates; a best value > 0 lies in a row of the task, the rows before j0 hold zeros)
+        const uint32_t rowA = (uint32_t) (q0 + 31 - (int) (bestcm & 31u) - (START ? A.segLen : 0));
+        const uint32_t rowB = (uint32_t) (q0 + 31 - (int) ((bestcm >> 16) & 31u) - (START ? B.segLen : 0));
         const uint32_t colA = (bestcol & 0xFFFFu) - (uint32_t) l, colB = (bestcol >> 16) - (uint32_t) l;   // step - lane
-        if (vA > 0) keyA = ((unsigned long long) vA << 40) | ((unsigned long long) (0xFFFFFu - colA) << 20) | (unsigned long long) (0xFFFFFu - rowA);
-        if (vB > 0) keyB = ((unsigned long long) vB << 40) | ((unsigned long long) (0xFFFFFu - colB) << 20) | (unsigned long long) (0xFFFFFu - rowB);
+        if (vA > 0 && l >= sA) keyA = ((unsigned long long) vA << 40) | ((unsigned long long) (0xFFFFFu - colA) << 20) | (unsigned long long) (0xFFFFFu - rowA);
+        if (vB > 0 && l >= sB) keyB = ((unsigned long long) vB << 40) | ((unsigned long long) (0xFFFFFu - colB) << 20) | (unsigned long long) (0xFFFFFu - rowB);
     }
 #pragma unroll
     for (int off = LW / 2; off >= 1; off >>= 1) {

@@ -537,6 +537,19 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
                 if (c) sd_sw_set_narrow_final(c, 0);
         }
     } narrowFinalMode(s, !(getenv("SD_SW_NARROW_FINAL") && atoi(getenv("SD_SW_NARROW_FINAL")) == 0));
+    // The lanes' narrow start-position tasks of a query of 129 .. 768 residues scan suffixes of the query's one profile instead of
+    // building a profile each (sd_sw_set_shared_start; same records).  SD_SW_SHARED_START=0: off, as in a direct caller's context.
+    struct SharedStartMode {
+        sd_ctx *al[4];
+        explicit SharedStartMode(sd_search *s_, bool on) : al{s_->ctxAl, s_->ctxAl2, s_->ctxAlMore[0], s_->ctxAlMore[1]} {
+            for (sd_ctx *c : al)
+                if (c) sd_sw_set_shared_start(c, on ? 1 : 0);
+        }
+        ~SharedStartMode() {
+            for (sd_ctx *c : al)
+                if (c) sd_sw_set_shared_start(c, 0);
+        }
+    } sharedStartMode(s, !(getenv("SD_SW_SHARED_START") && atoi(getenv("SD_SW_SHARED_START")) == 0));
     std::vector<uint32_t> qSetSize(Q->nSets, 0);
     if (aggregate)
         for (uint32_t i = 0; i < Q->n; i++)
