@@ -299,6 +299,23 @@ int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask, double mas
                     const uint64_t *seqOffsets, uint32_t nSeq, const double *maskRatios, const int8_t *selfScore,
                     const int16_t *ext2Score, const uint16_t *ext2Index, const int16_t *ext3Score, const uint16_t *ext3Index,
                     sd_target **out, uint64_t *stats);
+/* The index of a PROFILE target DB, built on the device (the profile branch of IndexBuilder::fillDatabase,
+ * M/src/prefiltering/IndexBuilder.cpp:61-62,94-128,200-219, with IndexTable::addSimilarKmerCount / addSimilarSequence,
+ * IndexTable.h:97-130,302-345): the lists hold the *similar* k-mers of every profile window whose query letters hold no X -- the list
+ * KmerGenerator::generateKmerList gives for the window's per-position rows at kmerThr (the profile threshold,
+ * sd_host_profile_kmer_threshold) -- one entry per (k-mer, target) at the smallest position (IndexTable.h:52), lists in
+ * (target, position) order; nothing is masked (Prefiltering.cpp:172-174) and the lookup holds the consensus letters
+ * (IndexBuilder.cpp:125-127).  The five arrays are sd_host_map_profiles' outputs, posOffsets in positions (nSeq + 1).
+ * sd_prefilter_batch on such a target looks up every query window's own k-mer only (takeOnlyBestKmer, Prefiltering.cpp:176-179,
+ * QueryMatcher.cpp:249-252): par->kmerThr and qKmerBias are ignored, stats[4q] is the number of windows without X;
+ * sd_prefilter_profile_batch refuses it (Prefiltering.cpp:144-148).  The target holds no 2-mer / 3-mer tables; sd_target_download,
+ * sd_target_sample_check and sd_target_build_peak work on it.  The build's scratch is bounded by the pass size (SD_INDEX_PASS records,
+ * 2^30 by default), not by the record total.  k = 6 only (SD_EUNSUPPORTED otherwise, and for a window of more than 2^23 similar
+ * k-mers, KmerGenerator.h:45); a profile of more than 65 535 positions is SD_EINVAL.
+ * stats (nullable): [0] entries, [1] 0, [2] k-mer range passes, [3] k-mer records before the per-target dedupe. */
+int sd_target_build_profile(sd_ctx *ctx, int kmerSize, int kmerThr, const uint8_t *queryLetters, const uint8_t *consensus,
+                            const int16_t *sortedScore /* positions x 20 */, const uint8_t *sortedIndex /* positions x 20 */,
+                            const uint64_t *posOffsets, uint32_t nSeq, sd_target **out, uint64_t *stats);
 /* what a target holds on the device (any pointer may be NULL): masked residues, absolute list starts (tableSize + 1),
  * entries as (sequence id, position) */
 /* sampled check of an index too large to download: n (k-mer, sequence, position) triples = all entries of the nSample sequences

@@ -595,6 +595,31 @@ class Target:
         self.build_stats = dict(entries=int(stats[0]), masked_residues=int(stats[1]), passes=int(stats[2]), records=int(stats[3]))
         return self
 
+    @classmethod
+    def build_profile_on_device(cls, ctx, host, prof, k=6, kmer_thr=None):
+        """sd_target_build_profile: the similar-k-mer index of a profile target DB, built on the GPU.  prof: the dict
+        Host.map_profiles returns; kmer_thr: the profile threshold (default: Host.profile_kmer_threshold(4.0, k)).  Sequence
+        queries (api.prefilter) look up their own k-mers only against it; api.prefilter_profile refuses it."""
+        self = cls.__new__(cls)
+        self.ctx, self.host, self.index = ctx, host, None
+        if kmer_thr is None:
+            kmer_thr = host.profile_kmer_threshold(4.0, k)
+        letters = np.ascontiguousarray(prof['letters'], np.uint8)
+        consensus = np.ascontiguousarray(prof['consensus'], np.uint8)
+        score = np.ascontiguousarray(prof['sorted_score'], np.int16)
+        index = np.ascontiguousarray(prof['sorted_index'], np.uint8)
+        offsets = np.ascontiguousarray(prof['offsets'], np.uint64)
+        h = C.c_void_p()
+        stats = np.zeros(4, np.uint64)
+        _check(ctx.h, ctx.L.sd_target_build_profile(ctx.h, k, kmer_thr, ptr(letters), ptr(consensus), ptr(score), ptr(index), ptr(offsets),
+                                                    len(offsets) - 1, C.byref(h), ptr(stats)), 'sd_target_build_profile')
+        self.h = h
+        self.n = len(offsets) - 1
+        self.k = k
+        self.total = int(offsets[-1])
+        self.build_stats = dict(entries=int(stats[0]), masked_residues=int(stats[1]), passes=int(stats[2]), records=int(stats[3]))
+        return self
+
     def build_peak(self):
         """sd_target_build_peak: the device bytes sd_target_build held at the fullest point of its phases"""
         b = C.c_uint64()

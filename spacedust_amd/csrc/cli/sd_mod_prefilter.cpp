@@ -302,12 +302,17 @@ int prefilterModule(const Args &a) {
     if (host.open(threads) != SD_OK) return fail("sd_host_create failed");
     std::string err;
     DbPair db;
-    if (!db.open(a.pos[0], a.pos[1], host.h, true, true, &err)) return fail(err);
+    if (!db.open(a.pos[0], a.pos[1], host.h, true, false, &err)) return fail(err);
     const bool sameDb = db.sameDb;
     const SeqDb *const qdb = db.qdb, *const tdb = db.tdb.get();
+    // A profile target DB (clusterdb's <target>_clu_rep_profile): its index holds the similar k-mers of every profile window and the
+    // sequence queries look up their own k-mers only (Prefiltering.cpp:172-179, IndexBuilder.cpp:61-62).  Profile queries against it
+    // are an error in the reference (Prefiltering.cpp:144-148).
+    const bool profileTarget = tdb->profile;
+    if (profileTarget && qdb->profile) return fail("Query-profiles cannot be searched against a target-profile database!");
     lap.mark("load DBs");
-    info(a, "Query database size: %u type: %s\nTarget database size: %u type: Aminoacid\n", qdb->n,
-         qdb->profile ? "Profile" : "Aminoacid", tdb->n);
+    info(a, "Query database size: %u type: %s\nTarget database size: %u type: %s\n", qdb->n, qdb->profile ? "Profile" : "Aminoacid", tdb->n,
+         profileTarget ? "Profile" : "Aminoacid");
 
     CtxH ctx;
     int rc = ctx.open(deviceOf(a));
@@ -316,10 +321,24 @@ int prefilterModule(const Args &a) {
 
     // --split: one index for the whole target (today's path, below) or one per target split (prefilterTargetSplit)
     SplitPlan plan;
-    // (a workflow that holds this DB's index on this device has nothing left to decide)
-    if (int rcP = resolveSplit(a, tdb->rd, tdb->totalResidues(), qdb->n, ctx.c, !residentTargetOf(a.pos[1], deviceOf(a)).empty(), plan)) return rcP;
+    if (profileTarget) {
+        // searched unsplit: sd_target_footprint models one index record per residue and does not describe the similar-k-mer index, so
+        // --split 0 has nothing to decide with (it means 1 here) and a split the user asks for is refused
+        if (a.integer("--split", 0) > 1)
+            return fail("--split " + std::to_string(a.integer("--split", 0)) + ": a profile target database is searched unsplit (--split 0 or 1)");
+        plan.k = (int) a.integer("-k", 0);
+    } else if (int rcP = resolveSplit(a, tdb->rd, tdb->totalResidues(), qdb->n, ctx.c, !residentTargetOf(a.pos[1], deviceOf(a)).empty(), plan)) {
+        // (a workflow that holds this DB's index on this device has nothing left to decide)
+        return rcP;
+    }
     PrefSetup PS;
-    if (int rcS = prefilterSetupFromArgs(a, host.h, *tdb, qdb->profile, PS, plan.k)) return rcS;
+    // a profile on either side makes it a profile search: the profile threshold, -s / --k-score prof: (Prefiltering.cpp:196-202)
+    if (int rcS = prefilterSetupFromArgs(a, host.h, *tdb, qdb->profile || profileTarget, PS, plan.k)) return rcS;
+    if (profileTarget) {
+        if (PS.k != 6) return fail("-k " + std::to_string(PS.k) + ": the index of a profile target is built at k=6 only");
+        PS.indexThr = PS.kmerThr;   // the similar k-mers are generated at the threshold itself
+        PS.mask = false;            // --mask is ignored: nothing of a profile is masked (Prefiltering.cpp:172-174)
+    }
     if (plan.target) return prefilterTargetSplit(a, host.h, ctx.c, *qdb, *tdb, sameDb, PS, plan, lap);
     const int k = PS.k, kmerThr = PS.kmerThr, indexThr = PS.indexThr;   // (profile searches index every k-mer: indexThr 0)
     const bool mask = PS.mask;
@@ -332,8 +351,10 @@ int prefilterModule(const Args &a) {
     uint64_t nEntries = 0, maskedRes = 0;
     TargetH target;
     // a workflow's resident target of exactly this index (same DB, k, threshold, masking, device) is taken as it is
+    // (the two kinds of target are different indexes: "p" in the masking field marks the similar-k-mer index of a profile DB)
     char tkey[96];
-    snprintf(tkey, sizeof(tkey), "|%d|%d|%d|%.6f|%d", k, indexThr, mask ? 1 : 0, maskProb, deviceOf(a));
+    if (profileTarget) snprintf(tkey, sizeof(tkey), "|%d|%d|p|%.6f|%d", k, indexThr, 0.0, deviceOf(a));
+    else snprintf(tkey, sizeof(tkey), "|%d|%d|%d|%.6f|%d", k, indexThr, mask ? 1 : 0, maskProb, deviceOf(a));
     const std::string targetKey = a.pos[1] + tkey;
     if (resident().enabled && resident().targets.count(targetKey)) {
         const Resident::TargetEntry &te = resident().targets[targetKey];
@@ -343,11 +364,18 @@ int prefilterModule(const Args &a) {
         maskedRes = te.masked;
         info(a, "Target index resident from the previous module of this workflow\n");
     }
-    const int got = target.t ? 1 : loadTargetIndex(a.pos[1], k, indexThr, mask ? 1 : 0, tdb->n, tdb->totalResidues(), loaded, &why);
+    // (createindex does not index profile DBs: no TARGET.idx to look for)
+    const int got = target.t || profileTarget ? 1 : loadTargetIndex(a.pos[1], k, indexThr, mask ? 1 : 0, tdb->n, tdb->totalResidues(), loaded, &why);
     if (got < 0) return fail(why);
-    if (got != 0 && sddb::fileExists(a.pos[1] + ".idx.index")) info(a, "Index file not used: %s\n", why.c_str());
+    if (got != 0 && !profileTarget && sddb::fileExists(a.pos[1] + ".idx.index")) info(a, "Index file not used: %s\n", why.c_str());
     if (target.t) {
         // resident
+    } else if (profileTarget) {
+        uint64_t st[2] = {0, 0};
+        rc = sdBuildProfileTarget(ctx.c, k, kmerThr, tdb->residues.data(), tdb->consensus.data(), tdb->sortedScore.data(), tdb->sortedIndex.data(),
+                                  tdb->offsets.data(), tdb->n, &target.t, st);
+        if (rc != SD_OK) return failCtx(ctx.c, rc, "sd_target_build_profile");
+        nEntries = st[0];
     } else if (got == 0) {
         nEntries = loaded.nEntries;
         info(a, "Use index %s.idx\n", a.pos[1].c_str());

@@ -879,12 +879,21 @@ std::vector<std::string> withSplit(const Args &a, std::vector<std::string> pref)
     return pref;
 }
 
+// The chains below run `prefilter` in this process.  That module takes a profile target DB on its own (the similar-k-mer index,
+// sd_target_build_profile); the modules behind it in these chains do not, so the workflows keep refusing such a target up front, with
+// the words DbPair::open uses.
+int refuseProfileTarget(const std::string &T) {
+    if (sddb::baseType(sddb::readDbType(T)) == sddb::DBTYPE_HMM_PROFILE) return fail("profile target databases are not supported on this path");
+    return 0;
+}
+
 // `search --num-iterations N` (M/src/workflow/Search.cpp:476-518 builds the per-step parameter strings,
 // M/data/workflow/blastpgp.sh:52-140 runs them): iteration 0 with --realign and the profile E-value, prefilter results of
 // later iterations minus what is aligned already, the last alignment with the user's -e, merged into the result DB
 int iterativeSearch(const Args &a, const std::string &Q, const std::string &T, const std::string &result, const std::string &tmp,
                     const std::string *inMemoryTsv = nullptr) {
     const int numIt = (int) a.integer("--num-iterations", 1);
+    if (int rc = refuseProfileTarget(T)) return rc;
     if (!inMemoryTsv) mkdir(tmp.c_str(), 0777);
     const std::string eUser = a.str("-e", "0.001"), eProfile = a.str("--e-profile", "0.001");
     const std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
@@ -993,6 +1002,7 @@ int checkUngappedAlign(const Args &a) {
 
 int ungappedAlignSearch(const Args &a, const std::string &Q, const std::string &T, const std::string &result, const std::string &tmp) {
     if (int rc = checkUngappedAlign(a)) return rc;
+    if (int rc = refuseProfileTarget(T)) return rc;
     mkdir(tmp.c_str(), 0777);
     const std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
     const bool ungapped = a.integer("--prefilter-mode", 0) == 1;
@@ -1040,6 +1050,7 @@ int checkAltAli(const Args &a, bool withClusters) {
 }
 
 int altAliSearch(const Args &a, const std::string &Q, const std::string &T, const std::string &result, const std::string &tmp) {
+    if (int rc = refuseProfileTarget(T)) return rc;
     mkdir(tmp.c_str(), 0777);
     const std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
     const bool ungapped = a.integer("--prefilter-mode", 0) == 1;

@@ -92,8 +92,8 @@ int failNotComputed(uint64_t n, const char *whatBecameOfThem);
 // QueryMatcher::prefilterHitToBuffer (QueryMatcher.h:118-130): targetKey \t score \t diagonal \n
 void appendPrefRow(std::string &text, uint32_t key, int score, int diagonal);
 
-// A workflow's resident target index of `db` on `device` ("db|k|threshold|mask|prob|device" in resident().targets; one per DB and
-// device).  erase: it is destroyed and forgotten.  Returns its key, or an empty string when there is none.
+// A workflow's resident target index of `db` on `device` ("db|k|threshold|mask|prob|device" in resident().targets, with "p" in the
+// mask field for the similar-k-mer index of a profile DB; one per DB and device).  erase: it is destroyed and forgotten.  Returns its key, or an empty string when there is none.
 std::string residentTargetOf(const std::string &db, int device, bool erase = false);
 // the target sequences of `db` on the device: a workflow's resident set ("db|device" in resident().seqSets; created and registered on
 // first use), else the module's own

@@ -332,7 +332,16 @@ struct sd_target {
     uint16_t *dExt2Index = nullptr;
     std::vector<uint64_t> hSeqOff;
     uint64_t buildPeak = 0;          // sd_target_build_peak
+    // built by sd_target_build_profile from a profile DB: the lists hold the *similar* k-mers of every profile window, dMasked the consensus
+    // letters, and there are no 2-mer / 3-mer tables -- a sequence query looks up its own k-mers only (takeOnlyBestKmer, Prefiltering.cpp:176-179)
+    bool similar = false;
 };
+
+// scratch entries per partial k-mer list of the per-position products (profile_kmers_kernel in sd_prefilter.hip, ib_profile_records_kernel
+// in sd_index_build.hip): the wide grid's tier and the tier of the few positions that outgrow it (the reference's own buffer holds 2^23
+// k-mers, KmerGenerator.h:45)
+constexpr uint32_t PROFILE_PARTIAL_CAP = 1u << 16;
+constexpr uint32_t PROFILE_PARTIAL_CAP_BIG = 1u << 23;
 
 int sdFail(sd_ctx *ctx, int code, const char *fmt, ...);
 int sdBuildExt3Cum(sd_ctx *ctx, sd_target *t);   // sd_prefilter.hip; after dExt3Score is resident

@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 
 #pragma clang fp contract(off)   // every fused multiply-add below is written out: the host build's contractions, no others
 
@@ -386,6 +387,186 @@ ib_records_kernel(const uint8_t *__restrict__ masked, const uint64_t *__restrict
     if (MODE == 1 && lane == 0 && s0 < nSeq) waveCount[wave] = count;
 }
 
+// ---- records of a *profile* target (sd_target_build_profile): every window of a profile contributes its whole similar-k-mer list
+// (IndexTable::addSimilarKmerCount / addSimilarSequence, IndexTable.h:97-130,302-345), which is KmerGenerator::generateKmerList over the
+// window's per-position rows of 20 (score, amino acid) pairs (setDivideStrategy(profile_matrix), KmerGenerator.cpp:30-39,143-165).  A
+// wavefront per window runs the k - 1 array products stage by stage exactly like profile_kmers_kernel (sd_prefilter.hip) does for a
+// profile *query*: the partial list lives in a per-wavefront scratch buffer, lanes take parents, each appends its run of children after
+// an exclusive scan of the run lengths; cutoffs are the reference's `short` expressions.  What differs is the last product: its
+// k-mers become index records (k-mer - lo, target << 16 | position) of the pass's k-mer range [lo, hi), compacted across the lanes.
+// A window's k-mers are distinct (one amino acid per seed position each), and the windows write at bases scanned in (target, position)
+// order, so the records of a pass leave in ascending (target, position) order: the stable sort by k-mer keeps it, and the first
+// record of a (k-mer, target) run is the one at the smallest position -- IndexEntryLocalTmp::comapreByIdAndPos (IndexTable.h:52).
+//   MODE 0: the list length of every window (winCount), its scratch tier (big), the histogram over IB_COARSE_BINS k-mer ranges
+//   MODE 1: the records of [lo, hi) per window (winCount);  MODE 2: the records themselves at recBase[window] + ...
+// Two tiers of scratch as in profile_kmers_kernel: PROFILE_PARTIAL_CAP entries per list on the wide grid, PROFILE_PARTIAL_CAP_BIG for
+// the windows MODE 0 flags.  errWin[0]: the first window whose list passes 2^23 k-mers (KmerGenerator.h:45); errWin[1]: the number of
+// windows flagged for the big tier.
+constexpr uint32_t IP_GRID = 1024, IP_GRID_BIG = 16;
+constexpr uint32_t IP_LIST_MAX = 1u << 23;
+__constant__ uint8_t c_ipSeed6[6] = {0, 1, 3, 5, 8, 9};   // spaced seed 1101010011 (M/src/commons/Sequence.h:23)
+
+template <int MODE>
+__global__ void __launch_bounds__(64)
+ib_profile_records_kernel(uint64_t nWin, const uint64_t *__restrict__ winBase /* first window of every target, nSeq + 1 */, uint32_t nSeq,
+                          const uint8_t *__restrict__ letters, const uint64_t *__restrict__ posOff, const int16_t *__restrict__ sortedScore,
+                          const uint8_t *__restrict__ sortedIndex, int kmerThr, uint2 *__restrict__ scratch, uint32_t cap,
+                          uint8_t *__restrict__ big, int bigTier, uint32_t binWidth, unsigned long long *__restrict__ coarse,
+                          unsigned long long *__restrict__ errWin, uint32_t lo, uint32_t hi, uint32_t *__restrict__ winCount,
+                          const uint64_t *__restrict__ recBase, uint32_t *__restrict__ keys, uint64_t *__restrict__ vals) {
+    constexpr int K = 6;
+    __shared__ int16_t rowS[K][20];
+    __shared__ uint8_t rowI[K][20];
+    __shared__ uint32_t hist[MODE == 0 ? IB_COARSE_BINS : 1];
+    const int lane = threadIdx.x;
+    if (MODE == 0)
+        for (uint32_t i = lane; i < IB_COARSE_BINS; i += 64) hist[i] = 0;
+    uint32_t histHeld = 0;   // records in hist (MODE 0): flushed before a 32-bit bin could wrap
+    auto flush = [&]() {
+        __syncthreads();
+        for (uint32_t i = lane; i < IB_COARSE_BINS; i += 64) {
+            if (hist[i]) atomicAdd(&coarse[i], (unsigned long long) hist[i]);
+            hist[i] = 0;
+        }
+        __syncthreads();
+        histHeld = 0;
+    };
+    uint2 *listA = scratch + (size_t) blockIdx.x * 2 * cap;
+    uint2 *listB = listA + cap;
+    const int thr = kmerThr > 0 ? kmerThr : 0;   // no composition bias: the generator's threshold is kmerThr as it is (IndexBuilder.cpp:96)
+    for (uint64_t p = blockIdx.x; p < nWin; p += gridDim.x) {
+        if ((big[p] != 0) != (bigTier != 0)) continue;   // block-uniform
+        uint32_t tl = 0, th = nSeq;   // last target with winBase[target] <= p
+        while (th - tl > 1) {
+            const uint32_t mid = (tl + th) >> 1;
+            if (winBase[mid] <= p) tl = mid;
+            else th = mid;
+        }
+        const uint32_t q = tl;
+        const int i = (int) (p - winBase[tl]);
+        const uint64_t r0 = posOff[q] + (uint64_t) i;
+        bool hasX = false;
+        for (int x = 0; x < K; x++) hasX |= letters[r0 + c_ipSeed6[x]] >= 20;   // kmerContainsX on the query letters (Sequence.h:397-403)
+        __syncthreads();   // the previous window's rows are no longer read
+        for (int x = lane; x < K * 20; x += 64) {
+            const int sIdx = x / 20, e = x % 20;
+            rowS[sIdx][e] = sortedScore[(r0 + c_ipSeed6[sIdx]) * 20 + e];
+            rowI[sIdx][e] = sortedIndex[(r0 + c_ipSeed6[sIdx]) * 20 + e];
+        }
+        __syncthreads();
+        uint32_t totalOut = 0;   // MODE 0: the list length; MODE 1 / 2: its records in [lo, hi)
+        if (!hasX) {
+            int rest[K];
+            rest[K - 1] = 0;
+            for (int x = K - 1; x >= 1; x--) rest[x - 1] = (int) (short) ((int) rowS[x][0] + rest[x]);
+            const int cutoff1 = (int) (short) (thr - rest[0]);
+            uint32_t nA = 0;
+            while (nA < 20 && (int) rowS[0][nA] >= cutoff1) nA++;
+            if ((uint32_t) lane < nA) listA[lane] = make_uint2((uint32_t) (int) rowS[0][lane], (uint32_t) rowI[0][lane]);
+            uint32_t mult = 1;
+            const uint64_t base = MODE == 2 ? recBase[p] : 0;
+            const uint64_t val = ((uint64_t) q << 16) | (uint64_t) i;
+            bool overflow = false;
+            for (int st = 0; st + 1 < K && !overflow; st++) {
+                mult *= 20u;
+                const bool last = st + 2 == K;
+                const int16_t *rs = rowS[st + 1];
+                const uint8_t *ri = rowI[st + 1];
+                const int restNext = rest[st + 1];
+                uint32_t nB = 0;
+                __threadfence_block();
+                for (uint32_t c0 = 0; c0 < nA; c0 += 64) {
+                    const uint32_t e = c0 + lane;
+                    int si = 0;
+                    uint32_t ki = 0, c = 0;
+                    if (e < nA) {
+                        // agent-scope loads: the entry was written by another lane of this wavefront a stage ago and the
+                        // vector L1 may still hold the line from the buffer's previous use
+                        const uint32_t px = __hip_atomic_load(&listA[e].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        ki = __hip_atomic_load(&listA[e].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        si = (int) (short) px;
+                        const int cutoff2 = (int) (short) (thr - si - restNext);
+                        while (c < 20 && (int) rs[c] >= cutoff2) c++;
+                    }
+                    if (!last) {
+                        uint32_t incl = c;
+#pragma unroll
+                        for (int off = 1; off < 64; off <<= 1) {
+                            const uint32_t o = __shfl_up(incl, off, 64);
+                            if (lane >= off) incl += o;
+                        }
+                        const uint32_t excl = incl - c;
+                        const uint32_t chunkTotal = __shfl(incl, 63, 64);
+                        if (nB + chunkTotal > cap) {
+                            overflow = true;
+                            break;
+                        }
+                        for (uint32_t j = 0; j < c; j++)
+                            listB[nB + excl + j] = make_uint2((uint32_t) (int) (short) (si + (int) rs[j]), ki + (uint32_t) ri[j] * mult);
+                        nB += chunkTotal;
+                    } else if (MODE == 0) {
+                        for (uint32_t j = 0; j < c; j++) atomicAdd(&hist[(ki + (uint32_t) ri[j] * mult) / binWidth], 1u);
+                        uint32_t sum = c;
+#pragma unroll
+                        for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+                        nB += sum;
+                    } else {
+                        uint32_t m = 0;   // this lane's children in [lo, hi)
+                        for (uint32_t j = 0; j < c; j++) {
+                            const uint32_t kmer = ki + (uint32_t) ri[j] * mult;
+                            m += (kmer >= lo && kmer < hi) ? 1u : 0u;
+                        }
+                        uint32_t incl = m;
+#pragma unroll
+                        for (int off = 1; off < 64; off <<= 1) {
+                            const uint32_t o = __shfl_up(incl, off, 64);
+                            if (lane >= off) incl += o;
+                        }
+                        if (MODE == 2 && m) {
+                            uint64_t w = base + nB + (incl - m);
+                            for (uint32_t j = 0; j < c; j++) {
+                                const uint32_t kmer = ki + (uint32_t) ri[j] * mult;
+                                if (kmer >= lo && kmer < hi) {
+                                    keys[w] = kmer - lo;
+                                    vals[w] = val;
+                                    w++;
+                                }
+                            }
+                        }
+                        nB += __shfl(incl, 63, 64);
+                    }
+                }
+                if (last) {
+                    totalOut = nB;
+                } else {
+                    uint2 *t = listA;
+                    listA = listB;
+                    listB = t;
+                    nA = nB;
+                }
+            }
+            if (MODE == 0) {
+                // (a partial list is never longer than the final one: an overflow of the big tier is a list beyond IP_LIST_MAX as well)
+                if (overflow && !bigTier) {
+                    if (lane == 0) {   // redone by the narrow grid; nothing of this window is in the histogram yet
+                        big[p] = 1;
+                        atomicAdd(&errWin[1], 1ull);
+                    }
+                } else if (overflow || totalOut > IP_LIST_MAX) {
+                    if (lane == 0) atomicMin(errWin, (unsigned long long) p);
+                }
+                if (overflow) totalOut = 0;
+            }
+        }
+        if (MODE != 2 && lane == 0) winCount[p] = totalOut;   // (0 for a window that moves to the big tier: its launch follows and writes it)
+        if (MODE == 0) {
+            histHeld += totalOut;
+            if (histHeld >= (1u << 31) - IP_LIST_MAX) flush();
+        }
+    }
+    if (MODE == 0) flush();
+}
+
 // ---- exclusive scan of up to 2^32 32-bit counts into 64-bit sums (three launches: tile sums, tile bases, apply)
 constexpr int IS_TILE = 4096, IS_NT = 256;
 __global__ void __launch_bounds__(IS_NT) is_tile_sums(const uint32_t *__restrict__ in, uint64_t n, uint64_t *__restrict__ tileSum) {
@@ -545,6 +726,138 @@ double firstRepeatOffsetProb(double probMult, int maxRepeatOffset) {
     return 1.0 / maxRepeatOffset;
 }
 
+// sd_target_build_peak: the free device memory is read where a phase holds the most
+struct PeakNote {
+    sd_target *t;
+    size_t freeAtStart = 0;
+    explicit PeakNote(sd_target *target) : t(target) {
+        size_t totalDev = 0;
+        (void) hipMemGetInfo(&freeAtStart, &totalDev);
+    }
+    void operator()() const {
+        size_t f = 0, tot = 0;
+        if (hipMemGetInfo(&f, &tot) == hipSuccess && f < freeAtStart) t->buildPeak = std::max<uint64_t>(t->buildPeak, freeAtStart - f);
+    }
+};
+
+// records per pass: bounded by the sort's 32-bit item count and by SD_INDEX_PASS (tests: many small passes)
+int ibPassCap(sd_ctx *ctx, const std::vector<unsigned long long> &coarse, uint64_t &cap, uint64_t &nRecords) {
+    uint64_t biggestBin = 0;
+    nRecords = 0;
+    for (unsigned long long c : coarse) {
+        nRecords += c;
+        biggestBin = std::max<uint64_t>(biggestBin, c);
+    }
+    cap = 1ull << 30;
+    if (getenv("SD_INDEX_PASS")) cap = std::max<uint64_t>(1, strtoull(getenv("SD_INDEX_PASS"), nullptr, 10));
+    cap = std::max(cap, biggestBin);
+    if (cap >= (1ull << 31))
+        return sdFail(ctx, SD_EUNSUPPORTED, "one of the %u k-mer ranges holds %llu index records (limit 2^31 per sort)", IB_COARSE_BINS,
+                      (unsigned long long) biggestBin);
+    return SD_OK;
+}
+
+// The passes both builders share: the k-mer space is cut into ranges of at most `cap` records along the coarse histogram; per range
+// countFn(lo, hi, slotCount) counts the records of [lo, hi) per slot (a slot: what one wavefront of the generator writes in order -- 16
+// sequences in sd_target_build, one profile window in sd_target_build_profile), emitFn(lo, hi, slotBase, keys, vals) writes them at the
+// scanned bases, in ascending (target, position) order over the whole pass; they are sorted by k-mer (stable), the first record of every
+// (k-mer, target) run is appended to t->dEntries and counted in t->dOffsets.  The scratch is bounded by cap, not by nRecords.
+template <typename CountFn, typename EmitFn>
+int ibPasses(sd_ctx *ctx, sd_target *t, const char *who, const std::vector<unsigned long long> &coarse, uint32_t binWidth, uint64_t nRecords,
+             uint64_t cap, uint32_t nSlots, CountFn countFn, EmitFn emitFn, const PeakNote &notePeak, uint64_t &nEntries, uint64_t &nPasses) {
+    const uint64_t bufN = std::min<uint64_t>(cap, nRecords);
+    Scoped<uint32_t> k0, k1, dWaveCount, dTileCount;
+    Scoped<uint64_t> v0, v1, dWaveBase, dTileBase, dTot;
+    Scoped<uint8_t> dTmp;
+    SD_HIP(ctx, k0.alloc(bufN));
+    SD_HIP(ctx, k1.alloc(bufN));
+    SD_HIP(ctx, v0.alloc(bufN));
+    SD_HIP(ctx, v1.alloc(bufN));
+    SD_HIP(ctx, dWaveCount.alloc(nSlots));
+    SD_HIP(ctx, dWaveBase.alloc(nSlots));
+    SD_HIP(ctx, dTileCount.alloc((bufN + IK_TILE - 1) / IK_TILE));
+    SD_HIP(ctx, dTileBase.alloc((bufN + IK_TILE - 1) / IK_TILE));
+    SD_HIP(ctx, dTot.alloc(1));
+    SD_HIP(ctx, dTmp.alloc(sdRadixSortCountsBytes()));   // the radix sort's count matrix (sd_scan_sort.h)
+    notePeak();
+    uint32_t bin = 0;
+    while (bin < IB_COARSE_BINS) {
+        uint32_t e = bin;
+        uint64_t n = 0;
+        while (e < IB_COARSE_BINS && n + coarse[e] <= cap) n += coarse[e++];
+        const uint32_t lo = bin * binWidth;
+        const uint32_t hi = (uint32_t) std::min<uint64_t>((uint64_t) e * binWidth, t->tableSize);
+        bin = e;
+        if (n == 0) continue;
+        nPasses++;
+        ProfScope ps(ctx, "index_pass");
+        int rc = countFn(lo, hi, dWaveCount.p);
+        if (rc != SD_OK) return rc;
+        SD_HIP(ctx, hipGetLastError());
+        rc = scan32to64(ctx, dWaveCount.p, nSlots, dWaveBase.p, dTot.p);
+        if (rc != SD_OK) return rc;
+        uint64_t got = 0;
+        SD_HIP(ctx, hipMemcpy(&got, dTot.p, sizeof(got), hipMemcpyDeviceToHost));
+        if (got != n) return sdFail(ctx, SD_EHIP, "%s: k-mer range [%u, %u) holds %llu records, the histogram said %llu", who, lo, hi,
+                                    (unsigned long long) got, (unsigned long long) n);
+        rc = emitFn(lo, hi, (const uint64_t *) dWaveBase.p, k0.p, v0.p);
+        if (rc != SD_OK) return rc;
+        SD_HIP(ctx, hipGetLastError());
+        int bits = 1;
+        while (bits < 32 && (1ull << bits) < (uint64_t) (hi - lo)) bits++;
+        // stable LSD radix sort of (k-mer, record) pairs by the range's k-mer bits (sd_scan_sort.h, 8 bits per pass), ping-pong between
+        // the two buffer pairs: with an odd number of passes the input pair doubles as the scratch pair (it is read by the first pass
+        // only and first written by the second) and the result lands in (k1, v1), with an even number in (k0, v0)
+        const int passes = std::max(1, (bits + 7) / 8);
+        const uint32_t *sk;
+        const uint64_t *sv;
+        if (passes & 1) {
+            SD_HIP(ctx, sdRadixSortPairs<uint64_t>(ctx->stream, k0.p, v0.p, k1.p, v1.p, k0.p, v0.p, (uint32_t) n, 0, bits, (uint32_t *) dTmp.p));
+            sk = k1.p;
+            sv = v1.p;
+        } else {
+            SD_HIP(ctx, sdRadixSortPairs<uint64_t>(ctx->stream, k0.p, v0.p, k0.p, v0.p, k1.p, v1.p, (uint32_t) n, 0, bits, (uint32_t *) dTmp.p));
+            sk = k0.p;
+            sv = v0.p;
+        }
+        const unsigned tiles = (unsigned) ((n + IK_TILE - 1) / IK_TILE);
+        hipLaunchKernelGGL(ib_keep_count, dim3(tiles), dim3(IK_NT), 0, ctx->stream, sk, sv, n, dTileCount.p);
+        SD_HIP(ctx, hipGetLastError());
+        rc = scan32to64(ctx, dTileCount.p, tiles, dTileBase.p, dTot.p);
+        if (rc != SD_OK) return rc;
+        uint64_t kept = 0;
+        SD_HIP(ctx, hipMemcpy(&kept, dTot.p, sizeof(kept), hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(ib_place, dim3(tiles), dim3(IK_NT), 0, ctx->stream, sk, sv, n, (const uint64_t *) dTileBase.p, nEntries, lo,
+                           t->dEntries, t->dOffsets);
+        SD_HIP(ctx, hipGetLastError());
+        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        nEntries += kept;
+    }
+    return SD_OK;
+}
+
+// list starts from the per-k-mer counts the passes left in t->dOffsets
+int ibListStarts(sd_ctx *ctx, sd_target *t, const char *who, uint64_t nEntries, const PeakNote &notePeak) {
+    Scoped<uint64_t> dStart, dTot;
+    SD_HIP(ctx, dStart.alloc(t->tableSize + 1));
+    SD_HIP(ctx, dTot.alloc(1));
+    notePeak();
+    int rc = scan32to64(ctx, t->dOffsets, t->tableSize + 1, dStart.p, dTot.p);
+    if (rc != SD_OK) return rc;
+    uint64_t sum = 0;
+    SD_HIP(ctx, hipMemcpy(&sum, dTot.p, sizeof(sum), hipMemcpyDeviceToHost));
+    if (sum != nEntries) return sdFail(ctx, SD_EHIP, "%s: %llu entries placed, %llu counted", who, (unsigned long long) nEntries,
+                                       (unsigned long long) sum);
+    const int wide = nEntries > 0xFFFFFFFFull || getenv("SD_INDEX_WIDE") != nullptr;
+    if (wide) SD_HIP(ctx, hipMalloc((void **) &t->dBlockBase, (((t->tableSize + 2) >> 16) + 1) * sizeof(uint64_t)));
+    if (wide) SD_HIP(ctx, hipMemsetAsync(t->dBlockBase, 0, (((t->tableSize + 2) >> 16) + 1) * sizeof(uint64_t), ctx->stream));
+    hipLaunchKernelGGL(ib_offsets, dim3((unsigned) ((t->tableSize + 1 + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *) dStart.p,
+                       t->tableSize + 1, wide, t->dOffsets, t->dBlockBase);
+    SD_HIP(ctx, hipGetLastError());
+    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SD_OK;
+}
+
 }  // namespace
 
 extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask, double maskProb, const uint8_t *residues,
@@ -578,13 +891,7 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
     t->hSeqOff.assign(seqOffsets, seqOffsets + nSeq + 1);
     const uint64_t total = seqOffsets[nSeq];
     const int span = kmerSize == 6 ? 10 : 11;
-    // sd_target_build_peak: the free device memory is read where a phase holds the most
-    size_t freeAtStart = 0, totalDev = 0;
-    (void) hipMemGetInfo(&freeAtStart, &totalDev);
-    auto notePeak = [&]() {
-        size_t f = 0, tot = 0;
-        if (hipMemGetInfo(&f, &tot) == hipSuccess && f < freeAtStart) t->buildPeak = std::max<uint64_t>(t->buildPeak, freeAtStart - f);
-    };
+    const PeakNote notePeak(t);
     {
         static const uint8_t s6[8] = {0, 1, 3, 5, 8, 9, 0, 0}, s7[8] = {0, 1, 3, 5, 6, 9, 10, 0};
         uint32_t pw[8] = {0};
@@ -731,128 +1038,192 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
         SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
         SD_HIP(ctx, hipMemcpy(coarse.data(), dCoarse.p, IB_COARSE_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
-    uint64_t nRecords = 0, biggestBin = 0;
-    for (unsigned long long c : coarse) {
-        nRecords += c;
-        biggestBin = std::max<uint64_t>(biggestBin, c);
-    }
-    // records per pass: bounded by the sort's 32-bit item count and by SD_INDEX_PASS (tests: many small passes)
-    uint64_t cap = 1ull << 30;
-    if (getenv("SD_INDEX_PASS")) cap = std::max<uint64_t>(1, strtoull(getenv("SD_INDEX_PASS"), nullptr, 10));
-    cap = std::max(cap, biggestBin);
-    if (cap >= (1ull << 31))
-        return sdFail(ctx, SD_EUNSUPPORTED, "one of the %u k-mer ranges holds %llu index records (limit 2^31 per sort)", IB_COARSE_BINS,
-                      (unsigned long long) biggestBin);
+    uint64_t nRecords = 0, cap = 0;
+    if (int rcCap = ibPassCap(ctx, coarse, cap, nRecords)) return rcCap;
     SD_HIP(ctx, hipMalloc((void **) &t->dEntries, (std::max<uint64_t>(nRecords, 1) + 8) * sizeof(uint2)));
     SD_HIP(ctx, hipMalloc((void **) &t->dOffsets, (t->tableSize + 1) * sizeof(uint32_t) + 64));
     SD_HIP(ctx, hipMemsetAsync(t->dOffsets, 0, (t->tableSize + 1) * sizeof(uint32_t), ctx->stream));   // counts first
     uint64_t nEntries = 0, nPasses = 0;
     if (nRecords) {
-        const uint64_t bufN = std::min<uint64_t>(cap, nRecords);
-        Scoped<uint32_t> k0, k1, dWaveCount, dTileCount;
-        Scoped<uint64_t> v0, v1, dWaveBase, dTileBase, dTot;
-        Scoped<uint8_t> dTmp;
-        SD_HIP(ctx, k0.alloc(bufN));
-        SD_HIP(ctx, k1.alloc(bufN));
-        SD_HIP(ctx, v0.alloc(bufN));
-        SD_HIP(ctx, v1.alloc(bufN));
-        SD_HIP(ctx, dWaveCount.alloc(nWavesR));
-        SD_HIP(ctx, dWaveBase.alloc(nWavesR));
-        SD_HIP(ctx, dTileCount.alloc((bufN + IK_TILE - 1) / IK_TILE));
-        SD_HIP(ctx, dTileBase.alloc((bufN + IK_TILE - 1) / IK_TILE));
-        SD_HIP(ctx, dTot.alloc(1));
-        SD_HIP(ctx, dTmp.alloc(sdRadixSortCountsBytes()));   // the radix sort's count matrix (sd_scan_sort.h)
-        notePeak();
-        uint32_t bin = 0;
-        while (bin < IB_COARSE_BINS) {
-            uint32_t e = bin;
-            uint64_t n = 0;
-            while (e < IB_COARSE_BINS && n + coarse[e] <= cap) n += coarse[e++];
-            const uint32_t lo = bin * binWidth;
-            const uint32_t hi = (uint32_t) std::min<uint64_t>((uint64_t) e * binWidth, t->tableSize);
-            bin = e;
-            if (n == 0) continue;
-            nPasses++;
-            ProfScope ps(ctx, "index_pass");
+        auto countFn = [&](uint32_t lo, uint32_t hi, uint32_t *waveCount) -> int {
             if (kmerSize == 6)
                 hipLaunchKernelGGL((ib_records_kernel<6, 1>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
                                    (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, (unsigned long long *) nullptr, lo, hi,
-                                   dWaveCount.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
+                                   waveCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
             else
                 hipLaunchKernelGGL((ib_records_kernel<7, 1>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
                                    (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, (unsigned long long *) nullptr, lo, hi,
-                                   dWaveCount.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-            SD_HIP(ctx, hipGetLastError());
-            int rc = scan32to64(ctx, dWaveCount.p, nWavesR, dWaveBase.p, dTot.p);
-            if (rc != SD_OK) return rc;
-            uint64_t got = 0;
-            SD_HIP(ctx, hipMemcpy(&got, dTot.p, sizeof(got), hipMemcpyDeviceToHost));
-            if (got != n) return sdFail(ctx, SD_EHIP, "sd_target_build: k-mer range [%u, %u) holds %llu records, the histogram said %llu", lo, hi,
-                                        (unsigned long long) got, (unsigned long long) n);
+                                   waveCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
+            return SD_OK;
+        };
+        auto emitFn = [&](uint32_t lo, uint32_t hi, const uint64_t *waveBase, uint32_t *keys, uint64_t *vals) -> int {
             if (kmerSize == 6)
                 hipLaunchKernelGGL((ib_records_kernel<6, 2>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
                                    (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, (unsigned long long *) nullptr, lo, hi,
-                                   (uint32_t *) nullptr, (const uint64_t *) dWaveBase.p, k0.p, v0.p);
+                                   (uint32_t *) nullptr, waveBase, keys, vals);
             else
                 hipLaunchKernelGGL((ib_records_kernel<7, 2>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
                                    (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, (unsigned long long *) nullptr, lo, hi,
-                                   (uint32_t *) nullptr, (const uint64_t *) dWaveBase.p, k0.p, v0.p);
-            SD_HIP(ctx, hipGetLastError());
-            int bits = 1;
-            while (bits < 32 && (1ull << bits) < (uint64_t) (hi - lo)) bits++;
-            // stable LSD radix sort of (k-mer, record) pairs by the range's k-mer bits (sd_scan_sort.h, 8 bits per pass), ping-pong between
-            // the two buffer pairs: with an odd number of passes the input pair doubles as the scratch pair (it is read by the first pass
-            // only and first written by the second) and the result lands in (k1, v1), with an even number in (k0, v0)
-            const int passes = std::max(1, (bits + 7) / 8);
-            const uint32_t *sk;
-            const uint64_t *sv;
-            if (passes & 1) {
-                SD_HIP(ctx, sdRadixSortPairs<uint64_t>(ctx->stream, k0.p, v0.p, k1.p, v1.p, k0.p, v0.p, (uint32_t) n, 0, bits, (uint32_t *) dTmp.p));
-                sk = k1.p;
-                sv = v1.p;
-            } else {
-                SD_HIP(ctx, sdRadixSortPairs<uint64_t>(ctx->stream, k0.p, v0.p, k0.p, v0.p, k1.p, v1.p, (uint32_t) n, 0, bits, (uint32_t *) dTmp.p));
-                sk = k0.p;
-                sv = v0.p;
-            }
-            const unsigned tiles = (unsigned) ((n + IK_TILE - 1) / IK_TILE);
-            hipLaunchKernelGGL(ib_keep_count, dim3(tiles), dim3(IK_NT), 0, ctx->stream, sk, sv, n, dTileCount.p);
-            SD_HIP(ctx, hipGetLastError());
-            rc = scan32to64(ctx, dTileCount.p, tiles, dTileBase.p, dTot.p);
-            if (rc != SD_OK) return rc;
-            uint64_t kept = 0;
-            SD_HIP(ctx, hipMemcpy(&kept, dTot.p, sizeof(kept), hipMemcpyDeviceToHost));
-            hipLaunchKernelGGL(ib_place, dim3(tiles), dim3(IK_NT), 0, ctx->stream, sk, sv, n, (const uint64_t *) dTileBase.p, nEntries, lo,
-                               t->dEntries, t->dOffsets);
-            SD_HIP(ctx, hipGetLastError());
-            SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            nEntries += kept;
-        }
+                                   (uint32_t *) nullptr, waveBase, keys, vals);
+            return SD_OK;
+        };
+        if (int rcP = ibPasses(ctx, t, "sd_target_build", coarse, binWidth, nRecords, cap, nWavesR, countFn, emitFn, notePeak, nEntries, nPasses))
+            return rcP;
     }
     // ---------------- 3. list starts
-    {
-        Scoped<uint64_t> dStart, dTot;
-        SD_HIP(ctx, dStart.alloc(t->tableSize + 1));
-        SD_HIP(ctx, dTot.alloc(1));
-        notePeak();
-        int rc = scan32to64(ctx, t->dOffsets, t->tableSize + 1, dStart.p, dTot.p);
-        if (rc != SD_OK) return rc;
-        uint64_t sum = 0;
-        SD_HIP(ctx, hipMemcpy(&sum, dTot.p, sizeof(sum), hipMemcpyDeviceToHost));
-        if (sum != nEntries) return sdFail(ctx, SD_EHIP, "sd_target_build: %llu entries placed, %llu counted", (unsigned long long) nEntries,
-                                           (unsigned long long) sum);
-        const int wide = nEntries > 0xFFFFFFFFull || getenv("SD_INDEX_WIDE") != nullptr;
-        if (wide) SD_HIP(ctx, hipMalloc((void **) &t->dBlockBase, (((t->tableSize + 2) >> 16) + 1) * sizeof(uint64_t)));
-        if (wide) SD_HIP(ctx, hipMemsetAsync(t->dBlockBase, 0, (((t->tableSize + 2) >> 16) + 1) * sizeof(uint64_t), ctx->stream));
-        hipLaunchKernelGGL(ib_offsets, dim3((unsigned) ((t->tableSize + 1 + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *) dStart.p,
-                           t->tableSize + 1, wide, t->dOffsets, t->dBlockBase);
-        SD_HIP(ctx, hipGetLastError());
-        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (int rcL = ibListStarts(ctx, t, "sd_target_build", nEntries, notePeak)) return rcL;
     t->nEntries = nEntries;
     if (stats) {
         stats[0] = nEntries;
         stats[1] = nMaskedResidues;
+        stats[2] = nPasses;
+        stats[3] = nRecords;
+    }
+    guard.t = nullptr;
+    *out = t;
+    return SD_OK;
+}
+
+// The index of a *profile* target DB (the profile branch of IndexBuilder::fillDatabase, IndexBuilder.cpp:61-62,94-128,200-219): the lists
+// hold the similar k-mers of every profile window at threshold kmerThr, one entry per (k-mer, target) at the smallest position, in
+// (target, position) order; nothing is masked (Prefiltering.cpp:172-174) and the lookup holds the consensus letters
+// (IndexBuilder.cpp:125-127).  The arrays are Sequence::mapProfile's (sd_host_map_profiles).  A window yields hundreds to tens of
+// thousands of records, so nothing here is sized by the record total except the entry array itself: the generator runs once for the
+// histogram and list lengths and, when the records do not fit one pass (SD_INDEX_PASS, 2^30), once to count and once to write per pass.
+extern "C" int sd_target_build_profile(sd_ctx *ctx, int kmerSize, int kmerThr, const uint8_t *queryLetters, const uint8_t *consensus,
+                                       const int16_t *sortedScore, const uint8_t *sortedIndex, const uint64_t *posOffsets, uint32_t nSeq,
+                                       sd_target **out, uint64_t *stats) {
+    if (!ctx || !out || !queryLetters || !consensus || !sortedScore || !sortedIndex || !posOffsets) return SD_EINVAL;
+    if (kmerSize == 7)
+        return sdFail(ctx, SD_EUNSUPPORTED, "k=7: the index of a profile target is built at k=6 only (no k=7 golden index of the reference to test against)");
+    if (kmerSize != 6) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the index of a profile target is built at k=6", kmerSize);
+    const int span = 10;
+    std::vector<uint64_t> winBase((size_t) nSeq + 1, 0);
+    for (uint32_t i = 0; i < nSeq; i++) {
+        const uint64_t len = posOffsets[i + 1] - posOffsets[i];
+        if (len > 65535)
+            return sdFail(ctx, SD_EINVAL, "target %u has %llu positions; index positions are 16 bit (limit 65535, --max-seq-len)", i,
+                          (unsigned long long) len);
+        winBase[i + 1] = winBase[i] + (len >= (uint64_t) span ? len - span + 1 : 0);
+    }
+    const uint64_t nWin = winBase[nSeq], total = posOffsets[nSeq];
+    if (nWin >= 0xFFFFFFFFull) return sdFail(ctx, SD_EUNSUPPORTED, "%llu profile windows (limit 2^32 per target)", (unsigned long long) nWin);
+    (void) hipSetDevice(ctx->device);
+    sd_target *t = new sd_target();
+    struct Guard {
+        sd_target *t;
+        ~Guard() { if (t) sd_target_destroy(t); }
+    } guard{t};
+    t->ctx = ctx;
+    t->k = kmerSize;
+    t->nSeq = nSeq;
+    t->similar = true;
+    t->tableSize = 64000000ull;
+    t->hSeqOff.assign(posOffsets, posOffsets + nSeq + 1);
+    const PeakNote notePeak(t);
+    auto up = [&](void **d, const void *h, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(d, bytes + 64);
+        if (e != hipSuccess) return e;
+        return hipMemcpy(*d, h, bytes, hipMemcpyDefault);
+    };
+    SD_HIP(ctx, up((void **) &t->dSeqOff, posOffsets, ((size_t) nSeq + 1) * sizeof(uint64_t)));
+    SD_HIP(ctx, up((void **) &t->dMasked, consensus, total));   // what the diagonal scoring reads
+    Scoped<uint8_t> dLetters, dIndex, dBig;
+    Scoped<int16_t> dScore;
+    Scoped<uint64_t> dWinBase;
+    Scoped<uint32_t> dWinCount;
+    Scoped<unsigned long long> dCoarse, dErr;
+    Scoped<uint2> dScratch, dScratchBig;
+    // (SD_INDEX_PROFILE_GRID: wavefronts of the wide tier, 1 MiB of scratch each -- a tuning knob, tools/bench_target_profile.py)
+    uint64_t wideGrid = IP_GRID;
+    if (getenv("SD_INDEX_PROFILE_GRID")) wideGrid = std::min<uint64_t>(std::max<uint64_t>(64, strtoull(getenv("SD_INDEX_PROFILE_GRID"), nullptr, 10)), 16384);
+    const uint32_t grid = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(nWin, 1), wideGrid);
+    const uint32_t gridBig = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(nWin, 1), IP_GRID_BIG);
+    SD_HIP(ctx, up((void **) &dLetters.p, queryLetters, total));
+    SD_HIP(ctx, up((void **) &dScore.p, sortedScore, total * 20 * sizeof(int16_t)));
+    SD_HIP(ctx, up((void **) &dIndex.p, sortedIndex, total * 20));
+    SD_HIP(ctx, up((void **) &dWinBase.p, winBase.data(), winBase.size() * sizeof(uint64_t)));
+    SD_HIP(ctx, dBig.alloc(nWin + 1));
+    SD_HIP(ctx, dWinCount.alloc(nWin + 1));
+    SD_HIP(ctx, dCoarse.alloc(IB_COARSE_BINS));
+    SD_HIP(ctx, dErr.alloc(2));
+    SD_HIP(ctx, dScratch.alloc((size_t) grid * 2 * PROFILE_PARTIAL_CAP));
+    notePeak();
+    const unsigned long long errInit[2] = {~0ull, 0ull};   // [0] first window beyond IP_LIST_MAX, [1] windows of the big tier
+    SD_HIP(ctx, hipMemcpy(dErr.p, errInit, sizeof(errInit), hipMemcpyHostToDevice));
+    SD_HIP(ctx, hipMemsetAsync(dBig.p, 0, nWin + 1, ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(dWinCount.p, 0, (nWin + 1) * sizeof(uint32_t), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(dCoarse.p, 0, IB_COARSE_BINS * sizeof(unsigned long long), ctx->stream));
+    const uint32_t binWidth = (uint32_t) ((t->tableSize + IB_COARSE_BINS - 1) / IB_COARSE_BINS);
+    bool anyBig = false;
+    // the generator in one of its modes, on the tier(s) the windows run in
+    auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *winCount, const uint64_t *recBase, uint32_t *keys, uint64_t *vals, bool bigTier) {
+        constexpr int MODE = decltype(mode)::value;
+        hipLaunchKernelGGL((ib_profile_records_kernel<MODE>), dim3(bigTier ? gridBig : grid), dim3(64), 0, ctx->stream, nWin,
+                           (const uint64_t *) dWinBase.p, nSeq, (const uint8_t *) dLetters.p, (const uint64_t *) t->dSeqOff,
+                           (const int16_t *) dScore.p, (const uint8_t *) dIndex.p, kmerThr, bigTier ? dScratchBig.p : dScratch.p,
+                           bigTier ? PROFILE_PARTIAL_CAP_BIG : PROFILE_PARTIAL_CAP, dBig.p, bigTier ? 1 : 0, binWidth, dCoarse.p, dErr.p, lo, hi,
+                           winCount, recBase, keys, vals);
+    };
+    std::vector<unsigned long long> coarse(IB_COARSE_BINS, 0);
+    if (nWin) {
+        unsigned long long hErr[2] = {~0ull, 0ull};
+        {
+            ProfScope ps(ctx, "index_profile_histogram");
+            generate(std::integral_constant<int, 0>(), 0u, 0u, dWinCount.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr, false);
+        }
+        SD_HIP(ctx, hipGetLastError());
+        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        SD_HIP(ctx, hipMemcpy(hErr, dErr.p, sizeof(hErr), hipMemcpyDeviceToHost));
+        anyBig = hErr[1] != 0;
+        if (anyBig) {
+            SD_HIP(ctx, dScratchBig.alloc((size_t) gridBig * 2 * PROFILE_PARTIAL_CAP_BIG));
+            notePeak();
+            {
+                ProfScope ps(ctx, "index_profile_histogram");
+                generate(std::integral_constant<int, 0>(), 0u, 0u, dWinCount.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr, true);
+            }
+            SD_HIP(ctx, hipGetLastError());
+            SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            SD_HIP(ctx, hipMemcpy(hErr, dErr.p, sizeof(hErr), hipMemcpyDeviceToHost));
+        }
+        if (hErr[0] != ~0ull) {
+            const uint32_t q = (uint32_t) (std::upper_bound(winBase.begin(), winBase.end(), (uint64_t) hErr[0]) - winBase.begin() - 1);
+            return sdFail(ctx, SD_EUNSUPPORTED, "target %u, position %llu: more than %u similar k-mers in one profile window (the reference's "
+                          "buffer ends there, KmerGenerator.h:45); raise the k-mer threshold", q, (unsigned long long) (hErr[0] - winBase[q]), IP_LIST_MAX);
+        }
+        SD_HIP(ctx, hipMemcpy(coarse.data(), dCoarse.p, IB_COARSE_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+    uint64_t nRecords = 0, cap = 0;
+    if (int rcCap = ibPassCap(ctx, coarse, cap, nRecords)) return rcCap;
+    SD_HIP(ctx, hipMalloc((void **) &t->dEntries, (std::max<uint64_t>(nRecords, 1) + 8) * sizeof(uint2)));   // (from the counted records)
+    SD_HIP(ctx, hipMalloc((void **) &t->dOffsets, (t->tableSize + 1) * sizeof(uint32_t) + 64));
+    SD_HIP(ctx, hipMemsetAsync(t->dOffsets, 0, (t->tableSize + 1) * sizeof(uint32_t), ctx->stream));   // counts first
+    uint64_t nEntries = 0, nPasses = 0;
+    if (nRecords) {
+        auto countFn = [&](uint32_t lo, uint32_t hi, uint32_t *winCount) -> int {
+            if (lo == 0 && hi >= t->tableSize) {   // one pass holds every record: the list lengths are its counts
+                SD_HIP(ctx, hipMemcpyAsync(winCount, dWinCount.p, nWin * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+                return SD_OK;
+            }
+            generate(std::integral_constant<int, 1>(), lo, hi, winCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr, false);
+            if (anyBig) generate(std::integral_constant<int, 1>(), lo, hi, winCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr, true);
+            return SD_OK;
+        };
+        auto emitFn = [&](uint32_t lo, uint32_t hi, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) -> int {
+            generate(std::integral_constant<int, 2>(), lo, hi, (uint32_t *) nullptr, recBase, keys, vals, false);
+            if (anyBig) generate(std::integral_constant<int, 2>(), lo, hi, (uint32_t *) nullptr, recBase, keys, vals, true);
+            return SD_OK;
+        };
+        if (int rcP = ibPasses(ctx, t, "sd_target_build_profile", coarse, binWidth, nRecords, cap, (uint32_t) nWin, countFn, emitFn, notePeak, nEntries,
+                               nPasses))
+            return rcP;
+    }
+    if (int rcL = ibListStarts(ctx, t, "sd_target_build_profile", nEntries, notePeak)) return rcL;
+    t->nEntries = nEntries;
+    if (stats) {
+        stats[0] = nEntries;
+        stats[1] = 0;
         stats[2] = nPasses;
         stats[3] = nRecords;
     }

@@ -112,6 +112,43 @@ emit_kmers_join_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint
     }
 }
 
+// ---- sequence queries against a *similar* target (sd_target::similar, a profile DB's index): takeOnlyBestKmer
+// (Prefiltering.cpp:176-179, QueryMatcher.cpp:249-252).  Every window without X looks up its own k-mer and nothing else; the k-mer
+// threshold and the k-mer composition bias play no part.  A thread per position.  K1: the count (1 or 0) ...
+__global__ void __launch_bounds__(256)
+exact_count_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t nQ, const uint8_t *__restrict__ qRes,
+                   const uint64_t *__restrict__ qOff, const int16_t *__restrict__ kmerBias, const uint32_t *__restrict__ posQuery,
+                   uint32_t *__restrict__ kmerCount) {
+    const uint64_t p = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+    if (p >= nPos) return;
+    kmerCount[p] = decodePos(p, posBase, nQ, qRes, qOff, kmerBias, 0, posQuery).ok ? 1u : 0u;
+}
+// ... K2: the k-mer itself, as the join's stream element (JOIN) or with its index list for the lookup path
+template <bool JOIN, bool WIDE>
+__global__ void __launch_bounds__(256)
+exact_emit_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t nQ, const uint8_t *__restrict__ qRes,
+                  const uint64_t *__restrict__ qOff, const int16_t *__restrict__ kmerBias, const uint32_t *__restrict__ posQuery,
+                  const uint64_t *__restrict__ kmerBase, uint64_t *__restrict__ elems, const uint32_t *__restrict__ idxOffsets,
+                  const uint64_t *__restrict__ blockBase, uint32_t *__restrict__ kStart, uint32_t *__restrict__ kStartHi,
+                  uint32_t *__restrict__ kLen, uint32_t *__restrict__ kPos) {
+    const uint64_t p = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+    if (p >= nPos) return;
+    const PosInfo pi = decodePos(p, posBase, nQ, qRes, qOff, kmerBias, 0, posQuery);
+    if (!pi.ok) return;
+    const uint32_t km = pi.idx0 + 8000u * pi.idx1;   // Indexer::int2index of the window
+    const uint64_t w = kmerBase[p];
+    if (JOIN) {
+        elems[w] = jpElem(km, w, pi.i);
+    } else {
+        uint32_t s0, h0, l0;
+        idxList<WIDE>(idxOffsets, blockBase, km, s0, h0, l0);
+        kStart[w] = s0;
+        if (WIDE) kStartHi[w] = h0;
+        kLen[w] = l0;
+        kPos[w] = (pi.q << 16) | (uint32_t) pi.i;
+    }
+}
+
 // first stream index of every query (32 bit: a sub-batch holds at most 2^30 k-mers); flag[0] |= 1 when a query has
 // JOIN_ORD_LIMIT k-mers or more
 __global__ void join_query_base_kernel(uint32_t nQ, const uint64_t *__restrict__ posBase, const uint64_t *__restrict__ kmerBase,

@@ -400,8 +400,7 @@ emit_kmers7_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t
 // Two tiers of scratch: every position first runs with PROFILE_PARTIAL_CAP partial k-mers per stage on a wide grid; the
 // few positions that outgrow it (a partial list is never longer than the final one, and the reference's own buffer
 // holds 2^23 k-mers, KmerGenerator.h:45) are flagged and redone by a narrow grid with PROFILE_PARTIAL_CAP_BIG.
-constexpr uint32_t PROFILE_PARTIAL_CAP = 1u << 16;
-constexpr uint32_t PROFILE_PARTIAL_CAP_BIG = 1u << 23;
+// (PROFILE_PARTIAL_CAP / PROFILE_PARTIAL_CAP_BIG: sd_common.h, shared with the index builder's generator)
 constexpr uint32_t PROFILE_GRID = 2048, PROFILE_GRID_BIG = 16;
 
 template <bool EMIT>
@@ -2828,6 +2827,8 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
     if (!ctx || !T || !par || !qResidues || !qOffsets || !identityId || !outHits || !outCount) return SD_EINVAL;
     if (!prof && (!qKmerBias || !qDiagBias)) return SD_EINVAL;
     if (par->kmerSize != T->k) return sdFail(ctx, SD_EINVAL, "k-mer size mismatch");
+    // a profile target's index holds similar k-mers already (sd_target_build_profile): the reference refuses the pair (Prefiltering.cpp:144-148)
+    if (T->similar && prof) return sdFail(ctx, SD_EUNSUPPORTED, "profile queries cannot be searched against a profile target");
     if (par->minDiagScore < 1) return sdFail(ctx, SD_EUNSUPPORTED, "minDiagScore must be >= 1");
     if (par->binSize == 0 || (par->binSize & (par->binSize - 1))) return sdFail(ctx, SD_EINVAL, "binSize must be a power of two");
     (void) hipSetDevice(ctx->device);
@@ -2973,7 +2974,10 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
                                            (uint32_t *) nullptr, (uint32_t *) nullptr, dErr.p, PROFILE_PARTIAL_CAP_BIG, dProfBig.p, 1,
                                            (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
                     }
-                } else if (T->k == 6)
+                } else if (T->similar)   // the query's own k-mers only; par->kmerThr and the k-mer bias are not read
+                    hipLaunchKernelGGL(exact_count_kernel, dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p,
+                                       dKB.p, (const uint32_t *) dPosQuery.p, dKmerCount.p);
+                else if (T->k == 6)
                     hipLaunchKernelGGL(count_kmers_kernel, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
                                        dQ.p, dQOff.p, dKB.p, par->kmerThr, T->dExt3Score, dKmerCount.p, (const uint16_t *) T->dExt3Cum, T->ext3Lo,
                                        (const uint32_t *) dPosQuery.p);
@@ -3034,6 +3038,15 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
                                            bq, dQ.p, dQOff.p, dPS.p, dPI.p, par->kmerThr, T->k, dProfScratch.p, (uint32_t *) nullptr,
                                            T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p, dErr.p, PROFILE_PARTIAL_CAP_BIG,
                                            dProfBig.p, 1, (const uint64_t *) T->dBlockBase, wideIdx ? dKStartHi.p : (uint32_t *) nullptr, (uint64_t *) nullptr);
+                } else if (T->similar) {
+                    if (wideIdx)
+                        hipLaunchKernelGGL((exact_emit_kernel<false, true>), dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
+                                           dQ.p, dQOff.p, dKB.p, (const uint32_t *) dPosQuery.p, dKmerBase.p, (uint64_t *) nullptr, T->dOffsets,
+                                           (const uint64_t *) T->dBlockBase, dKStart.p, dKStartHi.p, dKLen.p, dKPos.p);
+                    else
+                        hipLaunchKernelGGL((exact_emit_kernel<false, false>), dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
+                                           dQ.p, dQOff.p, dKB.p, (const uint32_t *) dPosQuery.p, dKmerBase.p, (uint64_t *) nullptr, T->dOffsets,
+                                           (const uint64_t *) nullptr, dKStart.p, (uint32_t *) nullptr, dKLen.p, dKPos.p);
                 } else if (T->k == 6) {
                     if (wideIdx)
                         hipLaunchKernelGGL(emit_kmers_kernel<true>, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
@@ -3118,7 +3131,11 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
                                            dQOff.p, dPS.p, dPI.p, par->kmerThr, T->k, dProfScratch.p, (uint32_t *) nullptr, (const uint32_t *) nullptr,
                                            dKmerBase.p, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, dErr.p,
                                            PROFILE_PARTIAL_CAP_BIG, dProfBig.p, 1, (const uint64_t *) nullptr, (uint32_t *) nullptr, dElems.p);
-                } else
+                } else if (T->similar)
+                    hipLaunchKernelGGL((exact_emit_kernel<true, false>), dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p,
+                                       dQOff.p, dKB.p, (const uint32_t *) dPosQuery.p, dKmerBase.p, dElems.p, (const uint32_t *) nullptr,
+                                       (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr);
+                else
                 hipLaunchKernelGGL(emit_kmers_join_kernel, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p,
                                    dQOff.p, dKB.p, par->kmerThr, T->dExt3Score, T->dExt3Index, dKmerBase.p, dElems.p, (const uint16_t *) T->dExt3Cum, T->ext3Lo,
                                    (const uint32_t *) dPosQuery.p);

@@ -64,4 +64,15 @@ static inline int sdBuildTarget(sd_host *host, sd_ctx *ctx, int k, int indexThr,
     return rc;
 }
 
+// the index of a profile target DB (similar k-mers of every profile window at the profile threshold, consensus lookup; no masking, no
+// extended tables) from Sequence::mapProfile's arrays.  stats: {entries, 0}.
+static inline int sdBuildProfileTarget(sd_ctx *ctx, int k, int kmerThr, const uint8_t *letters, const uint8_t *consensus, const int16_t *sortedScore,
+                                       const uint8_t *sortedIndex, const uint64_t *offsets, uint32_t n, sd_target **out, uint64_t stats[2]) {
+    uint64_t st[4] = {0, 0, 0, 0};
+    const int rc = sd_target_build_profile(ctx, k, kmerThr, letters, consensus, sortedScore, sortedIndex, offsets, n, out, st);
+    stats[0] = st[0];
+    stats[1] = st[1];
+    return rc;
+}
+
 #endif

@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""What the prefilter against a profile target costs on the device: set G of tests/golden/profile_vectors.npz (18 crafted profiles,
+5 084 positions) repeated to about 10^6 positions, indexed by sd_target_build_profile at the default profile threshold
+(Host.profile_kmer_threshold(4.0, 6)), then 8 192 sequence queries (the golden sequences, repeated) through sd_prefilter_batch.
+Every timed call ends in a device synchronise inside the library; the first build and the first query pass are warm-up.
+
+    python tools/bench_target_profile.py [--positions 1000000] [--queries 8192] [--runs 3] [--out profiles/target_profile.txt]
+
+The reference's build of the same input on a CPU: python tools/make_golden_target_profile.py --time-build REPS THR (dev container)."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GOLD = os.path.join(ROOT, 'tests', 'golden', 'profile_vectors.npz')
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--positions', type=int, default=1000000)
+    ap.add_argument('--queries', type=int, default=8192)
+    ap.add_argument('--runs', type=int, default=3)
+    ap.add_argument('--sensitivity', type=float, default=4.0)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    from spacedust_amd import api
+    lines = []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    host, gpu = api.Host(), api.Context(0)
+    d = np.load(GOLD)
+    reps = max(1, round(a.positions / (int(d['poff'][-1]) // 25)))
+    data = d['profiles'].tobytes() * reps
+    one = d['poff'].astype(np.uint64)
+    poff = np.concatenate([[0], (one[1:][None, :] + (np.arange(reps, dtype=np.uint64) * one[-1])[:, None]).reshape(-1)]).astype(np.uint64)
+    prof = host.map_profiles(data, poff)
+    thr = host.profile_kmer_threshold(a.sensitivity, 6)
+    n_prof, n_pos = len(poff) - 1, int(prof['offsets'][-1])
+    log('device: %s' % gpu.device_name())
+    log('target: set G x %d = %d profiles, %d positions; k = 6, profile threshold %d (-s %.1f)' % (reps, n_prof, n_pos, thr, a.sensitivity))
+    times, t = [], None
+    for r in range(a.runs + 1):
+        del t
+        t0 = time.time()
+        t = api.Target.build_profile_on_device(gpu, host, prof, k=6, kmer_thr=thr)
+        dt = time.time() - t0
+        if r:
+            times.append(dt)
+        log('build %s: %.3f s' % ('warm-up' if r == 0 else 'run %d' % r, dt))
+    st, med = t.build_stats, float(np.median(times))
+    log('sd_target_build_profile (upload of the mapped profiles included): median %.3f s of %d runs; %d records, %d entries, %d pass(es); '
+        '%.3g records/s, %.3g entries/s; sd_target_build_peak %d B (%.2f GiB)'
+        % (med, len(times), st['records'], st['entries'], st['passes'], st['records'] / med, st['entries'] / med, t.build_peak(), t.build_peak() / 2.0 ** 30))
+    off = d['off'].astype(np.int64)
+    blob = d['blob'].tobytes().decode()
+    base = [blob[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+    seqs = [base[i % len(base)] for i in range(a.queries)]
+    res, qoff = host.map_sequences(seqs)
+    _, dg_b, km_b = host.comp_bias(res, qoff)
+    par = api.prefilter_params(host, n_prof, kmer_thr=thr, max_hits=300, cov_mode=0, cov_thr=0.0, k=6)
+    ident = np.full(len(seqs), 0xFFFFFFFF, np.uint32)
+    times = []
+    for r in range(a.runs + 1):
+        t0 = time.time()
+        hits, cnt, stats = api.prefilter(gpu, t, par, res, qoff, km_b, dg_b, ident, want_stats=True)
+        dt = time.time() - t0
+        if r:
+            times.append(dt)
+        log('prefilter %s: %.3f s' % ('warm-up' if r == 0 else 'run %d' % r, dt))
+    med = float(np.median(times))
+    log('sd_prefilter_batch, %d sequence queries (%d residues) against it: median %.3f s of %d runs; %d exact k-mers looked up, %d index hits, '
+        '%d rows; %.3g queries/s'
+        % (len(seqs), int(qoff[-1]), med, len(times), int(stats[:, 0].sum()), int(stats[:, 1].sum()), int(cnt.sum()), len(seqs) / med))
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
