@@ -644,6 +644,32 @@ int sd_alntext_format(sd_alntext *t, const sd_aln_criteria *crit, uint32_t nQ, c
 /* text / entryOff[nQ+1] of the last sd_alntext_format; valid until the next call on t */
 int sd_alntext_get(sd_alntext *t, const char **text, const uint64_t **entryOff);
 
+/* ---- swapresults: a result DB keyed by query re-keyed by target (host; M/src/util/swapresults.cpp:18-348, doswap(par, false)) ------
+ * The step on both sides of `align` when the target DB holds profiles (M/data/workflow/searchtargetprofile.sh): the prefilter result is
+ * swapped so that the profile is the Smith-Waterman query, the alignment result is swapped back.  The form is that of the first line of
+ * the input:
+ *   3 columns (prefilter): `target score diag` of entry q becomes `q score -diag` (the diagonal negated in 16 bits) in target's entry;
+ *     an entry is ordered by score descending, then key.
+ *   10 / 11 columns (alignment): query and target columns exchanged, I <-> D in the backtrace, the E-value recomputed from the bit
+ *     score (Matcher::result_t::swapResult, Matcher.h:93-115) over firstDbResidues -- DBReader::getAminoAcidDBSize of the FIRST DB
+ *     argument of the module -- with the length of the sequence that was the target; rows above evalThr are dropped, the rest ordered
+ *     by Matcher::compareHits.  gapOpen / gapExtend: 11 / 1 (the built-in ALP preset; anything else SD_EUNSUPPORTED).
+ * Entries out: every key from 0 to the last key of secondDbKeys (the keys of the SECOND DB argument) that has rows; a key without
+ * surviving rows gets an empty entry when it is one of secondDbKeys or rows of it were dropped by the E-value.  SD_EINVAL: a line
+ * without a key, with a key behind the last of secondDbKeys, or with another column count than its form's.
+ * sd_host_swapresults: entry i = inText[inOff[i] .. inOff[i+1]) with key inKeys[i]; _entries: entry i = inData[i][0 .. inLen[i]) (the
+ * entries of a mapped DB).  Parse and print run on the caller's OpenMP team. */
+typedef struct sd_swap sd_swap;
+int sd_host_swapresults(uint32_t nIn, const uint32_t *inKeys, const uint64_t *inOff, const char *inText, uint64_t firstDbResidues,
+                        const uint32_t *secondDbKeys, uint32_t nSecondDbKeys, double evalThr, int gapOpen, int gapExtend, sd_swap **out);
+int sd_host_swapresults_entries(uint32_t nIn, const uint32_t *inKeys, const char *const *inData, const uint64_t *inLen, uint64_t firstDbResidues,
+                                const uint32_t *secondDbKeys, uint32_t nSecondDbKeys, double evalThr, int gapOpen, int gapExtend, sd_swap **out);
+/* the result (any pointer may be NULL): keys[nEntries] ascending, off[nEntries + 1] into text; rows read and rows written; valid until
+ * sd_swap_destroy */
+int sd_swap_get(sd_swap *s, uint32_t *nEntries, const uint32_t **keys, const uint64_t **off, const char **text, uint64_t *rowsIn,
+                uint64_t *rowsOut);
+void sd_swap_destroy(sd_swap *s);
+
 
 /* ---- the whole search in one object: host driver of the streaming pipeline (C++; replaces what the reference runs as
  * `search` + prefixid/besthitbyset/mergeresultsbyset/combinehits + `clusterhits`, R/data/clustersearch.sh:110-146) ------

@@ -269,6 +269,12 @@ def load():
         'sd_tcp_close': (None, [_vp]),
         'sd_tcp_bcast': (C.c_int, [_vp, _vp, C.c_uint64]),
         'sd_tcp_gather': (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        'sd_host_swapresults': (C.c_int, [C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_double, C.c_int, C.c_int, C.POINTER(_vp)]),
+        'sd_host_swapresults_entries': (C.c_int, [C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_double, C.c_int, C.c_int,
+                                                  C.POINTER(_vp)]),
+        'sd_swap_get': (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64)]),
+        'sd_swap_destroy': (None, [_vp]),
     }
     missing = []
     for name, (res, args) in sig.items():

@@ -145,6 +145,39 @@ def uncompress_cigar(c):
     return ''.join(out)
 
 
+def swapresults(entries, first_db_residues, second_db_keys, eval_thr=0.001, gap_open=11, gap_extend=1, want_counts=False):
+    """sd_host_swapresults: a result DB keyed by query re-keyed by target (the `swapresults` module without the DB files).
+    entries: dict key -> entry text (bytes) or a list of (key, bytes); first_db_residues: the amino-acid size of the module's first DB
+    argument; second_db_keys: the keys of its second.  Returns dict key -> bytes (empty entries included) and, with want_counts, the
+    rows read and written."""
+    L = _lib.load()
+    items = sorted(entries.items()) if isinstance(entries, dict) else list(entries)
+    keys = np.array([k for k, _ in items], np.uint32)
+    off = np.zeros(len(items) + 1, np.uint64)
+    if items:
+        np.cumsum([len(t) for _, t in items], out=off[1:])
+    blob = b''.join(bytes(t) for _, t in items) + b'\0'
+    tkeys = np.ascontiguousarray(second_db_keys, np.uint32)
+    h = C.c_void_p()
+    rc = L.sd_host_swapresults(len(items), ptr(keys), ptr(off), blob, int(first_db_residues), ptr(tkeys), len(tkeys), float(eval_thr),
+                               gap_open, gap_extend, C.byref(h))
+    _check(None, rc, 'sd_host_swapresults')
+    try:
+        n, rows_in, rows_out = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        k_p, o_p, t_p = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(None, L.sd_swap_get(h, C.byref(n), C.byref(k_p), C.byref(o_p), C.byref(t_p), C.byref(rows_in), C.byref(rows_out)), 'sd_swap_get')
+        out = {}
+        if n.value:
+            k = np.ctypeslib.as_array(C.cast(k_p, C.POINTER(C.c_uint32)), (n.value,))
+            o = np.ctypeslib.as_array(C.cast(o_p, C.POINTER(C.c_uint64)), (n.value + 1,))
+            text = C.string_at(t_p, int(o[-1])) if int(o[-1]) else b''
+            for i in range(n.value):
+                out[int(k[i])] = text[int(o[i]):int(o[i + 1])]
+    finally:
+        L.sd_swap_destroy(h)
+    return (out, rows_in.value, rows_out.value) if want_counts else out
+
+
 def result2profile(q_letters, q_off, edge_off, edge_t, edge_qstart, edge_tstart, backtraces, t_residues, t_off, **kw):
     """sd_r2p_batch: profiles (25 bytes per position, bytes object) of nQ centre sequences from their alignments"""
     L = _lib.load()

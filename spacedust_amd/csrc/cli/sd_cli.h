@@ -175,6 +175,7 @@ int clustersearchModule(const Args &a);
 int result2profileModule(const Args &a);
 int subtractdbsModule(const Args &a);
 int mergedbsModule(const Args &a);
+int swapresultsModule(const Args &a);
 
 }  // namespace sdcli
 #endif

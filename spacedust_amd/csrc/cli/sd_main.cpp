@@ -24,7 +24,7 @@ const Module kModules[] = {
     {"align", alignModule, "Smith-Waterman alignments on the GPU: <queryDB> <targetDB> <prefilterDB> <alignmentDB>"},
     {"rescorediagonal", rescorediagonalModule, "ungapped alignment on each hit's diagonal on the GPU (--alignment-mode 4): <queryDB> <targetDB> <prefilterDB> <resultDB>"},
     {"clusterhits", clusterhitsModule, "agglomerative hit clustering on the GPU: <querySetDB> <targetSetDB> <matchesDB> <clustersDB>"},
-    {"search", searchModule, "prefilter + align (and the --num-iterations profile loop): <queryDB> <targetDB> <alignmentDB> <tmpDir>"},
+    {"search", searchModule, "prefilter + align (the --num-iterations profile loop; a profile target DB through swapresults): <queryDB> <targetDB> <alignmentDB> <tmpDir>"},
     {"clustersearch", clustersearchModule, "the whole --search-mode 0 workflow in one process: <querySetDB> <targetSetDB> <out.tsv> <tmpDir>"},
     {"prefixid", prefixidModule, "host glue: prefix every line of a result DB with its entry key"},
     {"besthitbyset", besthitbysetModule, "host glue: best hit per (query protein, target set)"},
@@ -34,6 +34,7 @@ const Module kModules[] = {
     {"result2profile", result2profileModule, "host: alignment DB -> profile DB (between search iterations)"},
     {"subtractdbs", subtractdbsModule, "host glue: remove from result DB A the targets listed in result DB B"},
     {"mergedbs", mergedbsModule, "host glue: merge the entries of several DBs by key"},
+    {"swapresults", swapresultsModule, "host glue: re-key a prefilter / alignment DB by its targets: <queryDB> <targetDB> <resultDB> <outDB>"},
     {"createindex", createindexModule, "target k-mer index built once, in the reference's createindex file layout: <sequenceDB> <tmpDir>"},
     {"createsetdb", createsetdbModule, "FASTA files (Prodigal headers) -> setDB in the createsetdb layout"},
 };

@@ -717,4 +717,72 @@ int createsetdbModule(const Args &a) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// swapresults <queryDB> <targetDB> <resultDB> <outDB>  (M/src/util/swapresults.cpp:18-348,356-360): the result DB re-keyed by its target
+// column -- sd_host_swapresults_entries of the C ABI; this is the DB side.  Parameter set `swapresult` (Parameters.cpp:978-986):
+// --sub-mat, -e, --gap-open, --gap-extend, --threads, --compressed, -v are used; --split-memory-limit (the output is written as one
+// piece) and --db-load-mode are accepted and ignored.
+int swapresultsModule(const Args &a) {
+    if (a.pos.size() != 4) return fail("usage: swapresults <queryDB> <targetDB> <resultDB> <outDB> [options]");
+    if (int rc = checkCommon(a)) return rc;
+    const int gapOpen = atoi(a.multi("--gap-open", "aa", "11").c_str()), gapExtend = atoi(a.multi("--gap-extend", "aa", "1").c_str());
+    if (gapOpen != 11 || gapExtend != 1)
+        return fail("gap costs other than --gap-open 11 --gap-extend 1 need other E-value parameters than the built-in preset");
+    Lap lap("swapresults");
+    std::string err;
+    // the evaluer's residues come from the first DB (:75-76,99), the keys that get an entry from the second (:78-87); either may hold
+    // profiles (DBReader::getAminoAcidDBSize, DBReader.cpp:589-597: columns without the terminator for profiles, letters without "\n\0")
+    sddb::Reader first, second, in;
+    if (!first.open(a.pos[0], sddb::Reader::USE_INDEX, sddb::Reader::NOSORT, &err)) return fail(err);
+    uint64_t residues;
+    if (sddb::baseType(first.dbtype()) == sddb::DBTYPE_HMM_PROFILE) {
+        uint64_t bytes = 0;
+        for (size_t i = 0; i < first.size(); i++) bytes += first.entryLength(i);
+        residues = bytes / 25 - first.size();
+    } else {
+        residues = first.aminoAcidDbSize();
+    }
+    std::vector<uint32_t> keys;
+    if (a.pos[1] == a.pos[0]) {
+        for (size_t i = 0; i < first.size(); i++) keys.push_back(first.key(i));
+    } else {
+        if (!second.open(a.pos[1], sddb::Reader::USE_INDEX, sddb::Reader::NOSORT, &err)) return fail(err);
+        for (size_t i = 0; i < second.size(); i++) keys.push_back(second.key(i));
+    }
+    if (!in.open(a.pos[2], sddb::Reader::USE_INDEX | sddb::Reader::USE_DATA, sddb::Reader::LINEAR_ACCESS, &err)) return fail(err);
+    lap.mark("open DBs");
+    const size_t n = in.size();
+    std::vector<uint32_t> inKeys(n);
+    std::vector<const char *> data(n);
+    std::vector<uint64_t> len(n);
+    for (size_t i = 0; i < n; i++) {
+        inKeys[i] = in.key(i);
+        data[i] = in.data(i);
+        len[i] = in.entryLength(i) ? in.entryLength(i) - 1 : 0;
+    }
+    sd_swap *swap = nullptr;
+    const int rc = sd_host_swapresults_entries((uint32_t) n, inKeys.data(), data.data(), len.data(), residues, keys.data(), (uint32_t) keys.size(),
+                                               a.real("-e", 0.001), gapOpen, gapExtend, &swap);
+    if (rc == SD_EINVAL)
+        return fail("Invalid result record in " + a.pos[2] + " (a line without a key, with a key behind the last key of " + a.pos[1] +
+                    ", or with another column count than its DB's first line gives)");
+    if (rc != SD_OK) return fail("sd_host_swapresults_entries failed (" + std::to_string(rc) + ")");
+    std::unique_ptr<sd_swap, void (*)(sd_swap *)> guard(swap, sd_swap_destroy);
+    lap.mark("swap");
+    uint32_t nOut = 0;
+    const uint32_t *outKeys = nullptr;
+    const uint64_t *off = nullptr;
+    const char *text = nullptr;
+    uint64_t rowsIn = 0, rowsOut = 0;
+    sd_swap_get(swap, &nOut, &outKeys, &off, &text, &rowsIn, &rowsOut);
+    sddb::Writer out;
+    if (!out.open(a.pos[3], in.dbtype(), &err)) return fail(err);
+    for (uint32_t i = 0; i < nOut; i++)
+        if (!out.write(outKeys[i], text + off[i], (size_t) (off[i + 1] - off[i]))) return fail("cannot write " + a.pos[3]);
+    if (!out.close(&err)) return fail(err);
+    lap.mark("write");
+    info(a, "%llu rows of %zu entries swapped into %u entries (%llu rows kept)\n", (unsigned long long) rowsIn, n, nOut, (unsigned long long) rowsOut);
+    return 0;
+}
+
 }  // namespace sdcli

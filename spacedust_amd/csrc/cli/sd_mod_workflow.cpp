@@ -1084,10 +1084,73 @@ int altAliSearch(const Args &a, const std::string &Q, const std::string &T, cons
     return runModule(alignModule, "align", {Q, T, prefDb, result}, aln);
 }
 
+// `search <sequenceDB> <profileDB>` (M/src/workflow/Search.cpp:453-475 builds the parameter strings, M/data/workflow/searchtargetprofile.sh
+// runs them): the prefilter against the profile DB's similar-k-mer index, its result swapped so that every profile lists the sequences
+// that hit it, `align` with the profile as the Smith-Waterman query -- every listed sequence (--max-seqs INT_MAX), the coverage mode
+// swapped with the sides -- and that result swapped back, which recomputes the E-values for the search the user asked for.  The
+// intermediate DBs carry the script's names under <tmp>.
+bool isProfileDb(const std::string &db) { return sddb::baseType(sddb::readDbType(db)) == sddb::DBTYPE_HMM_PROFILE; }
+
+int swapCoverageMode(int covMode) {   // Util::swapCoverageMode (M/src/commons/Util.cpp:513-530)
+    switch (covMode) {
+        case 1: return 2;
+        case 2: return 1;
+        case 3: return 4;
+        case 4: return 3;
+        default: return covMode;
+    }
+}
+
+int targetProfileSearch(const Args &a, const std::string &Q, const std::string &T, const std::string &result, const std::string &tmp) {
+    // an entry of the swapped alignment DB is ordered by Matcher::compareHits, which ends at the key: two alignments of one pair
+    // (one key twice in an entry) have no order there
+    if (a.integer("--alt-ali", 0) != 0) return fail("--alt-ali with a profile target database: swapresults has no order for the alignments of one pair; run without --alt-ali");
+    mkdir(tmp.c_str(), 0777);
+    const std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
+    std::vector<std::string> pref = with(common, {"-s", a.str("-s", "5.7"), "-k", a.str("-k", "0"), "--max-seqs", a.str("--max-seqs", "300"), "-c",
+                                                  a.str("-c", "0"), "--cov-mode", a.str("--cov-mode", "0"), "--min-ungapped-score",
+                                                  a.str("--min-ungapped-score", "15"), "--comp-bias-corr", a.str("--comp-bias-corr", "1")});
+    for (const char *f : {"--k-score", "--device", "--bin-size", "--l2-cache-size", "--chunk-queries", "--split", "--split-mode", "--split-memory-limit"})
+        if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
+    std::vector<std::string> aln = with(common, {"-a", "1", "--alignment-mode", a.str("--alignment-mode", "2"), "-e", a.str("-e", "0.001"), "--max-seqs",
+                                                 std::to_string(INT_MAX), "-c", a.str("-c", "0"), "--cov-mode",
+                                                 std::to_string(swapCoverageMode((int) a.integer("--cov-mode", 0))), "--min-aln-len",
+                                                 a.str("--min-aln-len", "0"), "--min-seq-id", a.str("--min-seq-id", "0"), "--seq-id-mode",
+                                                 a.str("--seq-id-mode", "0"), "--comp-bias-corr", a.str("--comp-bias-corr", "1")});
+    if (a.has("--device")) aln = with(aln, {"--device", a.str("--device", "0")});
+    const std::vector<std::string> swap = with(common, {"-e", a.str("-e", "0.001")});
+    // Two targets are resident in turn: the profile DB with its index for `prefilter`, the sequence DB with its sequence set for
+    // `align` (Resident keys both by DB path, so they are entries of their own).  The index has no reader after the prefilter and is
+    // freed before `align` uploads.
+    struct ResidentScope {
+        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
+        ~ResidentScope() { resident().clear(); }
+    } residentScope;
+    const std::string prefDb = tmp + "/pref", prefSwapped = tmp + "/pref_swapped", alnSwapped = tmp + "/aln_swapped";
+    const bool keep = a.integer("--keep-tmp", 0) != 0;
+    struct RemoveTmp {
+        bool on;
+        std::vector<std::string> dbs;
+        ~RemoveTmp() { if (on) for (const std::string &d : dbs) sddb::removeDb(d); }
+    } removeTmp{!keep, {prefDb, prefSwapped, alnSwapped}};
+    if (int rc = runModule(prefilterModule, "prefilter", {Q, T, prefDb}, pref)) return rc;
+    residentTargetOf(T, deviceOf(a), true);
+    if (int rc = runModule(swapresultsModule, "swapresults", {Q, T, prefDb, prefSwapped}, swap)) return rc;
+    if (int rc = runModule(alignModule, "align", {T, Q, prefSwapped, alnSwapped}, aln)) return rc;
+    return runModule(swapresultsModule, "swapresults", {T, Q, alnSwapped, result}, swap);
+}
+
 }  // namespace
 
 int searchModule(const Args &a0) {
     if (int rc = checkPrefilterMode(a0)) return rc;
+    // a profile target DB on the one path that takes it: sequence queries, the k-mer prefilter, one pass, one rank, gapped alignments.
+    // Every other combination goes on to its own path below and is refused there
+    if (a0.pos.size() == 4 && isProfileDb(a0.pos[1]) && !isProfileDb(a0.pos[0]) && a0.integer("--prefilter-mode", 0) == 0 && a0.integer("--num-iterations", 1) <= 1 &&
+        a0.integer("--alignment-mode", 0) != 4 && envInt("WORLD_SIZE", 1) <= 1 && a0.integer("--world-size", 1) <= 1) {
+        if (int rc = checkWorkflowFlags(a0)) return rc;
+        return targetProfileSearch(a0, a0.pos[0], a0.pos[1], a0.pos[2], a0.pos[3]);
+    }
     Args a = a0;
     bool targetSplit = false;
     if (int rc = workflowSplit(a0, a, targetSplit)) return rc;

@@ -90,6 +90,9 @@ double computeEvalue(const Evaluer &e, double score, double qLen) {
 
 double computeBitScore(const Evaluer &e, double score) { return (e.lambda * score - e.logK) / log(2.0); }
 
+// EvalueComputation::computeRawScoreFromBitScore (EvalueComputation.h:22-24): the inverse of the line above, in its expression order
+double computeRawScoreFromBitScore(const Evaluer &e, double bitScore) { return (e.logK + bitScore * std::log(2.0)) / e.lambda; }
+
 bool canBeCovered(float covThr, int covMode, float queryLength, float targetLength) {
     switch (covMode) {
         case 0: return ((queryLength / targetLength >= covThr) && (targetLength / queryLength >= covThr));

@@ -713,3 +713,323 @@ int sd_agg_write_tsv(sd_agg *a, const char *path, const uint32_t *clusterOfHit, 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------
+// swapresults: doswap(par, false) of M/src/util/swapresults.cpp:18-348 -- a result DB keyed by query re-keyed by target.  Three passes, as
+// there: the bytes every target's lines will take (the line with the query key in place of the target key), an exclusive scan, the lines
+// copied to their places; then every target's lines are parsed, swapped, sorted by Matcher::compareHits and printed.
+//   prefilter lines (3 columns, :280-283,300-306): the diagonal negated in 16 bits, order = score descending, then query key
+//   alignment lines (10 / 11 columns, Matcher::result_t::swapResult, Matcher.h:93-115): E-value recomputed from the bit score over the
+//     first DB's residues with the length of the sequence that was the target, query and target columns exchanged, I <-> D in the
+//     run-length backtrace, rows above -e dropped
+namespace {
+
+struct SwapRec {
+    double eval;
+    int32_t score;
+    uint32_t dbLen, dbKey;
+    int32_t diag;                                   // prefilter form
+    int32_t qStart, qEnd, qLen, dbStart, dbEnd;     // alignment form, after the exchange
+    float seqId;
+    const char *bt;
+    uint32_t btLen;
+};
+
+inline bool swapRecLess(const SwapRec &a, const SwapRec &b) {   // Matcher::compareHits (Matcher.h:157-168)
+    if (a.eval != b.eval) return a.eval < b.eval;
+    if (a.score != b.score) return a.score > b.score;
+    if (a.dbLen != b.dbLen) return a.dbLen < b.dbLen;
+    return a.dbKey < b.dbKey;
+}
+
+// Util::fast_atoi<int> (M/src/commons/Util.h:107-121): an optional '-', digits, no range check (the value wraps)
+inline int32_t swapAtoi(const char *p, const char *e) {
+    bool neg = false;
+    if (p < e && *p == '-') {
+        neg = true;
+        p++;
+    }
+    uint32_t v = 0;
+    for (; p < e && *p >= '0' && *p <= '9'; p++) v = v * 10u + (uint32_t) (*p - '0');
+    return (int32_t) (neg ? 0u - v : v);
+}
+
+inline unsigned decimalDigits(uint32_t v) {
+    unsigned n = 1;
+    while (v >= 10) {
+        v /= 10;
+        n++;
+    }
+    return n;
+}
+
+// the lines of one entry: fn(lineStart, lineEnd) with lineEnd at the newline (or the end of an unterminated last line); empty lines are skipped
+template <typename F>
+inline bool swapForLines(const char *p, const char *end, F fn) {
+    while (p < end && *p != '\0') {
+        const char *le = (const char *) memchr(p, '\n', (size_t) (end - p));
+        if (!le) le = end;
+        const char *z = (const char *) memchr(p, '\0', (size_t) (le - p));
+        if (z) le = z;
+        if (le > p && !fn(p, le)) return false;
+        p = le < end && *le == '\n' ? le + 1 : le;
+    }
+    return true;
+}
+
+inline uint32_t swapColumns(const char *ls, const char *le, const char **col, uint32_t cap) {
+    uint32_t n = 0;
+    col[n++] = ls;
+    for (const char *c = ls; c < le; c++)
+        if (*c == '\t') {
+            if (n == cap) return cap + 1;
+            col[n++] = c + 1;
+        }
+    return n;
+}
+
+}  // namespace
+
+struct sd_swap {
+    std::vector<uint32_t> keys;
+    std::vector<uint64_t> off;
+    std::unique_ptr<char[]> text;
+    uint64_t rowsIn = 0, rowsOut = 0;
+};
+
+extern "C" {
+
+int sd_host_swapresults_entries(uint32_t nIn, const uint32_t *inKeys, const char *const *inData, const uint64_t *inLen, uint64_t firstDbResidues,
+                                const uint32_t *secondDbKeys, uint32_t nSecondDbKeys, double evalThr, int gapOpen, int gapExtend, sd_swap **out) {
+    if (!out || (nIn && (!inKeys || !inData || !inLen)) || (nSecondDbKeys && !secondDbKeys)) return SD_EINVAL;
+    *out = nullptr;
+    if (gapOpen != 11 || gapExtend != 1) return SD_EUNSUPPORTED;   // the one ALP preset of sd_evalue.cpp
+    std::unique_ptr<sd_swap> S(new sd_swap());
+    S->off.assign(1, 0);
+    if (nSecondDbKeys == 0) {
+        *out = S.release();
+        return SD_OK;
+    }
+    // DBReader::getLastKey and targetElementExists (:79-87)
+    uint32_t maxKey = 0;
+    for (uint32_t i = 0; i < nSecondDbKeys; i++) maxKey = std::max(maxKey, secondDbKeys[i]);
+    std::vector<uint8_t> exists((size_t) maxKey + 1, 0);
+    for (uint32_t i = 0; i < nSecondDbKeys; i++) exists[secondDbKeys[i]] = 1;
+    // the form of the DB: the column count of the first line there is (:217-229)
+    bool isAlignment = false, hasBacktrace = false;
+    for (uint32_t i = 0; i < nIn; i++) {
+        bool seen = false;
+        swapForLines(inData[i], inData[i] + inLen[i], [&](const char *ls, const char *le) {
+            uint32_t cols = 1;
+            for (const char *c = ls; c < le; c++) cols += *c == '\t';
+            isAlignment = cols >= 10;
+            hasBacktrace = cols >= 11;
+            seen = true;
+            return false;
+        });
+        if (seen) break;
+    }
+    // pass 1: bytes per target (:105-141)
+    std::vector<uint64_t> start((size_t) maxKey + 2, 0);
+    bool bad = false;
+    uint64_t rowsIn = 0;
+#pragma omp parallel for schedule(dynamic, 100) reduction(+ : rowsIn)
+    for (uint32_t i = 0; i < nIn; i++) {
+        const unsigned qDigits = decimalDigits(inKeys[i]);
+        const bool ok = swapForLines(inData[i], inData[i] + inLen[i], [&](const char *ls, const char *le) {
+            const char *k = ls;
+            uint64_t t = 0;
+            while (k < le && *k >= '0' && *k <= '9' && t <= UINT32_MAX) t = t * 10 + (uint64_t) (*k++ - '0');
+            if (k == ls || t > maxKey) return false;   // no key, or a key behind the last key of the DB the result is swapped onto
+            const uint64_t len = (uint64_t) (le - k) + qDigits + 1;
+#pragma omp atomic
+            start[t + 1] += len;
+            rowsIn++;
+            return true;
+        });
+        if (!ok) {
+#pragma omp atomic write
+            bad = true;
+        }
+    }
+    if (bad) return SD_EINVAL;
+    for (size_t k = 0; k <= maxKey; k++) start[k + 1] += start[k];   // AlignmentSymmetry::computeOffsetFromCounts
+    const uint64_t total = start[(size_t) maxKey + 1];
+    // pass 2: the lines at their places, the query key in front (:174-209)
+    std::unique_ptr<char[]> slab(new char[total + 1]);
+    {
+        std::vector<uint64_t> cursor(start.begin(), start.end() - 1);
+#pragma omp parallel for schedule(dynamic, 10)
+        for (uint32_t i = 0; i < nIn; i++) {
+            char qKey[16];
+            const size_t qDigits = (size_t) (sd::u32toa(inKeys[i], qKey) - qKey);
+            swapForLines(inData[i], inData[i] + inLen[i], [&](const char *ls, const char *le) {
+                const char *k = ls;
+                uint64_t t = 0;
+                while (k < le && *k >= '0' && *k <= '9') t = t * 10 + (uint64_t) (*k++ - '0');
+                const uint64_t len = (uint64_t) (le - k) + qDigits + 1;
+                uint64_t at;
+#pragma omp atomic capture
+                {
+                    at = cursor[t];
+                    cursor[t] += len;
+                }
+                memcpy(slab.get() + at, qKey, qDigits);
+                memcpy(slab.get() + at + qDigits, k, (size_t) (le - k));
+                slab[at + len - 1] = '\n';
+                return true;
+            });
+        }
+    }
+    // pass 3: every target's lines parsed, swapped, sorted and printed (:239-318).  Blocks of keys on the team; a block's entries lie back
+    // to back in the block's buffer, so the result is the blocks' buffers one after the other
+    sd::Evaluer ev;
+    sd::initEvaluer(ev, firstDbResidues);
+    const size_t BLOCK = 1024, nBlocks = ((size_t) maxKey + BLOCK) / BLOCK;
+    std::vector<std::string> blockText(nBlocks);
+    std::vector<uint64_t> outLen((size_t) maxKey + 1, 0);
+    std::vector<uint8_t> written((size_t) maxKey + 1, 0);
+    uint64_t rowsOut = 0;
+#pragma omp parallel reduction(+ : rowsOut)
+    {
+        std::vector<SwapRec> recs;
+        char head[16 * 12 + 64];
+#pragma omp for schedule(dynamic, 1)
+        for (size_t b = 0; b < nBlocks; b++) {
+            std::string &text = blockText[b];
+            const size_t k1 = std::min<size_t>((size_t) maxKey + 1, (b + 1) * BLOCK);
+            for (size_t key = b * BLOCK; key < k1; key++) {
+                recs.clear();
+                bool evalBreak = false, ok = true;
+                swapForLines(slab.get() + start[key], slab.get() + start[key + 1], [&](const char *ls, const char *le) {
+                    const char *col[12];
+                    const uint32_t cols = swapColumns(ls, le, col, 11);
+                    SwapRec r;
+                    memset(&r, 0, sizeof(r));
+                    r.dbKey = (uint32_t) swapAtoi(ls, le);
+                    if (!isAlignment) {
+                        if (cols != 3) return ok = false;   // QueryMatcher::parsePrefilterHit
+                        r.score = swapAtoi(col[1], le);
+                        // the diagonal is a 16-bit value on both sides of the sign change (:281)
+                        r.diag = (int32_t) (int16_t) (uint16_t) ((int32_t) (int16_t) (uint16_t) swapAtoi(col[2], le) * -1);
+                        r.eval = (double) -static_cast<float>(r.score);
+                        recs.push_back(r);
+                        return true;
+                    }
+                    if (cols != 10 && cols != 11) return ok = false;   // Matcher::parseAlignmentRecord (ORF columns are not on this path)
+                    r.score = swapAtoi(col[1], le);
+                    double sid = 0.0;
+                    std::from_chars(col[2], col[3] - 1, sid);
+                    r.seqId = (float) sid;
+                    // what was the target is the query now
+                    r.dbStart = swapAtoi(col[4], le);
+                    r.dbEnd = swapAtoi(col[5], le);
+                    r.dbLen = (uint32_t) swapAtoi(col[6], le);
+                    r.qStart = swapAtoi(col[7], le);
+                    r.qEnd = swapAtoi(col[8], le);
+                    r.qLen = swapAtoi(col[9], le);
+                    if (cols == 11) {
+                        r.bt = col[10];
+                        r.btLen = (uint32_t) (le - col[10]);
+                    }
+                    const double raw = sd::computeRawScoreFromBitScore(ev, (double) r.score);
+                    r.eval = sd::computeEvalue(ev, raw, (double) (uint32_t) r.qLen);   // the length of the sequence that was the target
+                    if (r.eval > evalThr) evalBreak = true;
+                    else recs.push_back(r);
+                    return true;
+                });
+                if (!ok) {
+#pragma omp atomic write
+                    bad = true;
+                    continue;
+                }
+                if (recs.empty()) {
+                    // a key without rows: an empty entry when the DB has the key or rows were dropped (:314-316)
+                    written[key] = evalBreak || exists[key];
+                    continue;
+                }
+                if (recs.size() > 1) std::sort(recs.begin(), recs.end(), swapRecLess);
+                const size_t before = text.size();
+                for (const SwapRec &r : recs) {
+                    char *p = sd::u32toa(r.dbKey, head);
+                    *p++ = '\t';
+                    p = sd::i32toa(r.score, p);
+                    *p++ = '\t';
+                    if (!isAlignment) {
+                        p = sd::i32toa(r.diag, p);
+                    } else {
+                        p = sd::seqIdToBuffer(r.seqId, p);
+                        *p++ = '\t';
+                        p += snprintf(p, 32, "%.3E", r.eval);
+                        for (const int32_t v : {r.qStart, r.qEnd, r.qLen, r.dbStart, r.dbEnd, (int32_t) r.dbLen}) {
+                            *p++ = '\t';
+                            p = sd::i32toa(v, p);
+                        }
+                        if (hasBacktrace) *p++ = '\t';
+                    }
+                    text.append(head, (size_t) (p - head));
+                    if (isAlignment && hasBacktrace && r.btLen) {
+                        const size_t at = text.size();
+                        text.append(r.bt, r.btLen);
+                        for (size_t x = at; x < text.size(); x++) {
+                            if (text[x] == 'I') text[x] = 'D';
+                            else if (text[x] == 'D') text[x] = 'I';
+                        }
+                    }
+                    text.push_back('\n');
+                }
+                rowsOut += recs.size();
+                outLen[key] = text.size() - before;
+                written[key] = 1;
+            }
+        }
+    }
+    if (bad) return SD_EINVAL;
+    std::vector<uint64_t> blockStart(nBlocks + 1, 0);
+    for (size_t b = 0; b < nBlocks; b++) blockStart[b + 1] = blockStart[b] + blockText[b].size();
+    S->text.reset(new char[blockStart[nBlocks] + 1]);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (size_t b = 0; b < nBlocks; b++)
+        if (!blockText[b].empty()) memcpy(S->text.get() + blockStart[b], blockText[b].data(), blockText[b].size());
+    uint64_t at = 0;
+    for (size_t key = 0; key <= maxKey; key++) {
+        if (!written[key]) continue;
+        S->keys.push_back((uint32_t) key);
+        at += outLen[key];
+        S->off.push_back(at);
+    }
+    S->rowsIn = rowsIn;
+    S->rowsOut = rowsOut;
+    *out = S.release();
+    return SD_OK;
+}
+
+int sd_host_swapresults(uint32_t nIn, const uint32_t *inKeys, const uint64_t *inOff, const char *inText, uint64_t firstDbResidues,
+                        const uint32_t *secondDbKeys, uint32_t nSecondDbKeys, double evalThr, int gapOpen, int gapExtend, sd_swap **out) {
+    if (nIn && (!inOff || !inText)) return SD_EINVAL;
+    std::vector<const char *> data(nIn);
+    std::vector<uint64_t> len(nIn);
+    for (uint32_t i = 0; i < nIn; i++) {
+        if (inOff[i + 1] < inOff[i]) return SD_EINVAL;
+        data[i] = inText + inOff[i];
+        len[i] = inOff[i + 1] - inOff[i];
+    }
+    return sd_host_swapresults_entries(nIn, inKeys, data.data(), len.data(), firstDbResidues, secondDbKeys, nSecondDbKeys, evalThr, gapOpen,
+                                       gapExtend, out);
+}
+
+int sd_swap_get(sd_swap *s, uint32_t *nEntries, const uint32_t **keys, const uint64_t **off, const char **text, uint64_t *rowsIn,
+                uint64_t *rowsOut) {
+    if (!s) return SD_EINVAL;
+    if (nEntries) *nEntries = (uint32_t) s->keys.size();
+    if (keys) *keys = s->keys.data();
+    if (off) *off = s->off.data();
+    if (text) *text = s->text.get();
+    if (rowsIn) *rowsIn = s->rowsIn;
+    if (rowsOut) *rowsOut = s->rowsOut;
+    return SD_OK;
+}
+
+void sd_swap_destroy(sd_swap *s) { delete s; }
+
+}  // extern "C"

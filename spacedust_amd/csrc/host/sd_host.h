@@ -154,6 +154,7 @@ struct Evaluer {
 void initEvaluer(Evaluer &e, uint64_t dbResidues);
 double computeEvalue(const Evaluer &e, double score, double qLen);
 double computeBitScore(const Evaluer &e, double score);
+double computeRawScoreFromBitScore(const Evaluer &e, double bitScore);
 
 // ---------------------------------------------------------------------------
 // Alignment post-processing / text (M/src/alignment/Matcher.cpp:100-137,166-185,280-327;

@@ -5,11 +5,16 @@
 Every timed call ends in a device synchronise inside the library; the first build and the first query pass are warm-up.
 
     python tools/bench_target_profile.py [--positions 1000000] [--queries 8192] [--runs 3] [--out profiles/target_profile.txt]
+    python tools/bench_target_profile.py --search      (adds: the same input as DBs through `sdgpu prefilter | swapresults | align |
+                                                        swapresults` one by one and through `sdgpu search`, wall time of each process)
 
 The reference's build of the same input on a CPU: python tools/make_golden_target_profile.py --time-build REPS THR (dev container)."""
 import argparse
 import os
+import struct
+import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -19,6 +24,54 @@ sys.path.insert(0, ROOT)
 GOLD = os.path.join(ROOT, 'tests', 'golden', 'profile_vectors.npz')
 
 
+def write_db(path, payloads, dbtype):
+    """entry i = payloads[i] with key i, in the reference's DB layout (data, .index, .dbtype)"""
+    off = 0
+    with open(path, 'wb') as f, open(path + '.index', 'w') as ix:
+        for key, p in enumerate(payloads):
+            f.write(p + b'\0')
+            ix.write('%d\t%d\t%d\n' % (key, off, len(p) + 1))
+            off += len(p) + 1
+    with open(path + '.dbtype', 'wb') as f:
+        f.write(struct.pack('<i', dbtype))
+
+
+def search_leg(log, data, poff, seqs, sensitivity, runs):
+    """the target-profile search on DBs: the four modules one by one, then `sdgpu search` (which runs them in one process with the
+    target resident); every time is the wall time of one process, DB loads and writes included"""
+    sdgpu = os.path.join(ROOT, 'spacedust_amd', 'sdgpu')
+    threads = str(min(16, os.cpu_count() or 1))
+    with tempfile.TemporaryDirectory() as tmp:
+        q, t = os.path.join(tmp, 'seq'), os.path.join(tmp, 'prof')
+        write_db(q, [s.encode() + b'\n' for s in seqs], 0)
+        write_db(t, [data[int(poff[i]):int(poff[i + 1])] for i in range(len(poff) - 1)], 2)
+        common = ['--threads', threads, '-v', '0']
+        pref = ['-s', str(sensitivity), '--max-seqs', '300', '-c', '0', '--cov-mode', '0', '--comp-bias-corr', '1', '--min-ungapped-score', '15']
+        aln = ['-a', '1', '-e', '0.001', '--max-seqs', '2147483647', '-c', '0', '--cov-mode', '0']
+        steps = (('prefilter', [q, t, tmp + '/pref'] + pref), ('swapresults (prefilter rows)', [q, t, tmp + '/pref', tmp + '/pref_swapped', '-e', '0.001']),
+                 ('align', [t, q, tmp + '/pref_swapped', tmp + '/aln_swapped'] + aln),
+                 ('swapresults (alignments)', [t, q, tmp + '/aln_swapped', tmp + '/result', '-e', '0.001']))
+
+        def rows(db):
+            with open(db, 'rb') as f:
+                return f.read().count(b'\n')
+        for r in range(runs):
+            total = 0.0
+            for name, args in steps:
+                t0 = time.time()
+                subprocess.check_call([sdgpu, name.split()[0]] + args + common)
+                dt = time.time() - t0
+                total += dt
+                log('search run %d: %-28s %.3f s' % (r + 1, name, dt))
+            log('search run %d: the four steps                 %.3f s (%d prefilter rows, %d aligned, %d after the second swap)'
+                % (r + 1, total, rows(tmp + '/pref'), rows(tmp + '/aln_swapped'), rows(tmp + '/result')))
+            t0 = time.time()
+            subprocess.check_call([sdgpu, 'search', q, t, tmp + '/result_search', tmp + '/tmp', '-e', '0.001'] + pref + common)
+            log('search run %d: sdgpu search                   %.3f s' % (r + 1, time.time() - t0))
+            same = all(open(tmp + '/result' + x, 'rb').read() == open(tmp + '/result_search' + x, 'rb').read() for x in ('', '.index'))
+            log('search run %d: `search` wrote the bytes of the four steps: %s' % (r + 1, same))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--positions', type=int, default=1000000)
@@ -26,6 +79,7 @@ def main():
     ap.add_argument('--runs', type=int, default=3)
     ap.add_argument('--sensitivity', type=float, default=4.0)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--search', action='store_true', help='also time the target-profile search on DBs (four modules, then `search`)')
     a = ap.parse_args()
     from spacedust_amd import api
     lines = []
@@ -78,6 +132,9 @@ def main():
     log('sd_prefilter_batch, %d sequence queries (%d residues) against it: median %.3f s of %d runs; %d exact k-mers looked up, %d index hits, '
         '%d rows; %.3g queries/s'
         % (len(seqs), int(qoff[-1]), med, len(times), int(stats[:, 0].sum()), int(stats[:, 1].sum()), int(cnt.sum()), len(seqs) / med))
+    if a.search:
+        del t
+        search_leg(log, data, poff, seqs, a.sensitivity, a.runs)
     if a.out:
         with open(a.out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
