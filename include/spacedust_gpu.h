@@ -411,6 +411,54 @@ int sd_rescore_diagonal_batch(sd_ctx *ctx, const sd_rescore_params *par, const s
                               uint32_t nHits, const uint32_t *hitQuery, const uint32_t *hitTarget, const uint16_t *hitDiagonal,
                               sd_rescore_result *out);
 
+/* ---- alignment expansion (`expandaln`, `clustersearch --profile-cluster-search 1`) ------------------------------------------
+ * Replaces BacktraceTranslator::translateResult (M/src/commons/BacktraceTranslator.h:51-153) as expandaln calls it for every
+ * (A -> B row, B -> C row) pair (M/src/util/expandaln.cpp:310-316), on run lists: a backtrace is its runs, one uint32 each,
+ * (length << 2) | state with state 0 = M, 1 = I, 2 = D -- what the DB text holds ("12M3I" = two runs; the text's "0M" is a run of
+ * one column, Matcher::uncompressAlignment).  AB row i has the runs abRuns[abRunOff[i] .. abRunOff[i + 1]) and reaches the BC
+ * entry ("cluster") abCluster[i]: the BC rows bcRowOff[c] .. bcRowOff[c + 1], each with its own starts and runs.  abCluster[i] =
+ * UINT32_MAX: the B key has no BC entry, the row makes no pair.  The pairs are numbered AB row by AB row, inside a row in the order
+ * of the cluster's rows; results[p] belongs to pair p.
+ * Pass 1 (sd_expand_batch) writes one record per pair; the caller selects (expandaln.cpp:322-377); pass 2 (sd_expand_backtraces)
+ * writes the run-length text of the kept pairs of the context's LAST sd_expand_batch call, as Matcher::compressAlignment prints
+ * it (a backtrace that does not begin with M begins "0M"), into one pool: pair keptPairs[k] at poolOff[k] .. poolOff[k + 1]).
+ * mode 0 (EXPAND_TRANSFER_EVALUE) needs no sequence: queries / targets / abQuery / bcTarget may be NULL.  mode 1
+ * (EXPAND_RESCORE_BACKTRACE) also walks the printed backtrace from (aStart, cStart) as rescoreResultByBacktrace does
+ * (expandaln.cpp:27-76): M adds matrix[a][c] plus the query position's composition bias (the set's int8 bias, 0 without one) and counts
+ * identities, I advances the query and D the target -- the opposite reading to the ends above --, a gap run costs gapOpen for its first
+ * column and gapExtend for every other; rawScore and identities come back in the record.  abQuery[i]: the sequence of `queries` AB
+ * row i belongs to; bcTarget[r]: the sequence of `targets` BC row r names.  The reference does not keep this walk inside the
+ * sequences (it reads stale buffer contents there); here an M column outside either sequence is never read: the pair comes back with
+ * SD_EXPAND_LEAVES_SEQUENCE and rawScore / identities 0 -- a documented deviation, callers drop such pairs.  Profile sets:
+ * SD_EUNSUPPORTED.
+ * SD_EINVAL: a run with state 3 or length 0, offsets that are not ascending, a cluster index that is neither below nClusters nor
+ * UINT32_MAX, 2^32 pairs or more, a kept pair that is out of range (a kept pair without a printed backtrace gets no text). */
+typedef struct {
+    int32_t mode;            /* --expansion-mode: 0 or 1 */
+    int32_t gapOpen, gapExtend; /* mode 1 */
+    int8_t matrix[21 * 21];  /* mode 1: blosum62 at 2 bit-factor, scoreBias 0: sd_host_matrix(h, 0, ...) */
+} sd_expand_params;
+typedef struct {
+    int32_t aStart, aEnd;    /* qStartPos, qEndPos of the A -> C result: the end counts every emitted M and D column */
+    int32_t cStart, cEnd;    /* dbStartPos, dbEndPos: the end counts every emitted M and I column */
+    int32_t btLen;           /* columns of the printed backtrace: up to the last emitted M (0: no M, the pair is skipped) */
+    int32_t nRuns;           /* runs of the printed text, a leading "0M" included */
+    int32_t textLen;         /* bytes of the printed text */
+    int32_t flags;           /* SD_EXPAND_EMPTY, SD_EXPAND_LEAVES_SEQUENCE */
+    int32_t rawScore, identities; /* mode 1; 0 in mode 0 */
+    uint32_t abRow, bcRow;   /* the pair */
+} sd_expand_result;
+enum { SD_EXPAND_EMPTY = 1, SD_EXPAND_LEAVES_SEQUENCE = 2 };
+int sd_expand_batch(sd_ctx *ctx, const sd_expand_params *par, uint32_t nAB, const int32_t *abStartA, const int32_t *abStartB,
+                    const uint64_t *abRunOff, const uint32_t *abRuns, const uint32_t *abCluster, uint32_t nClusters,
+                    const uint64_t *bcRowOff, const int32_t *bcStartB, const int32_t *bcStartC, const uint64_t *bcRunOff,
+                    const uint32_t *bcRuns, const sd_seqset *queries, const sd_seqset *targets, const uint32_t *abQuery,
+                    const uint32_t *bcTarget, uint64_t resultCap, sd_expand_result *results, uint64_t *nPairs);
+int sd_expand_backtraces(sd_ctx *ctx, uint64_t nKept, const uint64_t *keptPairs, char *pool, uint64_t poolCap, uint64_t *poolOff);
+/* of the context's last sd_expand_batch and the sd_expand_backtraces calls after it: pairs, runs read by pass 1 (both sides of every
+ * pair), bytes written by the kernels (records + text) */
+int sd_expand_last_stats(sd_ctx *ctx, uint64_t *pairs, uint64_t *runsRead, uint64_t *bytesWritten);
+
 /* ---- Profile queries (`--num-iterations` > 1 feeds profile DBs to prefilter and align) ----
  * sd_host_map_profiles restates Sequence::mapProfile (M/src/commons/Sequence.cpp:241-292) for n profile DB entries
  * (25 bytes per position, Sequence.h:458-471; byteOffsets[n+1] into profileData): per position the query letter,

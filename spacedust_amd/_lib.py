@@ -54,6 +54,16 @@ RESCORE_DTYPE = np.dtype([('score', '<i4'), ('startPos', '<i4'), ('endPos', '<i4
                           ('diagonal', '<i4'), ('idCnt', '<i4'), ('pad', '<i4')])   # sd_rescore_result
 
 
+class ExpandParams(C.Structure):   # sd_expand_params
+    _fields_ = [('mode', C.c_int32), ('gapOpen', C.c_int32), ('gapExtend', C.c_int32), ('matrix', C.c_int8 * 441)]
+
+
+EXPAND_DTYPE = np.dtype([('aStart', '<i4'), ('aEnd', '<i4'), ('cStart', '<i4'), ('cEnd', '<i4'), ('btLen', '<i4'), ('nRuns', '<i4'),
+                         ('textLen', '<i4'), ('flags', '<i4'), ('rawScore', '<i4'), ('identities', '<i4'), ('abRow', '<u4'),
+                         ('bcRow', '<u4')])   # sd_expand_result
+EXPAND_EMPTY, EXPAND_LEAVES_SEQUENCE = 1, 2
+
+
 HIT_DTYPE = np.dtype([('seqId', '<u4'), ('score', '<i4'), ('diagonal', '<u2'), ('pad', '<u2')])
 
 
@@ -275,6 +285,10 @@ def load():
         'sd_swap_get': (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_uint64),
                                   C.POINTER(C.c_uint64)]),
         'sd_swap_destroy': (None, [_vp]),
+        'sd_expand_batch': (C.c_int, [_vp, C.POINTER(ExpandParams), C.c_uint32] + [_vp] * 5 + [C.c_uint32] + [_vp] * 9 +
+                            [C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
+        'sd_expand_backtraces': (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp]),
+        'sd_expand_last_stats': (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     }
     missing = []
     for name, (res, args) in sig.items():

@@ -828,3 +828,75 @@ def clusterhits(ctx, host, hit_off, q_pos, t_pos, strands, pval, nq, max_gene_ga
                                              ptr(out['pCO']), ptr(out['pMH']), ptr(out['size'])),
            'sd_clusterhits_batch')
     return out
+
+
+EXPAND_STATES = 'MID'
+
+
+def cigar_runs(cigar):
+    """run-length backtrace text -> the uint32 runs sd_expand_batch takes, (length << 2) | state with M = 0, I = 1, D = 2; a count of
+    0 is one column (Matcher::uncompressAlignment)"""
+    runs, n = [], 0
+    for ch in cigar:
+        if ch.isdigit():
+            n = n * 10 + int(ch)
+        else:
+            runs.append((max(n, 1) << 2) | EXPAND_STATES.index(ch))
+            n = 0
+    return runs
+
+
+def expand(ctx, ab_start_a, ab_start_b, ab_runs, ab_cluster, bc_rows, mode=0, want_text=None, queries=None, targets=None, ab_query=None,
+           bc_target=None, matrix=None, gap_open=11, gap_extend=1):
+    """sd_expand_batch (+ sd_expand_backtraces): BacktraceTranslator::translateResult for every (AB row, BC row of its cluster) pair.
+    ab_runs: one run list per AB row (cigar_runs); ab_cluster[i]: index into bc_rows or -1 (the B key has no BC entry);
+    bc_rows: per cluster a list of (startB, startC, runs).  Returns EXPAND_DTYPE records, pair p = the p-th (AB row, member) in row order.
+    mode 1 (the walk of rescoreResultByBacktrace: rawScore, identities, EXPAND_LEAVES_SEQUENCE): queries / targets are SeqSets (the
+    queries' set carries the composition bias), ab_query[i] / bc_target[flat BC row] the sequences of the rows, matrix the 21 x 21 int8 one.
+    want_text: None, True (every pair with a printed backtrace) or an array of pair indices -> also (pool bytes, offsets[len + 1])."""
+    L = ctx.L
+    n_ab = len(ab_runs)
+    ab_off = np.zeros(n_ab + 1, np.uint64)
+    ab_off[1:] = np.cumsum([len(r) for r in ab_runs], dtype=np.uint64)
+    ab_flat = np.ascontiguousarray(np.concatenate([np.asarray(r, np.uint32) for r in ab_runs] + [np.zeros(0, np.uint32)]), np.uint32)
+    row_off = np.zeros(len(bc_rows) + 1, np.uint64)
+    row_off[1:] = np.cumsum([len(c) for c in bc_rows], dtype=np.uint64)
+    rows = [r for c in bc_rows for r in c]
+    bc_sb = np.array([r[0] for r in rows], np.int32)
+    bc_sc = np.array([r[1] for r in rows], np.int32)
+    bc_off = np.zeros(len(rows) + 1, np.uint64)
+    bc_off[1:] = np.cumsum([len(r[2]) for r in rows], dtype=np.uint64)
+    bc_flat = np.ascontiguousarray(np.concatenate([np.asarray(r[2], np.uint32) for r in rows] + [np.zeros(0, np.uint32)]), np.uint32)
+    sa = np.ascontiguousarray(ab_start_a, np.int32)
+    sb = np.ascontiguousarray(ab_start_b, np.int32)
+    clu = np.ascontiguousarray(np.asarray(ab_cluster, np.int64) & 0xFFFFFFFF, np.uint32)
+    assert len(sa) == len(sb) == len(clu) == n_ab
+    n_pairs = int(sum(len(bc_rows[c]) for c in np.asarray(ab_cluster, np.int64) if 0 <= c < len(bc_rows)))
+    par = _lib.ExpandParams()
+    par.mode, par.gapOpen, par.gapExtend = int(mode), int(gap_open), int(gap_extend)
+    if matrix is not None:
+        C.memmove(par.matrix, np.ascontiguousarray(matrix, np.int8).ctypes.data, 441)
+    abq = np.ascontiguousarray(ab_query, np.uint32) if ab_query is not None else None
+    bct = np.ascontiguousarray(bc_target, np.uint32) if bc_target is not None else None
+    assert abq is None or len(abq) == n_ab
+    assert bct is None or len(bct) == len(rows)
+    res = np.zeros(n_pairs, _lib.EXPAND_DTYPE)
+    got = C.c_uint64()
+    _check(ctx.h, L.sd_expand_batch(ctx.h, C.byref(par), n_ab, ptr(sa), ptr(sb), ptr(ab_off), ptr(ab_flat), ptr(clu), len(bc_rows),
+                                    ptr(row_off), ptr(bc_sb), ptr(bc_sc), ptr(bc_off), ptr(bc_flat), queries.h if queries is not None else None,
+                                    targets.h if targets is not None else None, ptr(abq), ptr(bct), n_pairs, ptr(res), C.byref(got)),
+           'sd_expand_batch')
+    assert got.value == n_pairs
+    if want_text is None:
+        return res
+    kept = np.flatnonzero(res['btLen'] > 0).astype(np.uint64) if want_text is True else np.ascontiguousarray(want_text, np.uint64)
+    pool = np.zeros(int(res['textLen'][kept.astype(np.int64)].sum()) + 1, np.uint8)
+    off = np.zeros(len(kept) + 1, np.uint64)
+    _check(ctx.h, L.sd_expand_backtraces(ctx.h, len(kept), ptr(kept), ptr(pool), len(pool), ptr(off)), 'sd_expand_backtraces')
+    return res, pool[:int(off[-1])], off
+
+
+def expand_last_stats(ctx):
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(ctx.h, ctx.L.sd_expand_last_stats(ctx.h, C.byref(a), C.byref(b), C.byref(c)), 'sd_expand_last_stats')
+    return dict(pairs=a.value, runs_read=b.value, bytes_written=c.value)

@@ -176,6 +176,7 @@ int result2profileModule(const Args &a);
 int subtractdbsModule(const Args &a);
 int mergedbsModule(const Args &a);
 int swapresultsModule(const Args &a);
+int expandalnModule(const Args &a);
 
 }  // namespace sdcli
 #endif

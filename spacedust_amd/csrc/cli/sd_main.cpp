@@ -25,7 +25,7 @@ const Module kModules[] = {
     {"rescorediagonal", rescorediagonalModule, "ungapped alignment on each hit's diagonal on the GPU (--alignment-mode 4): <queryDB> <targetDB> <prefilterDB> <resultDB>"},
     {"clusterhits", clusterhitsModule, "agglomerative hit clustering on the GPU: <querySetDB> <targetSetDB> <matchesDB> <clustersDB>"},
     {"search", searchModule, "prefilter + align (the --num-iterations profile loop; a profile target DB through swapresults): <queryDB> <targetDB> <alignmentDB> <tmpDir>"},
-    {"clustersearch", clustersearchModule, "the whole --search-mode 0 workflow in one process: <querySetDB> <targetSetDB> <out.tsv> <tmpDir>"},
+    {"clustersearch", clustersearchModule, "the whole --search-mode 0 workflow in one process (--profile-cluster-search 1: through the cluster representatives' profiles and expandaln): <querySetDB> <targetSetDB> <out.tsv> <tmpDir>"},
     {"prefixid", prefixidModule, "host glue: prefix every line of a result DB with its entry key"},
     {"besthitbyset", besthitbysetModule, "host glue: best hit per (query protein, target set)"},
     {"mergeresultsbyset", mergeresultsbysetModule, "host glue: concatenate the entries of a set's members"},
@@ -35,6 +35,7 @@ const Module kModules[] = {
     {"subtractdbs", subtractdbsModule, "host glue: remove from result DB A the targets listed in result DB B"},
     {"mergedbs", mergedbsModule, "host glue: merge the entries of several DBs by key"},
     {"swapresults", swapresultsModule, "host glue: re-key a prefilter / alignment DB by its targets: <queryDB> <targetDB> <resultDB> <outDB>"},
+    {"expandaln", expandalnModule, "A->B alignments carried over to the C's each B is aligned with, backtraces translated on the GPU: <queryDB> <targetDB> <resultDB_AB> <resultDB_BC> <outDB>"},
     {"createindex", createindexModule, "target k-mer index built once, in the reference's createindex file layout: <sequenceDB> <tmpDir>"},
     {"createsetdb", createsetdbModule, "FASTA files (Prodigal headers) -> setDB in the createsetdb layout"},
 };

@@ -76,7 +76,6 @@ void fillParams(const Args &a, sd_search_params &p, bool clustersearchDefaults) 
 int checkWorkflowFlags(const Args &a) {
     if (a.integer("--compressed", 0) != 0) return fail("--compressed 1 is not supported");
     if (a.integer("--search-mode", 0) != 0) return fail("--search-mode 1/2 (Foldseek) are outside this path; only --search-mode 0");
-    if (a.flag("--profile-cluster-search", false)) return fail("--profile-cluster-search is outside this path");
     if (a.integer("--gpu", 0) != 0) return fail("--gpu 1 selects the reference's CUDA ungapped prefilter (a different algorithm); run without it");
     if (a.multi("--sub-mat", "aa", "blosum62.out") != "blosum62.out") return fail("--sub-mat: only blosum62.out is built into this path");
     if (a.multi("--seed-sub-mat", "aa", "VTML80.out") != "VTML80.out") return fail("--seed-sub-mat: only VTML80.out is built into this path");
@@ -1140,9 +1139,58 @@ int targetProfileSearch(const Args &a, const std::string &Q, const std::string &
     return runModule(swapresultsModule, "swapresults", {T, Q, alnSwapped, result}, swap);
 }
 
+// `clustersearch --profile-cluster-search 1` (R/src/workflow/clustersearch.cpp:60-75, R/data/clustersearch.sh:69-80): the queries are
+// searched against the profiles of the target's cluster representatives (<T>_clu_rep_profile), every hit on a representative is carried
+// over to the members of its cluster by `expandaln` along <T>_clu_aln, and the module chain runs on the expanded alignment DB.  The
+// reference's default --exhaustive-search 1 sends its `search` down searchslicedtargetprofile.sh, which is not built: this path is
+// searchtargetprofile.sh (targetProfileSearch above) and wants --exhaustive-search 0 said.
+int profileClusterSearch(const Args &a) {
+    if (a.pos.size() != 4) return fail("usage: clustersearch <querySetDB> <targetSetDB> <out.tsv> <tmpDir> [options]");
+    if (int rc = checkWorkflowFlags(a)) return rc;
+    if (a.integer("--num-iterations", 1) > 1) return fail("Profile-profile cluster searches are currently not supported. Please use only 1 iteration.");
+    if (!a.has("--exhaustive-search") || a.has("--exhaustive-search#toggled") || a.str("--exhaustive-search", "1") != "0")
+        return fail("--profile-cluster-search 1 runs with --exhaustive-search 1 by default, which searches through searchslicedtargetprofile "
+                    "(not implemented); pass --exhaustive-search 0 for the searchtargetprofile chain");
+    if (envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1) return fail("--profile-cluster-search 1 runs on one rank");
+    if (a.integer("--prefilter-mode", 0) != 0) return fail("--profile-cluster-search 1 with --prefilter-mode " + a.str("--prefilter-mode", "0") + " is not implemented");
+    if (a.integer("--alignment-mode", 2) == 4) return fail("--profile-cluster-search 1 with --alignment-mode 4: cannot use the ungapped alignment mode with profile databases");
+    const std::string Q = a.pos[0], T = a.pos[1], tmp = a.pos[3];
+    const std::string repProfile = T + "_clu_rep_profile", cluAln = T + "_clu_aln";
+    if (sddb::readDbType(repProfile) < 0 || !sddb::fileExists(repProfile + ".index"))
+        return fail("--profile-cluster-search 1 needs " + repProfile + " (clusterdb writes it)");
+    if (sddb::readDbType(cluAln) < 0 || !sddb::fileExists(cluAln + ".index")) return fail("--profile-cluster-search 1 needs " + cluAln + " (clusterdb writes it)");
+    if (!isProfileDb(repProfile)) return fail(repProfile + " is not a profile database");
+    mkdir(tmp.c_str(), 0777);
+    Args s = a;   // the workflow's defaults for this mode (R/src/workflow/clustersearch.cpp:9-37,60-66)
+    auto def = [&](const char *f, const char *v) { if (!s.has(f)) s.opt[f] = v; };
+    def("-s", "5.7");
+    def("--cov-mode", "2");
+    def("-c", "0.8");
+    def("-e", "0.001");
+    def("--max-seqs", "100");
+    def("--min-aln-len", "30");
+    def("--alignment-mode", "2");
+    def("-a", "1");
+    for (const char *db : {"/result_clu", "/result", "/result_prefixed", "/aggregate", "/aggregate_merged", "/matches", "/matches_h", "/clusters", "/clusters_h"})
+        sddb::removeDb(tmp + db);
+    const std::string resultClu = tmp + "/result_clu";
+    struct RemoveTmp {
+        bool on;
+        std::string db;
+        ~RemoveTmp() { if (on) sddb::removeDb(db); }
+    } removeTmp{a.integer("--keep-tmp", 0) == 0, resultClu};
+    if (int rc = targetProfileSearch(s, Q, repProfile, resultClu, tmp + "/search")) return rc;
+    // clustersearch.sh:77-79 passes the threads parameter only: expandaln runs at its own defaults
+    std::vector<std::string> ex = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
+    if (a.has("--device")) ex = with(ex, {"--device", a.str("--device", "0")});
+    if (int rc = runModule(expandalnModule, "expandaln", {Q, repProfile, resultClu, cluAln, tmp + "/result"}, ex)) return rc;
+    return clusterChain(a, Q, T, tmp);
+}
+
 }  // namespace
 
 int searchModule(const Args &a0) {
+    if (a0.flag("--profile-cluster-search", false)) return fail("--profile-cluster-search is a flag of clustersearch");
     if (int rc = checkPrefilterMode(a0)) return rc;
     // a profile target DB on the one path that takes it: sequence queries, the k-mer prefilter, one pass, one rank, gapped alignments.
     // Every other combination goes on to its own path below and is refused there
@@ -1179,6 +1227,7 @@ int searchModule(const Args &a0) {
 }
 
 int clustersearchModule(const Args &a0) {
+    if (a0.flag("--profile-cluster-search", false)) return profileClusterSearch(a0);
     if (int rc = checkPrefilterMode(a0)) return rc;
     if (a0.integer("--alt-ali", 0) != 0) return checkAltAli(a0, true);
     Args a = a0;

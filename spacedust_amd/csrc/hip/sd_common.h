@@ -43,6 +43,15 @@ struct sd_ctx {
     bool sharedStart = false; // sd_sw_set_shared_start: narrow start-position tasks of a query of 129 .. 768 rows share the query's one profile
     bool narrowFinal = false; // sd_sw_set_narrow_final: a narrow forward score below 1023 is final, only the other saturating pairs rerun wide
     uint64_t d2hRecordBytes = 0, d2hPoolBytes = 0;  // what the alignment calls brought back (sd_sw_download_bytes)
+    // the last sd_expand_batch call as it lies in the workspace (valid until the next one): what sd_expand_backtraces walks again
+    struct ExpandState {
+        uint64_t nPairs = 0, runsRead = 0, bytesWritten = 0;
+        uint32_t nAB = 0;
+        const int32_t *abStartA = nullptr, *abStartB = nullptr, *bcStartB = nullptr, *bcStartC = nullptr;
+        const uint64_t *abRunOff = nullptr, *bcRowOff = nullptr, *bcRunOff = nullptr, *pairOff = nullptr;
+        const uint32_t *abRuns = nullptr, *bcRuns = nullptr, *abCluster = nullptr;
+        const sd_expand_result *res = nullptr;   // one record per pair
+    } expand;
     hipDeviceProp_t prop;
     // grow-only device workspace: hipMalloc/hipFree per call cost far more than the kernels they serve
     struct WsEntry { void *p = nullptr; size_t bytes = 0; };
