@@ -316,6 +316,18 @@ int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask, double mas
 int sd_target_build_profile(sd_ctx *ctx, int kmerSize, int kmerThr, const uint8_t *queryLetters, const uint8_t *consensus,
                             const int16_t *sortedScore /* positions x 20 */, const uint8_t *sortedIndex /* positions x 20 */,
                             const uint64_t *posOffsets, uint32_t nSeq, sd_target **out, uint64_t *stats);
+/* The similar-k-mer index of a SEQUENCE target DB, built on the device (--target-search-mode 1; the sequence branch of the same code,
+ * IndexBuilder.cpp:62,100,120-127): the lists hold KmerGenerator::generateKmerList of every window without X -- the product of the
+ * window's two sorted 3-mer rows at kmerThr, the sequence threshold itself (Prefiltering.cpp:525-527), no composition bias, possibly
+ * empty -- one entry per (k-mer, target) at the smallest position, lists in (target, position) order.  Nothing is masked: the lookup
+ * holds `residues` as they are.  ext3Score / ext3Index: sd_host_ext_matrix(3); they serve the build only and are not kept.
+ * sd_prefilter_batch on such a target is the exact lookup described above (par->kmerThr and qKmerBias ignored, stats[4q] the windows
+ * without X); sd_prefilter_profile_batch returns SD_EUNSUPPORTED.  sd_target_download, sd_target_sample_check and
+ * sd_target_build_peak work on it.  k = 6 only (SD_EUNSUPPORTED otherwise, and for a window whose list reaches 2^23 k-mers,
+ * KmerGenerator.h:45); a sequence of more than 65 535 residues is SD_EINVAL; SD_ENOMEM when the entry array, sized by the counted
+ * records, does not fit.  stats (nullable): [0] entries, [1] 0, [2] k-mer range passes, [3] k-mer records before the per-target dedupe. */
+int sd_target_build_similar(sd_ctx *ctx, int kmerSize, int kmerThr, const uint8_t *residues, const uint64_t *seqOffsets, uint32_t nSeq,
+                            const int16_t *ext3Score, const uint16_t *ext3Index, sd_target **out, uint64_t *stats);
 /* what a target holds on the device (any pointer may be NULL): masked residues, absolute list starts (tableSize + 1),
  * entries as (sequence id, position) */
 /* sampled check of an index too large to download: n (k-mer, sequence, position) triples = all entries of the nSample sequences

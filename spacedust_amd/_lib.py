@@ -179,6 +179,7 @@ def load():
         'sd_target_build': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                       C.POINTER(_vp), _vp]),
         'sd_target_build_profile': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(_vp), _vp]),
+        'sd_target_build_similar': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_uint32, _vp, _vp, C.POINTER(_vp), _vp]),
         'sd_target_download': (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp]),
         'sd_host_index_tables': (C.c_int, [_vp, _vp, _vp]),
         'sd_target_sample_check': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),

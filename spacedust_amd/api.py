@@ -653,6 +653,27 @@ class Target:
         self.build_stats = dict(entries=int(stats[0]), masked_residues=int(stats[1]), passes=int(stats[2]), records=int(stats[3]))
         return self
 
+    @classmethod
+    def build_similar_on_device(cls, ctx, host, residues, offsets, k=6, kmer_thr=112):
+        """sd_target_build_similar: the similar-k-mer index of a sequence target DB (--target-search-mode 1), built on the GPU from
+        the unmasked residues at the sequence threshold.  Sequence queries (api.prefilter) look up their own k-mers only against
+        it; api.prefilter_profile refuses it."""
+        self = cls.__new__(cls)
+        self.ctx, self.host, self.index = ctx, host, None
+        residues = np.ascontiguousarray(residues, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        s3, i3, _ = host.ext_matrix(3)
+        h = C.c_void_p()
+        stats = np.zeros(4, np.uint64)
+        _check(ctx.h, ctx.L.sd_target_build_similar(ctx.h, k, kmer_thr, ptr(residues), ptr(offsets), len(offsets) - 1, ptr(s3), ptr(i3),
+                                                    C.byref(h), ptr(stats)), 'sd_target_build_similar')
+        self.h = h
+        self.n = len(offsets) - 1
+        self.k = k
+        self.total = int(offsets[-1])
+        self.build_stats = dict(entries=int(stats[0]), masked_residues=int(stats[1]), passes=int(stats[2]), records=int(stats[3]))
+        return self
+
     def build_peak(self):
         """sd_target_build_peak: the device bytes sd_target_build held at the fullest point of its phases"""
         b = C.c_uint64()

@@ -117,6 +117,8 @@ int createindexModule(const Args &a) {
     if (a.pos.size() != 2) return fail("usage: createindex <sequenceDB> <tmpDir> [options]");
     if (a.integer("--spaced-kmer-mode", 1) != 1 || a.has("--spaced-kmer-pattern")) return fail("only the default spaced k-mer patterns are supported");
     if (a.integer("--split", 0) > 1) return fail("--split > 1 is not supported (the whole index is resident in HBM)");
+    if (a.integer("--target-search-mode", 0) != 0)
+        return fail("createindex --target-search-mode 1 is not implemented: the similar-k-mer index is built on the device by `prefilter --target-search-mode 1`");
     if (a.multi("--seed-sub-mat", "aa", "VTML80.out") != "VTML80.out") return fail("--seed-sub-mat: only VTML80.out is built in");
     const int threads = threadsOf(a);
     HostH host;

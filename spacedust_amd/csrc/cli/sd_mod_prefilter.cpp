@@ -289,7 +289,8 @@ int prefilterModule(const Args &a) {
         return fail("only the default spaced k-mer patterns are supported (--spaced-kmer-mode 1)");
     if (a.integer("--exact-kmer-matching", 0) != 0) return fail("--exact-kmer-matching 1 is not supported");
     if (!a.flag("--diag-score", true)) return fail("--diag-score 0 is not supported");
-    if (a.integer("--target-search-mode", 0) != 0) return fail("--target-search-mode 1 is not supported");
+    const long long tsm = a.integer("--target-search-mode", 0);
+    if (tsm != 0 && tsm != 1) return fail("--target-search-mode " + std::to_string(tsm) + ": 0 (regular k-mer index) or 1 (similar k-mer index)");
     if (a.integer("--mask-lower-case", 0) != 0 || a.integer("--mask-n-repeat", 0) != 0)
         return fail("--mask-lower-case / --mask-n-repeat are not supported");
     if (a.multi("--alph-size", "aa", "21") != "21") return fail("--alph-size aa:21 only");
@@ -310,6 +311,16 @@ int prefilterModule(const Args &a) {
     // are an error in the reference (Prefiltering.cpp:144-148).
     const bool profileTarget = tdb->profile;
     if (profileTarget && qdb->profile) return fail("Query-profiles cannot be searched against a target-profile database!");
+    // --target-search-mode 1 on a sequence target: the similar k-mers of every target window go into the index (at the sequence
+    // threshold, nothing masked) and the queries look up their own k-mers only (IndexBuilder.cpp:62,100; Prefiltering.cpp:176-179,525-527).
+    // A profile target is that kind of index already (isProfile || targetSearchMode): the flag changes nothing there.
+    const bool similarTarget = tsm == 1 && !profileTarget;
+    if (similarTarget && qdb->profile)
+        return fail("--target-search-mode 1 with a profile query database is not implemented (the reference allows it; the exact-lookup path "
+                    "here reads query sequences)");
+    // searched unsplit, as a profile target is: hundreds of index records per residue, which sd_target_footprint does not model
+    if (similarTarget && a.integer("--split", 0) > 1)
+        return fail("--split " + std::to_string(a.integer("--split", 0)) + ": --target-search-mode 1 searches the target unsplit (--split 0 or 1)");
     lap.mark("load DBs");
     info(a, "Query database size: %u type: %s\nTarget database size: %u type: %s\n", qdb->n, qdb->profile ? "Profile" : "Aminoacid", tdb->n,
          profileTarget ? "Profile" : "Aminoacid");
@@ -327,6 +338,8 @@ int prefilterModule(const Args &a) {
         if (a.integer("--split", 0) > 1)
             return fail("--split " + std::to_string(a.integer("--split", 0)) + ": a profile target database is searched unsplit (--split 0 or 1)");
         plan.k = (int) a.integer("-k", 0);
+    } else if (similarTarget) {
+        plan.k = (int) a.integer("-k", 0);   // unsplit (refused above): --split 0 means 1
     } else if (int rcP = resolveSplit(a, tdb->rd, tdb->totalResidues(), qdb->n, ctx.c, !residentTargetOf(a.pos[1], deviceOf(a)).empty(), plan)) {
         // (a workflow that holds this DB's index on this device has nothing left to decide)
         return rcP;
@@ -338,6 +351,11 @@ int prefilterModule(const Args &a) {
         if (PS.k != 6) return fail("-k " + std::to_string(PS.k) + ": the index of a profile target is built at k=6 only");
         PS.indexThr = PS.kmerThr;   // the similar k-mers are generated at the threshold itself
         PS.mask = false;            // --mask is ignored: nothing of a profile is masked (Prefiltering.cpp:172-174)
+    }
+    if (similarTarget) {
+        if (PS.k != 6) return fail("-k " + std::to_string(PS.k) + ": the similar-k-mer index of --target-search-mode 1 is built at k=6 only");
+        PS.indexThr = PS.kmerThr;   // the sequence threshold itself (Prefiltering.cpp:525-527)
+        PS.mask = false;            // --mask / --mask-prob are ignored: maskSequence is not called on this branch (IndexBuilder.cpp:120-131)
     }
     if (plan.target) return prefilterTargetSplit(a, host.h, ctx.c, *qdb, *tdb, sameDb, PS, plan, lap);
     const int k = PS.k, kmerThr = PS.kmerThr, indexThr = PS.indexThr;   // (profile searches index every k-mer: indexThr 0)
@@ -354,6 +372,7 @@ int prefilterModule(const Args &a) {
     // (the two kinds of target are different indexes: "p" in the masking field marks the similar-k-mer index of a profile DB)
     char tkey[96];
     if (profileTarget) snprintf(tkey, sizeof(tkey), "|%d|%d|p|%.6f|%d", k, indexThr, 0.0, deviceOf(a));
+    else if (similarTarget) snprintf(tkey, sizeof(tkey), "|%d|%d|s|%.6f|%d", k, indexThr, 0.0, deviceOf(a));   // "s": similar k-mers of sequences
     else snprintf(tkey, sizeof(tkey), "|%d|%d|%d|%.6f|%d", k, indexThr, mask ? 1 : 0, maskProb, deviceOf(a));
     const std::string targetKey = a.pos[1] + tkey;
     if (resident().enabled && resident().targets.count(targetKey)) {
@@ -364,10 +383,10 @@ int prefilterModule(const Args &a) {
         maskedRes = te.masked;
         info(a, "Target index resident from the previous module of this workflow\n");
     }
-    // (createindex does not index profile DBs: no TARGET.idx to look for)
-    const int got = target.t || profileTarget ? 1 : loadTargetIndex(a.pos[1], k, indexThr, mask ? 1 : 0, tdb->n, tdb->totalResidues(), loaded, &why);
+    // (createindex does not index profile DBs and writes no similar-k-mer index: no TARGET.idx to look for)
+    const int got = target.t || profileTarget || similarTarget ? 1 : loadTargetIndex(a.pos[1], k, indexThr, mask ? 1 : 0, tdb->n, tdb->totalResidues(), loaded, &why);
     if (got < 0) return fail(why);
-    if (got != 0 && !profileTarget && sddb::fileExists(a.pos[1] + ".idx.index")) info(a, "Index file not used: %s\n", why.c_str());
+    if (got != 0 && !profileTarget && !similarTarget && sddb::fileExists(a.pos[1] + ".idx.index")) info(a, "Index file not used: %s\n", why.c_str());
     if (target.t) {
         // resident
     } else if (profileTarget) {
@@ -376,6 +395,12 @@ int prefilterModule(const Args &a) {
                                   tdb->offsets.data(), tdb->n, &target.t, st);
         if (rc != SD_OK) return failCtx(ctx.c, rc, "sd_target_build_profile");
         nEntries = st[0];
+    } else if (similarTarget) {
+        uint64_t st[2] = {0, 0};
+        rc = sdBuildSimilarTarget(host.h, ctx.c, k, kmerThr, tdb->residues.data(), tdb->offsets.data(), tdb->n, &target.t, st);
+        if (rc != SD_OK) return failCtx(ctx.c, rc, "sd_target_build_similar");
+        nEntries = st[0];
+        info(a, "Target search mode 1: similar k-mers of every target window indexed, queries look up their own k-mers\n");
     } else if (got == 0) {
         nEntries = loaded.nEntries;
         info(a, "Use index %s.idx\n", a.pos[1].c_str());

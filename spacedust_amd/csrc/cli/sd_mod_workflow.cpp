@@ -1011,7 +1011,7 @@ int ungappedAlignSearch(const Args &a, const std::string &Q, const std::string &
     if (!ungapped)
         pref = with(pref, {"-s", a.str("-s", "5.7"), "-k", a.str("-k", "0"), "--mask", a.str("--mask", "1"), "--mask-prob", a.str("--mask-prob", "0.9")});
     // what each prefilter kind takes beyond that (ungappedprefilter has no index, bins or --add-self-matches)
-    const std::vector<const char *> kmerOnly = {"--device", "--bin-size", "--l2-cache-size", "--chunk-queries", "--add-self-matches"};
+    const std::vector<const char *> kmerOnly = {"--device", "--bin-size", "--l2-cache-size", "--chunk-queries", "--add-self-matches", "--target-search-mode"};
     const std::vector<const char *> ungappedOnly = {"--device", "--chunk-queries"};
     for (const char *f : ungapped ? ungappedOnly : kmerOnly)
         if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
@@ -1058,7 +1058,7 @@ int altAliSearch(const Args &a, const std::string &Q, const std::string &T, cons
                                                   a.str("--comp-bias-corr", "1")});
     if (!ungapped)
         pref = with(pref, {"-s", a.str("-s", "5.7"), "-k", a.str("-k", "0"), "--mask", a.str("--mask", "1"), "--mask-prob", a.str("--mask-prob", "0.9")});
-    const std::vector<const char *> kmerOnly = {"--device", "--bin-size", "--l2-cache-size", "--chunk-queries", "--add-self-matches"};
+    const std::vector<const char *> kmerOnly = {"--device", "--bin-size", "--l2-cache-size", "--chunk-queries", "--add-self-matches", "--target-search-mode"};
     const std::vector<const char *> ungappedOnly = {"--device", "--chunk-queries"};
     for (const char *f : ungapped ? ungappedOnly : kmerOnly)
         if (a.has(f)) pref = with(pref, {f, a.str(f, "")});
@@ -1187,10 +1187,31 @@ int profileClusterSearch(const Args &a) {
     return clusterChain(a, Q, T, tmp);
 }
 
+// --target-search-mode 1 (the similar-k-mer index of a sequence target, `prefilter --target-search-mode 1`): the workflows run the module
+// chain with it, as for a target split -- the streaming pipeline builds the regular index.  What the chain does not cover is refused
+// by name.  similar: the flag is 1 (a profile target makes it moot: the caller looks at the DB).
+int checkTargetSearchMode(const Args &a, bool &similar) {
+    const long long tsm = a.integer("--target-search-mode", 0);
+    similar = false;
+    if (tsm == 0) return 0;
+    if (tsm != 1) return fail("--target-search-mode " + std::to_string(tsm) + ": 0 (regular k-mer index) or 1 (similar k-mer index)");
+    if (a.flag("--profile-cluster-search", false))
+        return fail("--target-search-mode 1 with --profile-cluster-search 1: a profile target is a similar-k-mer index already; run without the flag");
+    if (a.integer("--num-iterations", 1) > 1)
+        return fail("--target-search-mode 1 with --num-iterations > 1 is not implemented (profile queries against the similar-k-mer index)");
+    if (a.integer("--prefilter-mode", 0) == 1) return fail("--target-search-mode 1 with --prefilter-mode 1: the ungapped prefilter has no k-mer index");
+    if (envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1) return fail("--target-search-mode 1 runs on one rank");
+    similar = true;
+    return 0;
+}
+
 }  // namespace
 
 int searchModule(const Args &a0) {
     if (a0.flag("--profile-cluster-search", false)) return fail("--profile-cluster-search is a flag of clustersearch");
+    bool similarTarget = false;
+    if (int rc = checkTargetSearchMode(a0, similarTarget)) return rc;
+    if (similarTarget && a0.pos.size() == 4 && isProfileDb(a0.pos[1])) similarTarget = false;   // isProfile || targetSearchMode (IndexBuilder.cpp:62)
     if (int rc = checkPrefilterMode(a0)) return rc;
     // a profile target DB on the one path that takes it: sequence queries, the k-mer prefilter, one pass, one rank, gapped alignments.
     // Every other combination goes on to its own path below and is refused there
@@ -1218,8 +1239,10 @@ int searchModule(const Args &a0) {
         if (int rc = checkWorkflowFlags(a)) return rc;
         return iterativeSearch(a, a.pos[0], a.pos[1], a.pos[2], a.pos[3]);
     }
-    if (targetSplit) {
-        // one pass over a split target: `prefilter --split N` then `align`, the chain altAliSearch runs (with --alt-ali 0)
+    if (targetSplit || similarTarget) {
+        // one pass over a split target, or over the similar-k-mer index: `prefilter --split N` / `prefilter --target-search-mode 1` then
+        // `align`, the chain altAliSearch runs (with --alt-ali 0)
+        if (a.pos.size() != 4) return fail("usage: search <queryDB> <targetDB> <alignmentDB> <tmpDir> [options]");
         if (int rc = checkWorkflowFlags(a)) return rc;
         return altAliSearch(a, a.pos[0], a.pos[1], a.pos[2], a.pos[3]);
     }
@@ -1227,6 +1250,8 @@ int searchModule(const Args &a0) {
 }
 
 int clustersearchModule(const Args &a0) {
+    bool similarTarget = false;
+    if (int rc = checkTargetSearchMode(a0, similarTarget)) return rc;
     if (a0.flag("--profile-cluster-search", false)) return profileClusterSearch(a0);
     if (int rc = checkPrefilterMode(a0)) return rc;
     if (a0.integer("--alt-ali", 0) != 0) return checkAltAli(a0, true);
@@ -1253,8 +1278,10 @@ int clustersearchModule(const Args &a0) {
         if (int rc = ungappedAlignSearch(s, Q, T, tmp + "/result", tmp + "/search")) return rc;
         return clusterChain(a, Q, T, tmp);
     }
-    if (a.integer("--num-iterations", 1) <= 1 && targetSplit) {
-        // one pass over a split target through the modules (prefilter --split N, align), then the module chain on its alignment DB
+    if (a.integer("--num-iterations", 1) <= 1 && (targetSplit || similarTarget)) {
+        // one pass over a split target, or over the similar-k-mer index, through the modules (prefilter --split N / --target-search-mode 1,
+        // align), then the module chain on its alignment DB
+        if (a.pos.size() != 4) return fail("usage: clustersearch <querySetDB> <targetSetDB> <out.tsv> <tmpDir> [options]");
         if (int rc = checkWorkflowFlags(a)) return rc;
         const std::string Q = a.pos[0], T = a.pos[1], tmp = a.pos[3];
         mkdir(tmp.c_str(), 0777);

@@ -344,7 +344,29 @@ struct sd_target {
     // built by sd_target_build_profile from a profile DB: the lists hold the *similar* k-mers of every profile window, dMasked the consensus
     // letters, and there are no 2-mer / 3-mer tables -- a sequence query looks up its own k-mers only (takeOnlyBestKmer, Prefiltering.cpp:176-179)
     bool similar = false;
+    // ... by sd_target_build_similar from a *sequence* DB (--target-search-mode 1): similar as above, dMasked the unmasked residues
+    bool similarSeq = false;
 };
+constexpr int EXT3_CUM_SPAN = 256;   // scores a row of dExt3Cum spans (sdBuildExt3Cum)
+
+// What the similar-k-mer enumerations share (the query side in sd_prefilter.hip / sd_pf_join.h, the target side of --target-search-mode 1
+// in sd_index_build.hip).
+// number of entries >= cutoff in a descending row of n int16
+__device__ __forceinline__ int countGE(const int16_t *__restrict__ row, int n, int cutoff) {
+    int lo = 0, hi = n;   // first index with row[idx] < cutoff
+    while (lo < hi) {
+        int mid = (lo + hi) >> 1;
+        if ((int) row[mid] >= cutoff) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// countGE of a whole 3-mer row from the cumulative table (sd_target::dExt3Cum): one read instead of a 13-step search.  Exactly the
+// same number -- the rows are sorted by descending score, so "first index below the cutoff" is "entries at or above it".
+__device__ __forceinline__ int countGETab(const uint16_t *__restrict__ cumRow, int lo, int cutoff) {
+    const int c = cutoff - lo;
+    return c <= 0 ? 8000 : (c >= EXT3_CUM_SPAN ? 0 : (int) cumRow[c]);
+}
 
 // scratch entries per partial k-mer list of the per-position products (profile_kmers_kernel in sd_prefilter.hip, ib_profile_records_kernel
 // in sd_index_build.hip): the wide grid's tier and the tier of the few positions that outgrow it (the reference's own buffer holds 2^23

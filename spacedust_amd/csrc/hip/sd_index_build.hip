@@ -567,6 +567,146 @@ ib_profile_records_kernel(uint64_t nWin, const uint64_t *__restrict__ winBase /*
     if (MODE == 0) flush();
 }
 
+// ---- records of a *sequence* target under --target-search-mode 1 (sd_target_build_similar): the sequence branch of the same reference
+// code (setDivideStrategy(&three, &two), IndexBuilder.cpp:100): a window without X contributes KmerGenerator::generateKmerList of its own
+// k-mer, which at k = 6 is ONE array product of two sorted 3-mer rows -- parents a of row0 with s0[a] >= short(thr - best1), children b
+// of row1 with s1[b] >= short(thr - s0[a]), k-mer i0[a] + 8000 i1[b] -- exactly what count_kmers_kernel / emit_kmers_kernel enumerate for
+// a query, without a bias term.  A wavefront per window: 64 parents at a time take their run lengths from ext3Cum (one read each), the
+// runs are scanned and then flattened over the lanes (slot t belongs to the lane o with excl[o] <= t < incl[o], found in LDS), so all
+// 64 lanes produce k-mers however unequal the runs are -- they span 1 to 8 000 between the best and the last parent -- and the records
+// of the pass's range [lo, hi) are compacted with a ballot into one contiguous, ascending store.  No partial list exists, so there is
+// no scratch and no tier.  A window's k-mers are distinct (a pair (a, b) gives one (i0, i1)) and the windows write at bases scanned in
+// (target, position) order: the order argument of the profile generator above holds word for word.
+//   MODE 0: the list length of every window (winCount) and the histogram over IB_COARSE_BINS k-mer ranges; errWin: the first window
+//           whose list reaches IP_LIST_MAX (calculateArrayProduct stops there, KmerGenerator.cpp:204-213)
+//   MODE 1: the records of [lo, hi) per window (winCount);  MODE 2: the records themselves at recBase[window] + ...
+constexpr uint32_t IS_GRID = 4096;
+template <int MODE>
+__global__ void __launch_bounds__(64)
+ib_similar_records_kernel(uint64_t nWin, const uint64_t *__restrict__ winBase /* first window of every target, nSeq + 1 */, uint32_t nSeq,
+                          const uint8_t *__restrict__ res, const uint64_t *__restrict__ seqOff, const int16_t *__restrict__ ext3Score,
+                          const uint16_t *__restrict__ ext3Index, const uint16_t *__restrict__ ext3Cum /* nullable */, int ext3Lo, int kmerThr,
+                          uint32_t binWidth, unsigned long long *__restrict__ coarse, unsigned long long *__restrict__ errWin, uint32_t lo,
+                          uint32_t hi, uint32_t *__restrict__ winCount, const uint64_t *__restrict__ recBase, uint32_t *__restrict__ keys,
+                          uint64_t *__restrict__ vals) {
+    __shared__ uint32_t hist[MODE == 0 ? IB_COARSE_BINS : 1];
+    __shared__ uint32_t sIncl[64], sK0[64];
+    const int lane = threadIdx.x;
+    if (MODE == 0)
+        for (uint32_t i = lane; i < IB_COARSE_BINS; i += 64) hist[i] = 0;
+    uint32_t histHeld = 0;   // records in hist (MODE 0): flushed before a 32-bit bin could wrap
+    auto flush = [&]() {
+        __syncthreads();
+        for (uint32_t i = lane; i < IB_COARSE_BINS; i += 64) {
+            if (hist[i]) atomicAdd(&coarse[i], (unsigned long long) hist[i]);
+            hist[i] = 0;
+        }
+        __syncthreads();
+        histHeld = 0;
+    };
+    if (MODE == 0) __syncthreads();
+    for (uint64_t p = blockIdx.x; p < nWin; p += gridDim.x) {
+        uint32_t tl = 0, th = nSeq;   // last target with winBase[target] <= p
+        while (th - tl > 1) {
+            const uint32_t mid = (tl + th) >> 1;
+            if (winBase[mid] <= p) tl = mid;
+            else th = mid;
+        }
+        const uint32_t q = tl;
+        const int i = (int) (p - winBase[tl]);
+        const uint8_t *s = res + seqOff[q] + (uint64_t) i;
+        uint32_t w[6];
+        bool hasX = false;
+#pragma unroll
+        for (int x = 0; x < 6; x++) {
+            w[x] = s[c_ipSeed6[x]];
+            hasX |= w[x] >= 20u;   // kmerContainsX (Sequence.h:397-403)
+        }
+        uint32_t totalOut = 0;   // MODE 0: the list length; MODE 1 / 2: its records in [lo, hi)
+        if (!hasX) {
+            const uint32_t idx0 = w[0] + 20u * w[1] + 400u * w[2], idx1 = w[3] + 20u * w[4] + 400u * w[5];
+            const int16_t *row0 = ext3Score + (size_t) idx0 * 8000, *row1 = ext3Score + (size_t) idx1 * 8000;
+            const uint16_t *ix0 = ext3Index + (size_t) idx0 * 8000, *ix1 = ext3Index + (size_t) idx1 * 8000;
+            const uint16_t *cum0 = ext3Cum ? ext3Cum + (size_t) idx0 * EXT3_CUM_SPAN : nullptr;
+            const uint16_t *cum1 = ext3Cum ? ext3Cum + (size_t) idx1 * EXT3_CUM_SPAN : nullptr;
+            const int thr = (int) (short) kmerThr;   // KmerGenerator::threshold is a short; no composition bias (IndexBuilder.cpp:96)
+            const int cutoff1 = (int) (short) (thr - (int) row1[0]);
+            const int n0 = cum0 ? countGETab(cum0, ext3Lo, cutoff1) : countGE(row0, 8000, cutoff1);
+            bool tooLong = false;
+            if (MODE == 0) {   // the length first: a list the reference would cut is refused before anything of it is counted
+                uint32_t total = 0;
+                for (int a = lane; a < n0; a += 64) {
+                    const int cutoff2 = (int) (short) (thr - (int) row0[a]);
+                    total += (uint32_t) (cum1 ? countGETab(cum1, ext3Lo, cutoff2) : countGE(row1, 8000, cutoff2));
+                }
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
+                totalOut = total;
+                tooLong = total >= IP_LIST_MAX;
+                if (tooLong && lane == 0) atomicMin(errWin, (unsigned long long) p);
+            }
+            const uint64_t base = MODE == 2 ? recBase[p] : 0;
+            const uint64_t val = ((uint64_t) q << 16) | (uint64_t) i;
+            uint32_t written = 0;
+            for (int a0 = 0; a0 < n0 && !tooLong; a0 += 64) {
+                const int a = a0 + lane;
+                uint32_t c = 0;
+                if (a < n0) {
+                    const int cutoff2 = (int) (short) (thr - (int) row0[a]);
+                    c = (uint32_t) (cum1 ? countGETab(cum1, ext3Lo, cutoff2) : countGE(row1, 8000, cutoff2));
+                }
+                uint32_t incl = c;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t o = __shfl_up(incl, off, 64);
+                    if (lane >= off) incl += o;
+                }
+                const uint32_t chunkTotal = __shfl(incl, 63, 64);
+                __builtin_amdgcn_wave_barrier();   // the previous chunk's readers are done
+                sIncl[lane] = incl;
+                sK0[lane] = a < n0 ? (uint32_t) ix0[a] : 0u;
+                __builtin_amdgcn_wave_barrier();
+                for (uint32_t t0 = 0; t0 < chunkTotal; t0 += 64) {
+                    const uint32_t t = t0 + (uint32_t) lane;
+                    uint32_t km = 0;
+                    bool in = false;
+                    if (t < chunkTotal) {
+                        int l = 0, h = 63;   // smallest o with incl[o] > t
+#pragma unroll
+                        for (int st = 0; st < 6; st++) {
+                            const int mid = (l + h) >> 1;
+                            if (sIncl[mid] > t) h = mid;
+                            else l = mid + 1;
+                        }
+                        const uint32_t before = l ? sIncl[l - 1] : 0u;
+                        km = sK0[l] + 8000u * (uint32_t) ix1[t - before];
+                        in = MODE == 0 || (km >= lo && km < hi);
+                    }
+                    if (MODE == 0) {
+                        if (in) atomicAdd(&hist[km / binWidth], 1u);
+                    } else {
+                        const unsigned long long b64 = __ballot(in);
+                        if (MODE == 2 && in) {
+                            const uint64_t at = base + written + __popcll(b64 & ((1ull << lane) - 1));
+                            keys[at] = km - lo;
+                            vals[at] = val;
+                        }
+                        written += (uint32_t) __popcll(b64);
+                    }
+                }
+            }
+            if (MODE != 0) totalOut = written;
+            if (tooLong) totalOut = 0;
+        }
+        if (MODE != 2 && lane == 0) winCount[p] = totalOut;
+        if (MODE == 0) {
+            histHeld += totalOut;
+            if (histHeld >= (1u << 31) - IP_LIST_MAX) flush();
+        }
+    }
+    if (MODE == 0) flush();
+}
+
 // ---- exclusive scan of up to 2^32 32-bit counts into 64-bit sums (three launches: tile sums, tile bases, apply)
 constexpr int IS_TILE = 4096, IS_NT = 256;
 __global__ void __launch_bounds__(IS_NT) is_tile_sums(const uint32_t *__restrict__ in, uint64_t n, uint64_t *__restrict__ tileSum) {
@@ -1220,6 +1360,140 @@ extern "C" int sd_target_build_profile(sd_ctx *ctx, int kmerSize, int kmerThr, c
             return rcP;
     }
     if (int rcL = ibListStarts(ctx, t, "sd_target_build_profile", nEntries, notePeak)) return rcL;
+    t->nEntries = nEntries;
+    if (stats) {
+        stats[0] = nEntries;
+        stats[1] = 0;
+        stats[2] = nPasses;
+        stats[3] = nRecords;
+    }
+    guard.t = nullptr;
+    *out = t;
+    return SD_OK;
+}
+
+// The similar-k-mer index of a *sequence* target DB (--target-search-mode 1; the sequence branch of the same reference code,
+// IndexBuilder.cpp:62,100,120-127): the lists hold generateKmerList of every window without X at kmerThr -- the sequence threshold
+// itself (Prefiltering.cpp:525-527) -- deduplicated and ordered like the profile index; nothing is masked and the lookup holds the
+// residues as they came.  Same pass pipeline; the generator needs no scratch (ib_similar_records_kernel).
+extern "C" int sd_target_build_similar(sd_ctx *ctx, int kmerSize, int kmerThr, const uint8_t *residues, const uint64_t *seqOffsets, uint32_t nSeq,
+                                       const int16_t *ext3Score, const uint16_t *ext3Index, sd_target **out, uint64_t *stats) {
+    if (!ctx || !out || !residues || !seqOffsets || !ext3Score || !ext3Index) return SD_EINVAL;
+    if (kmerSize == 7)
+        return sdFail(ctx, SD_EUNSUPPORTED, "k=7: the similar-k-mer index of a sequence target is built at k=6 only (the 3 x 3 array product; k=7 divides 2, 2, 3)");
+    if (kmerSize != 6) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the similar-k-mer index of a sequence target is built at k=6", kmerSize);
+    const int span = 10;
+    std::vector<uint64_t> winBase((size_t) nSeq + 1, 0);
+    for (uint32_t i = 0; i < nSeq; i++) {
+        const uint64_t len = seqOffsets[i + 1] - seqOffsets[i];
+        if (len > 65535)   // (as sd_target_build)
+            return sdFail(ctx, SD_EINVAL, "target %u has %llu residues; index positions are 16 bit (limit 65535, --max-seq-len)", i,
+                          (unsigned long long) len);
+        winBase[i + 1] = winBase[i] + (len >= (uint64_t) span ? len - span + 1 : 0);
+    }
+    const uint64_t nWin = winBase[nSeq], total = seqOffsets[nSeq];
+    if (nWin >= 0xFFFFFFFFull) return sdFail(ctx, SD_EUNSUPPORTED, "%llu sequence windows (limit 2^32 per target)", (unsigned long long) nWin);
+    (void) hipSetDevice(ctx->device);
+    sd_target *t = new sd_target();
+    struct Guard {
+        sd_target *t;
+        ~Guard() { if (t) sd_target_destroy(t); }
+    } guard{t};
+    t->ctx = ctx;
+    t->k = kmerSize;
+    t->nSeq = nSeq;
+    t->similar = true;
+    t->similarSeq = true;
+    t->tableSize = 64000000ull;
+    t->hSeqOff.assign(seqOffsets, seqOffsets + nSeq + 1);
+    const PeakNote notePeak(t);
+    auto up = [&](void **d, const void *h, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(d, bytes + 64);
+        if (e != hipSuccess) return e;
+        return hipMemcpy(*d, h, bytes, hipMemcpyDefault);
+    };
+    SD_HIP(ctx, up((void **) &t->dSeqOff, seqOffsets, ((size_t) nSeq + 1) * sizeof(uint64_t)));
+    SD_HIP(ctx, up((void **) &t->dMasked, residues, total));   // the lookup of the diagonal scoring: unmasked (IndexBuilder.cpp:125-127)
+    // the 3-mer tables serve the generator only: a query looks up its own k-mers, so they are released with the build
+    SD_HIP(ctx, up((void **) &t->dExt3Score, ext3Score, (size_t) 8000 * 8000 * sizeof(int16_t)));
+    SD_HIP(ctx, up((void **) &t->dExt3Index, ext3Index, (size_t) 8000 * 8000 * sizeof(uint16_t)));
+    if (int rcCum = sdBuildExt3Cum(ctx, t)) return rcCum;
+    auto dropTables = [&]() {
+        for (void **p : {(void **) &t->dExt3Score, (void **) &t->dExt3Index, (void **) &t->dExt3Cum}) {
+            if (*p) (void) hipFree(*p);
+            *p = nullptr;
+        }
+    };
+    Scoped<uint64_t> dWinBase;
+    Scoped<uint32_t> dWinCount;
+    Scoped<unsigned long long> dCoarse, dErr;
+    const uint32_t grid = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(nWin, 1), IS_GRID);
+    SD_HIP(ctx, up((void **) &dWinBase.p, winBase.data(), winBase.size() * sizeof(uint64_t)));
+    SD_HIP(ctx, dWinCount.alloc(nWin + 1));
+    SD_HIP(ctx, dCoarse.alloc(IB_COARSE_BINS));
+    SD_HIP(ctx, dErr.alloc(1));
+    notePeak();
+    const unsigned long long errInit = ~0ull;
+    SD_HIP(ctx, hipMemcpy(dErr.p, &errInit, sizeof(errInit), hipMemcpyHostToDevice));
+    SD_HIP(ctx, hipMemsetAsync(dWinCount.p, 0, (nWin + 1) * sizeof(uint32_t), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(dCoarse.p, 0, IB_COARSE_BINS * sizeof(unsigned long long), ctx->stream));
+    const uint32_t binWidth = (uint32_t) ((t->tableSize + IB_COARSE_BINS - 1) / IB_COARSE_BINS);
+    auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *winCount, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) {
+        constexpr int MODE = decltype(mode)::value;
+        hipLaunchKernelGGL((ib_similar_records_kernel<MODE>), dim3(grid), dim3(64), 0, ctx->stream, nWin, (const uint64_t *) dWinBase.p, nSeq,
+                           (const uint8_t *) t->dMasked, (const uint64_t *) t->dSeqOff, (const int16_t *) t->dExt3Score,
+                           (const uint16_t *) t->dExt3Index, (const uint16_t *) t->dExt3Cum, t->ext3Lo, kmerThr, binWidth, dCoarse.p, dErr.p, lo,
+                           hi, winCount, recBase, keys, vals);
+    };
+    std::vector<unsigned long long> coarse(IB_COARSE_BINS, 0);
+    if (nWin) {
+        {
+            ProfScope ps(ctx, "index_similar_histogram");
+            generate(std::integral_constant<int, 0>(), 0u, 0u, dWinCount.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
+        }
+        SD_HIP(ctx, hipGetLastError());
+        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        unsigned long long hErr = ~0ull;
+        SD_HIP(ctx, hipMemcpy(&hErr, dErr.p, sizeof(hErr), hipMemcpyDeviceToHost));
+        if (hErr != ~0ull) {
+            const uint32_t q = (uint32_t) (std::upper_bound(winBase.begin(), winBase.end(), (uint64_t) hErr) - winBase.begin() - 1);
+            return sdFail(ctx, SD_EUNSUPPORTED, "target %u, position %llu: %u similar k-mers or more in one sequence window (the reference's "
+                          "buffer ends there, KmerGenerator.h:45); raise the k-mer threshold", q, (unsigned long long) (hErr - winBase[q]), IP_LIST_MAX);
+        }
+        SD_HIP(ctx, hipMemcpy(coarse.data(), dCoarse.p, IB_COARSE_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+    uint64_t nRecords = 0, cap = 0;
+    if (int rcCap = ibPassCap(ctx, coarse, cap, nRecords)) return rcCap;
+    // the entry array is sized by the counted records (the dedupe only ever removes): hundreds of records per residue at the default threshold
+    if (hipMalloc((void **) &t->dEntries, (std::max<uint64_t>(nRecords, 1) + 8) * sizeof(uint2)) != hipSuccess) {
+        t->dEntries = nullptr;
+        (void) hipGetLastError();
+        return sdFail(ctx, SD_ENOMEM, "the similar-k-mer index of %llu records (%llu bytes of entries) does not fit the device memory; a higher "
+                      "--k-score (fewer similar k-mers per window) or a smaller target database is the way out", (unsigned long long) nRecords,
+                      (unsigned long long) ((nRecords + 8) * sizeof(uint2)));
+    }
+    SD_HIP(ctx, hipMalloc((void **) &t->dOffsets, (t->tableSize + 1) * sizeof(uint32_t) + 64));
+    SD_HIP(ctx, hipMemsetAsync(t->dOffsets, 0, (t->tableSize + 1) * sizeof(uint32_t), ctx->stream));   // counts first
+    uint64_t nEntries = 0, nPasses = 0;
+    if (nRecords) {
+        auto countFn = [&](uint32_t lo, uint32_t hi, uint32_t *winCount) -> int {
+            if (lo == 0 && hi >= t->tableSize) {   // one pass holds every record: the list lengths are its counts
+                SD_HIP(ctx, hipMemcpyAsync(winCount, dWinCount.p, nWin * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+                return SD_OK;
+            }
+            generate(std::integral_constant<int, 1>(), lo, hi, winCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
+            return SD_OK;
+        };
+        auto emitFn = [&](uint32_t lo, uint32_t hi, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) -> int {
+            generate(std::integral_constant<int, 2>(), lo, hi, (uint32_t *) nullptr, recBase, keys, vals);
+            return SD_OK;
+        };
+        if (int rcP = ibPasses(ctx, t, "sd_target_build_similar", coarse, binWidth, nRecords, cap, (uint32_t) nWin, countFn, emitFn, notePeak, nEntries,
+                               nPasses))
+            return rcP;
+    }
+    dropTables();
+    if (int rcL = ibListStarts(ctx, t, "sd_target_build_similar", nEntries, notePeak)) return rcL;
     t->nEntries = nEntries;
     if (stats) {
         stats[0] = nEntries;

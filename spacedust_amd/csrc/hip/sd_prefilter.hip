@@ -46,17 +46,6 @@ struct WsView {
 constexpr int SPAN6 = 10;
 __constant__ uint8_t c_seed6[6] = {0, 1, 3, 5, 8, 9};   // spaced seed 1101010011 (M/src/commons/Sequence.h:23)
 
-// number of entries >= cutoff in a descending row of n int16
-__device__ __forceinline__ int countGE(const int16_t *__restrict__ row, int n, int cutoff) {
-    int lo = 0, hi = n;   // first index with row[idx] < cutoff
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if ((int) row[mid] >= cutoff) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 struct PosInfo {
     uint32_t q;
     int i;
@@ -131,14 +120,6 @@ pos_query_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t n
         else hi = mid;
     }
     posQuery[p] = lo;
-}
-
-// countGE of a whole 3-mer row from the cumulative table (sd_target::dExt3Cum): one read instead of a 13-step search.  Exactly the
-// same number -- the rows are sorted by descending score, so "first index below the cutoff" is "entries at or above it".
-constexpr int EXT3_CUM_SPAN = 256;
-__device__ __forceinline__ int countGETab(const uint16_t *__restrict__ cumRow, int lo, int cutoff) {
-    const int c = cutoff - lo;
-    return c <= 0 ? 8000 : (c >= EXT3_CUM_SPAN ? 0 : (int) cumRow[c]);
 }
 
 __global__ void ext3_minmax_kernel(const int16_t *__restrict__ score, uint64_t n, int *__restrict__ mm /* [min, max] */) {
@@ -2828,6 +2809,8 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
     if (!prof && (!qKmerBias || !qDiagBias)) return SD_EINVAL;
     if (par->kmerSize != T->k) return sdFail(ctx, SD_EINVAL, "k-mer size mismatch");
     // a profile target's index holds similar k-mers already (sd_target_build_profile): the reference refuses the pair (Prefiltering.cpp:144-148)
+    if (T->similar && prof && T->similarSeq)   // (the reference takes this pair; the exact-lookup path here reads query letters only)
+        return sdFail(ctx, SD_EUNSUPPORTED, "profile queries against a similar-k-mer sequence target (--target-search-mode 1) are not implemented");
     if (T->similar && prof) return sdFail(ctx, SD_EUNSUPPORTED, "profile queries cannot be searched against a profile target");
     if (par->minDiagScore < 1) return sdFail(ctx, SD_EUNSUPPORTED, "minDiagScore must be >= 1");
     if (par->binSize == 0 || (par->binSize & (par->binSize - 1))) return sdFail(ctx, SD_EINVAL, "binSize must be a power of two");

@@ -75,4 +75,16 @@ static inline int sdBuildProfileTarget(sd_ctx *ctx, int k, int kmerThr, const ui
     return rc;
 }
 
+// the similar-k-mer index of a sequence target DB (--target-search-mode 1): similar k-mers of every window at the sequence threshold,
+// unmasked lookup.  stats: {entries, 0}.
+static inline int sdBuildSimilarTarget(sd_host *host, sd_ctx *ctx, int k, int kmerThr, const uint8_t *residues, const uint64_t *offsets, uint32_t n,
+                                       sd_target **out, uint64_t stats[2]) {
+    const SdExtTables x(host);
+    uint64_t st[4] = {0, 0, 0, 0};
+    const int rc = sd_target_build_similar(ctx, k, kmerThr, residues, offsets, n, x.s3, x.i3, out, st);
+    stats[0] = st[0];
+    stats[1] = st[1];
+    return rc;
+}
+
 #endif
