@@ -974,6 +974,41 @@ int sd_r2p_batch_device(sd_ctx *ctx, sd_r2p *r, const sd_r2p_params *par, uint32
                         const char *btPool, const uint64_t *btOff, const uint8_t *tResidues, const uint64_t *tOff, char *outProfiles,
                         uint8_t *outConsensus);
 
+
+/* ---- clust: a result DB of a set against itself -> a cluster DB (M/src/clustering).  Local ids are the reference's
+ * SORT_BY_LENGTH order of the sequence DB; a graph is CSR over them: rowOff[n + 1] (64-bit), elem (local id), score (16 bits), rows in
+ * file order.  n is at most 2^32 - 2 (4294967295 marks "no cluster").
+ *
+ * sd_clust_symmetrize (GPU) is what ClusteringAlgorithms::readInClusterData leaves behind: row c of the output holds row c of the input,
+ * unchanged and in input order, then one entry s for every input edge s -> c, at position p of row s, for which s does not occur among the
+ * INPUT entries of row c -- ordered by s, then p, each with score[s][p] (AlignmentSymmetry::addMissingLinks read literally: a row that
+ * lists c twice appends twice, the search never sees appended entries, a self edge is never missing).  stats[3] (nullable): entries in,
+ * entries added, largest output row -- filled whenever the input was accepted.  outCap: room of outElem / outScore in entries; fewer than
+ * entries in + added: SD_ENOMEM with stats filled and no output array written (outCap 0 with null arrays is the count-only form).  An
+ * element >= n: SD_EINVAL; more entries than the device sort counts (2^32 - 4097): SD_EUNSUPPORTED with a message, nothing truncated. */
+int sd_clust_symmetrize(sd_ctx *ctx, uint64_t n, const uint64_t *rowOff, const uint32_t *elem, const uint16_t *score, uint64_t outCap,
+                        uint64_t *outRowOff, uint32_t *outElem, uint16_t *outScore, uint64_t *stats);
+/* localToId[i] = position, in key order, of the sequence with local id i: index length descending, then key order (DBReader.cpp:325-342) */
+int sd_host_clust_order(uint64_t n, const uint64_t *indexLength, uint32_t *localToId);
+/* AlignmentSymmetry::readInData: entries[i] is the '\0'-terminated result entry of the sequence with local id i and key localKeys[i]; an
+ * entry without lines becomes the row [i].  Scores by the DB's type -- alignment: similarityType 2 (unsigned short)(atof(column 2) *
+ * 1000.0f), 1 (unsigned short) atof(column 1); prefilter: abs((short) atoi(column 1)); cluster: 65535; any other type: SD_EUNSUPPORTED.
+ * rowOff is always filled; cap 0 with null arrays is the count-only form, too small a cap SD_ENOMEM.  A listed key that localKeys lacks:
+ * SD_EINVAL with *badKey (nullable) = that key. */
+int sd_host_clust_parse(uint64_t n, const uint32_t *localKeys, const char *const *entries, int dbtype, int similarityType, uint64_t *rowOff,
+                        uint64_t cap, uint32_t *elem, uint16_t *score, uint32_t *badKey);
+/* The algorithms; assigned[i] = local id of i's representative (4294967295: none).  _setcover (--cluster-mode 0) and _connected
+ * (--cluster-mode 1, breadth-first to depth maxIterations) take the symmetric graph, _greedy (--cluster-mode 2 / 3) the parsed rows.
+ * _setcover compares the scores as signed shorts, as the reference does. */
+int sd_host_clust_setcover(uint64_t n, const uint64_t *rowOff, const uint32_t *elem, const uint16_t *score, uint32_t *assigned);
+int sd_host_clust_connected(uint64_t n, const uint64_t *rowOff, const uint32_t *elem, int maxIterations, uint32_t *assigned);
+int sd_host_clust_greedy(uint64_t n, const uint64_t *rowOff, const uint32_t *elem, uint32_t *assigned);
+/* The sorted pairs (representative key, member key) into repKey / memberKey [n] and, when nEntries is given, the cluster DB: entry e has
+ * key entryKey[e] and text[entryOff[e] .. entryOff[e + 1]) -- the representative's key, then the other members ascending, one per line.
+ * entryKey [n], entryOff [n + 1], text 22 bytes per node. */
+int sd_host_clust_format(uint64_t n, const uint32_t *localKeys, const uint32_t *assigned, uint32_t *repKey, uint32_t *memberKey,
+                         uint64_t *nEntries, uint32_t *entryKey, uint64_t *entryOff, char *text);
+
 #ifdef __cplusplus
 }
 #endif

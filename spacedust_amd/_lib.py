@@ -290,6 +290,13 @@ def load():
                             [C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
         'sd_expand_backtraces': (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp]),
         'sd_expand_last_stats': (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        'sd_clust_symmetrize': (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+        'sd_host_clust_order': (C.c_int, [C.c_uint64, _vp, _vp]),
+        'sd_host_clust_parse': (C.c_int, [C.c_uint64, _vp, _vp, C.c_int, C.c_int, _vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint32)]),
+        'sd_host_clust_setcover': (C.c_int, [C.c_uint64, _vp, _vp, _vp, _vp]),
+        'sd_host_clust_connected': (C.c_int, [C.c_uint64, _vp, _vp, C.c_int, _vp]),
+        'sd_host_clust_greedy': (C.c_int, [C.c_uint64, _vp, _vp, _vp]),
+        'sd_host_clust_format': (C.c_int, [C.c_uint64, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp]),
     }
     missing = []
     for name, (res, args) in sig.items():

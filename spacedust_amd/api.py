@@ -921,3 +921,95 @@ def expand_last_stats(ctx):
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     _check(ctx.h, ctx.L.sd_expand_last_stats(ctx.h, C.byref(a), C.byref(b), C.byref(c)), 'sd_expand_last_stats')
     return dict(pairs=a.value, runs_read=b.value, bytes_written=c.value)
+
+
+# ---- clust: the symmetric graph on the GPU, everything else on the host
+
+def clust_symmetrize(ctx, row_off, elem, score, cap=None):
+    """sd_clust_symmetrize: CSR graph over local ids -> (row_off uint64 [n + 1], elem uint32, score uint16, stats) with every missing back
+    edge appended to its row; stats = dict(entries_in, added, largest_row).  cap: room of the output in entries (default: exactly enough,
+    learned from a count-only call first)."""
+    L = _lib.load()
+    row_off = np.ascontiguousarray(row_off, np.uint64)
+    elem = np.ascontiguousarray(elem, np.uint32)
+    score = np.ascontiguousarray(score, np.uint16)
+    n = len(row_off) - 1
+    assert len(elem) == len(score) == int(row_off[-1])
+    stats = np.zeros(3, np.uint64)
+    if cap is None:
+        rc = L.sd_clust_symmetrize(ctx.h, n, ptr(row_off), ptr(elem), ptr(score), 0, None, None, None, ptr(stats))
+        if rc != _lib.SD_ENOMEM:
+            _check(ctx.h, rc, 'sd_clust_symmetrize')
+        cap = int(stats[0] + stats[1])
+    out_off = np.zeros(n + 1, np.uint64)
+    out_elem = np.zeros(max(cap, 1), np.uint32)
+    out_score = np.zeros(max(cap, 1), np.uint16)
+    _check(ctx.h, L.sd_clust_symmetrize(ctx.h, n, ptr(row_off), ptr(elem), ptr(score), cap, ptr(out_off), ptr(out_elem), ptr(out_score), ptr(stats)),
+           'sd_clust_symmetrize')
+    total = int(out_off[-1])
+    return out_off, out_elem[:total], out_score[:total], dict(entries_in=int(stats[0]), added=int(stats[1]), largest_row=int(stats[2]))
+
+
+def clust_order(index_lengths):
+    """sd_host_clust_order: local id -> position in key order (index length descending, then key order)"""
+    lens = np.ascontiguousarray(index_lengths, np.uint64)
+    out = np.zeros(len(lens), np.uint32)
+    _check(None, _lib.load().sd_host_clust_order(len(lens), ptr(lens), ptr(out)), 'sd_host_clust_order')
+    return out
+
+
+def clust_parse(local_keys, entries, dbtype, similarity_type=2):
+    """sd_host_clust_parse: entries[i] (bytes) is the result entry of local id i -> (row_off, elem, score)"""
+    L = _lib.load()
+    keys = np.ascontiguousarray(local_keys, np.uint32)
+    n = len(keys)
+    assert len(entries) == n
+    bufs = [C.create_string_buffer(bytes(e)) for e in entries]   # ('\0'-terminated)
+    arr = (C.c_char_p * max(n, 1))(*[C.cast(b, C.c_char_p) for b in bufs])
+    row_off = np.zeros(n + 1, np.uint64)
+    bad = C.c_uint32()
+    _check(None, L.sd_host_clust_parse(n, ptr(keys), arr, dbtype, similarity_type, ptr(row_off), 0, None, None, C.byref(bad)), 'sd_host_clust_parse')
+    total = int(row_off[-1])
+    elem, score = np.zeros(max(total, 1), np.uint32), np.zeros(max(total, 1), np.uint16)
+    rc = L.sd_host_clust_parse(n, ptr(keys), arr, dbtype, similarity_type, ptr(row_off), total, ptr(elem), ptr(score), C.byref(bad))
+    if rc == _lib.SD_EINVAL:
+        raise SdError('Element %d contained in some alignment list, but not contained in the sequence database!' % bad.value)
+    _check(None, rc, 'sd_host_clust_parse')
+    return row_off, elem[:total], score[:total]
+
+
+def clust_assign(mode, row_off, elem, score=None, max_iterations=1000):
+    """the host algorithms: mode 0 set cover and 1 connected component on the symmetric graph, 2 / 3 greedy on the parsed rows.
+    Returns assigned uint32 [n] (local id of the representative)."""
+    L = _lib.load()
+    row_off = np.ascontiguousarray(row_off, np.uint64)
+    elem = np.ascontiguousarray(elem, np.uint32)
+    n = len(row_off) - 1
+    out = np.zeros(max(n, 1), np.uint32)
+    if mode == 0:
+        score = np.ascontiguousarray(score, np.uint16)
+        rc = L.sd_host_clust_setcover(n, ptr(row_off), ptr(elem), ptr(score), ptr(out))
+    elif mode == 1:
+        rc = L.sd_host_clust_connected(n, ptr(row_off), ptr(elem), int(max_iterations), ptr(out))
+    elif mode in (2, 3):
+        rc = L.sd_host_clust_greedy(n, ptr(row_off), ptr(elem), ptr(out))
+    else:
+        raise SdError('Wrong clustering mode!')
+    _check(None, rc, 'sd_host_clust_* (mode %d)' % mode)
+    return out[:n]
+
+
+def clust_format(local_keys, assigned):
+    """sd_host_clust_format: (pairs uint32 [n, 2] sorted, cluster DB as dict key -> bytes)"""
+    L = _lib.load()
+    keys = np.ascontiguousarray(local_keys, np.uint32)
+    assigned = np.ascontiguousarray(assigned, np.uint32)
+    n = len(keys)
+    rep, mem = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    ekey, eoff, text = np.zeros(max(n, 1), np.uint32), np.zeros(n + 1, np.uint64), np.zeros(22 * n + 1, np.uint8)
+    ne = C.c_uint64()
+    _check(None, L.sd_host_clust_format(n, ptr(keys), ptr(assigned), ptr(rep), ptr(mem), C.byref(ne), ptr(ekey), ptr(eoff), ptr(text)),
+           'sd_host_clust_format')
+    raw = text.tobytes()
+    db = {int(ekey[e]): raw[int(eoff[e]):int(eoff[e + 1])] for e in range(ne.value)}
+    return np.stack([rep[:n], mem[:n]], axis=1), db

@@ -177,6 +177,7 @@ int subtractdbsModule(const Args &a);
 int mergedbsModule(const Args &a);
 int swapresultsModule(const Args &a);
 int expandalnModule(const Args &a);
+int clustModule(const Args &a);
 
 }  // namespace sdcli
 #endif
