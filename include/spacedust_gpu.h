@@ -1009,6 +1009,55 @@ int sd_host_clust_greedy(uint64_t n, const uint64_t *rowOff, const uint32_t *ele
 int sd_host_clust_format(uint64_t n, const uint32_t *localKeys, const uint32_t *assigned, uint32_t *repKey, uint32_t *memberKey,
                          uint64_t *nEntries, uint32_t *entryKey, uint64_t *entryOff, char *text);
 
+
+/* ---- kmermatcher: linclust's shared-k-mer grouping of an amino-acid sequence DB (M/src/linclust/kmermatcher.cpp), for
+ * an input that fits one split.  residues are the 21-letter codes of sd_host_matrix's aa2num, offsets[nSeq + 1] (64-bit), keys the DB keys.
+ *
+ * sd_host_reduced_alphabet restates ReducedMatrix's merging of letters (M/src/prefiltering/ReducedMatrix.cpp) over the joint
+ * probabilities of matrix `which` (sd_host_matrix numbering): letterMap[21] = reduced code of every 21-letter code, *reducedSize = the
+ * number of codes, X the last one.  alphabetSize 21: the identity.  2 .. 20 reduce; anything else SD_EINVAL.
+ *
+ * sd_kmermatch_batch (GPU): every sequence gives one identity record (key XXH64 of the polynomial hash of its reduced codes, position 0)
+ * and its kmerConsidered = min((size_t)(kmersPerSequence - 1 + kmersPerSequenceScale * L), windows without X) windows with the smallest
+ * 16-bit XXH64 scores, chosen as fillKmerPositionArray chooses them (its last-bin rule included).  Records are sorted by (key, seqLen
+ * descending, DB key, position); the first record of a run of equal keys is the representative; runs of one give nothing; the others give
+ * (rep, member, diagonal) where Util::canBeCovered holds (or, with includeOnlyExtendable, where the diagonal is extendable); sorted by
+ * (rep, member, diagonal) every run with member != rep is one hit: score = the run's length, diagonal = the last one of the longest runs of
+ * equal diagonals.  As in writeKmerMatcherResult the run is followed by MEMBER alone, so it continues into records of the next
+ * representative that start with the same member and into what assignGroup leaves behind its last record.
+ * Hits come back sorted by (rep, member).  stats[4] (nullable): records generated, records after grouping, hits, largest run of equal
+ * keys -- filled whenever the input was accepted.  outCap < hits: SD_ENOMEM with stats filled and no output array written (outCap 0 with
+ * null arrays is the count-only form).  Records that do not fit the device at once, or more than the device sort counts (2^32 - 4097):
+ * SD_ENOMEM with the bytes needed in the message -- the reference's split by hash range is not implemented. */
+#define SD_KMERMATCH_BYTES_PER_RECORD 80   /* device bytes per record, counted from sd_kmermatch.hip's workspace */
+typedef struct {
+    int32_t kmerSize;              /* -k (after the -k 0 rule) */
+    int32_t alphabetSize;          /* reduced size: 13 or 21 */
+    int32_t kmersPerSequence;      /* --kmer-per-seq (20 when 0) */
+    float kmersPerSequenceScale;   /* --kmer-per-seq-scale */
+    int32_t hashShift;             /* --hash-shift: the XXH64 seed */
+    int32_t covMode;               /* --cov-mode */
+    float covThr;                  /* -c */
+    int32_t includeOnlyExtendable; /* --include-only-extendable */
+} sd_kmermatch_params;
+int sd_host_reduced_alphabet(int which, int alphabetSize, uint8_t *letterMap21, int *reducedSize);
+/* setKmerLengthAndAlphabet's -k 0 rule for amino acids (kmermatcher.cpp:1278-1290): *kmerSize and *alphabetSize from --min-seq-id and
+ * the DB's residue count, in the reference's float arithmetic */
+int sd_host_kmermatch_auto_k(float seqIdThr, uint64_t residues, int *kmerSize, int *alphabetSize);
+/* kmerConsidered of a sequence of seqLen residues before the window count caps it: (size_t)(kmersPerSequence - 1 + scale * seqLen) in
+ * float, the product rounded before the sum (kmermatcher.cpp:206); what sd_kmermatch_batch uses per sequence */
+uint64_t sd_host_kmermatch_considered(int kmersPerSequence, float kmersPerSequenceScale, uint32_t seqLen);
+int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSeq, const uint8_t *residues, const uint64_t *offsets,
+                       const uint32_t *keys, const uint8_t *letterMap21, uint64_t outCap, uint32_t *outRep, uint32_t *outMember,
+                       uint32_t *outScore, int32_t *outDiag, uint64_t *stats);
+/* The prefilter DB of the hits (kmermatcherInner, kmermatcher.cpp:741-793): for every sequence key, ascending, one entry -- a
+ * representative with hits gets "rep\t0\t0\n" and one "member\tscore\tdiagonal\n" line per hit, every other sequence "key\t0\t0\n".
+ * keys[nSeq] need not be sorted; the hits are sorted by (rep, member).  entryKey [nSeq], entryOff [nSeq + 1]; text == NULL: only
+ * *textBytes is set; textCap too small: SD_ENOMEM.  A hit whose representative is no sequence key: SD_EINVAL. */
+int sd_host_kmermatch_format(uint64_t nSeq, const uint32_t *keys, uint64_t nHits, const uint32_t *rep, const uint32_t *member,
+                             const uint32_t *score, const int32_t *diag, uint32_t *entryKey, uint64_t *entryOff, uint64_t textCap,
+                             char *text, uint64_t *textBytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,11 @@ EXPAND_EMPTY, EXPAND_LEAVES_SEQUENCE = 1, 2
 HIT_DTYPE = np.dtype([('seqId', '<u4'), ('score', '<i4'), ('diagonal', '<u2'), ('pad', '<u2')])
 
 
+class KmParams(C.Structure):
+    _fields_ = [('kmerSize', C.c_int32), ('alphabetSize', C.c_int32), ('kmersPerSequence', C.c_int32), ('kmersPerSequenceScale', C.c_float),
+                ('hashShift', C.c_int32), ('covMode', C.c_int32), ('covThr', C.c_float), ('includeOnlyExtendable', C.c_int32)]
+
+
 class ChParams(C.Structure):
     _fields_ = [('maxGeneGap', C.c_uint32), ('clusterSize', C.c_uint32), ('alpha', C.c_double),
                 ('pCluThr', C.c_float), ('pMHThr', C.c_float)]
@@ -297,6 +302,12 @@ def load():
         'sd_host_clust_connected': (C.c_int, [C.c_uint64, _vp, _vp, C.c_int, _vp]),
         'sd_host_clust_greedy': (C.c_int, [C.c_uint64, _vp, _vp, _vp]),
         'sd_host_clust_format': (C.c_int, [C.c_uint64, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp]),
+        'sd_host_reduced_alphabet': (C.c_int, [C.c_int, C.c_int, _vp, C.POINTER(C.c_int)]),
+        'sd_host_kmermatch_auto_k': (C.c_int, [C.c_float, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        'sd_host_kmermatch_considered': (C.c_uint64, [C.c_int, C.c_float, C.c_uint32]),
+        'sd_kmermatch_batch': (C.c_int, [_vp, C.POINTER(KmParams), C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+        'sd_host_kmermatch_format': (C.c_int, [C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp,
+                                               C.POINTER(C.c_uint64)]),
     }
     missing = []
     for name, (res, args) in sig.items():

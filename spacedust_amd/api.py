@@ -1013,3 +1013,75 @@ def clust_format(local_keys, assigned):
     raw = text.tobytes()
     db = {int(ekey[e]): raw[int(eoff[e]):int(eoff[e + 1])] for e in range(ne.value)}
     return np.stack([rep[:n], mem[:n]], axis=1), db
+
+
+def reduced_alphabet(alphabet_size=13, which=0):
+    """sd_host_reduced_alphabet: (letter_map uint8 [21], reduced size) -- ReducedMatrix's merging of the 21 letters of matrix `which` down
+    to alphabet_size codes (X the last one); 21 is the identity."""
+    out = np.zeros(21, np.uint8)
+    size = C.c_int()
+    _check(None, _lib.load().sd_host_reduced_alphabet(int(which), int(alphabet_size), ptr(out), C.byref(size)), 'sd_host_reduced_alphabet')
+    return out, size.value
+
+
+def kmermatch_auto_k(min_seq_id, residues):
+    """sd_host_kmermatch_auto_k: (k, alphabet size) of `kmermatcher -k 0`"""
+    k, a = C.c_int(), C.c_int()
+    _check(None, _lib.load().sd_host_kmermatch_auto_k(float(min_seq_id), int(residues), C.byref(k), C.byref(a)), 'sd_host_kmermatch_auto_k')
+    return k.value, a.value
+
+
+def kmermatch_params(k=0, alph_size=13, kmer_per_seq=0, kmer_per_seq_scale=0.0, hash_shift=67, cov_mode=0, c=0.8,
+                     include_only_extendable=False, min_seq_id=0.0, residues=0):
+    """the kmermatcher module's parameters after its defaults (setLinearFilterDefault, setKmerLengthAndAlphabet): k = 0 chooses k and the
+    alphabet from min_seq_id and the residue count, kmer_per_seq = 0 is 20"""
+    if k == 0:
+        k, alph_size = kmermatch_auto_k(min_seq_id, residues)
+    return _lib.KmParams(int(k), int(alph_size), int(kmer_per_seq) if kmer_per_seq else 20, float(kmer_per_seq_scale), int(hash_shift),
+                         int(cov_mode), float(c), 1 if include_only_extendable else 0)
+
+
+def kmermatch(ctx, par, residues, offsets, keys, letter_map=None, cap=None):
+    """sd_kmermatch_batch: the hits of linclust's kmermatcher as (rep, member, score uint32, diagonal int32, stats), sorted by (rep, member);
+    stats = dict(records, grouped, hits, largest_group).  letter_map: default reduced_alphabet(par.alphabetSize).  cap: room of the output
+    in hits (default: exactly enough, learned from a count-only call first)."""
+    L = _lib.load()
+    residues = np.ascontiguousarray(residues, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    keys = np.ascontiguousarray(keys, np.uint32)
+    n = len(offsets) - 1
+    assert len(keys) == n and len(residues) == int(offsets[-1])
+    if letter_map is None:
+        letter_map = reduced_alphabet(par.alphabetSize)[0]
+    letter_map = np.ascontiguousarray(letter_map, np.uint8)
+    stats = np.zeros(4, np.uint64)
+    named = lambda: dict(records=int(stats[0]), grouped=int(stats[1]), hits=int(stats[2]), largest_group=int(stats[3]))
+    if cap is None:
+        rc = L.sd_kmermatch_batch(ctx.h, C.byref(par), n, ptr(residues), ptr(offsets), ptr(keys), ptr(letter_map), 0, None, None, None, None,
+                                  ptr(stats))
+        if rc != _lib.SD_ENOMEM or int(stats[2]) == 0:
+            _check(ctx.h, rc, 'sd_kmermatch_batch')
+        cap = int(stats[2])
+    rep, mem, score = (np.zeros(max(cap, 1), np.uint32) for _ in range(3))
+    diag = np.zeros(max(cap, 1), np.int32)
+    _check(ctx.h, L.sd_kmermatch_batch(ctx.h, C.byref(par), n, ptr(residues), ptr(offsets), ptr(keys), ptr(letter_map), cap, ptr(rep), ptr(mem),
+                                       ptr(score), ptr(diag), ptr(stats)), 'sd_kmermatch_batch')
+    h = int(stats[2])
+    return rep[:h], mem[:h], score[:h], diag[:h], named()
+
+
+def kmermatch_format(keys, rep, member, score, diag):
+    """sd_host_kmermatch_format: the prefilter DB of the hits as dict key -> bytes (every sequence key has an entry)"""
+    L = _lib.load()
+    keys = np.ascontiguousarray(keys, np.uint32)
+    rep, member, score = (np.ascontiguousarray(x, np.uint32) for x in (rep, member, score))
+    diag = np.ascontiguousarray(diag, np.int32)
+    n, h = len(keys), len(rep)
+    nbytes = C.c_uint64()
+    _check(None, L.sd_host_kmermatch_format(n, ptr(keys), h, ptr(rep), ptr(member), ptr(score), ptr(diag), None, None, 0, None, C.byref(nbytes)),
+           'sd_host_kmermatch_format')
+    ekey, eoff, text = np.zeros(max(n, 1), np.uint32), np.zeros(n + 1, np.uint64), np.zeros(nbytes.value + 1, np.uint8)
+    _check(None, L.sd_host_kmermatch_format(n, ptr(keys), h, ptr(rep), ptr(member), ptr(score), ptr(diag), ptr(ekey), ptr(eoff), nbytes.value,
+                                            ptr(text), C.byref(nbytes)), 'sd_host_kmermatch_format')
+    raw = text.tobytes()
+    return {int(ekey[e]): raw[int(eoff[e]):int(eoff[e + 1])] for e in range(n)}

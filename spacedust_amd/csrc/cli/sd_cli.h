@@ -178,6 +178,7 @@ int mergedbsModule(const Args &a);
 int swapresultsModule(const Args &a);
 int expandalnModule(const Args &a);
 int clustModule(const Args &a);
+int kmermatcherModule(const Args &a);
 
 }  // namespace sdcli
 #endif

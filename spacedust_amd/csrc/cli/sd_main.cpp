@@ -37,6 +37,7 @@ const Module kModules[] = {
     {"swapresults", swapresultsModule, "host glue: re-key a prefilter / alignment DB by its targets: <queryDB> <targetDB> <resultDB> <outDB>"},
     {"expandaln", expandalnModule, "A->B alignments carried over to the C's each B is aligned with, backtraces translated on the GPU: <queryDB> <targetDB> <resultDB_AB> <resultDB_BC> <outDB>"},
     {"clust", clustModule, "result DB of a set against itself -> cluster DB; the symmetric graph of --cluster-mode 0 / 1 is built on the GPU: <sequenceDB> <resultDB> <clusterDB>"},
+    {"kmermatcher", kmermatcherModule, "linclust's first stage: sequences sharing a selected k-mer grouped under the longest, records sorted and grouped on the GPU: <sequenceDB> <prefDB>"},
     {"createindex", createindexModule, "target k-mer index built once, in the reference's createindex file layout: <sequenceDB> <tmpDir>"},
     {"createsetdb", createsetdbModule, "FASTA files (Prodigal headers) -> setDB in the createsetdb layout"},
 };
