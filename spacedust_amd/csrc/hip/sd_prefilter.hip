@@ -19,6 +19,10 @@
 // candidate are dropped after one look.  The reference's overflow path (> 2*max(1e6,dbSize) hits per query), the rescoring
 // path (threshold >= 255) and result lists of any length (select_hits_big_kernel) are computed; what the device does not
 // compute is reported per query (outCount = UINT32_MAX) -- never silently approximated.
+// The host driver (end of the file) runs a call in sub-batches, PfBatch, one function per stage; PfKnobs lists the environment knobs:
+//   upload stageUpload | count k-mers stageCountKmers | emit + count hits stageEmitHits (emitLookup + lookupSplits, or joinHits)
+//   match stageMatch (coarseSplit, hotFilter, bucketMatch; sortFallback) | score + keep stageScoreKeep | select stageSelect
+//   download + scatter stageDownload | k-mer passes launchKmerPass | prefilterBatchImpl: the loop, halving a sub-batch or redoing it on the lookup path
 #include <memory>
 #include "sd_common.h"
 
@@ -1054,9 +1058,8 @@ __device__ __forceinline__ uint32_t cpQueryOfSeg(uint32_t seg, uint32_t nQ, cons
 }
 
 // target ranges per query for a sub-batch whose average query has avgQ hits (0: no split); see the comments where it is applied
-inline int coarseBitsFor(uint64_t avgQ, int tBits) {
-    const uint64_t perVQ = getenv("SD_PF_COARSE") ? (uint64_t) atoll(getenv("SD_PF_COARSE")) : 200000;
-    const uint64_t perVQsplit = getenv("SD_PF_COARSE") ? perVQ : 50000;
+// (perVQ: hits of the average query from which a split is made; perVQsplit: hits per range it aims at -- PfKnobs, SD_PF_COARSE)
+inline int coarseBitsFor(uint64_t avgQ, int tBits, uint64_t perVQ, uint64_t perVQsplit) {
     int cBits = 0;
     if (avgQ > perVQ)
         while (cBits < CP_MAX_BITS && tBits - (cBits + 1) >= 8 && (avgQ >> cBits) > perVQsplit) cBits++;
@@ -2793,18 +2796,926 @@ void sd_target_destroy(sd_target *t) {
     delete t;
 }
 
+}  // extern "C"
+
+// ---- the batch driver: per-call state (PfKnobs, PfCall), the sub-batch with its stages (PfBatch), and the loop over sub-batches (prefilterBatchImpl)
 namespace {
 struct ProfileQueries {          // profile queries: Sequence::mapProfile's outputs, concatenated like the letters
     const int16_t *sortedScore;  // [position][20] descending
     const uint8_t *sortedIndex;  // [position][20] amino acids in that order
     const int8_t *aln;           // [position][21] alignment profile
 };
-}  // namespace
 
-static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilter_params *par, uint32_t nQ,
-                              const uint8_t *qResidues, const uint64_t *qOffsets, const int16_t *qKmerBias,
-                              const int8_t *qDiagBias, const uint32_t *identityId, sd_hit *outHits, uint32_t *outCount,
-                              uint64_t *stats, const ProfileQueries *prof) {
+// The environment knobs of the driver, read once per call: tests and A/B tools change them between calls of one process (SD_PF_CUM: sdBuildExt3Cum)
+//   SD_PF_JOIN=0          no k-mer-major join: every sub-batch takes the lookup path
+//   SD_PF_JOIN_PROFILE=0  profile queries stay on the lookup path
+//   SD_PF_SORT (set)      global radix sort + match_diag instead of the bucketed match (and therefore the lookup path)
+//   SD_PF_FILTER=0        no hot-target filter (and no segment match) in front of the bucket machinery
+//   SD_PF_FILTER_MIN=n    segments below n hits pass the filter unread (256)
+//   SD_PF_BATCH=n         queries per sub-batch (2048; at most what the key's query bits carry)
+//   SD_PF_HIT_BUDGET=n    hits per sub-batch before it is halved (3 * 2^30; 2^16 ... 0xF0000000)
+//   SD_PF_COARSE=n        coarse split from n hits per average query on, into ranges of at most n (from 200 000, into 50 000)
+//   SD_DEBUG_TIMING (set) two lines on stderr: what the hot filter left, and why the bucket path fell back
+struct PfKnobs {
+    bool join, joinProfile, sort, filter, debugTiming, hasBatch;
+    uint32_t filterMin, batch;
+    uint64_t hitBudget, coarsePerVQ, coarsePerVQsplit;
+    PfKnobs() {
+        auto off = [](const char *name) { return getenv(name) && atoi(getenv(name)) == 0; };
+        join = !off("SD_PF_JOIN"), joinProfile = !off("SD_PF_JOIN_PROFILE"), filter = !off("SD_PF_FILTER");
+        sort = getenv("SD_PF_SORT") != nullptr, debugTiming = getenv("SD_DEBUG_TIMING") != nullptr;
+        filterMin = getenv("SD_PF_FILTER_MIN") ? (uint32_t) atoi(getenv("SD_PF_FILTER_MIN")) : 256u;
+        hasBatch = getenv("SD_PF_BATCH") != nullptr;
+        batch = hasBatch ? (uint32_t) atoi(getenv("SD_PF_BATCH")) : 0u;
+        hitBudget = 3ull << 30;
+        if (const char *e = getenv("SD_PF_HIT_BUDGET")) hitBudget = std::max<uint64_t>(1ull << 16, std::min<uint64_t>(0xF0000000ull, (uint64_t) atoll(e)));
+        coarsePerVQ = getenv("SD_PF_COARSE") ? (uint64_t) atoll(getenv("SD_PF_COARSE")) : 200000;
+        coarsePerVQsplit = getenv("SD_PF_COARSE") ? coarsePerVQ : 50000;
+    }
+};
+
+// what a call keeps for all its sub-batches
+struct PfCall {
+    sd_ctx *const ctx;
+    const sd_target *T;
+    const sd_prefilter_params *par;
+    const ProfileQueries *prof;
+    const uint8_t *qResidues;   // the caller's arrays, as sd_prefilter_batch takes them
+    const uint64_t *qOffsets;
+    const int16_t *qKmerBias;
+    const int8_t *qDiagBias;
+    const uint32_t *identityId;
+    sd_hit *outHits;
+    uint32_t *outCount;
+    uint64_t *stats;
+    const PfKnobs knobs;
+    int tBits = 1, binBits = 0, maxHits = 0;
+    uint64_t maxDbMatches = 0;
+    // Hits per sub-batch. The k-mer stream of a sub-batch carries 30-bit stream indices (jpElem) and the lookup path keeps 18 - 26 B per hit in its workspace, so
+    // those two stay at 2^30; the JOIN path's hit stream is bounded by its 32-bit write cursors alone (< 0xFFFFFFF0 hits, checked where the sub-batch is sized) --
+    // its tables (7.1 GB at 1 000 proteomes) are walked once per sub-batch, so the fewer sub-batches the better (knobs.hitBudget, SD_PF_HIT_BUDGET)
+    const uint64_t kmerBudget = 1ull << 30, lookupHitBudget = 1ull << 30;
+    // (workspace views, not allocations of this call: a hipFree at the end of every call waits for all streams of the device, i.e. the other lanes of a pipeline)
+    WsView<int8_t> dMat{ctx, "pf.mat"};
+    WsView<int> dErr{ctx, "pf.err"};
+    WsView<uint8_t> scanTmp{ctx, "pf.scanTmp"};
+    bool useBuckets() const { return !knobs.sort; }
+    int coarseBits(uint64_t avgQ) const { return coarseBitsFor(avgQ, tBits, knobs.coarsePerVQ, knobs.coarsePerVQsplit); }
+};
+
+// views of one length; a step of the driver that hands its status on
+template <typename... V>
+hipError_t allocAll(size_t count, V &...views) {
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? views.alloc(count) : e), ...);
+    return e;
+}
+#define SD_RC(call) do { const int rc_ = (call); if (rc_ != SD_OK) return rc_; } while (0)
+
+// the three passes of the k-mer generator
+enum KmerPass { KMERS_COUNT, KMERS_EMIT_LOOKUP, KMERS_EMIT_JOIN };
+
+// what a pass of profile_kmers_kernel writes (and reads to find the place): the rest is null
+struct ProfileKmerOut {
+    uint32_t *kmerCount;          // count pass
+    const uint32_t *idxOffsets;   // lookup emit: the index, and the three arrays per k-mer
+    const uint64_t *kmerBase;     // both emits
+    uint32_t *kStart, *kLen, *kPos;
+    const uint64_t *blockBase;    // lookup emit, wide index: the block bases and the high half of the starts
+    uint32_t *kStartHi;
+    uint64_t *joinElems;          // join emit
+};
+
+struct HitStream;
+
+// what a stage tells the loop: go on, or do the sub-batch again -- with half the queries, or on the lookup path
+enum PfNext { PF_GO, PF_RETRY_HALF, PF_RETRY_LOOKUP };
+
+// One sub-batch, the queries [qBeg, qBeg + bq): its stages, the views more than one of them touches, the host arrays a read (sdD2H) may outlive a stage in
+struct PfBatch {
+    PfCall &c;
+    sd_ctx *const ctx;
+    const uint32_t qBeg, bq;
+    const bool forceLookup;   // this sub-batch is redone on the lookup path (a regime the join path does not carry)
+    uint64_t nPos = 0, nKmers = 0, nHits = 0;
+    uint32_t nCand = 0, posMask = 0xFFFFFFu;
+    bool joinCandidate = false, useJoin = false, wideIdx = false, widePos = false, bucketDone = false;
+    uint32_t profGrid = 0;      // profile queries: the small tier's grid, and whether the count pass sent positions to the big tier
+    bool profAnyBig = false;
+    const int8_t *dProfAln = nullptr;
+    const uint64_t *nKeptPtr = nullptr;   // kept candidates (device); null: none
+    DiagSrc diagSrc;
+    std::vector<uint64_t> hOff, hPos, hStats;   // (hOff, hPos: sources of uploads, they stay until the sub-batch is done)
+    std::vector<uint8_t> hUnsupported;
+    std::unique_ptr<HostScope> hs;
+    // upload: residues, biases, offsets; profile queries: sorted scores and their amino acids
+    WsView<uint8_t> dQ{ctx, "pf.dQ"}, dPI{ctx, "pf.dProfIndex"};
+    WsView<int16_t> dKB{ctx, "pf.dKB"}, dPS{ctx, "pf.dProfScore"};
+    WsView<int8_t> dDB{ctx, "pf.dDB"};
+    WsView<uint64_t> dQOff{ctx, "pf.dQOff"}, dPosBase{ctx, "pf.dPosBase"};
+    WsView<uint32_t> dIdent{ctx, "pf.dIdent"};
+    // k-mer passes (dPosQuery: sequence queries, the query of every position; dKStartHi: wide indexes, high half of the list starts; dElems: the join's stream)
+    WsView<uint2> dProfScratch{ctx, "pf.dProfScratch"};
+    WsView<uint8_t> dProfBig{ctx, "pf.dProfBig"};
+    WsView<uint32_t> dKmerCount{ctx, "pf.dKmerCount"}, dPosQuery{ctx, "pf.dPosQuery"}, dQKmerBase{ctx, "pf.dQKmerBase"};
+    WsView<uint32_t> dKStart{ctx, "pf.dKStart"}, dKLen{ctx, "pf.dKLen"}, dKPos{ctx, "pf.dKPos"}, dKStartHi{ctx, "pf.dKStartHi"};
+    WsView<uint64_t> dKmerBase{ctx, "pf.dKmerBase"}, dHitBase{ctx, "pf.dHitBase"}, dElems{ctx, "pf.dElems"};
+    // statistics; overflows of the reference's hit buffer per query, and where (all of them)
+    WsView<uint64_t> dStats{ctx, "pf.dStats"};
+    WsView<uint32_t> dQSplit{ctx, "pf.dQSplit"}, dQParts{ctx, "pf.dQParts"}, dQSplits{ctx, "pf.dQSplits"};
+    WsView<int> dSplitFlag{ctx, "pf.dSplitFlag"};
+    // the hit stream: starts per query (either path); the join's hits with a byte per hit for the coarse split (null: not written); the lookup path's arrays
+    WsView<uint64_t> dQHitBase{ctx, "pf.dQHitBase"}, dEmitPos{ctx, "pf.dEmitPos"};
+    WsView<uint2> dHitsKV{ctx, "pf.dHitsKV"};
+    WsView<uint8_t> dHitR6{ctx, "pf.dHitR6"}, dEmit{ctx, "pf.dEmit"};
+    WsView<uint32_t> dKeyA{ctx, "pf.dKeyA"}, dKeyB{ctx, "pf.dKeyB"}, dValA{ctx, "pf.dValA"}, dValB{ctx, "pf.dValB"};
+    WsView<uint16_t> dDiag{ctx, "pf.dDiag"};
+    // candidates, kept candidates, result lists
+    WsView<uint32_t> dCKey{ctx, "pf.dCKey"}, dCVal{ctx, "pf.dCVal"}, dKKey{ctx, "pf.dKKey"}, dKVal{ctx, "pf.dKVal"}, dOutCount{ctx, "pf.dOutCount"};
+    WsView<int32_t> dKScore{ctx, "pf.dKScore"};
+    WsView<sd_hit> dOut{ctx, "pf.dOut"};
+    PfBatch(PfCall &call, uint32_t qBeg_, uint32_t bq_, bool forceLookup_) : c(call), ctx(call.ctx), qBeg(qBeg_), bq(bq_), forceLookup(forceLookup_) {}
+    void phase(const char *name) { hs.reset(new HostScope(ctx, name)); }   // (ends the phase before it)
+    PfNext next = PF_GO;
+    int retry(PfNext how) { next = how; return SD_OK; }
+    bool unsupported(uint32_t x) const { return x < hUnsupported.size() && hUnsupported[x]; }
+    template <bool EMIT> int profileKmerPass(const ProfileKmerOut &o);
+    int launchKmerPass(KmerPass pass);
+    int stageUpload();
+    int stageCountKmers();
+    int markUnsupportedQueries(const char *why);
+    int emitLookup();
+    int lookupSplits();
+    int joinHits();
+    int stageEmitHits();
+    void launchGatherHits(int wide);
+    int coarseSplit(HitStream &s);
+    int hotFilter(HitStream &s);
+    int bucketMatch(const HitStream &s);
+    int sortFallback();
+    int stageMatch();
+    int stageScoreKeep();
+    template <int CAP> void launchSelectHits(const uint32_t *dQStart, uint32_t *bigList, uint32_t *bigCount);
+    int stageSelect();
+    int stageDownload();
+};
+
+// ---- the k-mer generator, one launcher for its three passes
+// Profile queries: the wide grid's tier, then the few positions that outgrew it (the count pass finds out whether there are any, the emit passes follow it)
+template <bool EMIT>
+int PfBatch::profileKmerPass(const ProfileKmerOut &o) {
+    auto launch = [&](int tier) {
+        hipLaunchKernelGGL(profile_kmers_kernel<EMIT>, dim3(tier ? PROFILE_GRID_BIG : profGrid), dim3(64), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p,
+                           dPS.p, dPI.p, c.par->kmerThr, c.T->k, dProfScratch.p, o.kmerCount, o.idxOffsets, o.kmerBase, o.kStart, o.kLen, o.kPos, c.dErr.p,
+                           tier ? PROFILE_PARTIAL_CAP_BIG : PROFILE_PARTIAL_CAP, dProfBig.p, tier, o.blockBase, o.kStartHi, o.joinElems);
+    };
+    launch(0);
+    if (!EMIT) {
+        int hTier = 0;
+        SD_HIP(ctx, sdD2H(ctx, &hTier, c.dErr.p, sizeof(int)));
+        SD_HIP(ctx, sdStreamSync(ctx));
+        profAnyBig = hTier == 7;
+        if (profAnyBig) SD_HIP(ctx, hipMemsetAsync(c.dErr.p, 0, sizeof(int), ctx->stream));
+    }
+    if (profAnyBig) launch(1);
+    return SD_OK;
+}
+
+// The only ladder over (profile queries | similar-k-mer target | k = 6 | k = 7) x (narrow | wide index); the join takes k = 6 and narrow indexes only
+int PfBatch::launchKmerPass(KmerPass pass) {
+    const sd_target *T = c.T;
+    const int kmerThr = c.par->kmerThr;
+    const uint64_t *blockBase = wideIdx ? (const uint64_t *) T->dBlockBase : (const uint64_t *) nullptr;
+    uint32_t *kStartHi = wideIdx ? dKStartHi.p : (uint32_t *) nullptr;
+    const uint16_t *cum = (const uint16_t *) T->dExt3Cum;
+    const uint32_t *posQuery = (const uint32_t *) dPosQuery.p;
+    const dim3 perWave(gridFor(nPos, 4)), perThread(gridFor(nPos, 256)), block(256);
+    ProfScope ps(ctx, pass == KMERS_COUNT ? "prefilter_count_kmers" : "prefilter_emit_kmers");
+    if (c.prof) {
+        if (pass == KMERS_COUNT) {
+            profGrid = (uint32_t) std::min<uint64_t>(nPos, PROFILE_GRID);
+            SD_HIP(ctx, dProfScratch.alloc(std::max((size_t) PROFILE_GRID * 2 * PROFILE_PARTIAL_CAP, (size_t) PROFILE_GRID_BIG * 2 * PROFILE_PARTIAL_CAP_BIG)));
+            SD_HIP(ctx, dProfBig.alloc(nPos + 1));
+            SD_HIP(ctx, hipMemsetAsync(dProfBig.p, 0, nPos + 1, ctx->stream));
+            return profileKmerPass<false>({dKmerCount.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+        }
+        if (pass == KMERS_EMIT_LOOKUP)
+            return profileKmerPass<true>({nullptr, T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p, (const uint64_t *) T->dBlockBase, kStartHi, nullptr});
+        // the per-position products again, this time writing the stream (the tiers the count pass chose)
+        return profileKmerPass<true>({nullptr, nullptr, dKmerBase.p, nullptr, nullptr, nullptr, nullptr, nullptr, dElems.p});
+    }
+    if (T->similar) {   // the query's own k-mers only; par->kmerThr and the k-mer bias are not read
+        if (pass == KMERS_COUNT)
+            hipLaunchKernelGGL(exact_count_kernel, perThread, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, posQuery, dKmerCount.p);
+        else if (pass == KMERS_EMIT_JOIN)
+            hipLaunchKernelGGL((exact_emit_kernel<true, false>), perThread, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, posQuery, dKmerBase.p,
+                               dElems.p, (const uint32_t *) nullptr, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr,
+                               (uint32_t *) nullptr);
+        else
+            hipLaunchKernelGGL((wideIdx ? exact_emit_kernel<false, true> : exact_emit_kernel<false, false>), perThread, block, 0, ctx->stream, nPos, dPosBase.p, bq,
+                               dQ.p, dQOff.p, dKB.p, posQuery, dKmerBase.p, (uint64_t *) nullptr, T->dOffsets, blockBase, dKStart.p, kStartHi, dKLen.p, dKPos.p);
+    } else if (T->k == 6) {
+        if (pass == KMERS_COUNT)
+            hipLaunchKernelGGL(count_kmers_kernel, perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, kmerThr, T->dExt3Score, dKmerCount.p,
+                               cum, T->ext3Lo, posQuery);
+        else if (pass == KMERS_EMIT_JOIN)
+            hipLaunchKernelGGL(emit_kmers_join_kernel, perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, kmerThr, T->dExt3Score,
+                               T->dExt3Index, dKmerBase.p, dElems.p, cum, T->ext3Lo, posQuery);
+        else
+            hipLaunchKernelGGL((wideIdx ? emit_kmers_kernel<true> : emit_kmers_kernel<false>), perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p,
+                               dKB.p, kmerThr, T->dExt3Score, T->dExt3Index, T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p, blockBase, kStartHi, cum,
+                               T->ext3Lo, posQuery);
+    } else {
+        if (pass == KMERS_COUNT)
+            hipLaunchKernelGGL(count_kmers7_kernel, perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, kmerThr, T->dExt2Score,
+                               T->dExt3Score, dKmerCount.p, cum, T->ext3Lo, posQuery);
+        else
+            hipLaunchKernelGGL((wideIdx ? emit_kmers7_kernel<true> : emit_kmers7_kernel<false>), perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p,
+                               dKB.p, kmerThr, T->dExt2Score, T->dExt2Index, T->dExt3Score, T->dExt3Index, T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p,
+                               blockBase, kStartHi, cum, T->ext3Lo, posQuery);
+    }
+    return SD_OK;
+}
+
+// ---- stage 1: upload the sub-batch
+int PfBatch::stageUpload() {
+    phase("pf.upload_count");
+    const uint64_t r0 = c.qOffsets[qBeg], r1 = c.qOffsets[qBeg + bq];
+    hOff.assign(bq + 1, 0);
+    hPos.assign(bq + 1, 0);
+    for (uint32_t x = 0; x <= bq; x++) hOff[x] = c.qOffsets[qBeg + x] - r0;
+    for (uint32_t x = 0; x < bq; x++) {
+        const int64_t L = (int64_t) (hOff[x + 1] - hOff[x]);
+        hPos[x + 1] = hPos[x] + (uint64_t) std::max<int64_t>(0, L - (c.T->k == 6 ? SPAN6 : SPAN7) + 1);
+    }
+    nPos = hPos[bq];
+    if (nPos * 64 >= (1ull << 32) && bq > 1) return retry(PF_RETRY_HALF);   // a wavefront per position: a dispatch carries at most 2^32 work-items
+    SD_HIP(ctx, allocAll(r1 - r0 + 64, dQ, dKB, dDB));
+    SD_HIP(ctx, allocAll(bq + 1, dQOff, dPosBase));
+    SD_HIP(ctx, dIdent.alloc(bq));
+    SD_HIP(ctx, hipMemcpyAsync(dQ.p, c.qResidues + r0, r1 - r0, hipMemcpyHostToDevice, ctx->stream));
+    if (c.prof) {
+        WsView<int8_t> dPA(ctx, "pf.dProfAln");
+        SD_HIP(ctx, allocAll((r1 - r0) * 20 + 64, dPS, dPI));
+        SD_HIP(ctx, dPA.alloc((r1 - r0) * 21 + 64));
+        SD_HIP(ctx, hipMemcpyAsync(dPS.p, c.prof->sortedScore + r0 * 20, (r1 - r0) * 20 * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
+        SD_HIP(ctx, hipMemcpyAsync(dPI.p, c.prof->sortedIndex + r0 * 20, (r1 - r0) * 20, hipMemcpyHostToDevice, ctx->stream));
+        SD_HIP(ctx, hipMemcpyAsync(dPA.p, c.prof->aln + r0 * 21, (r1 - r0) * 21, hipMemcpyHostToDevice, ctx->stream));
+        dProfAln = dPA.p;
+    } else {
+        SD_HIP(ctx, hipMemcpyAsync(dKB.p, c.qKmerBias + r0, (r1 - r0) * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
+        SD_HIP(ctx, hipMemcpyAsync(dDB.p, c.qDiagBias + r0, r1 - r0, hipMemcpyHostToDevice, ctx->stream));
+    }
+    SD_HIP(ctx, hipMemcpyAsync(dQOff.p, hOff.data(), (bq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    SD_HIP(ctx, hipMemcpyAsync(dPosBase.p, hPos.data(), (bq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    SD_HIP(ctx, hipMemcpyAsync(dIdent.p, c.identityId + qBeg, bq * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(c.dErr.p, 0, sizeof(int), ctx->stream));
+    return SD_OK;
+}
+
+// ---- stage 2: count the similar k-mers of every position, their stream bases, and whether the join takes the sub-batch
+int PfBatch::stageCountKmers() {
+    const sd_target *T = c.T;
+    // k-mer-major join (sd_pf_join.h): k = 6, 32-bit list starts, the bucketed match, and a tie order of the result cut that fits its key (sequence id bits above
+    // the bin: 20); profile queries as well unless SD_PF_JOIN_PROFILE=0 (profile_kmers_kernel writes the join's stream elements)
+    joinCandidate = !forceLookup && T->k == 6 && T->dBlockBase == nullptr && c.useBuckets() && bq <= (uint32_t) JQ_MAX &&
+                    (!c.prof || c.knobs.joinProfile) && c.tBits - c.binBits <= 20 && c.binBits <= 12 && c.knobs.join;
+    wideIdx = T->dBlockBase != nullptr;
+    WsView<int> dJoinFlag(ctx, "pf.dJoinFlag");
+    int hJoinFlag = 0;
+    SD_HIP(ctx, allocAll(nPos + 1, dKmerCount, dKmerBase));
+    SD_HIP(ctx, hipMemsetAsync(dKmerCount.p, 0, (nPos + 1) * sizeof(uint32_t), ctx->stream));
+    if (nPos > 0 && !c.prof) {
+        SD_HIP(ctx, dPosQuery.alloc(nPos));
+        hipLaunchKernelGGL(pos_query_kernel, dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, (const uint64_t *) dPosBase.p, bq, dPosQuery.p);
+    }
+    if (nPos > 0) {
+        SD_RC(launchKmerPass(KMERS_COUNT));
+        SD_RC(exclusiveScanWiden(ctx, dKmerCount.p, dKmerBase.p, nPos + 1, c.scanTmp));
+        int hErrCount = 0;
+        if (joinCandidate) {
+            SD_HIP(ctx, dQKmerBase.alloc(bq + 1));
+            SD_HIP(ctx, dJoinFlag.alloc(1));
+            SD_HIP(ctx, hipMemsetAsync(dJoinFlag.p, 0, sizeof(int), ctx->stream));
+            hipLaunchKernelGGL(join_query_base_kernel, dim3(gridFor(bq + 1, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p, dKmerBase.p, dQKmerBase.p,
+                               dJoinFlag.p);
+            SD_HIP(ctx, sdD2H(ctx, &hJoinFlag, dJoinFlag.p, sizeof(int)));
+        }
+        SD_HIP(ctx, sdD2H(ctx, &nKmers, dKmerBase.p + nPos, sizeof(uint64_t)));
+        if (c.prof) SD_HIP(ctx, sdD2H(ctx, &hErrCount, c.dErr.p, sizeof(int)));
+        SD_HIP(ctx, sdStreamSync(ctx));
+        if (hErrCount == 8)
+            return sdFail(ctx, SD_EUNSUPPORTED, "more than %u similar k-mers at one profile position (the reference truncates there, KmerGenerator.cpp:202-210)",
+                          PROFILE_PARTIAL_CAP_BIG);
+    }
+    if (nKmers > c.kmerBudget && bq > 1) return retry(PF_RETRY_HALF);   // permissive thresholds: the k-mer list itself outgrows 32-bit device scans
+    if (nKmers >= 0x7FFFFFFFull) return sdFail(ctx, SD_EUNSUPPORTED, "more than 2^31 similar k-mers for one query");
+    useJoin = joinCandidate && !hJoinFlag && nKmers > 0;
+    return SD_OK;
+}
+
+// Queries the device does not compute (>= 2^32 index hits, more than PF_SPLITS_MAX overflows of the reference's hit buffer, or a single index list as large as
+// that buffer) are taken out of the batch and reported per query (outCount = UINT32_MAX): the marks left in dQSplit go into hUnsupported; `why`: the path's words
+int PfBatch::markUnsupportedQueries(const char *why) {
+    std::vector<uint32_t> hSplit(bq);
+    SD_HIP(ctx, sdD2H(ctx, hSplit.data(), dQSplit.p, (size_t) bq * sizeof(uint32_t)));
+    SD_HIP(ctx, sdStreamSync(ctx));
+    hUnsupported.assign(bq, 0);
+    uint32_t nBad = 0, firstBad = 0;
+    for (uint32_t x = 0; x < bq; x++)
+        if (hSplit[x] == QUERY_UNSUPPORTED) {
+            hUnsupported[x] = 1;
+            if (!nBad) firstBad = qBeg + x;
+            nBad++;
+        }
+    sdFail(ctx, SD_EUNSUPPORTED, "%u quer%s of the batch [%u, %u) (first: %u) %s: reported with outCount = UINT32_MAX, the rest of the batch is computed",
+           nBad, nBad == 1 ? "y" : "ies", qBeg, qBeg + bq, firstBad, why);
+    return SD_OK;
+}
+
+// ---- stage 3, lookup path: every similar k-mer with its index list (start, length), the hits' stream offsets and their number
+int PfBatch::emitLookup() {
+    SD_HIP(ctx, dKStart.alloc(nKmers + 1));
+    if (wideIdx) SD_HIP(ctx, dKStartHi.alloc(nKmers + 1));
+    SD_HIP(ctx, allocAll(nKmers + 1, dKLen, dKPos, dHitBase));
+    SD_HIP(ctx, hipMemsetAsync(dKLen.p, 0, (nKmers + 1) * sizeof(uint32_t), ctx->stream));
+    if (nKmers > 0) {
+        SD_RC(launchKmerPass(KMERS_EMIT_LOOKUP));
+        SD_RC(exclusiveScanWiden(ctx, dKLen.p, dHitBase.p, nKmers + 1, c.scanTmp));
+        SD_HIP(ctx, sdD2H(ctx, &nHits, dHitBase.p + nKmers, sizeof(uint64_t)));
+        SD_HIP(ctx, sdStreamSync(ctx));
+    }
+    return SD_OK;
+}
+
+// ---- stage 3, lookup path: the statistics, where a query overflows the reference's hit buffer, and the queries that are left out
+int PfBatch::lookupSplits() {
+    if (nHits > std::min(c.knobs.hitBudget, c.lookupHitBudget) && bq > 1) return retry(PF_RETRY_HALF);   // too many hits for one sort
+    if (nHits >= 0xFFFFFFFFull) return sdFail(ctx, SD_EUNSUPPORTED, "more than 2^32 hits in one query batch");
+    hipLaunchKernelGGL(stats_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p, dKmerBase.p, dHitBase.p, nKmers, nHits, dStats.p);
+    // Stream positions: 24 bits of the value word beside the diagonal byte -- or, for sub-batches with a query of 2^24 hits and more, the whole word, the diagonal
+    // byte travelling in the key (bucket path only: it needs the coarse split)
+    const uint64_t posLimit = c.useBuckets() ? 0xFFFFFFF0ull : (1ull << 24);
+    // the reference's hit buffer holds maxDbMatches entries per query; where a query overflows it, the match runs on the parts separately (query_split_kernel)
+    auto querySplit = [&]() {
+        hipLaunchKernelGGL(query_split_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p, dKmerBase.p, dHitBase.p, c.maxDbMatches, dQSplit.p,
+                           dQParts.p, dQSplits.p, dSplitFlag.p, posLimit);
+    };
+    querySplit();
+    int hSplitFlag = 0;
+    SD_HIP(ctx, sdD2H(ctx, &hSplitFlag, dSplitFlag.p, sizeof(int)));
+    SD_HIP(ctx, sdD2H(ctx, hStats.data(), dStats.p, (size_t) bq * 4 * sizeof(uint64_t)));
+    SD_HIP(ctx, sdStreamSync(ctx));
+    if (hSplitFlag) {
+        // the queries taken out: their index lists emptied, the offsets scanned again
+        SD_RC(markUnsupportedQueries("have >= 2^32 index hits or overflow the reference's hit buffer more than 32 times"));
+        hipLaunchKernelGGL(drop_query_kmers_kernel, dim3(gridFor(nKmers, 256)), dim3(256), 0, ctx->stream, nKmers, dKPos.p, dQSplit.p, dKLen.p);
+        SD_RC(exclusiveScanWiden(ctx, dKLen.p, dHitBase.p, nKmers + 1, c.scanTmp));
+        SD_HIP(ctx, sdD2H(ctx, &nHits, dHitBase.p + nKmers, sizeof(uint64_t)));
+        SD_HIP(ctx, hipMemsetAsync(dSplitFlag.p, 0, sizeof(int), ctx->stream));
+        querySplit();
+        SD_HIP(ctx, sdStreamSync(ctx));
+    }
+    return SD_OK;
+}
+
+// ---- stage 3, join path: the k-mer stream, its k-mer-sorted copy, the hits per query, the hit-buffer overflows (in k-mer ordinals), the scatter into segments
+int PfBatch::joinHits() {
+    const sd_target *T = c.T;
+    WsView<uint64_t> dSorted(ctx, "pf.dSorted"), dKpBase(ctx, "pf.dKpBase");
+    WsView<uint32_t> dKpCounts(ctx, "pf.dKpCounts"), dKpTotal(ctx, "pf.dKpTotal"), dJqCounts(ctx, "pf.dJqCounts");
+    WsView<uint32_t> dQHits(ctx, "pf.dQHits"), dQEff(ctx, "pf.dQEff");
+    WsView<unsigned long long> dWgTotal(ctx, "pf.dWgTotal");
+    WsView<uint16_t> dChunkBin(ctx, "pf.dChunkBin");
+    const uint64_t nSortedCap = nKmers + (uint64_t) KP_BINS * JC;   // every k-mer range padded to whole join chunks
+    SD_HIP(ctx, dElems.alloc(nKmers + 1));
+    SD_HIP(ctx, dSorted.alloc(nSortedCap));
+    SD_HIP(ctx, dChunkBin.alloc(nSortedCap / JC + 1));
+    SD_HIP(ctx, dKpCounts.alloc((size_t) JP_WGS * KP_BINS));
+    SD_HIP(ctx, dKpTotal.alloc(KP_BINS));
+    SD_HIP(ctx, dKpBase.alloc(KP_BINS + 1));
+    SD_HIP(ctx, dJqCounts.alloc((size_t) JJ_WGS * bq));
+    SD_HIP(ctx, dQHits.alloc(bq));
+    SD_HIP(ctx, dWgTotal.alloc(JJ_WGS));
+    SD_RC(launchKmerPass(KMERS_EMIT_JOIN));
+    {
+        ProfScope ps(ctx, "prefilter_kmer_partition");
+        hipLaunchKernelGGL(kp_hist_kernel, dim3(JP_WGS), dim3(JP_NT), 0, ctx->stream, (const uint64_t *) dElems.p, nKmers, dKpCounts.p);
+        hipLaunchKernelGGL(col_prefix_kernel, dim3(KP_BINS / 64), dim3(256), 0, ctx->stream, dKpCounts.p, JP_WGS, KP_BINS, dKpTotal.p);
+        hipLaunchKernelGGL(small_scan_kernel, dim3(1), dim3(SS_NT), 0, ctx->stream, (const uint32_t *) dKpTotal.p, KP_BINS, dKpBase.p, (uint32_t) JC);
+        hipLaunchKernelGGL(kp_scatter_kernel, dim3(JP_WGS), dim3(JP_NT), 0, ctx->stream, (const uint64_t *) dElems.p, nKmers, (const uint32_t *) dKpCounts.p,
+                           (const uint64_t *) dKpBase.p, (const uint32_t *) dQKmerBase.p, bq, dSorted.p);
+        hipLaunchKernelGGL(kp_finish_kernel, dim3(KP_BINS), dim3(256), 0, ctx->stream, (const uint32_t *) dKpTotal.p, (const uint64_t *) dKpBase.p, dSorted.p,
+                           dChunkBin.p);
+    }
+    // (the join kernels read the padded length of the sorted stream where the partition left it: no round trip to the host)
+    const uint64_t *nSortedPtr = dKpBase.p + KP_BINS;
+    {
+        ProfScope ps(ctx, "prefilter_join_count");
+        hipLaunchKernelGGL(join_count_kernel, dim3(JJ_WGS), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr, (const uint16_t *) dChunkBin.p,
+                           (const uint32_t *) T->dOffsets, dJqCounts.p, (int) bq, dWgTotal.p);
+        hipLaunchKernelGGL(col_prefix_kernel, dim3(gridFor(bq, 64)), dim3(256), 0, ctx->stream, dJqCounts.p, JJ_WGS, (int) bq, dQHits.p);
+    }
+    // overflow of the reference's hit buffer, in k-mer ordinals
+    hipLaunchKernelGGL(query_splits_join_kernel, dim3(bq), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQKmerBase.p, (const uint64_t *) dElems.p,
+                       (const uint32_t *) T->dOffsets, (const uint32_t *) dQHits.p, c.maxDbMatches, dQSplit.p, dQParts.p, dQSplits.p, dSplitFlag.p);
+    hipLaunchKernelGGL(join_stats_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQKmerBase.p, (const uint32_t *) dQHits.p,
+                       dStats.p);
+    std::vector<unsigned long long> hWg((size_t) JJ_WGS);
+    std::vector<uint32_t> hQHits(bq);
+    int hSplitFlagJ = 0;
+    SD_HIP(ctx, sdD2H(ctx, hWg.data(), dWgTotal.p, (size_t) JJ_WGS * sizeof(unsigned long long)));
+    SD_HIP(ctx, sdD2H(ctx, hQHits.data(), dQHits.p, bq * sizeof(uint32_t)));
+    SD_HIP(ctx, sdD2H(ctx, &hSplitFlagJ, dSplitFlag.p, sizeof(int)));
+    SD_HIP(ctx, sdStreamSync(ctx));
+    uint64_t all = 0;
+    for (unsigned long long v : hWg) all += v;
+    if (all > c.knobs.hitBudget && bq > 1) return retry(PF_RETRY_HALF);   // too many hits for one sub-batch: halve it and retry
+    if (all >= 0xFFFFFFF0ull) return retry(PF_RETRY_LOOKUP);   // the per-query counters are 32 bit: this query goes the lookup path
+    for (uint32_t x = 0; x < bq; x++) hStats[(size_t) x * 4 + 1] = hQHits[x];
+    nHits = all;
+    if (hSplitFlagJ) {   // the join leaves the lists of the queries taken out aside
+        SD_RC(markUnsupportedQueries("overflow the reference's hit buffer more than 32 times or hold an index list as large as that buffer"));
+        for (uint32_t x = 0; x < bq; x++)
+            if (hUnsupported[x]) nHits -= hQHits[x];
+    }
+    SD_HIP(ctx, dQEff.alloc(bq));
+    SD_HIP(ctx, dQHitBase.alloc(bq + 1));
+    hipLaunchKernelGGL(join_effective_totals_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQHits.p,
+                       (const uint32_t *) dQSplit.p, dQEff.p);
+    hipLaunchKernelGGL(small_scan_kernel, dim3(1), dim3(SS_NT), 0, ctx->stream, (const uint32_t *) dQEff.p, (int) bq, dQHitBase.p, 0u);
+    if (nHits > 0) {
+        SD_HIP(ctx, dHitsKV.alloc(nHits));
+        // the coarse split's count pass needs a hit's range and nothing else: one byte per hit beside the 8-byte stream (the top six target bits: any split of up to
+        // 2^6 ranges reads its range off them) -- 1.5 MB per query written here for 12.3 MB per query not read there
+        if (c.tBits >= CP_MAX_BITS + 8 && c.coarseBits(nHits / std::max<uint32_t>(bq, 1)) > 0)
+            SD_HIP(ctx, dHitR6.alloc(nHits + 8));
+        ProfScope ps(ctx, "prefilter_join_scatter");
+        hipLaunchKernelGGL(join_scatter_kernel, dim3(JJ_WGS), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr, (const uint16_t *) dChunkBin.p,
+                           (const uint32_t *) T->dOffsets, (const uint2 *) T->dEntries, bq, (const uint32_t *) dJqCounts.p, (const uint64_t *) dQHitBase.p, c.tBits,
+                           (const uint32_t *) dQSplit.p, dHitsKV.p, dHitR6.p, c.tBits - CP_MAX_BITS);
+    }
+    SD_HIP(ctx, hipGetLastError());
+    return SD_OK;
+}
+
+// ---- stage 3: emit the k-mers and count the hits
+int PfBatch::stageEmitHits() {
+    phase("pf.emit");
+    if (!useJoin) SD_RC(emitLookup());
+    phase("pf.stats");
+    hStats.assign((size_t) bq * 4, 0);
+    SD_HIP(ctx, dStats.alloc((size_t) bq * 4));
+    SD_HIP(ctx, hipMemsetAsync(dStats.p, 0, (size_t) bq * 4 * sizeof(uint64_t), ctx->stream));
+    SD_HIP(ctx, allocAll(bq, dQSplit, dQParts));
+    SD_HIP(ctx, dQSplits.alloc((size_t) bq * PF_SPLITS_MAX));
+    SD_HIP(ctx, dSplitFlag.alloc(1));
+    SD_HIP(ctx, hipMemsetAsync(dSplitFlag.p, 0, sizeof(int), ctx->stream));
+    return useJoin ? joinHits() : lookupSplits();
+}
+
+// the (seqId, pos) index lists of the lookup path's k-mers into the hit stream
+void PfBatch::launchGatherHits(int wide) {
+    ProfScope ps(ctx, "prefilter_gather_hits");
+    hipLaunchKernelGGL(gather_hits_kernel, dim3(gridFor(nKmers, 256)), dim3(256), 0, ctx->stream, nKmers, dKStart.p, dKLen.p, dKPos.p, dHitBase.p, dPosBase.p, bq,
+                       (const uint2 *) c.T->dEntries, c.tBits, dQHitBase.p, dKeyA.p, dValA.p, dDiag.p,
+                       wideIdx ? (const uint32_t *) dKStartHi.p : (const uint32_t *) nullptr, wide);
+}
+
+// ---- stage 4, the double-diagonal match.  The hit stream as the bucketed match sees it: per (virtual) query a segment, as two arrays or as (key, value) pairs
+struct HitStream {
+    uint32_t nVQ;            // (virtual) queries: bq << cBits
+    int cBits, tBitsV;       // target bits the coarse split took off the key, and those left in it
+    const uint64_t *pHitBase;
+    const uint32_t *pKey, *pVal;
+    const uint2 *pKV;
+    uint64_t nLeft;          // hits the hot filter left, with their number and dense place per segment (null: unfiltered)
+    const uint32_t *pSegCount;
+    const uint64_t *pOutBase;
+};
+
+// very hit-rich queries (large target sets): coarse split into virtual queries first (see coarse_*_kernel)
+int PfBatch::coarseSplit(HitStream &s) {
+    const uint32_t nVQ0 = bq;
+    const int tBits0 = c.tBits;
+    // decided by the average query of the sub-batch (a few long queries are what the adaptive bucket count and the oversize-bucket launch are for): ~100 hits per
+    // bucket at 2^11 buckets
+    const uint64_t avgQ = nHits / std::max<uint32_t>(nVQ0, 1);
+    // no split up to 2 * 10^5 hits per average query (the filter takes such a segment in one round; at 100 proteomes, 1.5 * 10^5 hits per query, a split would only
+    // add its 24 B per hit); beyond that, ranges of at most 5 * 10^4 hits: the filter's Bloom filter has more bits per key (7.2 % of the hit stream left, 12.3 %
+    // with ranges of 10^5) and what is left comes in segments the LDS sorter takes whole (segment_match) -- 328 -> 315 ms per 8 192 queries at 1 000 proteomes, 323
+    // ms at 2.5 * 10^4 (profiles/r06y_split.txt; two more bitmaps in the filter were tried on top and removed, profiles/r06x_hf_multi.txt)
+    // (coarseBitsFor is this rule; the join's scatter asks it whether a split will follow)
+    int cBits = c.coarseBits(avgQ);
+    // wide stream positions need the split: it is where the diagonal byte moves into the key (8 free bits)
+    while (widePos && cBits < CP_MAX_BITS && tBits0 - (cBits + 1) >= 8 && (cBits < 1 || tBits0 - cBits > 24)) cBits++;
+    if (widePos && (cBits < 1 || tBits0 - cBits > 24))
+        return sdFail(ctx, SD_EUNSUPPORTED, "a query with >= 2^24 index hits against a target set of %u sequences", c.T->nSeq);
+    s.cBits = cBits;
+    if (cBits == 0) return SD_OK;
+    // segments of CP_SEG hits per query. The join path knows every query's hits on the host already (the read that sized the sub-batch), the lookup path reads the
+    // segment starts back; the segment table goes up through a pinned buffer, so nothing here waits for the stream a second time
+    std::vector<uint64_t> hQHB(nVQ0 + 1, 0);
+    if (useJoin) {
+        for (uint32_t x = 0; x < nVQ0; x++) hQHB[x + 1] = hQHB[x] + (unsupported(x) ? 0ull : hStats[(size_t) x * 4 + 1]);
+    } else {
+        SD_HIP(ctx, sdD2H(ctx, hQHB.data(), s.pHitBase, (nVQ0 + 1) * sizeof(uint64_t)));
+        SD_HIP(ctx, sdStreamSync(ctx));
+    }
+    WsView<uint64_t> dVQHitBase(ctx, "pf.dVQHitBase");  // hits of (query, range) start here
+    WsView<uint32_t> dSegBase(ctx, "pf.dSegBase"), dSegCount(ctx, "pf.dSegCount");
+    WsView<uint2> dKVC(ctx, "pf.dKVC");
+    ProfScope ps(ctx, "prefilter_coarse_split");
+    const uint32_t C = 1u << cBits;
+    uint32_t *hSegBase = nullptr;
+    SD_HIP(ctx, pinGet(ctx, "pf.hSegBase", (size_t) nVQ0 + 1, &hSegBase));
+    hSegBase[0] = 0;
+    for (uint32_t x = 0; x < nVQ0; x++)
+        hSegBase[x + 1] = hSegBase[x] + (uint32_t) ((hQHB[x + 1] - hQHB[x] + CP_SEG - 1) / CP_SEG);
+    const uint32_t nSeg = hSegBase[nVQ0];
+    s.nVQ = nVQ0 * C;
+    s.tBitsV = tBits0 - cBits;
+    SD_HIP(ctx, dVQHitBase.alloc((size_t) s.nVQ + 1));
+    SD_HIP(ctx, dSegBase.alloc(nVQ0 + 1));
+    SD_HIP(ctx, dSegCount.alloc((size_t) std::max<uint32_t>(nSeg, 1) * C));
+    SD_HIP(ctx, dKVC.alloc(nHits));
+    SD_HIP(ctx, hipMemcpyAsync(dSegBase.p, hSegBase, (nVQ0 + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (nSeg > 0)
+        hipLaunchKernelGGL(coarse_count_kernel, dim3(nSeg), dim3(256), 0, ctx->stream, nVQ0, s.pHitBase, dSegBase.p, tBits0, cBits, dKeyA.p, s.pKV, dSegCount.p,
+                           useJoin ? (const uint8_t *) dHitR6.p : (const uint8_t *) nullptr);
+    hipLaunchKernelGGL(coarse_offsets_kernel, dim3(nVQ0), dim3(256), 0, ctx->stream, nVQ0, s.pHitBase, dSegBase.p, cBits, dSegCount.p, dVQHitBase.p);
+    if (nSeg > 0)
+        hipLaunchKernelGGL(coarse_scatter_kernel, dim3(nSeg), dim3(256), 0, ctx->stream, nVQ0, s.pHitBase, dSegBase.p, tBits0, cBits, dSegCount.p, dKeyA.p, dValA.p,
+                           s.pKV, dKVC.p, widePos ? (const uint16_t *) dDiag.p : (const uint16_t *) nullptr);
+    // (hSegBase is pinned and persistent: the upload may still be reading it; the next sub-batch writes it only after several waits for this stream)
+    s.pHitBase = dVQHitBase.p;
+    s.pKey = nullptr;   // the ranges' hits are (key, value) pairs, like the join's stream
+    s.pVal = nullptr;
+    s.pKV = dKVC.p;
+    return SD_OK;
+}
+
+// hot-target filter: every (virtual) query's segment is compacted in place to the hits of targets that can still emit a candidate, laid out densely
+int PfBatch::hotFilter(HitStream &s) {
+    const uint32_t nVQ = s.nVQ;
+    WsView<uint32_t> dHotCount(ctx, "pf.dHotCount");
+    WsView<uint64_t> dHotBase(ctx, "pf.dHotBase");
+    SD_HIP(ctx, allocAll((size_t) nVQ + 1, dHotCount, dHotBase));
+    SD_HIP(ctx, hipMemsetAsync(dHotCount.p + nVQ, 0, sizeof(uint32_t), ctx->stream));
+    {
+        ProfScope ps(ctx, "prefilter_hot_filter");
+        // One workgroup per CU that loops over the segments. A 128-KB workgroup needs a drained CU; beside the score wavefronts of the other streams every new
+        // workgroup waited for one again, the persistent one keeps the CU it has waited for. Round 5, interleaved runs on one box: the kernel's time inside the
+        // pipeline 7 - 11 s -> 2.7 s per 14 steps at 1 000 proteomes, 2 417 -> 2 444 genome-pairs/s (three runs each), 1 905 -> 1 929 at 100 proteomes
+        const uint32_t hfGrid = std::min<uint32_t>(nVQ, (uint32_t) ctx->prop.multiProcessorCount);
+        hipLaunchKernelGGL(hot_filter_kernel, dim3(hfGrid), dim3(HF_NT), 0, ctx->stream, nVQ, s.pHitBase, s.tBitsV, (uint32_t *) s.pKey, (uint32_t *) s.pVal,
+                           (uint2 *) s.pKV, widePos ? s.tBitsV : 0, c.knobs.filterMin, dHotCount.p);
+    }
+    SD_RC(exclusiveScanWiden(ctx, dHotCount.p, dHotBase.p, (uint64_t) nVQ + 1, c.scanTmp));
+    SD_HIP(ctx, sdD2H(ctx, &s.nLeft, dHotBase.p + nVQ, sizeof(uint64_t)));
+    SD_HIP(ctx, sdStreamSync(ctx));
+    s.pSegCount = dHotCount.p;
+    s.pOutBase = dHotBase.p;
+    if (ctx->profiling) {   // a counter beside the kernel times: hits that passed the filter (bench.py's algorithmic bytes)
+        sd_profile_entry &pe = ctx->profile["stat.prefilter_hits_left"];
+        pe.ms += (double) s.nLeft;
+        pe.launches += 1;
+    }
+    if (c.knobs.debugTiming)
+        fprintf(stderr, "[prefilter] hot filter: %llu of %llu hits left (%.2f %%), %u segments\n", (unsigned long long) s.nLeft,
+                (unsigned long long) nHits, 100.0 * (double) s.nLeft / (double) std::max<uint64_t>(nHits, 1), nVQ);
+    return SD_OK;
+}
+
+// the bucketed LDS match of what is left: whole segments (segment_match), the rest through partition_hits / bucket_match; not done: a bucket beyond the LDS
+int PfBatch::bucketMatch(const HitStream &s) {
+    const uint32_t nVQ = s.nVQ;
+    const int tBitsV = s.tBitsV, cBits = s.cBits;
+    const int wideBits = widePos ? tBitsV : 0;
+    if (useJoin) SD_HIP(ctx, allocAll(s.nLeft, dKeyA, dValA));   // the match's output arrays (lookup path: allocated for the gather, all hits)
+    const size_t nSlots = (size_t) nVQ * PF_NB_MAX;
+    WsView<uint32_t> dSlotList(ctx, "pf.dSlotList"), dBktCount(ctx, "pf.dBktCount"), dBktEmit(ctx, "pf.dBktEmit");
+    WsView<uint32_t> dQLog2(ctx, "pf.dQLog2"), dQBins(ctx, "pf.dQBins");
+    WsView<uint64_t> dBktStart(ctx, "pf.dBktStart"), dEmitOff(ctx, "pf.dEmitOff"), dBinBase(ctx, "pf.dBinBase");
+    WsView<int> dFlag(ctx, "pf.dFlag");
+    SD_HIP(ctx, allocAll(nSlots, dBktStart, dBktCount));
+    SD_HIP(ctx, allocAll(nSlots + 1, dBktEmit, dEmitOff));
+    SD_HIP(ctx, dQLog2.alloc(nVQ));
+    SD_HIP(ctx, allocAll(nVQ + 1, dQBins, dBinBase));
+    SD_HIP(ctx, dFlag.alloc(1));
+    WsView<uint2> dKVB(ctx, "pf.dKVB");
+    SD_HIP(ctx, dKVB.alloc(s.nLeft));
+    SD_HIP(ctx, hipMemsetAsync(dBktEmit.p, 0, (nSlots + 1) * sizeof(uint32_t), ctx->stream));
+    SD_HIP(ctx, hipMemsetAsync(dFlag.p, 0, sizeof(int), ctx->stream));
+    // the matched hits leave in dKeyA / dValA -- unless those hold the input (lookup path without the coarse split)
+    const bool inA = !s.pKV && s.pKey == dKeyA.p;
+    uint32_t *outK = inA ? dKeyB.p : dKeyA.p, *outV = inA ? dValB.p : dValA.p;
+    WsView<uint8_t> dSegDone(ctx, "pf.dSegDone");
+    const uint8_t *pSegDone = nullptr;
+    if (c.knobs.filter) {
+        // filtered segments that fit the LDS sorter are matched as a whole; the rest goes through partition / bucket_match
+        SD_HIP(ctx, dSegDone.alloc((size_t) nVQ + 1));
+        ProfScope ps(ctx, "prefilter_segment_match");
+        // (one workgroup per segment: a persistent grid of one or two per CU was measured, round 5, interleaved -- the kernel's in-pipeline time 3.5 - 3.9 s -> 1.5
+        // s per 14 steps, the throughput 2 347 / 2 436 vs 2 434 (one per CU) vs 2 225 / 2 330 (two): the waiting moves to the other kernels; round 7 again inside
+        // the noise, profiles/r07e_sm_persist_ab.txt)
+        hipLaunchKernelGGL((segment_match_kernel<512, 8192>), dim3(nVQ), dim3(512), 0, ctx->stream, nVQ, s.pHitBase, s.pSegCount, s.pOutBase, tBitsV, s.pKey, s.pVal,
+                           s.pKV, outK, outV, dQLog2.p, dBktStart.p, dBktCount.p, dBktEmit.p, dSegDone.p, (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p,
+                           (const uint32_t *) dQSplits.p, cBits, wideBits);
+        pSegDone = dSegDone.p;
+    }
+    {
+        ProfScope ps(ctx, "prefilter_partition_hits");
+        // large tiles where the virtual queries are large (proteome-scale target sets), the small form for small inputs
+        // (<1024, 8192>, fastest alone, waits for whole CUs beside the other streams' score wavefronts and lost inside the pipeline: removed)
+        const bool large = s.nLeft / std::max<uint32_t>(nVQ, 1) >= 16384;
+        hipLaunchKernelGGL((large ? partition_hits_kernel<512, 4096> : partition_hits_kernel<256, 2048>), dim3(nVQ), dim3(large ? 512 : 256), 0, ctx->stream, nVQ,
+                           s.pHitBase, tBitsV, s.pKey, s.pVal, s.pKV, dKVB.p, dQLog2.p, dBktStart.p, dBktCount.p, dFlag.p, s.pSegCount, s.pOutBase, pSegDone);
+    }
+    hipLaunchKernelGGL(bin_count_kernel, dim3(gridFor(nVQ + 1, 256)), dim3(256), 0, ctx->stream, nVQ, dQLog2.p, dQBins.p);
+    SD_RC(exclusiveScanWiden(ctx, dQBins.p, dBinBase.p, nVQ + 1, c.scanTmp));
+    int hFlag = 0;
+    uint64_t totalBins = 0;
+    SD_HIP(ctx, sdD2H(ctx, &hFlag, dFlag.p, sizeof(int)));
+    SD_HIP(ctx, sdD2H(ctx, &totalBins, dBinBase.p + nVQ, sizeof(uint64_t)));
+    SD_HIP(ctx, sdStreamSync(ctx));
+    if (hFlag == 0 && totalBins > 0) {
+        const uint32_t bigCap = (uint32_t) std::min<size_t>(nSlots, 1u << 26);   // every bucket may be oversize on very large target sets
+        WsView<uint32_t> dBigList(ctx, "pf.dBigList");
+        SD_HIP(ctx, dBigList.alloc(bigCap + 1));
+        uint32_t *dBigCount = dBigList.p + bigCap;
+        SD_HIP(ctx, hipMemsetAsync(dBigCount, 0, sizeof(uint32_t), ctx->stream));
+        {
+            ProfScope ps(ctx, "prefilter_bucket_match");
+            SD_HIP(ctx, dSlotList.alloc(totalBins));
+            hipLaunchKernelGGL(slot_list_kernel, dim3(gridFor(totalBins, 256)), dim3(256), 0, ctx->stream, (uint32_t) totalBins, nVQ, (const uint64_t *) dBinBase.p,
+                               dSlotList.p);
+            hipLaunchKernelGGL((bucket_match_kernel<128, PF_BUCKET_CAP>), dim3((unsigned) totalBins), dim3(128), 0, ctx->stream, nVQ, dBinBase.p, dQLog2.p, tBitsV,
+                               dBktStart.p, dBktCount.p, (const uint2 *) dKVB.p, outK, outV, dBktEmit.p, dFlag.p, (const uint32_t *) dSlotList.p, dBigList.p,
+                               dBigCount, bigCap, dQSplit.p, dQParts.p, dQSplits.p, cBits, wideBits, (const uint32_t *) nullptr, 0u);
+        }
+        // the few buckets with one very hit-rich target (e.g. the query itself): their number stays on the device -- a launch of BIG_GRID workgroups that compare
+        // their index with the list's length takes them without a round trip to the host; a list longer than that (every bucket can be oversize on a very large
+        // target set) is finished after the next read
+        constexpr uint32_t BIG_GRID = 2048;
+        auto launchBig = [&](uint32_t first, uint32_t grid) {
+            ProfScope ps(ctx, "prefilter_bucket_match_big");
+            hipLaunchKernelGGL((bucket_match_kernel<256, PF_BUCKET_CAP_BIG>), dim3(grid), dim3(256), 0, ctx->stream, nVQ, dBinBase.p, dQLog2.p, tBitsV, dBktStart.p,
+                               dBktCount.p, (const uint2 *) dKVB.p, outK, outV, dBktEmit.p, dFlag.p, (const uint32_t *) dBigList.p, (uint32_t *) nullptr,
+                               (uint32_t *) nullptr, 0u, dQSplit.p, dQParts.p, dQSplits.p, cBits, wideBits, (const uint32_t *) dBigCount, first);
+        };
+        launchBig(0, std::min<uint32_t>(BIG_GRID, bigCap));
+        SD_RC(exclusiveScanWiden(ctx, dBktEmit.p, dEmitOff.p, nSlots + 1, c.scanTmp));
+        uint64_t nc64 = 0;
+        uint32_t nBig = 0;
+        SD_HIP(ctx, sdD2H(ctx, &nBig, dBigCount, sizeof(uint32_t)));
+        SD_HIP(ctx, sdD2H(ctx, &hFlag, dFlag.p, sizeof(int)));
+        SD_HIP(ctx, sdD2H(ctx, &nc64, dEmitOff.p + nSlots, sizeof(uint64_t)));
+        SD_HIP(ctx, sdStreamSync(ctx));
+        if (hFlag == 0 && nBig > BIG_GRID && nBig <= bigCap) {   // the rest of a long list, then the offsets again
+            for (uint32_t first = BIG_GRID; first < nBig; first += 1u << 20) launchBig(first, std::min<uint32_t>(nBig - first, 1u << 20));
+            SD_RC(exclusiveScanWiden(ctx, dBktEmit.p, dEmitOff.p, nSlots + 1, c.scanTmp));
+            SD_HIP(ctx, sdD2H(ctx, &hFlag, dFlag.p, sizeof(int)));
+            SD_HIP(ctx, sdD2H(ctx, &nc64, dEmitOff.p + nSlots, sizeof(uint64_t)));
+            SD_HIP(ctx, sdStreamSync(ctx));
+        }
+        if (hFlag == 0) {
+            nCand = (uint32_t) nc64;
+            bucketDone = true;
+            if (nCand > 0) {
+                SD_HIP(ctx, allocAll(nCand, dCKey, dCVal));
+                hipLaunchKernelGGL(bucket_collect_kernel, dim3((unsigned) totalBins), dim3(64), 0, ctx->stream, nVQ, dBinBase.p, dBktStart.p, dBktEmit.p, dEmitOff.p,
+                                   outK, outV, dCKey.p, dCVal.p, (const uint32_t *) dSlotList.p);
+            }
+        }
+    }
+    if (!bucketDone && c.knobs.debugTiming)
+        fprintf(stderr, "[prefilter] bucket path fell back: flag %d, %llu bins, %llu hits, %u queries\n", hFlag,
+                (unsigned long long) totalBins, (unsigned long long) nHits, bq);
+    if (!bucketDone && useJoin) next = PF_RETRY_LOOKUP;   // the global-sort fallback belongs to the lookup path
+    return SD_OK;
+}
+
+// The global-sort fallback (SD_PF_SORT, a bucket larger than the LDS capacity, more target bits than the slots cover): a radix sort of the whole hit stream and
+// match_diag. Lookup path only. It matches across one split and carries 24-bit stream positions: the queries that need more are reported, not guessed.
+int PfBatch::sortFallback() {
+    if (nHits > 0) {
+        if (c.useBuckets()) launchGatherHits(0);   // dKeyA / dValA were overwritten by the emitted hits, so gather again
+        {
+            ProfScope ps(ctx, "prefilter_sort_hits");
+            // Hits arrive grouped by query in emission order. A stable sort on the target bits alone makes every (target, query) group contiguous with its emission
+            // order intact, which is all match_diag needs; the few surviving candidates are put back into (query, target) order by the score stage. 19 target bits =
+            // 3 radix passes instead of the 4 that (query, target) would take.
+            SD_RC(sortPairs(ctx, dKeyA.p, dKeyB.p, dValA.p, dValB.p, nHits, 0, c.tBits));
+        }
+        SD_HIP(ctx, allocAll(nHits + 1, dEmit, dEmitPos));
+        {
+            ProfScope ps(ctx, "prefilter_match_diag");
+            hipLaunchKernelGGL(match_diag_kernel, dim3(gridFor(nHits, 256)), dim3(256), 0, ctx->stream, nHits, dKeyB.p, dValB.p, dQSplit.p, c.tBits, dEmit.p);
+        }
+        SD_HIP(ctx, hipMemsetAsync(dEmit.p + nHits, 0, 1, ctx->stream));
+        SD_RC(exclusiveScanWiden(ctx, dEmit.p, dEmitPos.p, nHits + 1, c.scanTmp));
+        uint64_t nc64 = 0;
+        SD_HIP(ctx, sdD2H(ctx, &nc64, dEmitPos.p + nHits, sizeof(uint64_t)));
+        SD_HIP(ctx, sdStreamSync(ctx));
+        nCand = (uint32_t) nc64;
+        // queries whose hit buffer overflows more than once
+        std::vector<uint32_t> hParts(bq);
+        SD_HIP(ctx, sdD2H(ctx, hParts.data(), dQParts.p, (size_t) bq * sizeof(uint32_t)));
+        SD_HIP(ctx, sdStreamSync(ctx));
+        bool any = false;
+        for (uint32_t x = 0; x < bq; x++)
+            if (hParts[x] >= 2) {
+                if (hUnsupported.empty()) hUnsupported.assign(bq, 0);
+                hUnsupported[x] = 1;
+                any = true;
+            }
+        if (any)
+            sdFail(ctx, SD_EUNSUPPORTED, "queries whose hit buffer overflows more than once in a sub-batch that fell back to the global sort "
+                   "(batch [%u, %u)): reported with outCount = UINT32_MAX", qBeg, qBeg + bq);
+    }
+    if (widePos) {   // the heavy queries of this sub-batch
+        if (hUnsupported.empty()) hUnsupported.assign(bq, 0);
+        for (uint32_t x = 0; x < bq; x++)
+            if (hStats[(size_t) x * 4 + 1] >= (1ull << 24)) hUnsupported[x] = 1;
+        sdFail(ctx, SD_EUNSUPPORTED, "queries with >= 2^24 index hits in a sub-batch that fell back to the global sort (batch [%u, %u)): "
+               "reported with outCount = UINT32_MAX", qBeg, qBeg + bq);
+    }
+    return SD_OK;
+}
+
+// ---- stage 4: gather the hits (lookup path) and match them: bucketed LDS path, or (fallback / SD_PF_SORT=1) global radix sort + match
+int PfBatch::stageMatch() {
+    phase("pf.gather_sort_match");
+    if (c.useBuckets() && !useJoin)
+        for (uint32_t x = 0; x < bq && !widePos; x++) widePos = hStats[(size_t) x * 4 + 1] >= (1ull << 24) && !unsupported(x);
+    posMask = widePos ? 0xFFFFFFFFu : 0xFFFFFFu;
+    if (!useJoin) SD_HIP(ctx, dQHitBase.alloc(bq + 1));
+    if (nHits > 0 && !useJoin) {
+        SD_HIP(ctx, allocAll(nHits, dKeyA, dValA, dKeyB, dValB));
+        SD_HIP(ctx, dDiag.alloc(nHits));
+        hipLaunchKernelGGL(query_hit_base_kernel, dim3(gridFor(bq + 1, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p, dKmerBase.p, dHitBase.p, dQHitBase.p);
+        launchGatherHits(widePos ? 1 : 0);
+    }
+    if (nHits > 0 && c.useBuckets()) {
+        // join path: the hits arrive interleaved (key, value)
+        HitStream s = {bq, 0, c.tBits, dQHitBase.p, dKeyA.p, dValA.p, useJoin ? (const uint2 *) dHitsKV.p : (const uint2 *) nullptr, nHits, nullptr, nullptr};
+        SD_RC(coarseSplit(s));
+        if (c.knobs.filter) SD_RC(hotFilter(s));
+        SD_RC(bucketMatch(s));
+        if (next != PF_GO) return SD_OK;
+    }
+    return bucketDone ? SD_OK : sortFallback();
+}
+
+// ---- stage 5: score the candidates' diagonals and keep the first of every target's maxima
+int PfBatch::stageScoreKeep() {
+    const sd_target *T = c.T;
+    const int tBits = c.tBits;
+    phase("pf.score_keep");
+    diagSrc = {useJoin ? (const uint16_t *) nullptr : (const uint16_t *) dDiag.p, dQHitBase.p, dElems.p, dKmerBase.p, dPosBase.p, T->dOffsets, T->dEntries};
+    if (nCand == 0) {
+        SD_HIP(ctx, allocAll(1, dKKey, dKVal, dKScore));
+        SD_HIP(ctx, dDiag.alloc(std::max<uint64_t>(nHits, 1)));
+        return SD_OK;
+    }
+    WsView<uint32_t> dCLen(ctx, "pf.dCLen");
+    WsView<int32_t> dCScore(ctx, "pf.dCScore");
+    WsView<uint8_t> dKeep(ctx, "pf.dKeep");
+    if (!bucketDone) SD_HIP(ctx, allocAll(nCand, dCKey, dCVal));
+    SD_HIP(ctx, allocAll(nCand, dCScore, dCLen));
+    if (!bucketDone) {
+        // compact into scratch, then a stable sort on the query bits restores (query, target, emission) order
+        WsView<uint32_t> dCKey0(ctx, "pf.dCKey0"), dCVal0(ctx, "pf.dCVal0");
+        SD_HIP(ctx, allocAll(nCand, dCKey0, dCVal0));
+        hipLaunchKernelGGL(compact_kernel, dim3(gridFor(nHits, 256)), dim3(256), 0, ctx->stream, nHits, dEmit.p, dEmitPos.p, dKeyB.p, dValB.p,
+                           (const int32_t *) nullptr, dCKey0.p, dCVal0.p, (int32_t *) nullptr);
+        int endBit = tBits;
+        uint32_t qb = bq - 1;
+        while (qb) { endBit++; qb >>= 1; }
+        endBit = std::min(32, std::max(endBit, tBits + 1));
+        SD_RC(sortPairs(ctx, dCKey0.p, dCKey.p, dCVal0.p, dCVal.p, nCand, tBits, endBit));
+    }
+    {
+        ProfScope ps(ctx, "prefilter_score_diag");
+        // (one thread per candidate: a cooperative form, eight lanes per candidate down the diagonal, was no faster -- the diagonal, not the walk, is what the
+        // kernel costs -- and was removed: profiles/r06n_score_coop.txt, r07d_score_coop_res.txt) the diagonal of a candidate from the target's residues (join path:
+        // 8-byte hits without a stored diagonal; k = 6 with 24-bit ordinals beside the diagonal byte); otherwise from the index
+        const int diagRes = (useJoin && T->k == 6 && posMask == 0xFFFFFFu) ? 1 : 0;
+        hipLaunchKernelGGL(score_diag_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCVal.p, diagSrc, tBits, dQ.p, dQOff.p, dDB.p,
+                           T->dMasked, T->dSeqOff, c.dMat.p, dCScore.p, dCLen.p, dProfAln, posMask, diagRes);
+    }
+    hipLaunchKernelGGL(cand_stats_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCLen.p, tBits, (unsigned long long *) dStats.p);
+    SD_HIP(ctx, dKeep.alloc(nCand));
+    {
+        ProfScope ps(ctx, "prefilter_keep_max");
+        hipLaunchKernelGGL(keep_max_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCVal.p, dCScore.p, dKeep.p, tBits, posMask,
+                           (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p, diagSrc);
+    }
+    WsView<uint64_t> dK64(ctx, "pf.dK64"), dKPos64(ctx, "pf.dKPos64");
+    SD_HIP(ctx, allocAll(nCand + 1, dK64, dKPos64));
+    SD_HIP(ctx, hipMemsetAsync(dK64.p + nCand, 0, sizeof(uint64_t), ctx->stream));
+    hipLaunchKernelGGL(flag_to_u64_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, (uint64_t) nCand, dKeep.p, dK64.p);
+    SD_RC(exclusiveScan(ctx, dK64.p, dKPos64.p, (uint64_t) nCand + 1, c.scanTmp));
+    // the number of kept candidates stays on the device (query_bounds_kernel reads it where the scan left it): the kept arrays are sized by the candidates, no round
+    // trip to the host
+    nKeptPtr = dKPos64.p + nCand;
+    SD_HIP(ctx, allocAll((size_t) nCand + 1, dKKey, dKVal, dKScore));
+    hipLaunchKernelGGL(compact_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, (uint64_t) nCand, dKeep.p, dKPos64.p, dCKey.p, dCVal.p, dCScore.p,
+                       dKKey.p, dKVal.p, dKScore.p);
+    return SD_OK;
+}
+
+// select_hits_kernel with a sorter of CAP entries; bigList / bigCount: where the queries that outgrow it go (null: there are none)
+template <int CAP>
+void PfBatch::launchSelectHits(const uint32_t *dQStart, uint32_t *bigList, uint32_t *bigCount) {
+    const sd_prefilter_params *par = c.par;
+    hipLaunchKernelGGL(select_hits_kernel<CAP>, dim3(bq), dim3(256), 0, ctx->stream, bq, dQStart, dKKey.p, dKVal.p, dKScore.p, diagSrc, c.tBits, par->binSize - 1,
+                       c.maxHits, par->minDiagScore, dIdent.p, dQOff.p, c.T->dSeqOff, par->covMode, par->covThr, dQ.p, dDB.p, c.dMat.p, dOut.p, dOutCount.p,
+                       c.dErr.p, dProfAln, posMask, useJoin ? c.binBits : -1, (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p,
+                       (const uint32_t *) dQSplits.p, bigList, bigCount);
+}
+
+// ---- stage 6: the result list of every query
+int PfBatch::stageSelect() {
+    const sd_prefilter_params *par = c.par;
+    const int maxHits = c.maxHits, tBits = c.tBits;
+    phase("pf.select");
+    WsView<uint32_t> dQStart(ctx, "pf.dQStart");
+    SD_HIP(ctx, dQStart.alloc(bq + 1));
+    hipLaunchKernelGGL(query_bounds_kernel, dim3(gridFor(bq + 1, 256)), dim3(256), 0, ctx->stream, bq, 0u, nKeptPtr, (const uint32_t *) dKKey.p, tBits, dQStart.p);
+    SD_HIP(ctx, dOut.alloc((size_t) bq * maxHits));
+    SD_HIP(ctx, dOutCount.alloc(bq));
+    const bool selBig = maxHits + 1 > 2048;
+    WsView<uint32_t> dSelBig(ctx, "pf.dSelBig");   // [bq] query list + [1] count
+    if (selBig) {
+        SD_HIP(ctx, dSelBig.alloc((size_t) bq + 1));
+        SD_HIP(ctx, hipMemsetAsync(dSelBig.p + bq, 0, sizeof(uint32_t), ctx->stream));
+    }
+    {
+        ProfScope ps(ctx, "prefilter_select_hits");
+        if (maxHits + 1 <= 512)   // short result lists: a 12-KB sorter instead of 48 KB (more workgroups per CU)
+            launchSelectHits<1024>(dQStart.p, nullptr, nullptr);
+        else if (maxHits + 1 <= 2048)
+            launchSelectHits<4096>(dQStart.p, nullptr, nullptr);
+        else   // longer lists: queries with more candidates at the cut than the LDS sorter holds go on to select_hits_big_kernel
+            launchSelectHits<8192>(dQStart.p, dSelBig.p, dSelBig.p + bq);
+    }
+    SD_HIP(ctx, hipGetLastError());
+    if (selBig) {
+        // queries whose list is longer than the LDS sorter carries, with more candidates at the cut than it holds
+        uint32_t nBigSel = 0;
+        SD_HIP(ctx, sdD2H(ctx, &nBigSel, dSelBig.p + bq, sizeof(uint32_t)));
+        SD_HIP(ctx, sdStreamSync(ctx));
+        if (nBigSel > 0) {
+            uint32_t stride = 1;
+            while (stride < (uint32_t) maxHits) stride <<= 1;
+            // scratch: 12 B per slot entry; at most ~1 GB per launch
+            const uint32_t perLaunch = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>(nBigSel, (1ull << 30) / ((uint64_t) stride * 12)));
+            WsView<unsigned long long> dSelKeys(ctx, "pf.dSelKeys");
+            WsView<uint32_t> dSelPay(ctx, "pf.dSelPay");
+            SD_HIP(ctx, allocAll((size_t) perLaunch * stride, dSelKeys, dSelPay));
+            ProfScope ps(ctx, "prefilter_select_hits_big");
+            for (uint32_t b0 = 0; b0 < nBigSel; b0 += perLaunch) {
+                const uint32_t nb = std::min(perLaunch, nBigSel - b0);
+                hipLaunchKernelGGL(select_hits_big_kernel, dim3(nb), dim3(SELB_NT), 0, ctx->stream, (const uint32_t *) dSelBig.p + b0, (const uint32_t *) dQStart.p,
+                                   (const uint32_t *) dKKey.p, (const uint32_t *) dKVal.p, (const int32_t *) dKScore.p, diagSrc, tBits, par->binSize - 1, maxHits,
+                                   par->minDiagScore, (const uint32_t *) dIdent.p, (const uint64_t *) dQOff.p, (const uint64_t *) c.T->dSeqOff, par->covMode,
+                                   par->covThr, (const uint8_t *) dQ.p, (const int8_t *) dDB.p, (const int8_t *) c.dMat.p, dOut.p, dOutCount.p, dProfAln, posMask,
+                                   useJoin ? c.binBits : -1, (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p, dSelKeys.p,
+                                   dSelPay.p, stride);
+            }
+            SD_HIP(ctx, hipGetLastError());
+        }
+    }
+    return SD_OK;
+}
+
+// ---- stage 7: download the lists and scatter them into the caller's rows
+int PfBatch::stageDownload() {
+    const sd_prefilter_params *par = c.par;
+    const int maxHits = c.maxHits;
+    phase("pf.download");
+    sd_hit *hOutP = nullptr;   // pinned, persistent: a pageable destination makes this copy a staged, synchronous one
+    SD_HIP(ctx, pinGet(ctx, "pf.hOut", (size_t) bq * maxHits + 1, &hOutP));
+    SD_HIP(ctx, hipMemcpyAsync(hOutP, dOut.p, (size_t) bq * maxHits * sizeof(sd_hit), hipMemcpyDeviceToHost, ctx->stream));
+    SD_HIP(ctx, sdD2H(ctx, c.outCount + qBeg, dOutCount.p, bq * sizeof(uint32_t)));
+    if (c.stats) SD_HIP(ctx, sdD2H(ctx, c.stats + (size_t) qBeg * 4, dStats.p, (size_t) bq * 4 * sizeof(uint64_t)));
+    SD_HIP(ctx, sdStreamSync(ctx));
+    phase("pf.scatter");
+    // the caller's rows are par->maxHitsPerQuery wide
+    for (uint32_t x = 0; x < bq; x++)
+        if (c.outCount[qBeg + x] != UINT32_MAX)
+            memcpy(c.outHits + (size_t) (qBeg + x) * par->maxHitsPerQuery, hOutP + (size_t) x * maxHits, (size_t) std::min<uint32_t>(c.outCount[qBeg + x],
+                   maxHits) * sizeof(sd_hit));
+    for (uint32_t x = 0; x < (uint32_t) hUnsupported.size(); x++)
+        if (hUnsupported[x]) c.outCount[qBeg + x] = UINT32_MAX;   // per-query error slot: not computed (see above)
+    return SD_OK;
+}
+
+int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilter_params *par, uint32_t nQ, const uint8_t *qResidues,
+                       const uint64_t *qOffsets, const int16_t *qKmerBias, const int8_t *qDiagBias, const uint32_t *identityId,
+                       sd_hit *outHits, uint32_t *outCount, uint64_t *stats, const ProfileQueries *prof) {
     if (!ctx || !T || !par || !qResidues || !qOffsets || !identityId || !outHits || !outCount) return SD_EINVAL;
     if (!prof && (!qKmerBias || !qDiagBias)) return SD_EINVAL;
     if (par->kmerSize != T->k) return sdFail(ctx, SD_EINVAL, "k-mer size mismatch");
@@ -2816,968 +3727,54 @@ static int prefilterBatchImpl(sd_ctx *ctx, const sd_target *T, const sd_prefilte
     if (par->binSize == 0 || (par->binSize & (par->binSize - 1))) return sdFail(ctx, SD_EINVAL, "binSize must be a power of two");
     (void) hipSetDevice(ctx->device);
     sdD2HReset(ctx);   // (reads an earlier, failed call left pending)
-    const int maxHits = (int) std::min<uint64_t>((uint64_t) par->maxHitsPerQuery, T->nSeq);
-    int tBits = 1;
-    while ((1ull << tBits) < T->nSeq) tBits++;
-    const uint32_t maxBatchQ = 1u << std::min(32 - tBits, 16);
-    const uint64_t maxDbMatches = std::max<uint64_t>(1000000, T->nSeq) * 2;   // QueryMatcher.cpp:43-47
-    // Hits per sub-batch.  The k-mer stream of a sub-batch carries 30-bit stream indices (jpElem) and the lookup path keeps
-    // 18 - 26 B per hit in its workspace, so those two stay at 2^30; the JOIN path's hit stream is bounded by its 32-bit
-    // write cursors alone (< 0xFFFFFFF0 hits, checked where the sub-batch is sized) -- its tables (offsets + entries: 7.1 GB
-    // at 1 000 proteomes) are walked once per sub-batch by join_count / join_scatter, so the fewer sub-batches the better:
-    // against 3 * 10^6 targets a sub-batch is now maxBatchQ = 1 024 queries (1.5 * 10^9 hits) where the old bound of 2^30
-    // (a limit of the library sort that left the hot path in round 5) cut it into 375-query pieces.  SD_PF_HIT_BUDGET: hits.
-    const uint64_t KMER_BUDGET = 1ull << 30, LOOKUP_HIT_BUDGET = 1ull << 30;
-    uint64_t HIT_BUDGET = 3ull << 30;
-    if (const char *e = getenv("SD_PF_HIT_BUDGET")) HIT_BUDGET = std::max<uint64_t>(1ull << 16, std::min<uint64_t>(0xF0000000ull, (uint64_t) atoll(e)));
-
-    // (workspace views, not allocations of this call: a hipFree at the end of every call waits for all streams of the device,
-    // i.e. for the other lanes of a pipeline)
-    WsView<int8_t> dMat(ctx, "pf.mat");
-    SD_HIP(ctx, dMat.alloc(448));
-    SD_HIP(ctx, hipMemcpyAsync(dMat.p, par->ungappedMatrix, 441, hipMemcpyHostToDevice, ctx->stream));
-    WsView<int> dErr(ctx, "pf.err");
-    SD_HIP(ctx, dErr.alloc(1));
-    WsView<uint8_t> scanTmp(ctx, "pf.scanTmp"), sortTmp(ctx, "pf.sortTmp");
-
+    PfCall c = {ctx, T, par, prof, qResidues, qOffsets, qKmerBias, qDiagBias, identityId, outHits, outCount, stats};
+    c.maxHits = (int) std::min<uint64_t>((uint64_t) par->maxHitsPerQuery, T->nSeq);
+    while ((1ull << c.tBits) < T->nSeq) c.tBits++;
+    while ((1u << c.binBits) < par->binSize) c.binBits++;
+    const uint32_t maxBatchQ = 1u << std::min(32 - c.tBits, 16);
+    c.maxDbMatches = std::max<uint64_t>(1000000, T->nSeq) * 2;   // QueryMatcher.cpp:43-47
+    SD_HIP(ctx, c.dMat.alloc(448));
+    SD_HIP(ctx, hipMemcpyAsync(c.dMat.p, par->ungappedMatrix, 441, hipMemcpyHostToDevice, ctx->stream));
+    SD_HIP(ctx, c.dErr.alloc(1));
     for (uint32_t x = 0; x < nQ; x++)
         if (qOffsets[x + 1] - qOffsets[x] > 65535)
             return sdFail(ctx, SD_EINVAL, "query %u has %llu residues; k-mer positions are 16 bit (limit 65535, --max-seq-len)", x,
                           (unsigned long long) (qOffsets[x + 1] - qOffsets[x]));
-    uint32_t qBeg = 0;
-    bool forceLookup = false;   // this sub-batch is redone on the lookup path (a regime the join path does not carry)
-    // queries per sub-batch: the k-mer stream, its sorted copy and the hit stream of a sub-batch are what the prefilter keeps in
-    // HBM (~3.4 MB per query on a proteome-scale target); the tables are walked once per sub-batch (~1 GB at 100 proteomes)
+    // queries per sub-batch: the k-mer stream, its sorted copy and the hit stream of a sub-batch are what the prefilter keeps in HBM (~3.4 MB per query on a
+    // proteome-scale target); the tables are walked once per sub-batch (~1 GB at 100 proteomes)
     uint32_t batchQ = std::min<uint32_t>(maxBatchQ, 2048);
-    if (const char *e = getenv("SD_PF_BATCH")) batchQ = std::max<uint32_t>(1, std::min<uint32_t>(maxBatchQ, (uint32_t) atoi(e)));
+    if (c.knobs.hasBatch) batchQ = std::max<uint32_t>(1, std::min<uint32_t>(maxBatchQ, c.knobs.batch));
+    static int (PfBatch::*const stages[])() = {&PfBatch::stageUpload, &PfBatch::stageCountKmers, &PfBatch::stageEmitHits, &PfBatch::stageMatch,
+                                                       &PfBatch::stageScoreKeep, &PfBatch::stageSelect, &PfBatch::stageDownload};
+    uint32_t qBeg = 0;
+    bool forceLookup = false;
     while (qBeg < nQ) {
         // the rest of the call in equal sub-batches of at most batchQ queries
         const uint32_t left = nQ - qBeg, parts = (left + batchQ - 1) / batchQ;
-        uint32_t bq = (left + parts - 1) / parts;
-        std::unique_ptr<HostScope> hs(new HostScope(ctx, "pf.upload_count"));
-        // ---- upload the sub-batch
-        const uint64_t r0 = qOffsets[qBeg], r1 = qOffsets[qBeg + bq];
-        std::vector<uint64_t> hOff(bq + 1), hPos(bq + 1);
-        hPos[0] = 0;
-        for (uint32_t x = 0; x <= bq; x++) hOff[x] = qOffsets[qBeg + x] - r0;
-        for (uint32_t x = 0; x < bq; x++) {
-            const int64_t L = (int64_t) (hOff[x + 1] - hOff[x]);
-            hPos[x + 1] = hPos[x] + (uint64_t) std::max<int64_t>(0, L - (T->k == 6 ? SPAN6 : SPAN7) + 1);
+        PfBatch b(c, qBeg, (left + parts - 1) / parts, forceLookup);
+        for (auto stage : stages) {
+            SD_RC((b.*stage)());
+            if (b.next != PF_GO) break;
         }
-        const uint64_t nPos = hPos[bq];
-        if (nPos * 64 >= (1ull << 32) && bq > 1) {   // a wavefront per position: a dispatch carries at most 2^32 work-items
-            batchQ = std::max<uint32_t>(1, bq / 2);
-            continue;
-        }
-        WsView<uint8_t> dQ(ctx, "pf.dQ");
-        WsView<int16_t> dKB(ctx, "pf.dKB");
-        WsView<int8_t> dDB(ctx, "pf.dDB");
-        WsView<uint64_t> dQOff(ctx, "pf.dQOff");
-        WsView<uint64_t> dPosBase(ctx, "pf.dPosBase");
-        WsView<uint32_t> dIdent(ctx, "pf.dIdent");
-        SD_HIP(ctx, dQ.alloc(r1 - r0 + 64));
-        SD_HIP(ctx, dKB.alloc(r1 - r0 + 64));
-        SD_HIP(ctx, dDB.alloc(r1 - r0 + 64));
-        SD_HIP(ctx, dQOff.alloc(bq + 1));
-        SD_HIP(ctx, dPosBase.alloc(bq + 1));
-        SD_HIP(ctx, dIdent.alloc(bq));
-        SD_HIP(ctx, hipMemcpyAsync(dQ.p, qResidues + r0, r1 - r0, hipMemcpyHostToDevice, ctx->stream));
-        WsView<int16_t> dPS(ctx, "pf.dProfScore");
-        WsView<uint8_t> dPI(ctx, "pf.dProfIndex");
-        WsView<int8_t> dPA(ctx, "pf.dProfAln");
-        const int8_t *dProfAln = nullptr;
-        if (prof) {
-            SD_HIP(ctx, dPS.alloc((r1 - r0) * 20 + 64));
-            SD_HIP(ctx, dPI.alloc((r1 - r0) * 20 + 64));
-            SD_HIP(ctx, dPA.alloc((r1 - r0) * 21 + 64));
-            SD_HIP(ctx, hipMemcpyAsync(dPS.p, prof->sortedScore + r0 * 20, (r1 - r0) * 20 * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
-            SD_HIP(ctx, hipMemcpyAsync(dPI.p, prof->sortedIndex + r0 * 20, (r1 - r0) * 20, hipMemcpyHostToDevice, ctx->stream));
-            SD_HIP(ctx, hipMemcpyAsync(dPA.p, prof->aln + r0 * 21, (r1 - r0) * 21, hipMemcpyHostToDevice, ctx->stream));
-            dProfAln = dPA.p;
-        } else {
-            SD_HIP(ctx, hipMemcpyAsync(dKB.p, qKmerBias + r0, (r1 - r0) * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
-            SD_HIP(ctx, hipMemcpyAsync(dDB.p, qDiagBias + r0, r1 - r0, hipMemcpyHostToDevice, ctx->stream));
-        }
-        SD_HIP(ctx, hipMemcpyAsync(dQOff.p, hOff.data(), (bq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(ctx, hipMemcpyAsync(dPosBase.p, hPos.data(), (bq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(ctx, hipMemcpyAsync(dIdent.p, identityId + qBeg, bq * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(ctx, hipMemsetAsync(dErr.p, 0, sizeof(int), ctx->stream));
-
-        uint64_t nKmers = 0, nHits = 0;
-        // k-mer-major join (sd_pf_join.h): k = 6, 32-bit list starts, sequence queries, the bucketed match, and a tie order of
-        // the result cut that fits its key (sequence id bits above the bin: 20)
-        const bool useBuckets = getenv("SD_PF_SORT") == nullptr;
-        int binBits = 0;
-        while ((1u << binBits) < par->binSize) binBits++;
-        // (round 6: profile queries as well -- profile_kmers_kernel writes the join's stream elements; SD_PF_JOIN_PROFILE=0 keeps them on
-        // the lookup path)
-        const bool joinCandidate = !forceLookup && T->k == 6 && T->dBlockBase == nullptr && useBuckets && bq <= (uint32_t) JQ_MAX &&
-                                   (!prof || !(getenv("SD_PF_JOIN_PROFILE") && atoi(getenv("SD_PF_JOIN_PROFILE")) == 0)) &&
-                                   tBits - binBits <= 20 && binBits <= 12 && !(getenv("SD_PF_JOIN") && atoi(getenv("SD_PF_JOIN")) == 0);
-        WsView<uint32_t> dQKmerBase(ctx, "pf.dQKmerBase");
-        WsView<int> dJoinFlag(ctx, "pf.dJoinFlag");
-        int hJoinFlag = 0;
-        uint32_t profGrid = 0;
-        bool profAnyBig = false;
-        WsView<uint2> dProfScratch(ctx, "pf.dProfScratch");
-        WsView<uint8_t> dProfBig(ctx, "pf.dProfBig");
-        WsView<uint32_t> dKmerCount(ctx, "pf.dKmerCount");
-        WsView<uint64_t> dKmerBase(ctx, "pf.dKmerBase");
-        SD_HIP(ctx, dKmerCount.alloc(nPos + 1));
-        SD_HIP(ctx, dKmerBase.alloc(nPos + 1));
-        SD_HIP(ctx, hipMemsetAsync(dKmerCount.p, 0, (nPos + 1) * sizeof(uint32_t), ctx->stream));
-        WsView<uint32_t> dPosQuery(ctx, "pf.dPosQuery");   // sequence queries: the query of every position, looked up once
-        if (nPos > 0 && !prof) {
-            SD_HIP(ctx, dPosQuery.alloc(nPos));
-            hipLaunchKernelGGL(pos_query_kernel, dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, (const uint64_t *) dPosBase.p, bq, dPosQuery.p);
-        }
-        if (nPos > 0) {
-            {
-                ProfScope ps(ctx, "prefilter_count_kmers");
-                if (prof) {
-                    profGrid = (uint32_t) std::min<uint64_t>(nPos, PROFILE_GRID);
-                    SD_HIP(ctx, dProfScratch.alloc(std::max((size_t) PROFILE_GRID * 2 * PROFILE_PARTIAL_CAP,
-                                                            (size_t) PROFILE_GRID_BIG * 2 * PROFILE_PARTIAL_CAP_BIG)));
-                    SD_HIP(ctx, dProfBig.alloc(nPos + 1));
-                    SD_HIP(ctx, hipMemsetAsync(dProfBig.p, 0, nPos + 1, ctx->stream));
-                    hipLaunchKernelGGL(profile_kmers_kernel<false>, dim3(profGrid), dim3(64), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                       dQ.p, dQOff.p, dPS.p, dPI.p, par->kmerThr, T->k, dProfScratch.p, dKmerCount.p,
-                                       (const uint32_t *) nullptr, (const uint64_t *) nullptr, (uint32_t *) nullptr,
-                                       (uint32_t *) nullptr, (uint32_t *) nullptr, dErr.p, PROFILE_PARTIAL_CAP, dProfBig.p, 0,
-                                       (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-                    int hTier = 0;
-                    SD_HIP(ctx, sdD2H(ctx, &hTier, dErr.p, sizeof(int)));
-                    SD_HIP(ctx, sdStreamSync(ctx));
-                    profAnyBig = hTier == 7;
-                    if (profAnyBig) {
-                        SD_HIP(ctx, hipMemsetAsync(dErr.p, 0, sizeof(int), ctx->stream));
-                        hipLaunchKernelGGL(profile_kmers_kernel<false>, dim3(PROFILE_GRID_BIG), dim3(64), 0, ctx->stream, nPos, dPosBase.p,
-                                           bq, dQ.p, dQOff.p, dPS.p, dPI.p, par->kmerThr, T->k, dProfScratch.p, dKmerCount.p,
-                                           (const uint32_t *) nullptr, (const uint64_t *) nullptr, (uint32_t *) nullptr,
-                                           (uint32_t *) nullptr, (uint32_t *) nullptr, dErr.p, PROFILE_PARTIAL_CAP_BIG, dProfBig.p, 1,
-                                           (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-                    }
-                } else if (T->similar)   // the query's own k-mers only; par->kmerThr and the k-mer bias are not read
-                    hipLaunchKernelGGL(exact_count_kernel, dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p,
-                                       dKB.p, (const uint32_t *) dPosQuery.p, dKmerCount.p);
-                else if (T->k == 6)
-                    hipLaunchKernelGGL(count_kmers_kernel, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                       dQ.p, dQOff.p, dKB.p, par->kmerThr, T->dExt3Score, dKmerCount.p, (const uint16_t *) T->dExt3Cum, T->ext3Lo,
-                                       (const uint32_t *) dPosQuery.p);
-                else
-                    hipLaunchKernelGGL(count_kmers7_kernel, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                       dQ.p, dQOff.p, dKB.p, par->kmerThr, T->dExt2Score, T->dExt3Score, dKmerCount.p, (const uint16_t *) T->dExt3Cum, T->ext3Lo,
-                                       (const uint32_t *) dPosQuery.p);
-            }
-            int rc = exclusiveScanWiden(ctx, dKmerCount.p, dKmerBase.p, nPos + 1, scanTmp);
-            if (rc != SD_OK) return rc;
-            int hErrCount = 0;
-            if (joinCandidate) {
-                SD_HIP(ctx, dQKmerBase.alloc(bq + 1));
-                SD_HIP(ctx, dJoinFlag.alloc(1));
-                SD_HIP(ctx, hipMemsetAsync(dJoinFlag.p, 0, sizeof(int), ctx->stream));
-                hipLaunchKernelGGL(join_query_base_kernel, dim3(gridFor(bq + 1, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p,
-                                   dKmerBase.p, dQKmerBase.p, dJoinFlag.p);
-                SD_HIP(ctx, sdD2H(ctx, &hJoinFlag, dJoinFlag.p, sizeof(int)));
-            }
-            SD_HIP(ctx, sdD2H(ctx, &nKmers, dKmerBase.p + nPos, sizeof(uint64_t)));
-            if (prof) SD_HIP(ctx, sdD2H(ctx, &hErrCount, dErr.p, sizeof(int)));
-            SD_HIP(ctx, sdStreamSync(ctx));
-            if (hErrCount == 8)
-                return sdFail(ctx, SD_EUNSUPPORTED, "more than %u similar k-mers at one profile position (the reference truncates there, KmerGenerator.cpp:202-210)",
-                              PROFILE_PARTIAL_CAP_BIG);
-        }
-        if (nKmers > KMER_BUDGET && bq > 1) {   // permissive thresholds: the k-mer list itself outgrows 32-bit device scans
-            batchQ = std::max<uint32_t>(1, bq / 2);
-            continue;
-        }
-        if (nKmers >= 0x7FFFFFFFull) return sdFail(ctx, SD_EUNSUPPORTED, "more than 2^31 similar k-mers for one query");
-        hs.reset(new HostScope(ctx, "pf.emit"));
-        WsView<uint32_t> dKStart(ctx, "pf.dKStart");
-        WsView<uint32_t> dKLen(ctx, "pf.dKLen");
-        WsView<uint32_t> dKPos(ctx, "pf.dKPos");
-        WsView<uint64_t> dHitBase(ctx, "pf.dHitBase");
-        WsView<uint32_t> dKStartHi(ctx, "pf.dKStartHi");   // wide indexes only: high half of the list starts
-        const bool wideIdx = T->dBlockBase != nullptr;
-        const bool useJoin = joinCandidate && !hJoinFlag && nKmers > 0;
-        if (!useJoin) {
-        SD_HIP(ctx, dKStart.alloc(nKmers + 1));
-        if (wideIdx) SD_HIP(ctx, dKStartHi.alloc(nKmers + 1));
-        SD_HIP(ctx, dKLen.alloc(nKmers + 1));
-        SD_HIP(ctx, dKPos.alloc(nKmers + 1));
-        SD_HIP(ctx, dHitBase.alloc(nKmers + 1));
-        SD_HIP(ctx, hipMemsetAsync(dKLen.p, 0, (nKmers + 1) * sizeof(uint32_t), ctx->stream));
-        }
-        if (nKmers > 0 && !useJoin) {
-            {
-                ProfScope ps(ctx, "prefilter_emit_kmers");
-                if (prof) {
-                    hipLaunchKernelGGL(profile_kmers_kernel<true>, dim3(profGrid), dim3(64), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                       dQ.p, dQOff.p, dPS.p, dPI.p, par->kmerThr, T->k, dProfScratch.p, (uint32_t *) nullptr,
-                                       T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p, dErr.p, PROFILE_PARTIAL_CAP, dProfBig.p, 0,
-                                       (const uint64_t *) T->dBlockBase, wideIdx ? dKStartHi.p : (uint32_t *) nullptr, (uint64_t *) nullptr);
-                    if (profAnyBig)
-                        hipLaunchKernelGGL(profile_kmers_kernel<true>, dim3(PROFILE_GRID_BIG), dim3(64), 0, ctx->stream, nPos, dPosBase.p,
-                                           bq, dQ.p, dQOff.p, dPS.p, dPI.p, par->kmerThr, T->k, dProfScratch.p, (uint32_t *) nullptr,
-                                           T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p, dErr.p, PROFILE_PARTIAL_CAP_BIG,
-                                           dProfBig.p, 1, (const uint64_t *) T->dBlockBase, wideIdx ? dKStartHi.p : (uint32_t *) nullptr, (uint64_t *) nullptr);
-                } else if (T->similar) {
-                    if (wideIdx)
-                        hipLaunchKernelGGL((exact_emit_kernel<false, true>), dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                           dQ.p, dQOff.p, dKB.p, (const uint32_t *) dPosQuery.p, dKmerBase.p, (uint64_t *) nullptr, T->dOffsets,
-                                           (const uint64_t *) T->dBlockBase, dKStart.p, dKStartHi.p, dKLen.p, dKPos.p);
-                    else
-                        hipLaunchKernelGGL((exact_emit_kernel<false, false>), dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                           dQ.p, dQOff.p, dKB.p, (const uint32_t *) dPosQuery.p, dKmerBase.p, (uint64_t *) nullptr, T->dOffsets,
-                                           (const uint64_t *) nullptr, dKStart.p, (uint32_t *) nullptr, dKLen.p, dKPos.p);
-                } else if (T->k == 6) {
-                    if (wideIdx)
-                        hipLaunchKernelGGL(emit_kmers_kernel<true>, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                           dQ.p, dQOff.p, dKB.p, par->kmerThr, T->dExt3Score, T->dExt3Index, T->dOffsets,
-                                           dKmerBase.p, dKStart.p, dKLen.p, dKPos.p, (const uint64_t *) T->dBlockBase, dKStartHi.p,
-                                           (const uint16_t *) T->dExt3Cum, T->ext3Lo, (const uint32_t *) dPosQuery.p);
-                    else
-                        hipLaunchKernelGGL(emit_kmers_kernel<false>, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                           dQ.p, dQOff.p, dKB.p, par->kmerThr, T->dExt3Score, T->dExt3Index, T->dOffsets,
-                                           dKmerBase.p, dKStart.p, dKLen.p, dKPos.p, (const uint64_t *) nullptr, (uint32_t *) nullptr,
-                                           (const uint16_t *) T->dExt3Cum, T->ext3Lo, (const uint32_t *) dPosQuery.p);
-                } else {
-                    if (wideIdx)
-                        hipLaunchKernelGGL(emit_kmers7_kernel<true>, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                           dQ.p, dQOff.p, dKB.p, par->kmerThr, T->dExt2Score, T->dExt2Index, T->dExt3Score,
-                                           T->dExt3Index, T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p,
-                                           (const uint64_t *) T->dBlockBase, dKStartHi.p,
-                                           (const uint16_t *) T->dExt3Cum, T->ext3Lo, (const uint32_t *) dPosQuery.p);
-                    else
-                        hipLaunchKernelGGL(emit_kmers7_kernel<false>, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq,
-                                           dQ.p, dQOff.p, dKB.p, par->kmerThr, T->dExt2Score, T->dExt2Index, T->dExt3Score,
-                                           T->dExt3Index, T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p,
-                                           (const uint64_t *) nullptr, (uint32_t *) nullptr,
-                                           (const uint16_t *) T->dExt3Cum, T->ext3Lo, (const uint32_t *) dPosQuery.p);
-                }
-            }
-            int rc = exclusiveScanWiden(ctx, dKLen.p, dHitBase.p, nKmers + 1, scanTmp);
-            if (rc != SD_OK) return rc;
-            SD_HIP(ctx, sdD2H(ctx, &nHits, dHitBase.p + nKmers, sizeof(uint64_t)));
-            SD_HIP(ctx, sdStreamSync(ctx));
-        }
-        hs.reset(new HostScope(ctx, "pf.stats"));
-        std::vector<uint64_t> hStats((size_t) bq * 4, 0);
-        WsView<uint64_t> dStats(ctx, "pf.dStats");
-        SD_HIP(ctx, dStats.alloc((size_t) bq * 4));
-        SD_HIP(ctx, hipMemsetAsync(dStats.p, 0, (size_t) bq * 4 * sizeof(uint64_t), ctx->stream));
-        WsView<uint32_t> dQSplit(ctx, "pf.dQSplit");
-        WsView<int> dSplitFlag(ctx, "pf.dSplitFlag");
-        WsView<uint32_t> dQParts(ctx, "pf.dQParts");     // overflows of the reference's hit buffer per query, and where (all of them)
-        WsView<uint32_t> dQSplits(ctx, "pf.dQSplits");
-        SD_HIP(ctx, dQSplit.alloc(bq));
-        SD_HIP(ctx, dQParts.alloc(bq));
-        SD_HIP(ctx, dQSplits.alloc((size_t) bq * PF_SPLITS_MAX));
-        SD_HIP(ctx, dSplitFlag.alloc(1));
-        SD_HIP(ctx, hipMemsetAsync(dSplitFlag.p, 0, sizeof(int), ctx->stream));
-        std::vector<uint8_t> hUnsupported;
-        // join path: the k-mer stream, its k-mer-sorted copy, the hits grouped by query group
-        WsView<uint64_t> dElems(ctx, "pf.dElems");
-        WsView<uint64_t> dSorted(ctx, "pf.dSorted");
-        WsView<uint2> dHitsKV(ctx, "pf.dHitsKV");
-        WsView<uint8_t> dHitR6(ctx, "pf.dHitR6");   // join path: a byte per hit for the coarse split's count pass (nullptr: not written)
-        WsView<uint64_t> dQHitBase(ctx, "pf.dQHitBase");   // hits of query q start at dQHitBase[q] (either path)
-        WsView<uint64_t> dVQHitBase(ctx, "pf.dVQHitBase");  // with a split into target ranges: hits of (query, range) start here
-        if (useJoin) {
-            WsView<uint32_t> dKpCounts(ctx, "pf.dKpCounts");
-            WsView<uint32_t> dKpTotal(ctx, "pf.dKpTotal");
-            WsView<uint64_t> dKpBase(ctx, "pf.dKpBase");
-            WsView<uint32_t> dJqCounts(ctx, "pf.dJqCounts");
-            WsView<uint32_t> dQHits(ctx, "pf.dQHits");
-            WsView<unsigned long long> dWgTotal(ctx, "pf.dWgTotal");
-            WsView<uint32_t> dQEff(ctx, "pf.dQEff");
-            const uint64_t nSortedCap = nKmers + (uint64_t) KP_BINS * JC;   // every k-mer range padded to whole join chunks
-            WsView<uint16_t> dChunkBin(ctx, "pf.dChunkBin");
-            SD_HIP(ctx, dElems.alloc(nKmers + 1));
-            SD_HIP(ctx, dSorted.alloc(nSortedCap));
-            SD_HIP(ctx, dChunkBin.alloc(nSortedCap / JC + 1));
-            SD_HIP(ctx, dKpCounts.alloc((size_t) JP_WGS * KP_BINS));
-            SD_HIP(ctx, dKpTotal.alloc(KP_BINS));
-            SD_HIP(ctx, dKpBase.alloc(KP_BINS + 1));
-            SD_HIP(ctx, dJqCounts.alloc((size_t) JJ_WGS * bq));
-            SD_HIP(ctx, dQHits.alloc(bq));
-            SD_HIP(ctx, dWgTotal.alloc(JJ_WGS));
-            {
-                ProfScope ps(ctx, "prefilter_emit_kmers");
-                if (prof) {   // the per-position products again, this time writing the stream (the tiers the count pass chose)
-                    hipLaunchKernelGGL(profile_kmers_kernel<true>, dim3(profGrid), dim3(64), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dPS.p,
-                                       dPI.p, par->kmerThr, T->k, dProfScratch.p, (uint32_t *) nullptr, (const uint32_t *) nullptr, dKmerBase.p,
-                                       (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, dErr.p, PROFILE_PARTIAL_CAP, dProfBig.p, 0,
-                                       (const uint64_t *) nullptr, (uint32_t *) nullptr, dElems.p);
-                    if (profAnyBig)
-                        hipLaunchKernelGGL(profile_kmers_kernel<true>, dim3(PROFILE_GRID_BIG), dim3(64), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p,
-                                           dQOff.p, dPS.p, dPI.p, par->kmerThr, T->k, dProfScratch.p, (uint32_t *) nullptr, (const uint32_t *) nullptr,
-                                           dKmerBase.p, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, dErr.p,
-                                           PROFILE_PARTIAL_CAP_BIG, dProfBig.p, 1, (const uint64_t *) nullptr, (uint32_t *) nullptr, dElems.p);
-                } else if (T->similar)
-                    hipLaunchKernelGGL((exact_emit_kernel<true, false>), dim3(gridFor(nPos, 256)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p,
-                                       dQOff.p, dKB.p, (const uint32_t *) dPosQuery.p, dKmerBase.p, dElems.p, (const uint32_t *) nullptr,
-                                       (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr);
-                else
-                hipLaunchKernelGGL(emit_kmers_join_kernel, dim3(gridFor(nPos, 4)), dim3(256), 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p,
-                                   dQOff.p, dKB.p, par->kmerThr, T->dExt3Score, T->dExt3Index, dKmerBase.p, dElems.p, (const uint16_t *) T->dExt3Cum, T->ext3Lo,
-                                   (const uint32_t *) dPosQuery.p);
-            }
-            {
-                ProfScope ps(ctx, "prefilter_kmer_partition");
-                hipLaunchKernelGGL(kp_hist_kernel, dim3(JP_WGS), dim3(JP_NT), 0, ctx->stream, (const uint64_t *) dElems.p, nKmers, dKpCounts.p);
-                hipLaunchKernelGGL(col_prefix_kernel, dim3(KP_BINS / 64), dim3(256), 0, ctx->stream, dKpCounts.p, JP_WGS, KP_BINS, dKpTotal.p);
-                hipLaunchKernelGGL(small_scan_kernel, dim3(1), dim3(SS_NT), 0, ctx->stream, (const uint32_t *) dKpTotal.p, KP_BINS, dKpBase.p, (uint32_t) JC);
-                hipLaunchKernelGGL(kp_scatter_kernel, dim3(JP_WGS), dim3(JP_NT), 0, ctx->stream, (const uint64_t *) dElems.p, nKmers,
-                                   (const uint32_t *) dKpCounts.p, (const uint64_t *) dKpBase.p, (const uint32_t *) dQKmerBase.p, bq, dSorted.p);
-                hipLaunchKernelGGL(kp_finish_kernel, dim3(KP_BINS), dim3(256), 0, ctx->stream, (const uint32_t *) dKpTotal.p,
-                                   (const uint64_t *) dKpBase.p, dSorted.p, dChunkBin.p);
-            }
-            // (the join kernels read the padded length of the sorted stream where the partition left it: no round trip to the host)
-            const uint64_t *nSortedPtr = dKpBase.p + KP_BINS;
-            {
-                ProfScope ps(ctx, "prefilter_join_count");
-                hipLaunchKernelGGL(join_count_kernel, dim3(JJ_WGS), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr,
-                                   (const uint16_t *) dChunkBin.p, (const uint32_t *) T->dOffsets, dJqCounts.p, (int) bq, dWgTotal.p);
-                hipLaunchKernelGGL(col_prefix_kernel, dim3(gridFor(bq, 64)), dim3(256), 0, ctx->stream, dJqCounts.p, JJ_WGS, (int) bq, dQHits.p);
-            }
-            // overflow of the reference's hit buffer, in k-mer ordinals
-            hipLaunchKernelGGL(query_splits_join_kernel, dim3(bq), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQKmerBase.p,
-                               (const uint64_t *) dElems.p, (const uint32_t *) T->dOffsets, (const uint32_t *) dQHits.p, maxDbMatches,
-                               dQSplit.p, dQParts.p, dQSplits.p, dSplitFlag.p);
-            hipLaunchKernelGGL(join_stats_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQKmerBase.p,
-                               (const uint32_t *) dQHits.p, dStats.p);
-            std::vector<unsigned long long> hWg((size_t) JJ_WGS);
-            std::vector<uint32_t> hQHits(bq);
-            int hSplitFlagJ = 0;
-            SD_HIP(ctx, sdD2H(ctx, hWg.data(), dWgTotal.p, (size_t) JJ_WGS * sizeof(unsigned long long)));
-            SD_HIP(ctx, sdD2H(ctx, hQHits.data(), dQHits.p, bq * sizeof(uint32_t)));
-            SD_HIP(ctx, sdD2H(ctx, &hSplitFlagJ, dSplitFlag.p, sizeof(int)));
-            SD_HIP(ctx, sdStreamSync(ctx));
-            uint64_t all = 0;
-            for (unsigned long long v : hWg) all += v;
-            if (all > HIT_BUDGET && bq > 1) {   // too many hits for one sub-batch: halve it and retry
-                batchQ = std::max<uint32_t>(1, bq / 2);
-                continue;
-            }
-            if (all >= 0xFFFFFFF0ull) {   // the per-query counters are 32 bit: this query goes the lookup path
-                forceLookup = true;
-                continue;
-            }
-            for (uint32_t x = 0; x < bq; x++) hStats[(size_t) x * 4 + 1] = hQHits[x];
-            nHits = all;
-            if (hSplitFlagJ) {
-                // queries the device does not compute (more than PF_SPLITS_MAX overflows of the reference's hit buffer, or a single
-                // index list as large as that buffer) are taken out of the batch and reported per query (outCount = UINT32_MAX); the
-                // join leaves their lists out
-                std::vector<uint32_t> hSplit(bq);
-                SD_HIP(ctx, sdD2H(ctx, hSplit.data(), dQSplit.p, (size_t) bq * sizeof(uint32_t)));
-                SD_HIP(ctx, sdStreamSync(ctx));
-                hUnsupported.assign(bq, 0);
-                uint32_t nBad = 0, firstBad = 0;
-                for (uint32_t x = 0; x < bq; x++)
-                    if (hSplit[x] == QUERY_UNSUPPORTED) {
-                        hUnsupported[x] = 1;
-                        nHits -= hQHits[x];
-                        if (!nBad) firstBad = qBeg + x;
-                        nBad++;
-                    }
-                sdFail(ctx, SD_EUNSUPPORTED, "%u quer%s of the batch [%u, %u) (first: %u) overflow the reference's hit buffer more than 32 times or hold "
-                       "an index list as large as that buffer: reported with outCount = UINT32_MAX, the rest of the batch is computed",
-                       nBad, nBad == 1 ? "y" : "ies", qBeg, qBeg + bq, firstBad);
-            }
-            // per-query segments of the hit array (the layout the bucket machinery takes), then the scatter pass of the join
-            SD_HIP(ctx, dQEff.alloc(bq));
-            SD_HIP(ctx, dQHitBase.alloc(bq + 1));
-            hipLaunchKernelGGL(join_effective_totals_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, (const uint32_t *) dQHits.p,
-                               (const uint32_t *) dQSplit.p, dQEff.p);
-            hipLaunchKernelGGL(small_scan_kernel, dim3(1), dim3(SS_NT), 0, ctx->stream, (const uint32_t *) dQEff.p, (int) bq, dQHitBase.p, 0u);
-            if (nHits > 0) {
-                SD_HIP(ctx, dHitsKV.alloc(nHits));
-                // the coarse split's count pass needs a hit's range and nothing else: one byte per hit beside the 8-byte stream (the top
-                // six target bits: any split of up to 2^6 ranges reads its range off them) -- 1.5 MB per query written here for 12.3 MB
-                // per query not read there
-                if (tBits >= CP_MAX_BITS + 8 && coarseBitsFor(nHits / std::max<uint32_t>(bq, 1), tBits) > 0)
-                    SD_HIP(ctx, dHitR6.alloc(nHits + 8));
-                ProfScope ps(ctx, "prefilter_join_scatter");
-                hipLaunchKernelGGL(join_scatter_kernel, dim3(JJ_WGS), dim3(JJ_NT), 0, ctx->stream, (const uint64_t *) dSorted.p, nSortedPtr,
-                                   (const uint16_t *) dChunkBin.p, (const uint32_t *) T->dOffsets, (const uint2 *) T->dEntries, bq,
-                                   (const uint32_t *) dJqCounts.p, (const uint64_t *) dQHitBase.p, tBits, (const uint32_t *) dQSplit.p,
-                                   dHitsKV.p, dHitR6.p, tBits - CP_MAX_BITS);
-            }
-            SD_HIP(ctx, hipGetLastError());
-        }
-        if (!useJoin) {
-        if (nHits > std::min(HIT_BUDGET, LOOKUP_HIT_BUDGET) && bq > 1) {   // too many hits for one sort: halve the sub-batch and retry
-            batchQ = std::max<uint32_t>(1, bq / 2);
-            continue;
-        }
-        if (nHits >= 0xFFFFFFFFull) return sdFail(ctx, SD_EUNSUPPORTED, "more than 2^32 hits in one query batch");
-        hipLaunchKernelGGL(stats_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p, dKmerBase.p,
-                           dHitBase.p, nKmers, nHits, dStats.p);
-        // Stream positions: 24 bits of the value word beside the diagonal byte -- or, for sub-batches with a query of 2^24 hits
-        // and more, the whole word, the diagonal byte travelling in the key (bucket path only: it needs the coarse split)
-        const uint64_t posLimit = useBuckets ? 0xFFFFFFF0ull : (1ull << 24);
-        // the reference's hit buffer holds maxDbMatches entries per query; where a query overflows it once, the match runs
-        // on the two parts separately (query_split_kernel); two overflows are not implemented
-        hipLaunchKernelGGL(query_split_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p, dKmerBase.p,
-                           dHitBase.p, maxDbMatches, dQSplit.p, dQParts.p, dQSplits.p, dSplitFlag.p, posLimit);
-        int hSplitFlag = 0;
-        SD_HIP(ctx, sdD2H(ctx, &hSplitFlag, dSplitFlag.p, sizeof(int)));
-        SD_HIP(ctx, sdD2H(ctx, hStats.data(), dStats.p, (size_t) bq * 4 * sizeof(uint64_t)));
-        SD_HIP(ctx, sdStreamSync(ctx));
-        if (hSplitFlag) {
-            // Queries with >= 2^32 index hits (or more than PF_SPLITS_MAX overflows of the reference's hit buffer, or an index list as
-            // large as that buffer) cannot be computed here.  They are taken out of the batch -- their index lists emptied,
-            // offsets re-scanned -- and reported per query (outCount = UINT32_MAX); every other query is computed as usual.
-            std::vector<uint32_t> hSplit(bq);
-            SD_HIP(ctx, sdD2H(ctx, hSplit.data(), dQSplit.p, (size_t) bq * sizeof(uint32_t)));
-            SD_HIP(ctx, sdStreamSync(ctx));
-            hUnsupported.assign(bq, 0);
-            uint32_t nBad = 0, firstBad = 0;
-            for (uint32_t x = 0; x < bq; x++)
-                if (hSplit[x] == QUERY_UNSUPPORTED) {
-                    hUnsupported[x] = 1;
-                    if (!nBad) firstBad = qBeg + x;
-                    nBad++;
-                }
-            sdFail(ctx, SD_EUNSUPPORTED, "%u quer%s of the batch [%u, %u) (first: %u) have >= 2^32 index hits or overflow the reference's hit buffer "
-                   "more than 32 times: reported with outCount = UINT32_MAX, the rest of the batch is computed",
-                   nBad, nBad == 1 ? "y" : "ies", qBeg, qBeg + bq, firstBad);
-            hipLaunchKernelGGL(drop_query_kmers_kernel, dim3(gridFor(nKmers, 256)), dim3(256), 0, ctx->stream, nKmers, dKPos.p, dQSplit.p, dKLen.p);
-            int rc2 = exclusiveScanWiden(ctx, dKLen.p, dHitBase.p, nKmers + 1, scanTmp);
-            if (rc2 != SD_OK) return rc2;
-            SD_HIP(ctx, sdD2H(ctx, &nHits, dHitBase.p + nKmers, sizeof(uint64_t)));
-            SD_HIP(ctx, hipMemsetAsync(dSplitFlag.p, 0, sizeof(int), ctx->stream));
-            hipLaunchKernelGGL(query_split_kernel, dim3(gridFor(bq, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p, dKmerBase.p,
-                               dHitBase.p, maxDbMatches, dQSplit.p, dQParts.p, dQSplits.p, dSplitFlag.p, posLimit);
-            SD_HIP(ctx, sdStreamSync(ctx));
-        }
-        }   // lookup path
-
-        hs.reset(new HostScope(ctx, "pf.gather_sort_match"));
-        uint32_t nCand = 0;
-        const uint64_t *nKeptPtr = nullptr;   // kept candidates (device); null: none
-        bool bucketDone = false;
-        bool widePos = false;
-        if (useBuckets && !useJoin)
-            for (uint32_t x = 0; x < bq && !widePos; x++)
-                widePos = hStats[(size_t) x * 4 + 1] >= (1ull << 24) && !(x < hUnsupported.size() && hUnsupported[x]);
-        const uint32_t posMask = widePos ? 0xFFFFFFFFu : 0xFFFFFFu;
-        WsView<uint32_t> dKeyA(ctx, "pf.dKeyA");
-        WsView<uint32_t> dKeyB(ctx, "pf.dKeyB");
-        WsView<uint32_t> dValA(ctx, "pf.dValA");
-        WsView<uint32_t> dValB(ctx, "pf.dValB");
-        WsView<uint16_t> dDiag(ctx, "pf.dDiag");
-        if (!useJoin) SD_HIP(ctx, dQHitBase.alloc(bq + 1));
-        WsView<uint8_t> dEmit(ctx, "pf.dEmit");
-        WsView<uint64_t> dEmitPos(ctx, "pf.dEmitPos");
-        WsView<uint64_t> dEmit64(ctx, "pf.dEmit64");
-        WsView<uint32_t> dCKey(ctx, "pf.dCKey");
-        WsView<uint32_t> dCVal(ctx, "pf.dCVal");
-        WsView<uint32_t> dCLen(ctx, "pf.dCLen");
-        WsView<uint32_t> dKKey(ctx, "pf.dKKey");
-        WsView<uint32_t> dKVal(ctx, "pf.dKVal");
-        WsView<uint32_t> dQStart(ctx, "pf.dQStart");
-        WsView<int32_t> dCScore(ctx, "pf.dCScore");
-        WsView<int32_t> dKScore(ctx, "pf.dKScore");
-        WsView<uint8_t> dKeep(ctx, "pf.dKeep");
-        if (nHits > 0) {
-            if (!useJoin) {
-            SD_HIP(ctx, dKeyA.alloc(nHits));
-            SD_HIP(ctx, dValA.alloc(nHits));
-            SD_HIP(ctx, dKeyB.alloc(nHits));
-            SD_HIP(ctx, dValB.alloc(nHits));
-            SD_HIP(ctx, dDiag.alloc(nHits));
-            hipLaunchKernelGGL(query_hit_base_kernel, dim3(gridFor(bq + 1, 256)), dim3(256), 0, ctx->stream, bq, dPosBase.p,
-                               dKmerBase.p, dHitBase.p, dQHitBase.p);
-            }
-            if (!useJoin) {
-                ProfScope ps(ctx, "prefilter_gather_hits");
-                hipLaunchKernelGGL(gather_hits_kernel, dim3(gridFor(nKmers, 256)), dim3(256), 0, ctx->stream, nKmers, dKStart.p,
-                                   dKLen.p, dKPos.p, dHitBase.p, dPosBase.p, bq, (const uint2 *) T->dEntries, tBits, dQHitBase.p,
-                                   dKeyA.p, dValA.p, dDiag.p, wideIdx ? (const uint32_t *) dKStartHi.p : (const uint32_t *) nullptr, widePos ? 1 : 0);
-            }
-            // ---- double-diagonal match: bucketed LDS path, or (fallback / SD_PF_SORT=1) global radix sort + match
-            if (useBuckets) {
-                // very hit-rich queries (large target sets): coarse split into virtual queries first (see coarse_*_kernel)
-                uint32_t nVQ = bq;
-                const uint32_t nVQ0 = nVQ;
-                const int tBits0 = tBits;
-                int cBits = 0, tBitsV = tBits0;
-                const uint64_t *pHitBase = dQHitBase.p;
-                const uint32_t *pKey = dKeyA.p, *pVal = dValA.p;
-                // join path: the hits arrive interleaved (key, value)
-                const uint2 *pKV = useJoin ? (const uint2 *) dHitsKV.p : (const uint2 *) nullptr;
-                WsView<uint32_t> dSegBase(ctx, "pf.dSegBase");
-                WsView<uint32_t> dSegCount(ctx, "pf.dSegCount");
-                WsView<uint2> dKVC(ctx, "pf.dKVC");
-                // decided by the average query of the sub-batch (a few long queries are what the adaptive bucket count and
-                // the oversize-bucket launch are for): ~100 hits per bucket at 2^11 buckets
-                const uint64_t avgQ = nHits / std::max<uint32_t>(nVQ0, 1);
-                // no split up to 2 * 10^5 hits per average query (the filter takes such a segment in one round); beyond that, ranges of
-                // at most 10^5 hits: the filter's Bloom rounds, the partition and the bucket sort all run on half-size segments for one more
-                // level of the (cheap, streaming) split -- isolated prefilter at 1 000 proteomes 443 -> 390 ms per 8 192 queries, +4 % end
-                // to end; at 100 proteomes (1.5 * 10^5 hits per query) a split would only add its 24 B per hit (1 915 -> 1 767)
-                // (coarseBitsFor below is this rule; the join's scatter asks it whether a split will follow)
-                // Round 6: ranges of at most 5 * 10^4 hits (10^5 until then) -- 32 ranges at 1 000 proteomes.  The filter's
-                // Bloom filter then has twice the bits per key: 7.2 % of the hit stream left instead of 12.3 % (4.7 % at 2.5 * 10^4), and what
-                // is left comes in segments the LDS sorter takes whole (segment_match) instead of through partition_hits / bucket_match.
-                // Isolated, per 8 192 queries, interleaved in one process (profiles/r06y_split.txt): 328 ms at 10^5 (coarse split 69, filter
-                // 74, partition + bucket + segment match 59), **315 ms at 5 * 10^4** (80 / 67 / 43), 323 ms at 2.5 * 10^4 (92 / 66 / 37: the
-                // split's cost grows with its ranges).  Round 5 had measured finer ranges as a loss (388 - 442 vs 385 ms): the filter read
-                // two arrays then and the split wrote them.  (Two more bitmaps in the filter -- a target must be hit twice to be nominated --
-                // were tried on top and removed: 7.4 % left instead of 7.2 %, the kernel 8 ms slower; what passes the filter at this
-                // granularity are targets that do have two hits on one diagonal byte, profiles/r06x_hf_multi.txt.)
-                cBits = coarseBitsFor(avgQ, tBits0);
-                // wide stream positions need the split: it is where the diagonal byte moves into the key (8 free bits)
-                while (widePos && cBits < CP_MAX_BITS && tBits - (cBits + 1) >= 8 && (cBits < 1 || tBits - cBits > 24)) cBits++;
-                if (widePos && (cBits < 1 || tBits - cBits > 24))
-                    return sdFail(ctx, SD_EUNSUPPORTED, "a query with >= 2^24 index hits against a target set of %u sequences", T->nSeq);
-                if (cBits > 0) {
-                    // segments of CP_SEG hits per query.  The join path knows every query's hits on the host already (the read that
-                    // sized the sub-batch), the lookup path reads the segment starts back; the segment table goes up through a pinned
-                    // buffer, so nothing here waits for the stream a second time
-                    std::vector<uint64_t> hQHB(nVQ0 + 1, 0);
-                    if (useJoin) {
-                        for (uint32_t x = 0; x < nVQ0; x++)
-                            hQHB[x + 1] = hQHB[x] + ((x < hUnsupported.size() && hUnsupported[x]) ? 0ull : hStats[(size_t) x * 4 + 1]);
-                    } else {
-                        SD_HIP(ctx, sdD2H(ctx, hQHB.data(), pHitBase, (nVQ0 + 1) * sizeof(uint64_t)));
-                        SD_HIP(ctx, sdStreamSync(ctx));
-                    }
-                    ProfScope ps(ctx, "prefilter_coarse_split");
-                    const uint32_t C = 1u << cBits;
-                    uint32_t *hSegBase = nullptr;
-                    SD_HIP(ctx, pinGet(ctx, "pf.hSegBase", (size_t) nVQ0 + 1, &hSegBase));
-                    hSegBase[0] = 0;
-                    for (uint32_t x = 0; x < nVQ0; x++)
-                        hSegBase[x + 1] = hSegBase[x] + (uint32_t) ((hQHB[x + 1] - hQHB[x] + CP_SEG - 1) / CP_SEG);
-                    const uint32_t nSeg = hSegBase[nVQ0];
-                    nVQ = nVQ0 * C;
-                    tBitsV = tBits0 - cBits;
-                    SD_HIP(ctx, dVQHitBase.alloc((size_t) nVQ + 1));
-                    SD_HIP(ctx, dSegBase.alloc(nVQ0 + 1));
-                    SD_HIP(ctx, dSegCount.alloc((size_t) std::max<uint32_t>(nSeg, 1) * C));
-                    SD_HIP(ctx, dKVC.alloc(nHits));
-                    SD_HIP(ctx, hipMemcpyAsync(dSegBase.p, hSegBase, (nVQ0 + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-                    if (nSeg > 0)
-                        hipLaunchKernelGGL(coarse_count_kernel, dim3(nSeg), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, tBits0,
-                                           cBits, dKeyA.p, pKV, dSegCount.p, useJoin ? (const uint8_t *) dHitR6.p : (const uint8_t *) nullptr);
-                    hipLaunchKernelGGL(coarse_offsets_kernel, dim3(nVQ0), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, cBits,
-                                       dSegCount.p, dVQHitBase.p);
-                    if (nSeg > 0)
-                        hipLaunchKernelGGL(coarse_scatter_kernel, dim3(nSeg), dim3(256), 0, ctx->stream, nVQ0, pHitBase, dSegBase.p, tBits0,
-                                           cBits, dSegCount.p, dKeyA.p, dValA.p, pKV, dKVC.p,
-                                           widePos ? (const uint16_t *) dDiag.p : (const uint16_t *) nullptr);
-                    // (hSegBase is pinned and persistent: the upload may still be reading it; the next sub-batch writes it only after
-                    // several waits for this stream)
-                    pHitBase = dVQHitBase.p;
-                    pKey = nullptr;   // the ranges' hits are (key, value) pairs, like the join's stream
-                    pVal = nullptr;
-                    pKV = dKVC.p;
-                }
-                // hot-target filter (hot_filter_kernel): every (virtual) query's segment is compacted in place to the hits of
-                // targets that can still emit a candidate; the bucket machinery below runs on what is left, laid out densely
-                uint64_t nLeft = nHits;
-                WsView<uint32_t> dHotCount(ctx, "pf.dHotCount");
-                WsView<uint64_t> dHotBase(ctx, "pf.dHotBase");
-                const uint32_t *pSegCount = nullptr;
-                const uint64_t *pOutBase = nullptr;
-                const bool useFilter = !(getenv("SD_PF_FILTER") && atoi(getenv("SD_PF_FILTER")) == 0);
-                if (useFilter) {
-                    const uint32_t minSeg = getenv("SD_PF_FILTER_MIN") ? (uint32_t) atoi(getenv("SD_PF_FILTER_MIN")) : 256u;
-                    SD_HIP(ctx, dHotCount.alloc((size_t) nVQ + 1));
-                    SD_HIP(ctx, dHotBase.alloc((size_t) nVQ + 1));
-                    SD_HIP(ctx, hipMemsetAsync(dHotCount.p + nVQ, 0, sizeof(uint32_t), ctx->stream));
-                    {
-                        ProfScope ps(ctx, "prefilter_hot_filter");
-                        // One workgroup per CU that loops over the segments.  A 128-KB workgroup needs a drained CU; beside the score
-                        // wavefronts of the other streams every new workgroup waited for one again, the persistent one keeps the CU it has
-                        // waited for.  Round 5, interleaved runs on one box: the kernel's time inside the pipeline 7 - 11 s -> 2.7 s per 14
-                        // steps at 1 000 proteomes, 2 417 -> 2 444 genome-pairs/s (three runs each), 1 905 -> 1 929 at 100 proteomes
-                        const uint32_t hfGrid = std::min<uint32_t>(nVQ, (uint32_t) ctx->prop.multiProcessorCount);
-                        hipLaunchKernelGGL(hot_filter_kernel, dim3(hfGrid), dim3(HF_NT), 0, ctx->stream, nVQ, pHitBase, tBitsV, (uint32_t *) pKey,
-                                           (uint32_t *) pVal, (uint2 *) pKV, widePos ? tBitsV : 0, minSeg, dHotCount.p);
-                    }
-                    int rcF = exclusiveScanWiden(ctx, dHotCount.p, dHotBase.p, (uint64_t) nVQ + 1, scanTmp);
-                    if (rcF != SD_OK) return rcF;
-                    SD_HIP(ctx, sdD2H(ctx, &nLeft, dHotBase.p + nVQ, sizeof(uint64_t)));
-                    SD_HIP(ctx, sdStreamSync(ctx));
-                    pSegCount = dHotCount.p;
-                    pOutBase = dHotBase.p;
-                    if (ctx->profiling) {   // a counter beside the kernel times: hits that passed the filter (bench.py's algorithmic bytes)
-                        sd_profile_entry &pe = ctx->profile["stat.prefilter_hits_left"];
-                        pe.ms += (double) nLeft;
-                        pe.launches += 1;
-                    }
-                    if (getenv("SD_DEBUG_TIMING"))
-                        fprintf(stderr, "[prefilter] hot filter: %llu of %llu hits left (%.2f %%), %u segments\n", (unsigned long long) nLeft,
-                                (unsigned long long) nHits, 100.0 * (double) nLeft / (double) std::max<uint64_t>(nHits, 1), nVQ);
-                }
-                if (useJoin) {   // the match's output arrays (lookup path: allocated for the gather, all hits)
-                    SD_HIP(ctx, dKeyA.alloc(nLeft));
-                    SD_HIP(ctx, dValA.alloc(nLeft));
-                }
-                const size_t nSlots = (size_t) nVQ * PF_NB_MAX;
-                WsView<uint32_t> dSlotList(ctx, "pf.dSlotList");
-                WsView<uint64_t> dBktStart(ctx, "pf.dBktStart");
-                WsView<uint32_t> dBktCount(ctx, "pf.dBktCount");
-                WsView<uint32_t> dBktEmit(ctx, "pf.dBktEmit");
-                WsView<uint64_t> dEmitOff(ctx, "pf.dEmitOff");
-                WsView<uint32_t> dQLog2(ctx, "pf.dQLog2");
-                WsView<uint32_t> dQBins(ctx, "pf.dQBins");
-                WsView<uint64_t> dBinBase(ctx, "pf.dBinBase");
-                WsView<int> dFlag(ctx, "pf.dFlag");
-                SD_HIP(ctx, dBktStart.alloc(nSlots));
-                SD_HIP(ctx, dBktCount.alloc(nSlots));
-                SD_HIP(ctx, dBktEmit.alloc(nSlots + 1));
-                SD_HIP(ctx, dEmitOff.alloc(nSlots + 1));
-                SD_HIP(ctx, dQLog2.alloc(nVQ));
-                SD_HIP(ctx, dQBins.alloc(nVQ + 1));
-                SD_HIP(ctx, dBinBase.alloc(nVQ + 1));
-                SD_HIP(ctx, dFlag.alloc(1));
-                WsView<uint2> dKVB(ctx, "pf.dKVB");
-                SD_HIP(ctx, dKVB.alloc(nLeft));
-                SD_HIP(ctx, hipMemsetAsync(dBktEmit.p, 0, (nSlots + 1) * sizeof(uint32_t), ctx->stream));
-                SD_HIP(ctx, hipMemsetAsync(dFlag.p, 0, sizeof(int), ctx->stream));
-                // the matched hits leave in dKeyA / dValA -- unless those hold the input (lookup path without the coarse split)
-                uint32_t *outK = dKeyA.p, *outV = dValA.p;
-                if (!pKV && pKey == dKeyA.p) {
-                    outK = dKeyB.p;
-                    outV = dValB.p;
-                }
-                WsView<uint8_t> dSegDone(ctx, "pf.dSegDone");
-                const uint8_t *pSegDone = nullptr;
-                if (useFilter) {
-                    // filtered segments that fit the LDS sorter are matched as a whole; the rest goes through partition / bucket_match
-                    SD_HIP(ctx, dSegDone.alloc((size_t) nVQ + 1));
-                    ProfScope ps(ctx, "prefilter_segment_match");
-                    // (one workgroup per segment: a persistent grid of one or two per CU was measured, round 5, interleaved -- the
-                    // kernel's in-pipeline time 3.5 - 3.9 s -> 1.5 s per 14 steps, the throughput 2 347 / 2 436 vs 2 434 (one per CU) vs
-                    // 2 225 / 2 330 (two): the waiting moves to the other kernels; round 7 again inside the noise, profiles/r07e_sm_persist_ab.txt)
-                    hipLaunchKernelGGL((segment_match_kernel<512, 8192>), dim3(nVQ), dim3(512), 0, ctx->stream, nVQ, pHitBase, pSegCount, pOutBase,
-                                       tBitsV, pKey, pVal, pKV, outK, outV, dQLog2.p, dBktStart.p, dBktCount.p, dBktEmit.p, dSegDone.p,
-                                       (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p, cBits,
-                                       widePos ? tBitsV : 0);
-                    pSegDone = dSegDone.p;
-                }
-                {
-                    ProfScope ps(ctx, "prefilter_partition_hits");
-                    // large tiles where the virtual queries are large (proteome-scale target sets), the small form for small inputs
-                    // (<1024, 8192>, fastest alone, waits for whole CUs beside the other streams' score wavefronts and lost inside the
-                    // pipeline: removed)
-                    if (nLeft / std::max<uint32_t>(nVQ, 1) >= 16384)
-                        hipLaunchKernelGGL((partition_hits_kernel<512, 4096>), dim3(nVQ), dim3(512), 0, ctx->stream, nVQ, pHitBase, tBitsV, pKey,
-                                           pVal, pKV, dKVB.p, dQLog2.p, dBktStart.p, dBktCount.p, dFlag.p, pSegCount, pOutBase, pSegDone);
-                    else
-                        hipLaunchKernelGGL((partition_hits_kernel<256, 2048>), dim3(nVQ), dim3(256), 0, ctx->stream, nVQ, pHitBase, tBitsV, pKey,
-                                           pVal, pKV, dKVB.p, dQLog2.p, dBktStart.p, dBktCount.p, dFlag.p, pSegCount, pOutBase, pSegDone);
-                }
-                hipLaunchKernelGGL(bin_count_kernel, dim3(gridFor(nVQ + 1, 256)), dim3(256), 0, ctx->stream, nVQ, dQLog2.p, dQBins.p);
-                int rc = exclusiveScanWiden(ctx, dQBins.p, dBinBase.p, nVQ + 1, scanTmp);
-                if (rc != SD_OK) return rc;
-                int hFlag = 0;
-                uint64_t totalBins = 0;
-                SD_HIP(ctx, sdD2H(ctx, &hFlag, dFlag.p, sizeof(int)));
-                SD_HIP(ctx, sdD2H(ctx, &totalBins, dBinBase.p + nVQ, sizeof(uint64_t)));
-                SD_HIP(ctx, sdStreamSync(ctx));
-                if (hFlag == 0 && totalBins > 0) {
-                    const uint32_t bigCap = (uint32_t) std::min<size_t>(nSlots, 1u << 26);   // every bucket may be oversize on very large target sets
-                    WsView<uint32_t> dBigList(ctx, "pf.dBigList");
-                    SD_HIP(ctx, dBigList.alloc(bigCap + 1));
-                    uint32_t *dBigCount = dBigList.p + bigCap;
-                    SD_HIP(ctx, hipMemsetAsync(dBigCount, 0, sizeof(uint32_t), ctx->stream));
-                    {
-                        ProfScope ps(ctx, "prefilter_bucket_match");
-                        SD_HIP(ctx, dSlotList.alloc(totalBins));
-                        hipLaunchKernelGGL(slot_list_kernel, dim3(gridFor(totalBins, 256)), dim3(256), 0, ctx->stream, (uint32_t) totalBins, nVQ,
-                                           (const uint64_t *) dBinBase.p, dSlotList.p);
-                        hipLaunchKernelGGL((bucket_match_kernel<128, PF_BUCKET_CAP>), dim3((unsigned) totalBins), dim3(128), 0, ctx->stream,
-                                           nVQ, dBinBase.p, dQLog2.p, tBitsV, dBktStart.p, dBktCount.p, (const uint2 *) dKVB.p, outK,
-                                           outV, dBktEmit.p, dFlag.p, (const uint32_t *) dSlotList.p, dBigList.p, dBigCount, bigCap,
-                                           dQSplit.p, dQParts.p, dQSplits.p, cBits, widePos ? tBitsV : 0, (const uint32_t *) nullptr, 0u);
-                    }
-                    // the few buckets with one very hit-rich target (e.g. the query itself): their number stays on the device -- a launch of
-                    // BIG_GRID workgroups that compare their index with the list's length takes them without a round trip to the host; a
-                    // list longer than that (every bucket can be oversize on a very large target set) is finished after the next read
-                    constexpr uint32_t BIG_GRID = 2048;
-                    auto launchBig = [&](uint32_t first, uint32_t grid) {
-                        ProfScope ps(ctx, "prefilter_bucket_match_big");
-                        hipLaunchKernelGGL((bucket_match_kernel<256, PF_BUCKET_CAP_BIG>), dim3(grid), dim3(256), 0, ctx->stream, nVQ,
-                                           dBinBase.p, dQLog2.p, tBitsV, dBktStart.p, dBktCount.p, (const uint2 *) dKVB.p, outK, outV,
-                                           dBktEmit.p, dFlag.p, (const uint32_t *) dBigList.p, (uint32_t *) nullptr,
-                                           (uint32_t *) nullptr, 0u, dQSplit.p, dQParts.p, dQSplits.p, cBits, widePos ? tBitsV : 0,
-                                           (const uint32_t *) dBigCount, first);
-                    };
-                    launchBig(0, std::min<uint32_t>(BIG_GRID, bigCap));
-                    rc = exclusiveScanWiden(ctx, dBktEmit.p, dEmitOff.p, nSlots + 1, scanTmp);
-                    if (rc != SD_OK) return rc;
-                    uint64_t nc64 = 0;
-                    uint32_t nBig = 0;
-                    SD_HIP(ctx, sdD2H(ctx, &nBig, dBigCount, sizeof(uint32_t)));
-                    SD_HIP(ctx, sdD2H(ctx, &hFlag, dFlag.p, sizeof(int)));
-                    SD_HIP(ctx, sdD2H(ctx, &nc64, dEmitOff.p + nSlots, sizeof(uint64_t)));
-                    SD_HIP(ctx, sdStreamSync(ctx));
-                    if (hFlag == 0 && nBig > BIG_GRID && nBig <= bigCap) {   // the rest of a long list, then the offsets again
-                        for (uint32_t first = BIG_GRID; first < nBig; first += 1u << 20) launchBig(first, std::min<uint32_t>(nBig - first, 1u << 20));
-                        rc = exclusiveScanWiden(ctx, dBktEmit.p, dEmitOff.p, nSlots + 1, scanTmp);
-                        if (rc != SD_OK) return rc;
-                        SD_HIP(ctx, sdD2H(ctx, &hFlag, dFlag.p, sizeof(int)));
-                        SD_HIP(ctx, sdD2H(ctx, &nc64, dEmitOff.p + nSlots, sizeof(uint64_t)));
-                        SD_HIP(ctx, sdStreamSync(ctx));
-                    }
-                    if (hFlag == 0) {
-                        nCand = (uint32_t) nc64;
-                        bucketDone = true;
-                        if (nCand > 0) {
-                            SD_HIP(ctx, dCKey.alloc(nCand));
-                            SD_HIP(ctx, dCVal.alloc(nCand));
-                            hipLaunchKernelGGL(bucket_collect_kernel, dim3((unsigned) totalBins), dim3(64), 0, ctx->stream, nVQ, dBinBase.p,
-                                               dBktStart.p, dBktEmit.p, dEmitOff.p, outK, outV, dCKey.p, dCVal.p, (const uint32_t *) dSlotList.p);
-                        }
-                    }
-                }
-                if (!bucketDone && getenv("SD_DEBUG_TIMING"))
-                    fprintf(stderr, "[prefilter] bucket path fell back: flag %d, %llu bins, %llu hits, %u queries\n", hFlag,
-                            (unsigned long long) totalBins, (unsigned long long) nHits, bq);
-                if (!bucketDone && useJoin) {   // the global-sort fallback belongs to the lookup path: redo the sub-batch there
-                    forceLookup = true;
-                    continue;
-                }
-                if (!bucketDone) {
-                    // a bucket larger than the LDS capacity (or more target bits than the slots cover): redo this
-                    // sub-batch with the global sort; dKeyA / dValA were overwritten by the emitted hits, so gather again
-                    ProfScope ps(ctx, "prefilter_gather_hits");
-                    hipLaunchKernelGGL(gather_hits_kernel, dim3(gridFor(nKmers, 256)), dim3(256), 0, ctx->stream, nKmers, dKStart.p,
-                                       dKLen.p, dKPos.p, dHitBase.p, dPosBase.p, bq, (const uint2 *) T->dEntries, tBits, dQHitBase.p,
-                                       dKeyA.p, dValA.p, dDiag.p, wideIdx ? (const uint32_t *) dKStartHi.p : (const uint32_t *) nullptr, 0);
-                }
-            }
-            if (!bucketDone) {
-            {
-                ProfScope ps(ctx, "prefilter_sort_hits");
-                // Hits arrive grouped by query in emission order.  A stable sort on the target bits alone makes every
-                // (target, query) group contiguous with its emission order intact, which is all match_diag needs; the
-                // few surviving candidates are put back into (query, target) order below.  19 target bits = 3 radix
-                // passes instead of the 4 that (query, target) would take.
-                const int rcS = sortPairs(ctx, dKeyA.p, dKeyB.p, dValA.p, dValB.p, nHits, 0, tBits);
-                if (rcS != SD_OK) return rcS;
-            }
-            SD_HIP(ctx, dEmit.alloc(nHits + 1));
-            SD_HIP(ctx, dEmitPos.alloc(nHits + 1));
-            {
-                ProfScope ps(ctx, "prefilter_match_diag");
-                hipLaunchKernelGGL(match_diag_kernel, dim3(gridFor(nHits, 256)), dim3(256), 0, ctx->stream, nHits, dKeyB.p, dValB.p,
-                                   dQSplit.p, tBits, dEmit.p);
-            }
-            SD_HIP(ctx, hipMemsetAsync(dEmit.p + nHits, 0, 1, ctx->stream));
-            int rc = exclusiveScanWiden(ctx, dEmit.p, dEmitPos.p, nHits + 1, scanTmp);
-            if (rc != SD_OK) return rc;
-            uint64_t nc64 = 0;
-            SD_HIP(ctx, sdD2H(ctx, &nc64, dEmitPos.p + nHits, sizeof(uint64_t)));
-            SD_HIP(ctx, sdStreamSync(ctx));
-            nCand = (uint32_t) nc64;
-            }
-        }
-        if (!bucketDone && nHits > 0) {
-            // the global-sort fallback matches across one split only: queries whose hit buffer overflows more than once are
-            // reported there, not guessed
-            std::vector<uint32_t> hParts(bq);
-            SD_HIP(ctx, sdD2H(ctx, hParts.data(), dQParts.p, (size_t) bq * sizeof(uint32_t)));
-            SD_HIP(ctx, sdStreamSync(ctx));
-            bool any = false;
-            for (uint32_t x = 0; x < bq; x++)
-                if (hParts[x] >= 2) {
-                    if (hUnsupported.empty()) hUnsupported.assign(bq, 0);
-                    hUnsupported[x] = 1;
-                    any = true;
-                }
-            if (any)
-                sdFail(ctx, SD_EUNSUPPORTED, "queries whose hit buffer overflows more than once in a sub-batch that fell back to the global sort "
-                       "(batch [%u, %u)): reported with outCount = UINT32_MAX", qBeg, qBeg + bq);
-        }
-        if (widePos && !bucketDone) {
-            // the global-sort fallback carries 24-bit positions only: the heavy queries of this sub-batch are reported, not guessed
-            if (hUnsupported.empty()) hUnsupported.assign(bq, 0);
-            for (uint32_t x = 0; x < bq; x++)
-                if (hStats[(size_t) x * 4 + 1] >= (1ull << 24)) hUnsupported[x] = 1;
-            sdFail(ctx, SD_EUNSUPPORTED, "queries with >= 2^24 index hits in a sub-batch that fell back to the global sort (batch [%u, %u)): "
-                   "reported with outCount = UINT32_MAX", qBeg, qBeg + bq);
-        }
-        hs.reset(new HostScope(ctx, "pf.score_keep"));
-        DiagSrc diagSrc;
-        diagSrc.hitDiag = useJoin ? (const uint16_t *) nullptr : (const uint16_t *) dDiag.p;
-        diagSrc.qHitBase = dQHitBase.p;
-        diagSrc.elems = dElems.p;
-        diagSrc.kmerBase = dKmerBase.p;
-        diagSrc.posBase = dPosBase.p;
-        diagSrc.idxOffsets = T->dOffsets;
-        diagSrc.entries = T->dEntries;
-        if (nCand > 0) {
-            if (!bucketDone) {
-                SD_HIP(ctx, dCKey.alloc(nCand));
-                SD_HIP(ctx, dCVal.alloc(nCand));
-            }
-            SD_HIP(ctx, dCScore.alloc(nCand));
-            SD_HIP(ctx, dCLen.alloc(nCand));
-            if (!bucketDone) {
-                // compact into scratch, then a stable sort on the query bits restores (query, target, emission) order
-                WsView<uint32_t> dCKey0(ctx, "pf.dCKey0");
-                WsView<uint32_t> dCVal0(ctx, "pf.dCVal0");
-                SD_HIP(ctx, dCKey0.alloc(nCand));
-                SD_HIP(ctx, dCVal0.alloc(nCand));
-                hipLaunchKernelGGL(compact_kernel, dim3(gridFor(nHits, 256)), dim3(256), 0, ctx->stream, nHits, dEmit.p, dEmitPos.p,
-                                   dKeyB.p, dValB.p, (const int32_t *) nullptr, dCKey0.p, dCVal0.p, (int32_t *) nullptr);
-                int endBit = tBits;
-                uint32_t qb = bq - 1;
-                while (qb) { endBit++; qb >>= 1; }
-                endBit = std::min(32, std::max(endBit, tBits + 1));
-                const int rcS = sortPairs(ctx, dCKey0.p, dCKey.p, dCVal0.p, dCVal.p, nCand, tBits, endBit);
-                if (rcS != SD_OK) return rcS;
-            }
-            {
-                ProfScope ps(ctx, "prefilter_score_diag");
-                // (one thread per candidate: a cooperative form, eight lanes per candidate down the diagonal, was no faster -- the
-                // diagonal, not the walk, is what the kernel costs -- and was removed: profiles/r06n_score_coop.txt, r07d_score_coop_res.txt)
-                // the diagonal of a candidate from the target's residues (join path: 8-byte hits without a stored diagonal; k = 6 with
-                // 24-bit ordinals beside the diagonal byte); otherwise from the index
-                const int diagRes = (useJoin && T->k == 6 && posMask == 0xFFFFFFu) ? 1 : 0;
-                hipLaunchKernelGGL(score_diag_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCVal.p,
-                                   diagSrc, tBits, dQ.p, dQOff.p, dDB.p, T->dMasked, T->dSeqOff, dMat.p, dCScore.p, dCLen.p,
-                                   dProfAln, posMask, diagRes);
-            }
-            hipLaunchKernelGGL(cand_stats_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCLen.p, tBits,
-                               (unsigned long long *) dStats.p);
-            SD_HIP(ctx, dKeep.alloc(nCand));
-            {
-                ProfScope ps(ctx, "prefilter_keep_max");
-                hipLaunchKernelGGL(keep_max_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, nCand, dCKey.p, dCVal.p, dCScore.p, dKeep.p,
-                                   tBits, posMask, (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p, diagSrc);
-            }
-        WsView<uint64_t> dK64(ctx, "pf.dK64");
-        WsView<uint64_t> dKPos64(ctx, "pf.dKPos64");
-            SD_HIP(ctx, dK64.alloc(nCand + 1));
-            SD_HIP(ctx, dKPos64.alloc(nCand + 1));
-            SD_HIP(ctx, hipMemsetAsync(dK64.p + nCand, 0, sizeof(uint64_t), ctx->stream));
-            hipLaunchKernelGGL(flag_to_u64_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, (uint64_t) nCand, dKeep.p, dK64.p);
-            int rc = exclusiveScan(ctx, dK64.p, dKPos64.p, (uint64_t) nCand + 1, scanTmp);
-            if (rc != SD_OK) return rc;
-            // the number of kept candidates stays on the device (query_bounds_kernel reads it where the scan left it): the kept arrays
-            // are sized by the candidates, no round trip to the host
-            nKeptPtr = dKPos64.p + nCand;
-            SD_HIP(ctx, dKKey.alloc((size_t) nCand + 1));
-            SD_HIP(ctx, dKVal.alloc((size_t) nCand + 1));
-            SD_HIP(ctx, dKScore.alloc((size_t) nCand + 1));
-            hipLaunchKernelGGL(compact_kernel, dim3(gridFor(nCand, 256)), dim3(256), 0, ctx->stream, (uint64_t) nCand, dKeep.p,
-                               dKPos64.p, dCKey.p, dCVal.p, dCScore.p, dKKey.p, dKVal.p, dKScore.p);
-        } else {
-            SD_HIP(ctx, dKKey.alloc(1));
-            SD_HIP(ctx, dKVal.alloc(1));
-            SD_HIP(ctx, dKScore.alloc(1));
-            SD_HIP(ctx, dDiag.alloc(std::max<uint64_t>(nHits, 1)));
-        }
-        hs.reset(new HostScope(ctx, "pf.select"));
-        SD_HIP(ctx, dQStart.alloc(bq + 1));
-        hipLaunchKernelGGL(query_bounds_kernel, dim3(gridFor(bq + 1, 256)), dim3(256), 0, ctx->stream, bq, 0u, nKeptPtr, (const uint32_t *) dKKey.p, tBits, dQStart.p);
-        WsView<sd_hit> dOut(ctx, "pf.dOut");
-        WsView<uint32_t> dOutCount(ctx, "pf.dOutCount");
-        SD_HIP(ctx, dOut.alloc((size_t) bq * maxHits));
-        SD_HIP(ctx, dOutCount.alloc(bq));
-        const bool selBig = maxHits + 1 > 2048;
-        WsView<uint32_t> dSelBig(ctx, "pf.dSelBig");   // [bq] query list + [1] count
-        if (selBig) {
-            SD_HIP(ctx, dSelBig.alloc((size_t) bq + 1));
-            SD_HIP(ctx, hipMemsetAsync(dSelBig.p + bq, 0, sizeof(uint32_t), ctx->stream));
-        }
-        {
-            ProfScope ps(ctx, "prefilter_select_hits");
-            if (maxHits + 1 <= 512)   // short result lists: a 12-KB sorter instead of 48 KB (more workgroups per CU)
-                hipLaunchKernelGGL(select_hits_kernel<1024>, dim3(bq), dim3(256), 0, ctx->stream, bq, dQStart.p, dKKey.p, dKVal.p, dKScore.p,
-                                   diagSrc, tBits, par->binSize - 1, maxHits, par->minDiagScore, dIdent.p, dQOff.p, T->dSeqOff,
-                                   par->covMode, par->covThr, dQ.p, dDB.p, dMat.p, dOut.p, dOutCount.p, dErr.p, dProfAln, posMask, useJoin ? binBits : -1,
-                                   (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p,
-                                   (uint32_t *) nullptr, (uint32_t *) nullptr);
-            else if (maxHits + 1 <= 2048)
-                hipLaunchKernelGGL(select_hits_kernel<4096>, dim3(bq), dim3(256), 0, ctx->stream, bq, dQStart.p, dKKey.p, dKVal.p, dKScore.p,
-                                   diagSrc, tBits, par->binSize - 1, maxHits, par->minDiagScore, dIdent.p, dQOff.p, T->dSeqOff,
-                                   par->covMode, par->covThr, dQ.p, dDB.p, dMat.p, dOut.p, dOutCount.p, dErr.p, dProfAln, posMask, useJoin ? binBits : -1,
-                                   (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p,
-                                   (uint32_t *) nullptr, (uint32_t *) nullptr);
-            else   // longer lists: queries with more candidates at the cut than the LDS sorter holds go on to select_hits_big_kernel
-                hipLaunchKernelGGL(select_hits_kernel<8192>, dim3(bq), dim3(256), 0, ctx->stream, bq, dQStart.p, dKKey.p, dKVal.p, dKScore.p,
-                                   diagSrc, tBits, par->binSize - 1, maxHits, par->minDiagScore, dIdent.p, dQOff.p, T->dSeqOff,
-                                   par->covMode, par->covThr, dQ.p, dDB.p, dMat.p, dOut.p, dOutCount.p, dErr.p, dProfAln, posMask, useJoin ? binBits : -1,
-                                   (const uint32_t *) dQSplit.p, (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p, dSelBig.p, dSelBig.p + bq);
-        }
-        SD_HIP(ctx, hipGetLastError());
-        if (selBig) {
-            // queries whose list is longer than the LDS sorter carries, with more candidates at the cut than it holds
-            uint32_t nBigSel = 0;
-            SD_HIP(ctx, sdD2H(ctx, &nBigSel, dSelBig.p + bq, sizeof(uint32_t)));
-            SD_HIP(ctx, sdStreamSync(ctx));
-            if (nBigSel > 0) {
-                uint32_t stride = 1;
-                while (stride < (uint32_t) maxHits) stride <<= 1;
-                // scratch: 12 B per slot entry; at most ~1 GB per launch
-                const uint32_t perLaunch = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>(nBigSel, (1ull << 30) / ((uint64_t) stride * 12)));
-                WsView<unsigned long long> dSelKeys(ctx, "pf.dSelKeys");
-                WsView<uint32_t> dSelPay(ctx, "pf.dSelPay");
-                SD_HIP(ctx, dSelKeys.alloc((size_t) perLaunch * stride));
-                SD_HIP(ctx, dSelPay.alloc((size_t) perLaunch * stride));
-                ProfScope ps(ctx, "prefilter_select_hits_big");
-                for (uint32_t b0 = 0; b0 < nBigSel; b0 += perLaunch) {
-                    const uint32_t nb = std::min(perLaunch, nBigSel - b0);
-                    hipLaunchKernelGGL(select_hits_big_kernel, dim3(nb), dim3(SELB_NT), 0, ctx->stream, (const uint32_t *) dSelBig.p + b0,
-                                       (const uint32_t *) dQStart.p, (const uint32_t *) dKKey.p, (const uint32_t *) dKVal.p,
-                                       (const int32_t *) dKScore.p, diagSrc, tBits, par->binSize - 1, maxHits, par->minDiagScore,
-                                       (const uint32_t *) dIdent.p, (const uint64_t *) dQOff.p, (const uint64_t *) T->dSeqOff, par->covMode,
-                                       par->covThr, (const uint8_t *) dQ.p, (const int8_t *) dDB.p, (const int8_t *) dMat.p, dOut.p,
-                                       dOutCount.p, dProfAln, posMask, useJoin ? binBits : -1, (const uint32_t *) dQSplit.p,
-                                       (const uint32_t *) dQParts.p, (const uint32_t *) dQSplits.p, dSelKeys.p, dSelPay.p, stride);
-                }
-                SD_HIP(ctx, hipGetLastError());
-            }
-        }
-        hs.reset(new HostScope(ctx, "pf.download"));
-        int hErr = 0;
-        sd_hit *hOutP = nullptr;   // pinned, persistent: a pageable destination makes this copy a staged, synchronous one
-        SD_HIP(ctx, pinGet(ctx, "pf.hOut", (size_t) bq * maxHits + 1, &hOutP));
-        SD_HIP(ctx, sdD2H(ctx, &hErr, dErr.p, sizeof(int)));
-        SD_HIP(ctx, hipMemcpyAsync(hOutP, dOut.p, (size_t) bq * maxHits * sizeof(sd_hit), hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(ctx, sdD2H(ctx, outCount + qBeg, dOutCount.p, bq * sizeof(uint32_t)));
-        if (stats) SD_HIP(ctx, sdD2H(ctx, stats + (size_t) qBeg * 4, dStats.p, (size_t) bq * 4 * sizeof(uint64_t)));
-        SD_HIP(ctx, sdStreamSync(ctx));
-        (void) hErr;
-        hs.reset(new HostScope(ctx, "pf.scatter"));
-        // the caller's rows are par->maxHitsPerQuery wide
-        for (uint32_t x = 0; x < bq; x++)
-            if (outCount[qBeg + x] != UINT32_MAX)
-                memcpy(outHits + (size_t) (qBeg + x) * par->maxHitsPerQuery, hOutP + (size_t) x * maxHits,
-                       (size_t) std::min<uint32_t>(outCount[qBeg + x], maxHits) * sizeof(sd_hit));
-        for (uint32_t x = 0; x < (uint32_t) hUnsupported.size(); x++)
-            if (hUnsupported[x]) outCount[qBeg + x] = UINT32_MAX;   // per-query error slot: not computed (see above)
-        hs.reset();
-        forceLookup = false;
-        qBeg += bq;
+        if (b.next == PF_RETRY_HALF) batchQ = std::max<uint32_t>(1, b.bq / 2);
+        else if (b.next == PF_RETRY_LOOKUP) forceLookup = true;
+        else forceLookup = false, qBeg += b.bq;
     }
     return SD_OK;
 }
+}  // namespace
 
-}  // extern "C"
+extern "C" {
 
-int sd_prefilter_batch(sd_ctx *ctx, const sd_target *T, const sd_prefilter_params *par, uint32_t nQ,
-                       const uint8_t *qResidues, const uint64_t *qOffsets, const int16_t *qKmerBias,
-                       const int8_t *qDiagBias, const uint32_t *identityId, sd_hit *outHits, uint32_t *outCount,
-                       uint64_t *stats) {
-    return prefilterBatchImpl(ctx, T, par, nQ, qResidues, qOffsets, qKmerBias, qDiagBias, identityId, outHits, outCount, stats,
-                              nullptr);
+int sd_prefilter_batch(sd_ctx *ctx, const sd_target *T, const sd_prefilter_params *par, uint32_t nQ, const uint8_t *qResidues,
+                       const uint64_t *qOffsets, const int16_t *qKmerBias, const int8_t *qDiagBias, const uint32_t *identityId,
+                       sd_hit *outHits, uint32_t *outCount, uint64_t *stats) {
+    return prefilterBatchImpl(ctx, T, par, nQ, qResidues, qOffsets, qKmerBias, qDiagBias, identityId, outHits, outCount, stats, nullptr);
 }
 
-int sd_prefilter_profile_batch(sd_ctx *ctx, const sd_target *T, const sd_prefilter_params *par, uint32_t nQ,
-                               const uint8_t *qLetters, const uint64_t *qOffsets, const int16_t *sortedScore,
-                               const uint8_t *sortedIndex, const int8_t *alnProfile, const uint32_t *identityId,
-                               sd_hit *outHits, uint32_t *outCount, uint64_t *stats) {
+int sd_prefilter_profile_batch(sd_ctx *ctx, const sd_target *T, const sd_prefilter_params *par, uint32_t nQ, const uint8_t *qLetters,
+                               const uint64_t *qOffsets, const int16_t *sortedScore, const uint8_t *sortedIndex, const int8_t *alnProfile,
+                               const uint32_t *identityId, sd_hit *outHits, uint32_t *outCount, uint64_t *stats) {
     if (!sortedScore || !sortedIndex || !alnProfile) return SD_EINVAL;
     ProfileQueries pq = {sortedScore, sortedIndex, alnProfile};
     std::vector<uint32_t> noIdentity;
@@ -3787,3 +3784,6 @@ int sd_prefilter_profile_batch(sd_ctx *ctx, const sd_target *T, const sd_prefilt
     }
     return prefilterBatchImpl(ctx, T, par, nQ, qLetters, qOffsets, nullptr, nullptr, identityId, outHits, outCount, stats, &pq);
 }
+
+}  // extern "C"
+

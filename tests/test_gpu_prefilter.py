@@ -512,3 +512,43 @@ def test_prefilter_cumulative_score_table_equals_row_search(gpu, host, monkeypat
         for q in range(ps.n):
             n = int(a[1][q])
             assert np.array_equal(a[0][q, :n], b[0][q, :n]), (env, q)
+
+
+def test_prefilter_hit_budget_retry_equals_one_pass(gpu, host, monkeypatch):
+    """A sub-batch with more hits than SD_PF_HIT_BUDGET is done again at half its size, on the join path (the count read after
+    join_count) and on the lookup path (the count read after the emit pass): with the smallest budget the clamp allows, counts,
+    statistics and rows per query equal the run with default knobs exactly.  That the retry ran is read off the launches of
+    prefilter_select_hits, one per sub-batch: the 3 000 queries are two sub-batches of 1 500 with default knobs (at most 2 048
+    queries each, equal parts), and more with the budget."""
+    from spacedust_amd.synth import make_proteomes
+    ps = make_proteomes(n_proteomes=6, genes_per_proteome=500, n_families=800, seed=93)
+    ident = np.arange(ps.n, dtype=np.uint32)
+    sw_b, dg_b, km_b = host.comp_bias(ps.residues, ps.offsets, 6)
+    tgt = api.Target(gpu, host, host.build_index(ps.residues, ps.offsets, 6, 112))
+    par = api.prefilter_params(host, ps.n, kmer_thr=112, max_hits=100, cov_thr=0.0, bin_size=2, k=6)
+
+    def run():
+        gpu.profile(True)
+        try:
+            r = api.prefilter(gpu, tgt, par, ps.residues, ps.offsets, km_b, dg_b, ident, want_stats=True)
+            return r, int(gpu.profile_report()['prefilter_select_hits'][1])
+        finally:
+            gpu.profile(False)
+
+    base, base_launches = run()
+    print('select launches, default knobs:', base_launches)
+    assert base_launches == -(-ps.n // 2048)
+    assert int(base[1].sum()) > 1000
+    for env in ({}, {'SD_PF_JOIN': '0'}):
+        monkeypatch.setenv('SD_PF_HIT_BUDGET', '65536')
+        for k_, v_ in env.items():
+            monkeypatch.setenv(k_, v_)
+        r, launches = run()
+        for k_ in list(env) + ['SD_PF_HIT_BUDGET']:
+            monkeypatch.delenv(k_)
+        print('select launches, budget 65536,', env, ':', launches)
+        assert launches > base_launches, env
+        assert np.array_equal(base[1], r[1]) and np.array_equal(base[2], r[2]), env
+        for q in range(ps.n):
+            n = int(base[1][q])
+            assert np.array_equal(base[0][q, :n], r[0][q, :n]), (env, q)

@@ -1,6 +1,6 @@
 """The prefilter stage ALONE on one GPU at a bench size, per-kernel HIP-event times, for A/B runs of environment knobs in ONE
 process (same box, same index, same queries): every variant's rows must equal the first variant's.
-usage: python tools/pf_iso.py [--proteomes 1000] [--queries 8192] [--reps 1] VARIANT [VARIANT ...]
+usage: python tools/pf_iso.py [--proteomes 1000] [--queries 8192] [--reps 1] [--save first.npz] VARIANT [VARIANT ...]
   VARIANT = name[:ENV=VALUE[,ENV=VALUE...]]     e.g.  base:SD_PF_HIT_BUDGET=1073741824  new
 Writes one JSON line per variant (kernel ms by name, total, queries, algorithmic bytes per query) to stdout."""
 import argparse
@@ -21,6 +21,7 @@ def main():
     ap.add_argument('--queries', type=int, default=8192)
     ap.add_argument('--max-seqs', type=int, default=0)
     ap.add_argument('--reps', type=int, default=1)
+    ap.add_argument('--save', default='', help='write (hits, cnt, stats) of the first variant to this .npz: two builds compare them')
     ap.add_argument('variants', nargs='+')
     args = ap.parse_args()
     from spacedust_amd import api
@@ -67,6 +68,8 @@ def main():
         same = None
         if first is None:
             first = r
+            if args.save:
+                np.savez(args.save, hits=r[0], cnt=r[1], stats=r[2])
         else:
             same = bool(np.array_equal(first[1], r[1]) and np.array_equal(first[2], r[2]) and
                         all(np.array_equal(first[0][q, :int(r[1][q])], r[0][q, :int(r[1][q])]) for q in range(nq) if r[1][q] != 0xFFFFFFFF))
