@@ -1,11 +1,21 @@
-// Target index construction on the device: sd_target_build.
+// Target index construction on the device.  Three builders, one per kind of target index:
+//   sd_target_build          the plain sequence index (k = 6 or 7): every target tantan-masked, its own k-mers at or above kmerThr
+//   sd_target_build_profile  a profile target DB (k = 6): the similar k-mers of every profile window, nothing masked
+//   sd_target_build_similar  a sequence target under --target-search-mode 1 (k = 6): the similar k-mers of every sequence window
 //
-// What IndexBuilder::fillDatabase does on the host (M/src/prefiltering/IndexBuilder.cpp:55-239; sd_index.cpp is the host
-// restatement this file is tested against, entry for entry):
+// What IndexBuilder::fillDatabase does on the host for the first (M/src/prefiltering/IndexBuilder.cpp:55-239; sd_index.cpp is the
+// host restatement this file is tested against, entry for entry):
 //   1. every target is tantan-masked to X (M/src/commons/Masker.cpp:15-55, M/lib/tantan/tantan.cpp:308-460),
 //   2. per target, the spaced k-mers without X whose self score reaches kmerThr are collected, each distinct k-mer once per
 //      target at its smallest position (IndexTable.h:131-166,376-392),
 //   3. the lists are ordered by (target, position) (IndexTable.h:182-189).
+// The other two differ in step 2 only (the comments at their generators say how).
+//
+// What the builders share (IndexBuild): a builder uploads what is its own and supplies a record generator that runs in three
+// modes -- 0: histogram of its records over IB_COARSE_BINS k-mer ranges, 1: records of a k-mer range [lo, hi) per slot (what one
+// wavefront writes in order), 2: the records themselves.  The frame cuts the k-mer space into passes along the histogram
+// (ibPassCap) and per pass counts, scans, emits, sorts and dedupes (ibPasses), then turns the per-k-mer counts into list starts
+// (ibListStarts).
 //
 // On the MI355X:
 //   ib_mask_kernel     one lane per target sequence, 64 sequences of similar length per wavefront (the host deals them out by
@@ -15,13 +25,15 @@
 //                      sums over the offsets combined as (s0 + s2) + (s1 + s3), see sd_tantan.cpp), so the float posterior
 //                      that is compared with --mask-prob has the same bits.  The forward posteriors (one float per residue)
 //                      and the rescaling factors are kept between the passes in a scratch buffer laid out [position][lane].
-//   ib_count / ib_emit per k-mer range [lo, hi) that fits the sort buffers: (k-mer - lo, target << 16 | position) records of
-//                      the masked sequences in (target, position) order -- a wavefront walks its sequences 64 positions at a
-//                      time, ballots keep the order -- then a stable radix sort by k-mer (hipCUB; setup path, not the search),
-//   ib_keep_* / ib_place  adjacent records of one (k-mer, target) collapse to the first (= smallest position), the survivors are
-//                      appended to the entry array (8 B each, the layout the prefilter kernels read) and counted per k-mer,
-//   offsets            64-bit exclusive scan of the counts; stored as 32-bit starts, relative to one 64-bit base per 65 536
-//                      k-mers when the index has 2^32 entries or more (the wide form of sd_target_create_wide).
+//   ib_records_kernel<K, MODE>  the plain builder's generator.  Per k-mer range [lo, hi) that fits the sort buffers: (k-mer - lo,
+//                      target << 16 | position) records of the masked sequences in (target, position) order -- a wavefront walks
+//                      its 16 sequences 64 positions at a time, ballots keep the order.  ib_profile_records_kernel<MODE> and
+//                      ib_similar_records_kernel<MODE> are the generators of the other two builders: a wavefront per window.
+//   sdRadixSortPairs   stable radix sort of a pass's records by k-mer (sd_scan_sort.h: this library's own, as are the scans),
+//   ib_keep_count / ib_place  adjacent records of one (k-mer, target) collapse to the first (= smallest position), the survivors
+//                      are appended to the entry array (8 B each, the layout the prefilter kernels read) and counted per k-mer,
+//   ib_offsets         after a 64-bit exclusive scan of the counts (sdScanLaunch): 32-bit starts, relative to one 64-bit base
+//                      per 65 536 k-mers when the index has 2^32 entries or more (the wide form of sd_target_create_wide).
 // Algorithmic bytes: 1 B read + 1 B written per residue for the mask (+ 8 B of scratch traffic), 8 B written per entry; the
 // sort moves 12 B x 2 x 4 passes per record.
 #include "sd_common.h"
@@ -37,7 +49,7 @@
 
 namespace {
 
-// the radix sort of the (k-mer, record) pairs: this library's own kernels
+// the radix sort of the (k-mer, record) pairs and the scans of the counts: this library's own kernels
 #include "sd_scan_sort.h"
 
 constexpr int TT_OFF = 50;       // maxCycleLength (Masker.cpp:20-32)
@@ -707,77 +719,6 @@ ib_similar_records_kernel(uint64_t nWin, const uint64_t *__restrict__ winBase /*
     if (MODE == 0) flush();
 }
 
-// ---- exclusive scan of up to 2^32 32-bit counts into 64-bit sums (three launches: tile sums, tile bases, apply)
-constexpr int IS_TILE = 4096, IS_NT = 256;
-__global__ void __launch_bounds__(IS_NT) is_tile_sums(const uint32_t *__restrict__ in, uint64_t n, uint64_t *__restrict__ tileSum) {
-    __shared__ unsigned long long part[IS_NT / 64];
-    const uint64_t base = (uint64_t) blockIdx.x * IS_TILE;
-    unsigned long long v = 0;
-    for (int x = threadIdx.x; x < IS_TILE; x += IS_NT)
-        if (base + x < n) v += in[base + x];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) tileSum[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-}
-__global__ void __launch_bounds__(1024) is_tile_bases(uint64_t *__restrict__ tileSum, uint64_t nTiles, uint64_t *__restrict__ total) {
-    // one workgroup: every thread owns a contiguous run of tiles
-    __shared__ unsigned long long part[1024];
-    const uint64_t per = (nTiles + 1023) / 1024;
-    const uint64_t b = threadIdx.x * per, e = min(nTiles, b + per);
-    unsigned long long v = 0;
-    for (uint64_t i = b; i < e; i++) v += tileSum[i];
-    part[threadIdx.x] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long run = 0;
-        for (int i = 0; i < 1024; i++) {
-            const unsigned long long c = part[i];
-            part[i] = run;
-            run += c;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    unsigned long long run = part[threadIdx.x];
-    for (uint64_t i = b; i < e; i++) {
-        const unsigned long long c = tileSum[i];
-        tileSum[i] = run;
-        run += c;
-    }
-}
-__global__ void __launch_bounds__(IS_NT) is_apply(const uint32_t *__restrict__ in, uint64_t n, const uint64_t *__restrict__ tileBase,
-                                                  uint64_t *__restrict__ out) {
-    __shared__ unsigned long long wsum[IS_NT / 64];
-    const uint64_t base = (uint64_t) blockIdx.x * IS_TILE;
-    constexpr int PER = IS_TILE / IS_NT;
-    uint32_t c[PER];
-    unsigned long long mine = 0;
-#pragma unroll
-    for (int x = 0; x < PER; x++) {
-        const uint64_t i = base + (uint64_t) threadIdx.x * PER + x;
-        c[x] = i < n ? in[i] : 0u;
-        mine += c[x];
-    }
-    unsigned long long incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long up = __shfl_up(incl, o, 64);
-        if ((int) (threadIdx.x & 63) >= o) incl += up;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    unsigned long long run = tileBase[blockIdx.x] + incl - mine;
-    for (int w = 0; w < (int) (threadIdx.x >> 6); w++) run += wsum[w];
-#pragma unroll
-    for (int x = 0; x < PER; x++) {
-        const uint64_t i = base + (uint64_t) threadIdx.x * PER + x;
-        if (i < n) out[i] = run;
-        run += c[x];
-    }
-}
-
 // ---- survivors of the sorted records: the first of every (k-mer, target) run
 constexpr int IK_TILE = 2048, IK_NT = 256;
 __device__ __forceinline__ bool ikKept(const uint32_t *__restrict__ keys, const uint64_t *__restrict__ vals, uint64_t i) {
@@ -841,36 +782,43 @@ __global__ void __launch_bounds__(256) ib_offsets(const uint64_t *__restrict__ s
     offsets[i] = (uint32_t) (start[i] - b);
 }
 
-template <typename T>
-struct Scoped {   // device allocation released at scope exit
-    T *p = nullptr;
-    ~Scoped() { if (p) (void) hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void **) &p, std::max<size_t>(n, 1) * sizeof(T)); }
-    void release() { if (p) (void) hipFree(p); p = nullptr; }
-};
-
-int scan32to64(sd_ctx *ctx, const uint32_t *in, uint64_t n, uint64_t *out, uint64_t *dTotal) {
-    const uint64_t nTiles = (n + IS_TILE - 1) / IS_TILE;
-    Scoped<uint64_t> tile;
-    SD_HIP(ctx, tile.alloc(nTiles));
-    hipLaunchKernelGGL(is_tile_sums, dim3((unsigned) nTiles), dim3(IS_NT), 0, ctx->stream, in, n, tile.p);
-    hipLaunchKernelGGL(is_tile_bases, dim3(1), dim3(1024), 0, ctx->stream, tile.p, nTiles, dTotal);
-    hipLaunchKernelGGL(is_apply, dim3((unsigned) nTiles), dim3(IS_NT), 0, ctx->stream, in, n, (const uint64_t *) tile.p, out);
-    SD_HIP(ctx, hipGetLastError());
-    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SD_OK;
-}
-
 double firstRepeatOffsetProb(double probMult, int maxRepeatOffset) {
     if (probMult < 1 || probMult > 1) return (1 - probMult) / (1 - std::pow(probMult, maxRepeatOffset));
     return 1.0 / maxRepeatOffset;
 }
 
+// The environment knobs of a build, read once per call (not once per process: the tests flip them between builds).
+//   knob                   what it is for                                           default                   clamp
+//   SD_INDEX_PASS          records per sort pass (tests: many small passes)         2^30                      >= 1; ibPassCap raises it to
+//                                                                                                             the fullest histogram range
+//   SD_INDEX_WIDE          set to anything: list starts in the wide form (tests)    wide from 2^32 entries    --
+//   SD_INDEX_MASK_BUDGET   bytes of tantan's scratch between its two passes (tests) an eighth of the device   <= half of the free memory,
+//                                                                                                             >= one row per wavefront
+//   SD_INDEX_PROFILE_GRID  wavefronts of the profile generator's wide tier, 1 MiB   IP_GRID (1 024)           64 .. 16 384
+//                          of list scratch each (tools/bench_target_profile.py)
+struct IndexKnobs {
+    uint64_t passCap = 1ull << 30;
+    bool wide = false;
+    bool haveMaskBudget = false;
+    uint64_t maskBudget = 0;
+    uint64_t profileGrid = IP_GRID;
+    IndexKnobs() {
+        if (const char *s = getenv("SD_INDEX_PASS")) passCap = std::max<uint64_t>(1, strtoull(s, nullptr, 10));
+        wide = getenv("SD_INDEX_WIDE") != nullptr;
+        if (const char *s = getenv("SD_INDEX_MASK_BUDGET")) {
+            haveMaskBudget = true;
+            maskBudget = strtoull(s, nullptr, 10);
+        }
+        if (const char *s = getenv("SD_INDEX_PROFILE_GRID")) profileGrid = std::min<uint64_t>(std::max<uint64_t>(64, strtoull(s, nullptr, 10)), 16384);
+    }
+};
+
 // sd_target_build_peak: the free device memory is read where a phase holds the most
 struct PeakNote {
-    sd_target *t;
+    sd_target *t = nullptr;
     size_t freeAtStart = 0;
-    explicit PeakNote(sd_target *target) : t(target) {
+    void begin(sd_target *target) {
+        t = target;
         size_t totalDev = 0;
         (void) hipMemGetInfo(&freeAtStart, &totalDev);
     }
@@ -880,46 +828,142 @@ struct PeakNote {
     }
 };
 
-// records per pass: bounded by the sort's 32-bit item count and by SD_INDEX_PASS (tests: many small passes)
-int ibPassCap(sd_ctx *ctx, const std::vector<unsigned long long> &coarse, uint64_t &cap, uint64_t &nRecords) {
+// The masking phase of sd_target_build: the residues go to the device and, tantan-masked (ib_mask_kernel) or as they are, into
+// t->dMasked.  The sequences are dealt to the wavefronts by length; the forward posteriors and rescaling factors between the kernel's
+// two passes take 64 lanes x (4 + 8 / 16) bytes per row of a wavefront, four to five times the residue bytes of the whole DB -- so the
+// wavefronts run in slices against a scratch budget (IndexKnobs; never less than the longest wavefront needs).
+int ibMaskPhase(sd_ctx *ctx, sd_target *t, const IndexKnobs &knobs, const uint8_t *residues, const uint64_t *seqOffsets, uint32_t nSeq, int mask,
+                double maskProb, const double *maskRatios, const PeakNote &notePeak, uint64_t &nMaskedResidues) {
+    const uint64_t total = seqOffsets[nSeq];
+    nMaskedResidues = 0;
+    DevBuf<uint8_t> dRes;
+    SD_HIP(ctx, dRes.alloc(total + 64));
+    SD_HIP(ctx, hipMemcpy(dRes.p, residues, total, hipMemcpyDefault));
+    if (!mask || nSeq == 0) {
+        SD_HIP(ctx, hipMemcpyAsync(t->dMasked, dRes.p, total, hipMemcpyDeviceToDevice, ctx->stream));
+        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return SD_OK;
+    }
+    TantanPar par;
+    const double repeatProb = 0.005, repeatEndProb = 0.05, decay = 0.9;
+    par.b2b = 1 - repeatProb;
+    par.f2b = repeatEndProb;
+    par.f2f0 = 1 - repeatEndProb;
+    double p = repeatProb * firstRepeatOffsetProb(decay, TT_OFF);
+    for (int i = 0; i < TT_OFF; i++) {
+        par.b2f[i] = p;
+        p *= decay;
+    }
+    SD_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_tt), &par, sizeof(par)));
+    // sequences dealt to the wavefronts by length (counting sort, stable)
+    auto len = [&](uint32_t i) { return seqOffsets[i + 1] - seqOffsets[i]; };
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < nSeq; i++) longest = std::max(longest, len(i));
+    std::vector<uint32_t> order(nSeq);
+    {
+        std::vector<uint32_t> cnt((size_t) longest + 2, 0);
+        for (uint32_t i = 0; i < nSeq; i++) cnt[(size_t) len(i) + 1]++;
+        for (size_t l = 1; l < cnt.size(); l++) cnt[l] += cnt[l - 1];
+        for (uint32_t i = 0; i < nSeq; i++) order[cnt[(size_t) len(i)]++] = i;
+    }
+    // rows of the scratch per wavefront: its longest (= last) sequence rounded up to the rescaling period
+    const uint32_t nWaves = (nSeq + 63) / 64;
+    std::vector<uint64_t> waveRow((size_t) nWaves + 1, 0);
+    for (uint32_t w = 0; w < nWaves; w++) {
+        const uint64_t last = len(order[std::min<uint64_t>((uint64_t) w * 64 + 63, nSeq - 1)]);
+        waveRow[w + 1] = waveRow[w] + ((last + TT_SCALE - 1) / TT_SCALE) * TT_SCALE;
+    }
+    // slices of wavefronts whose rows fit the budget (a wavefront beyond it runs alone)
+    size_t freeB = 0, totalB = 0;
+    (void) hipMemGetInfo(&freeB, &totalB);
+    const uint64_t budget = std::min<uint64_t>(knobs.haveMaskBudget ? knobs.maskBudget : (uint64_t) totalB / 8, (uint64_t) freeB / 2);
+    const uint64_t budgetRows = std::max<uint64_t>(budget / (64 * (sizeof(float) + sizeof(double) / TT_SCALE + 1)), 1);
+    std::vector<uint32_t> sliceEnd;
+    uint64_t sliceRows = 0;   // the largest slice
+    for (uint32_t w0 = 0; w0 < nWaves;) {
+        uint32_t w1 = w0 + 1;
+        while (w1 < nWaves && waveRow[w1 + 1] - waveRow[w0] <= budgetRows) w1++;
+        sliceRows = std::max(sliceRows, waveRow[w1] - waveRow[w0]);
+        sliceEnd.push_back(w1);
+        w0 = w1;
+    }
+    DevBuf<uint32_t> dOrder;
+    DevBuf<uint64_t> dWaveRow;
+    DevBuf<float> dProb;
+    DevBuf<double> dScale, dLr;
+    DevBuf<unsigned long long> dN;
+    SD_HIP(ctx, dOrder.alloc(nSeq));
+    SD_HIP(ctx, dWaveRow.alloc(nWaves + 1));
+    SD_HIP(ctx, dProb.alloc(std::max<uint64_t>(sliceRows * 64, 1)));   // (no row at all when every sequence is empty)
+    SD_HIP(ctx, dScale.alloc(sliceRows / TT_SCALE * 64 + 64));
+    SD_HIP(ctx, dLr.alloc(IB_ALPH * IB_ALPH));
+    SD_HIP(ctx, dN.alloc(1));
+    notePeak();
+    SD_HIP(ctx, hipMemcpy(dOrder.p, order.data(), (size_t) nSeq * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SD_HIP(ctx, hipMemcpy(dWaveRow.p, waveRow.data(), ((size_t) nWaves + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    SD_HIP(ctx, hipMemcpy(dLr.p, maskRatios, IB_ALPH * IB_ALPH * sizeof(double), hipMemcpyHostToDevice));
+    SD_HIP(ctx, hipMemsetAsync(dN.p, 0, sizeof(unsigned long long), ctx->stream));
+    uint32_t w0 = 0;
+    for (uint32_t w1 : sliceEnd) {   // one after the other on the stream: they share the scratch
+        ProfScope ps(ctx, "index_mask");
+        hipLaunchKernelGGL(ib_mask_kernel, dim3(w1 - w0), dim3(64), 0, ctx->stream, (const uint8_t *) dRes.p, (const uint64_t *) t->dSeqOff,
+                           (const uint32_t *) dOrder.p, nSeq, (const double *) dLr.p, (const uint64_t *) dWaveRow.p, dProb.p, dScale.p, maskProb,
+                           t->dMasked, dN.p, w0);
+        w0 = w1;
+    }
+    SD_HIP(ctx, hipGetLastError());
+    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long h = 0;
+    SD_HIP(ctx, hipMemcpy(&h, dN.p, sizeof(h), hipMemcpyDeviceToHost));
+    nMaskedResidues = h;
+    return SD_OK;
+}
+
+// records per pass: bounded by the sort's 32-bit item count and by SD_INDEX_PASS
+int ibPassCap(sd_ctx *ctx, const IndexKnobs &knobs, const std::vector<unsigned long long> &coarse, uint64_t &cap, uint64_t &nRecords) {
     uint64_t biggestBin = 0;
     nRecords = 0;
     for (unsigned long long c : coarse) {
         nRecords += c;
         biggestBin = std::max<uint64_t>(biggestBin, c);
     }
-    cap = 1ull << 30;
-    if (getenv("SD_INDEX_PASS")) cap = std::max<uint64_t>(1, strtoull(getenv("SD_INDEX_PASS"), nullptr, 10));
-    cap = std::max(cap, biggestBin);
+    cap = std::max(knobs.passCap, biggestBin);
     if (cap >= (1ull << 31))
         return sdFail(ctx, SD_EUNSUPPORTED, "one of the %u k-mer ranges holds %llu index records (limit 2^31 per sort)", IB_COARSE_BINS,
                       (unsigned long long) biggestBin);
     return SD_OK;
 }
 
-// The passes both builders share: the k-mer space is cut into ranges of at most `cap` records along the coarse histogram; per range
+// exclusive 64-bit scan of n 32-bit counts and of one element more, which the caller keeps at zero: out[n] is the total
+hipError_t ibScan(sd_ctx *ctx, const uint32_t *in, uint64_t n, uint64_t *out, uint64_t *tmp) {
+    return sdScanLaunch<uint32_t, ScanSum64, false, uint64_t>(ctx->stream, in, out, n + 1, tmp);
+}
+
+// The passes the builders share: the k-mer space is cut into ranges of at most `cap` records along the coarse histogram; per range
 // countFn(lo, hi, slotCount) counts the records of [lo, hi) per slot (a slot: what one wavefront of the generator writes in order -- 16
-// sequences in sd_target_build, one profile window in sd_target_build_profile), emitFn(lo, hi, slotBase, keys, vals) writes them at the
-// scanned bases, in ascending (target, position) order over the whole pass; they are sorted by k-mer (stable), the first record of every
-// (k-mer, target) run is appended to t->dEntries and counted in t->dOffsets.  The scratch is bounded by cap, not by nRecords.
+// sequences in sd_target_build, one window in the other two), emitFn(lo, hi, slotBase, keys, vals) writes them at the scanned bases, in
+// ascending (target, position) order over the whole pass; they are sorted by k-mer (stable), the first record of every (k-mer, target)
+// run is appended to t->dEntries and counted in t->dOffsets.  The scratch is bounded by cap, not by nRecords.
 template <typename CountFn, typename EmitFn>
 int ibPasses(sd_ctx *ctx, sd_target *t, const char *who, const std::vector<unsigned long long> &coarse, uint32_t binWidth, uint64_t nRecords,
              uint64_t cap, uint32_t nSlots, CountFn countFn, EmitFn emitFn, const PeakNote &notePeak, uint64_t &nEntries, uint64_t &nPasses) {
-    const uint64_t bufN = std::min<uint64_t>(cap, nRecords);
-    Scoped<uint32_t> k0, k1, dWaveCount, dTileCount;
-    Scoped<uint64_t> v0, v1, dWaveBase, dTileBase, dTot;
-    Scoped<uint8_t> dTmp;
+    const uint64_t bufN = std::min<uint64_t>(cap, nRecords);   // (>= 1: the caller has records)
+    const uint64_t maxTiles = (bufN + IK_TILE - 1) / IK_TILE;
+    DevBuf<uint32_t> k0, k1, dSlotCount, dTileCount;
+    DevBuf<uint64_t> v0, v1, dSlotBase, dTileBase;
+    DevBuf<uint8_t> dSortTmp, dScanTmp;
     SD_HIP(ctx, k0.alloc(bufN));
     SD_HIP(ctx, k1.alloc(bufN));
     SD_HIP(ctx, v0.alloc(bufN));
     SD_HIP(ctx, v1.alloc(bufN));
-    SD_HIP(ctx, dWaveCount.alloc(nSlots));
-    SD_HIP(ctx, dWaveBase.alloc(nSlots));
-    SD_HIP(ctx, dTileCount.alloc((bufN + IK_TILE - 1) / IK_TILE));
-    SD_HIP(ctx, dTileBase.alloc((bufN + IK_TILE - 1) / IK_TILE));
-    SD_HIP(ctx, dTot.alloc(1));
-    SD_HIP(ctx, dTmp.alloc(sdRadixSortCountsBytes()));   // the radix sort's count matrix (sd_scan_sort.h)
+    SD_HIP(ctx, dSlotCount.alloc((size_t) nSlots + 1));   // one more than the generators write: it stays zero, its scanned value is the total
+    SD_HIP(ctx, dSlotBase.alloc((size_t) nSlots + 1));
+    SD_HIP(ctx, dTileCount.alloc(maxTiles + 1));
+    SD_HIP(ctx, dTileBase.alloc(maxTiles + 1));
+    SD_HIP(ctx, dSortTmp.alloc(sdRadixSortCountsBytes()));   // the radix sort's count matrix (sd_scan_sort.h)
+    SD_HIP(ctx, dScanTmp.alloc(sdScanTmpBytes(std::max<uint64_t>(nSlots, maxTiles) + 1)));
     notePeak();
+    SD_HIP(ctx, hipMemsetAsync(dSlotCount.p + nSlots, 0, sizeof(uint32_t), ctx->stream));
     uint32_t bin = 0;
     while (bin < IB_COARSE_BINS) {
         uint32_t e = bin;
@@ -931,16 +975,16 @@ int ibPasses(sd_ctx *ctx, sd_target *t, const char *who, const std::vector<unsig
         if (n == 0) continue;
         nPasses++;
         ProfScope ps(ctx, "index_pass");
-        int rc = countFn(lo, hi, dWaveCount.p);
+        int rc = countFn(lo, hi, dSlotCount.p);
         if (rc != SD_OK) return rc;
         SD_HIP(ctx, hipGetLastError());
-        rc = scan32to64(ctx, dWaveCount.p, nSlots, dWaveBase.p, dTot.p);
-        if (rc != SD_OK) return rc;
+        SD_HIP(ctx, ibScan(ctx, dSlotCount.p, nSlots, dSlotBase.p, (uint64_t *) dScanTmp.p));
+        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
         uint64_t got = 0;
-        SD_HIP(ctx, hipMemcpy(&got, dTot.p, sizeof(got), hipMemcpyDeviceToHost));
+        SD_HIP(ctx, hipMemcpy(&got, dSlotBase.p + nSlots, sizeof(got), hipMemcpyDeviceToHost));
         if (got != n) return sdFail(ctx, SD_EHIP, "%s: k-mer range [%u, %u) holds %llu records, the histogram said %llu", who, lo, hi,
                                     (unsigned long long) got, (unsigned long long) n);
-        rc = emitFn(lo, hi, (const uint64_t *) dWaveBase.p, k0.p, v0.p);
+        rc = emitFn(lo, hi, (const uint64_t *) dSlotBase.p, k0.p, v0.p);
         if (rc != SD_OK) return rc;
         SD_HIP(ctx, hipGetLastError());
         int bits = 1;
@@ -952,21 +996,22 @@ int ibPasses(sd_ctx *ctx, sd_target *t, const char *who, const std::vector<unsig
         const uint32_t *sk;
         const uint64_t *sv;
         if (passes & 1) {
-            SD_HIP(ctx, sdRadixSortPairs<uint64_t>(ctx->stream, k0.p, v0.p, k1.p, v1.p, k0.p, v0.p, (uint32_t) n, 0, bits, (uint32_t *) dTmp.p));
+            SD_HIP(ctx, sdRadixSortPairs<uint64_t>(ctx->stream, k0.p, v0.p, k1.p, v1.p, k0.p, v0.p, (uint32_t) n, 0, bits, (uint32_t *) dSortTmp.p));
             sk = k1.p;
             sv = v1.p;
         } else {
-            SD_HIP(ctx, sdRadixSortPairs<uint64_t>(ctx->stream, k0.p, v0.p, k0.p, v0.p, k1.p, v1.p, (uint32_t) n, 0, bits, (uint32_t *) dTmp.p));
+            SD_HIP(ctx, sdRadixSortPairs<uint64_t>(ctx->stream, k0.p, v0.p, k0.p, v0.p, k1.p, v1.p, (uint32_t) n, 0, bits, (uint32_t *) dSortTmp.p));
             sk = k0.p;
             sv = v0.p;
         }
         const unsigned tiles = (unsigned) ((n + IK_TILE - 1) / IK_TILE);
         hipLaunchKernelGGL(ib_keep_count, dim3(tiles), dim3(IK_NT), 0, ctx->stream, sk, sv, n, dTileCount.p);
         SD_HIP(ctx, hipGetLastError());
-        rc = scan32to64(ctx, dTileCount.p, tiles, dTileBase.p, dTot.p);
-        if (rc != SD_OK) return rc;
+        SD_HIP(ctx, hipMemsetAsync(dTileCount.p + tiles, 0, sizeof(uint32_t), ctx->stream));   // (a longer pass left its last count there)
+        SD_HIP(ctx, ibScan(ctx, dTileCount.p, tiles, dTileBase.p, (uint64_t *) dScanTmp.p));
+        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
         uint64_t kept = 0;
-        SD_HIP(ctx, hipMemcpy(&kept, dTot.p, sizeof(kept), hipMemcpyDeviceToHost));
+        SD_HIP(ctx, hipMemcpy(&kept, dTileBase.p + tiles, sizeof(kept), hipMemcpyDeviceToHost));
         hipLaunchKernelGGL(ib_place, dim3(tiles), dim3(IK_NT), 0, ctx->stream, sk, sv, n, (const uint64_t *) dTileBase.p, nEntries, lo,
                            t->dEntries, t->dOffsets);
         SD_HIP(ctx, hipGetLastError());
@@ -976,19 +1021,20 @@ int ibPasses(sd_ctx *ctx, sd_target *t, const char *who, const std::vector<unsig
     return SD_OK;
 }
 
-// list starts from the per-k-mer counts the passes left in t->dOffsets
-int ibListStarts(sd_ctx *ctx, sd_target *t, const char *who, uint64_t nEntries, const PeakNote &notePeak) {
-    Scoped<uint64_t> dStart, dTot;
+// list starts from the per-k-mer counts the passes left in t->dOffsets (tableSize of them and a zero: the scan's total)
+int ibListStarts(sd_ctx *ctx, sd_target *t, const char *who, uint64_t nEntries, bool forceWide, const PeakNote &notePeak) {
+    DevBuf<uint64_t> dStart;
+    DevBuf<uint8_t> dScanTmp;
     SD_HIP(ctx, dStart.alloc(t->tableSize + 1));
-    SD_HIP(ctx, dTot.alloc(1));
+    SD_HIP(ctx, dScanTmp.alloc(sdScanTmpBytes(t->tableSize + 1)));
     notePeak();
-    int rc = scan32to64(ctx, t->dOffsets, t->tableSize + 1, dStart.p, dTot.p);
-    if (rc != SD_OK) return rc;
+    SD_HIP(ctx, ibScan(ctx, t->dOffsets, t->tableSize, dStart.p, (uint64_t *) dScanTmp.p));
+    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t sum = 0;
-    SD_HIP(ctx, hipMemcpy(&sum, dTot.p, sizeof(sum), hipMemcpyDeviceToHost));
+    SD_HIP(ctx, hipMemcpy(&sum, dStart.p + t->tableSize, sizeof(sum), hipMemcpyDeviceToHost));
     if (sum != nEntries) return sdFail(ctx, SD_EHIP, "%s: %llu entries placed, %llu counted", who, (unsigned long long) nEntries,
                                        (unsigned long long) sum);
-    const int wide = nEntries > 0xFFFFFFFFull || getenv("SD_INDEX_WIDE") != nullptr;
+    const int wide = nEntries > 0xFFFFFFFFull || forceWide;
     if (wide) SD_HIP(ctx, hipMalloc((void **) &t->dBlockBase, (((t->tableSize + 2) >> 16) + 1) * sizeof(uint64_t)));
     if (wide) SD_HIP(ctx, hipMemsetAsync(t->dBlockBase, 0, (((t->tableSize + 2) >> 16) + 1) * sizeof(uint64_t), ctx->stream));
     hipLaunchKernelGGL(ib_offsets, dim3((unsigned) ((t->tableSize + 1 + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *) dStart.p,
@@ -997,6 +1043,153 @@ int ibListStarts(sd_ctx *ctx, sd_target *t, const char *who, uint64_t nEntries, 
     SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SD_OK;
 }
+
+template <int MODE>
+using IbMode = std::integral_constant<int, MODE>;
+
+// what a builder says in its own words
+struct IbWords {
+    const char *who;           // the exported function
+    const char *unit;          // what the length of a target counts
+    const char *window;        // the kind of its windows (windowed builders)
+    const char *histScope;     // profiling scope of the generator's mode 0
+    const char *listTooLong;   // a window whose list the reference would cut: format of (target, position, IP_LIST_MAX)
+};
+
+// The frame of the three builders.  open() checks the lengths, creates the target (destroyed again unless finish() hands it over) and
+// uploads the offsets -- for a windowed builder (span > 0: one generator slot per window of `span` positions) the window prefix as
+// well; a builder then uploads what is its own and calls passes() with its generator
+//     gen(IbMode<M>(), lo, hi, slotCount, slotBase, keys, vals) -> SD_* code
+// which launches its records kernel(s) in mode M on ctx->stream with dCoarse.p, dErr.p and binWidth of the frame (mode 0 counts
+// every record into dCoarse, and a windowed generator leaves the first window it refuses in dErr[0]; dErr[1] is the generator's
+// own); finish() makes the list starts and fills the statistics.
+struct IndexBuild {
+    sd_ctx *const ctx;
+    const IbWords words;
+    const IndexKnobs knobs;
+    sd_target *t = nullptr;
+    PeakNote notePeak;
+    std::vector<uint64_t> winBase;   // windowed builders: the first window of every target, nSeq + 1
+    uint64_t nWin = 0;
+    uint32_t binWidth = 0;
+    DevBuf<uint64_t> dWinBase;
+    DevBuf<unsigned long long> dCoarse, dErr;   // mode 0 only: released once the histogram is on the host
+    DevBuf<uint32_t> dMode0Count;               // the per-slot counts of mode 0, where a generator leaves them
+    uint64_t nRecords = 0, nEntries = 0, nPasses = 0;
+
+    IndexBuild(sd_ctx *c, const IbWords &w) : ctx(c), words(w) {}
+    ~IndexBuild() { if (t) sd_target_destroy(t); }
+    IndexBuild(const IndexBuild &) = delete;
+
+    template <typename T>
+    static hipError_t up(T *&d, const void *h, size_t bytes) {
+        hipError_t e = hipMalloc((void **) &d, bytes + 64);
+        if (e != hipSuccess) return e;
+        return hipMemcpy(d, h, bytes, hipMemcpyDefault);
+    }
+
+    int open(int k, uint64_t tableSize, const uint64_t *offsets, uint32_t nSeq, int span) {
+        if (span) winBase.assign((size_t) nSeq + 1, 0);
+        for (uint32_t i = 0; i < nSeq; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (len > 65535)
+                return sdFail(ctx, SD_EINVAL, "target %u has %llu %s; index positions are 16 bit (limit 65535, --max-seq-len)", i,
+                              (unsigned long long) len, words.unit);
+            if (span) winBase[i + 1] = winBase[i] + (len >= (uint64_t) span ? len - span + 1 : 0);
+        }
+        if (span) nWin = winBase[nSeq];
+        if (nWin >= 0xFFFFFFFFull)
+            return sdFail(ctx, SD_EUNSUPPORTED, "%llu %s windows (limit 2^32 per target)", (unsigned long long) nWin, words.window);
+        (void) hipSetDevice(ctx->device);
+        t = new sd_target();
+        t->ctx = ctx;
+        t->k = k;
+        t->nSeq = nSeq;
+        t->tableSize = tableSize;
+        t->hSeqOff.assign(offsets, offsets + nSeq + 1);
+        binWidth = (uint32_t) ((tableSize + IB_COARSE_BINS - 1) / IB_COARSE_BINS);
+        notePeak.begin(t);
+        SD_HIP(ctx, up(t->dSeqOff, offsets, ((size_t) nSeq + 1) * sizeof(uint64_t)));
+        if (span) {
+            SD_HIP(ctx, up(dWinBase.p, winBase.data(), winBase.size() * sizeof(uint64_t)));
+            const unsigned long long errInit[2] = {~0ull, 0ull};
+            SD_HIP(ctx, dErr.alloc(2));
+            SD_HIP(ctx, hipMemcpy(dErr.p, errInit, sizeof(errInit), hipMemcpyHostToDevice));
+        }
+        return SD_OK;
+    }
+
+    // mode0Counts: the generator's mode 0 leaves the records of every slot in slotCount, so a single pass over the whole k-mer space
+    // takes its counts from there instead of running mode 1
+    template <typename Gen>
+    int passes(uint32_t nSlots, bool mode0Counts, Gen gen) {
+        std::vector<unsigned long long> coarse(IB_COARSE_BINS, 0);
+        if (nSlots) {
+            SD_HIP(ctx, dCoarse.alloc(IB_COARSE_BINS));
+            SD_HIP(ctx, hipMemsetAsync(dCoarse.p, 0, IB_COARSE_BINS * sizeof(unsigned long long), ctx->stream));
+            if (mode0Counts) {
+                SD_HIP(ctx, dMode0Count.alloc(nSlots));
+                SD_HIP(ctx, hipMemsetAsync(dMode0Count.p, 0, (size_t) nSlots * sizeof(uint32_t), ctx->stream));
+            }
+            {
+                ProfScope ps(ctx, words.histScope);
+                if (int rc = gen(IbMode<0>(), 0u, 0u, dMode0Count.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr)) return rc;
+            }
+            SD_HIP(ctx, hipGetLastError());
+            SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (dErr.p) {
+                unsigned long long first = ~0ull;
+                SD_HIP(ctx, hipMemcpy(&first, dErr.p, sizeof(first), hipMemcpyDeviceToHost));
+                if (first != ~0ull) {
+                    const uint32_t q = (uint32_t) (std::upper_bound(winBase.begin(), winBase.end(), (uint64_t) first) - winBase.begin() - 1);
+                    return sdFail(ctx, SD_EUNSUPPORTED, words.listTooLong, q, (unsigned long long) (first - winBase[q]), IP_LIST_MAX);
+                }
+            }
+            SD_HIP(ctx, hipMemcpy(coarse.data(), dCoarse.p, IB_COARSE_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            dCoarse.release();
+            dErr.release();
+        }
+        uint64_t cap = 0;
+        if (int rc = ibPassCap(ctx, knobs, coarse, cap, nRecords)) return rc;
+        // the entry array is sized by the counted records (the dedupe only ever removes): one per residue at most in sd_target_build,
+        // hundreds per position in the other two
+        if (hipMalloc((void **) &t->dEntries, (std::max<uint64_t>(nRecords, 1) + 8) * sizeof(uint2)) != hipSuccess) {
+            t->dEntries = nullptr;
+            (void) hipGetLastError();
+            return sdFail(ctx, SD_ENOMEM, "%s: the entry array of %llu index records (%llu bytes) does not fit the device memory; a higher "
+                          "--k-score (fewer k-mers per target) or a smaller target database is the way out", words.who,
+                          (unsigned long long) nRecords, (unsigned long long) ((std::max<uint64_t>(nRecords, 1) + 8) * sizeof(uint2)));
+        }
+        SD_HIP(ctx, hipMalloc((void **) &t->dOffsets, (t->tableSize + 1) * sizeof(uint32_t) + 64));
+        SD_HIP(ctx, hipMemsetAsync(t->dOffsets, 0, (t->tableSize + 1) * sizeof(uint32_t), ctx->stream));   // counts first
+        if (!nRecords) return SD_OK;
+        auto countFn = [&](uint32_t lo, uint32_t hi, uint32_t *slotCount) -> int {
+            if (mode0Counts && lo == 0 && hi >= t->tableSize) {   // one pass holds every record: reuse the histogram's counts
+                SD_HIP(ctx, hipMemcpyAsync(slotCount, dMode0Count.p, (size_t) nSlots * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+                return SD_OK;
+            }
+            return gen(IbMode<1>(), lo, hi, slotCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
+        };
+        auto emitFn = [&](uint32_t lo, uint32_t hi, const uint64_t *slotBase, uint32_t *keys, uint64_t *vals) -> int {
+            return gen(IbMode<2>(), lo, hi, (uint32_t *) nullptr, slotBase, keys, vals);
+        };
+        return ibPasses(ctx, t, words.who, coarse, binWidth, nRecords, cap, nSlots, countFn, emitFn, notePeak, nEntries, nPasses);
+    }
+
+    int finish(uint64_t nMaskedResidues, sd_target **out, uint64_t *stats) {
+        if (int rc = ibListStarts(ctx, t, words.who, nEntries, knobs.wide, notePeak)) return rc;
+        t->nEntries = nEntries;
+        if (stats) {
+            stats[0] = nEntries;
+            stats[1] = nMaskedResidues;
+            stats[2] = nPasses;
+            stats[3] = nRecords;
+        }
+        *out = t;
+        t = nullptr;
+        return SD_OK;
+    }
+};
 
 }  // namespace
 
@@ -1007,31 +1200,13 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
     if (!ctx || !out || !residues || !seqOffsets || !maskRatios || !selfScore || !ext3Score || !ext3Index) return SD_EINVAL;
     if (kmerSize != 6 && kmerSize != 7) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the device implements k=6 and k=7", kmerSize);
     if (kmerSize == 7 && (!ext2Score || !ext2Index)) return sdFail(ctx, SD_EINVAL, "k=7 needs the 2-mer score matrix");
-    uint32_t longest = 0;
-    for (uint32_t i = 0; i < nSeq; i++) {
-        const uint64_t len = seqOffsets[i + 1] - seqOffsets[i];
-        if (len > 65535)
-            return sdFail(ctx, SD_EINVAL, "target %u has %llu residues; index positions are 16 bit (limit 65535, --max-seq-len)", i,
-                          (unsigned long long) len);
-        longest = std::max<uint32_t>(longest, (uint32_t) len);
-    }
     // the kernels read their tables (seed positions, powers, tantan constants) from __constant__ memory: one build at a time
     static std::mutex buildMutex;
     std::lock_guard<std::mutex> buildLock(buildMutex);
-    (void) hipSetDevice(ctx->device);
-    sd_target *t = new sd_target();
-    struct Guard {
-        sd_target *t;
-        ~Guard() { if (t) sd_target_destroy(t); }
-    } guard{t};
-    t->ctx = ctx;
-    t->k = kmerSize;
-    t->nSeq = nSeq;
-    t->tableSize = kmerSize == 6 ? 64000000ull : 1280000000ull;
-    t->hSeqOff.assign(seqOffsets, seqOffsets + nSeq + 1);
-    const uint64_t total = seqOffsets[nSeq];
+    IndexBuild b(ctx, {"sd_target_build", "residues", nullptr, "index_kmer_histogram", nullptr});
+    if (int rc = b.open(kmerSize, kmerSize == 6 ? 64000000ull : 1280000000ull, seqOffsets, nSeq, 0)) return rc;
+    sd_target *t = b.t;
     const int span = kmerSize == 6 ? 10 : 11;
-    const PeakNote notePeak(t);
     {
         static const uint8_t s6[8] = {0, 1, 3, 5, 8, 9, 0, 0}, s7[8] = {0, 1, 3, 5, 6, 9, 10, 0};
         uint32_t pw[8] = {0};
@@ -1046,182 +1221,27 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
         SD_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_ibPow), pw, sizeof(pw)));
         SD_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_ibSelf), self, sizeof(self)));
     }
-    auto up = [&](void **d, const void *h, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes + 64);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*d, h, bytes, hipMemcpyDefault);
-    };
-    SD_HIP(ctx, up((void **) &t->dSeqOff, seqOffsets, (nSeq + 1) * sizeof(uint64_t)));
-    SD_HIP(ctx, up((void **) &t->dExt3Score, ext3Score, (size_t) 8000 * 8000 * sizeof(int16_t)));
-    SD_HIP(ctx, up((void **) &t->dExt3Index, ext3Index, (size_t) 8000 * 8000 * sizeof(uint16_t)));
-    {
-        const int rcCum = sdBuildExt3Cum(ctx, t);
-        if (rcCum != SD_OK) return rcCum;
-    }
+    SD_HIP(ctx, b.up(t->dExt3Score, ext3Score, (size_t) 8000 * 8000 * sizeof(int16_t)));
+    SD_HIP(ctx, b.up(t->dExt3Index, ext3Index, (size_t) 8000 * 8000 * sizeof(uint16_t)));
+    if (int rc = sdBuildExt3Cum(ctx, t)) return rc;
     if (ext2Score && ext2Index) {
-        SD_HIP(ctx, up((void **) &t->dExt2Score, ext2Score, (size_t) 400 * 400 * sizeof(int16_t)));
-        SD_HIP(ctx, up((void **) &t->dExt2Index, ext2Index, (size_t) 400 * 400 * sizeof(uint16_t)));
+        SD_HIP(ctx, b.up(t->dExt2Score, ext2Score, (size_t) 400 * 400 * sizeof(int16_t)));
+        SD_HIP(ctx, b.up(t->dExt2Index, ext2Index, (size_t) 400 * 400 * sizeof(uint16_t)));
     }
-    SD_HIP(ctx, hipMalloc((void **) &t->dMasked, std::max<uint64_t>(total, 1) + 64));
-
-    // ---------------- 1. masking
+    SD_HIP(ctx, hipMalloc((void **) &t->dMasked, std::max<uint64_t>(seqOffsets[nSeq], 1) + 64));
     uint64_t nMaskedResidues = 0;
-    {
-        Scoped<uint8_t> dRes;
-        SD_HIP(ctx, dRes.alloc(total + 64));
-        SD_HIP(ctx, hipMemcpy(dRes.p, residues, total, hipMemcpyDefault));
-        if (!mask || nSeq == 0) {
-            SD_HIP(ctx, hipMemcpyAsync(t->dMasked, dRes.p, total, hipMemcpyDeviceToDevice, ctx->stream));
-            SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        } else {
-            TantanPar par;
-            const double repeatProb = 0.005, repeatEndProb = 0.05, decay = 0.9;
-            par.b2b = 1 - repeatProb;
-            par.f2b = repeatEndProb;
-            par.f2f0 = 1 - repeatEndProb;
-            double p = repeatProb * firstRepeatOffsetProb(decay, TT_OFF);
-            for (int i = 0; i < TT_OFF; i++) {
-                par.b2f[i] = p;
-                p *= decay;
-            }
-            SD_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_tt), &par, sizeof(par)));
-            // sequences dealt to the wavefronts by length (counting sort, stable)
-            std::vector<uint32_t> order(nSeq);
-            {
-                std::vector<uint32_t> cnt((size_t) longest + 2, 0);
-                for (uint32_t i = 0; i < nSeq; i++) cnt[(size_t) (seqOffsets[i + 1] - seqOffsets[i]) + 1]++;
-                for (size_t l = 1; l < cnt.size(); l++) cnt[l] += cnt[l - 1];
-                for (uint32_t i = 0; i < nSeq; i++) order[cnt[(size_t) (seqOffsets[i + 1] - seqOffsets[i])]++] = i;
-            }
-            const uint32_t nWaves = (nSeq + 63) / 64;
-            std::vector<uint64_t> waveRow((size_t) nWaves + 1, 0);
-            for (uint32_t w = 0; w < nWaves; w++) {
-                const uint32_t lastSeq = order[std::min<uint64_t>((uint64_t) w * 64 + 63, nSeq - 1)];
-                const uint64_t len = seqOffsets[lastSeq + 1] - seqOffsets[lastSeq];
-                waveRow[w + 1] = waveRow[w] + ((len + TT_SCALE - 1) / TT_SCALE) * TT_SCALE;
-            }
-            Scoped<uint32_t> dOrder;
-            Scoped<uint64_t> dWaveRow;
-            Scoped<float> dProb;
-            Scoped<double> dScale, dLr;
-            Scoped<unsigned long long> dN;
-            // the forward posteriors and rescaling factors between the passes: 64 lanes x (4 + 8 / 16) bytes per row of a wavefront,
-            // four to five times the residue bytes of the whole DB -- so the wavefronts run in slices against a scratch budget (an
-            // eighth of the device memory, SD_INDEX_MASK_BUDGET bytes for the tests; never less than the longest wavefront needs)
-            uint64_t maskBudgetRows;
-            {
-                size_t freeB = 0, totalB = 0;
-                (void) hipMemGetInfo(&freeB, &totalB);
-                uint64_t budget = getenv("SD_INDEX_MASK_BUDGET") ? strtoull(getenv("SD_INDEX_MASK_BUDGET"), nullptr, 10) : (uint64_t) totalB / 8;
-                budget = std::min<uint64_t>(budget, (uint64_t) freeB / 2);
-                maskBudgetRows = std::max<uint64_t>(budget / (64 * (sizeof(float) + sizeof(double) / TT_SCALE + 1)), 1);
-            }
-            uint64_t sliceRows = 0;   // the largest slice
-            {
-                uint32_t w0 = 0;
-                while (w0 < nWaves) {
-                    uint32_t w1 = w0 + 1;
-                    while (w1 < nWaves && waveRow[w1 + 1] - waveRow[w0] <= maskBudgetRows) w1++;
-                    sliceRows = std::max(sliceRows, waveRow[w1] - waveRow[w0]);
-                    w0 = w1;
-                }
-            }
-            SD_HIP(ctx, dOrder.alloc(nSeq));
-            SD_HIP(ctx, dWaveRow.alloc(nWaves + 1));
-            SD_HIP(ctx, dProb.alloc(sliceRows * 64));
-            SD_HIP(ctx, dScale.alloc(sliceRows / TT_SCALE * 64 + 64));
-            SD_HIP(ctx, dLr.alloc(IB_ALPH * IB_ALPH));
-            SD_HIP(ctx, dN.alloc(1));
-            notePeak();
-            SD_HIP(ctx, hipMemcpy(dOrder.p, order.data(), (size_t) nSeq * sizeof(uint32_t), hipMemcpyHostToDevice));
-            SD_HIP(ctx, hipMemcpy(dWaveRow.p, waveRow.data(), ((size_t) nWaves + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-            SD_HIP(ctx, hipMemcpy(dLr.p, maskRatios, IB_ALPH * IB_ALPH * sizeof(double), hipMemcpyHostToDevice));
-            SD_HIP(ctx, hipMemsetAsync(dN.p, 0, sizeof(unsigned long long), ctx->stream));
-            for (uint32_t w0 = 0; w0 < nWaves;) {   // slices of wavefronts, one after the other on the stream (they share the scratch)
-                uint32_t w1 = w0 + 1;
-                while (w1 < nWaves && waveRow[w1 + 1] - waveRow[w0] <= maskBudgetRows) w1++;
-                ProfScope ps(ctx, "index_mask");
-                hipLaunchKernelGGL(ib_mask_kernel, dim3(w1 - w0), dim3(64), 0, ctx->stream, (const uint8_t *) dRes.p, (const uint64_t *) t->dSeqOff,
-                                   (const uint32_t *) dOrder.p, nSeq, (const double *) dLr.p, (const uint64_t *) dWaveRow.p, dProb.p, dScale.p,
-                                   maskProb, t->dMasked, dN.p, w0);
-                w0 = w1;
-            }
-            SD_HIP(ctx, hipGetLastError());
-            SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            unsigned long long h = 0;
-            SD_HIP(ctx, hipMemcpy(&h, dN.p, sizeof(h), hipMemcpyDeviceToHost));
-            nMaskedResidues = h;
-        }
-    }
-
-    // ---------------- 2. records per k-mer range, sorted; survivors appended to the entries
+    if (int rc = ibMaskPhase(ctx, t, b.knobs, residues, seqOffsets, nSeq, mask, maskProb, maskRatios, b.notePeak, nMaskedResidues)) return rc;
+    // a slot: the IB_SEQ_PER_WAVE sequences of one wavefront
     const uint32_t nWavesR = (uint32_t) (((uint64_t) nSeq + IB_SEQ_PER_WAVE - 1) / IB_SEQ_PER_WAVE);
-    const unsigned gridR = (nWavesR + 3) / 4;
-    const uint32_t binWidth = (uint32_t) ((t->tableSize + IB_COARSE_BINS - 1) / IB_COARSE_BINS);
-    std::vector<unsigned long long> coarse(IB_COARSE_BINS, 0);
-    if (nSeq) {
-        Scoped<unsigned long long> dCoarse;
-        SD_HIP(ctx, dCoarse.alloc(IB_COARSE_BINS));
-        SD_HIP(ctx, hipMemsetAsync(dCoarse.p, 0, IB_COARSE_BINS * sizeof(unsigned long long), ctx->stream));
-        {
-            ProfScope ps(ctx, "index_kmer_histogram");
-            if (kmerSize == 6)
-                hipLaunchKernelGGL((ib_records_kernel<6, 0>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
-                                   (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, dCoarse.p, 0u, 0u, (uint32_t *) nullptr,
-                                   (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-            else
-                hipLaunchKernelGGL((ib_records_kernel<7, 0>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
-                                   (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, dCoarse.p, 0u, 0u, (uint32_t *) nullptr,
-                                   (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-        }
-        SD_HIP(ctx, hipGetLastError());
-        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        SD_HIP(ctx, hipMemcpy(coarse.data(), dCoarse.p, IB_COARSE_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    }
-    uint64_t nRecords = 0, cap = 0;
-    if (int rcCap = ibPassCap(ctx, coarse, cap, nRecords)) return rcCap;
-    SD_HIP(ctx, hipMalloc((void **) &t->dEntries, (std::max<uint64_t>(nRecords, 1) + 8) * sizeof(uint2)));
-    SD_HIP(ctx, hipMalloc((void **) &t->dOffsets, (t->tableSize + 1) * sizeof(uint32_t) + 64));
-    SD_HIP(ctx, hipMemsetAsync(t->dOffsets, 0, (t->tableSize + 1) * sizeof(uint32_t), ctx->stream));   // counts first
-    uint64_t nEntries = 0, nPasses = 0;
-    if (nRecords) {
-        auto countFn = [&](uint32_t lo, uint32_t hi, uint32_t *waveCount) -> int {
-            if (kmerSize == 6)
-                hipLaunchKernelGGL((ib_records_kernel<6, 1>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
-                                   (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, (unsigned long long *) nullptr, lo, hi,
-                                   waveCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-            else
-                hipLaunchKernelGGL((ib_records_kernel<7, 1>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
-                                   (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, (unsigned long long *) nullptr, lo, hi,
-                                   waveCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-            return SD_OK;
-        };
-        auto emitFn = [&](uint32_t lo, uint32_t hi, const uint64_t *waveBase, uint32_t *keys, uint64_t *vals) -> int {
-            if (kmerSize == 6)
-                hipLaunchKernelGGL((ib_records_kernel<6, 2>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
-                                   (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, (unsigned long long *) nullptr, lo, hi,
-                                   (uint32_t *) nullptr, waveBase, keys, vals);
-            else
-                hipLaunchKernelGGL((ib_records_kernel<7, 2>), dim3(gridR), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked,
-                                   (const uint64_t *) t->dSeqOff, nSeq, span, kmerThr, binWidth, (unsigned long long *) nullptr, lo, hi,
-                                   (uint32_t *) nullptr, waveBase, keys, vals);
-            return SD_OK;
-        };
-        if (int rcP = ibPasses(ctx, t, "sd_target_build", coarse, binWidth, nRecords, cap, nWavesR, countFn, emitFn, notePeak, nEntries, nPasses))
-            return rcP;
-    }
-    // ---------------- 3. list starts
-    if (int rcL = ibListStarts(ctx, t, "sd_target_build", nEntries, notePeak)) return rcL;
-    t->nEntries = nEntries;
-    if (stats) {
-        stats[0] = nEntries;
-        stats[1] = nMaskedResidues;
-        stats[2] = nPasses;
-        stats[3] = nRecords;
-    }
-    guard.t = nullptr;
-    *out = t;
-    return SD_OK;
+    auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *waveCount, const uint64_t *waveBase, uint32_t *keys, uint64_t *vals) -> int {
+        constexpr int MODE = decltype(mode)::value;
+        const auto kernel = kmerSize == 6 ? ib_records_kernel<6, MODE> : ib_records_kernel<7, MODE>;
+        hipLaunchKernelGGL(kernel, dim3((nWavesR + 3) / 4), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked, (const uint64_t *) t->dSeqOff,
+                           nSeq, span, kmerThr, b.binWidth, b.dCoarse.p, lo, hi, waveCount, waveBase, keys, vals);
+        return SD_OK;
+    };
+    if (int rc = b.passes(nWavesR, false, generate)) return rc;
+    return b.finish(nMaskedResidues, out, stats);
 }
 
 // The index of a *profile* target DB (the profile branch of IndexBuilder::fillDatabase, IndexBuilder.cpp:61-62,94-128,200-219): the lists
@@ -1237,139 +1257,48 @@ extern "C" int sd_target_build_profile(sd_ctx *ctx, int kmerSize, int kmerThr, c
     if (kmerSize == 7)
         return sdFail(ctx, SD_EUNSUPPORTED, "k=7: the index of a profile target is built at k=6 only (no k=7 golden index of the reference to test against)");
     if (kmerSize != 6) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the index of a profile target is built at k=6", kmerSize);
-    const int span = 10;
-    std::vector<uint64_t> winBase((size_t) nSeq + 1, 0);
-    for (uint32_t i = 0; i < nSeq; i++) {
-        const uint64_t len = posOffsets[i + 1] - posOffsets[i];
-        if (len > 65535)
-            return sdFail(ctx, SD_EINVAL, "target %u has %llu positions; index positions are 16 bit (limit 65535, --max-seq-len)", i,
-                          (unsigned long long) len);
-        winBase[i + 1] = winBase[i] + (len >= (uint64_t) span ? len - span + 1 : 0);
-    }
-    const uint64_t nWin = winBase[nSeq], total = posOffsets[nSeq];
-    if (nWin >= 0xFFFFFFFFull) return sdFail(ctx, SD_EUNSUPPORTED, "%llu profile windows (limit 2^32 per target)", (unsigned long long) nWin);
-    (void) hipSetDevice(ctx->device);
-    sd_target *t = new sd_target();
-    struct Guard {
-        sd_target *t;
-        ~Guard() { if (t) sd_target_destroy(t); }
-    } guard{t};
-    t->ctx = ctx;
-    t->k = kmerSize;
-    t->nSeq = nSeq;
+    IndexBuild b(ctx, {"sd_target_build_profile", "positions", "profile", "index_profile_histogram",
+                       "target %u, position %llu: more than %u similar k-mers in one profile window (the reference's buffer ends there, "
+                       "KmerGenerator.h:45); raise the k-mer threshold"});
+    if (int rc = b.open(kmerSize, 64000000ull, posOffsets, nSeq, 10)) return rc;
+    sd_target *t = b.t;
     t->similar = true;
-    t->tableSize = 64000000ull;
-    t->hSeqOff.assign(posOffsets, posOffsets + nSeq + 1);
-    const PeakNote notePeak(t);
-    auto up = [&](void **d, const void *h, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes + 64);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*d, h, bytes, hipMemcpyDefault);
-    };
-    SD_HIP(ctx, up((void **) &t->dSeqOff, posOffsets, ((size_t) nSeq + 1) * sizeof(uint64_t)));
-    SD_HIP(ctx, up((void **) &t->dMasked, consensus, total));   // what the diagonal scoring reads
-    Scoped<uint8_t> dLetters, dIndex, dBig;
-    Scoped<int16_t> dScore;
-    Scoped<uint64_t> dWinBase;
-    Scoped<uint32_t> dWinCount;
-    Scoped<unsigned long long> dCoarse, dErr;
-    Scoped<uint2> dScratch, dScratchBig;
-    // (SD_INDEX_PROFILE_GRID: wavefronts of the wide tier, 1 MiB of scratch each -- a tuning knob, tools/bench_target_profile.py)
-    uint64_t wideGrid = IP_GRID;
-    if (getenv("SD_INDEX_PROFILE_GRID")) wideGrid = std::min<uint64_t>(std::max<uint64_t>(64, strtoull(getenv("SD_INDEX_PROFILE_GRID"), nullptr, 10)), 16384);
-    const uint32_t grid = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(nWin, 1), wideGrid);
+    const uint64_t nWin = b.nWin, total = posOffsets[nSeq];
+    SD_HIP(ctx, b.up(t->dMasked, consensus, total));   // what the diagonal scoring reads
+    DevBuf<uint8_t> dLetters, dIndex, dBig;
+    DevBuf<int16_t> dScore;
+    DevBuf<uint2> dScratch, dScratchBig;
+    const uint32_t grid = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(nWin, 1), b.knobs.profileGrid);
     const uint32_t gridBig = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(nWin, 1), IP_GRID_BIG);
-    SD_HIP(ctx, up((void **) &dLetters.p, queryLetters, total));
-    SD_HIP(ctx, up((void **) &dScore.p, sortedScore, total * 20 * sizeof(int16_t)));
-    SD_HIP(ctx, up((void **) &dIndex.p, sortedIndex, total * 20));
-    SD_HIP(ctx, up((void **) &dWinBase.p, winBase.data(), winBase.size() * sizeof(uint64_t)));
+    SD_HIP(ctx, b.up(dLetters.p, queryLetters, total));
+    SD_HIP(ctx, b.up(dScore.p, sortedScore, total * 20 * sizeof(int16_t)));
+    SD_HIP(ctx, b.up(dIndex.p, sortedIndex, total * 20));
     SD_HIP(ctx, dBig.alloc(nWin + 1));
-    SD_HIP(ctx, dWinCount.alloc(nWin + 1));
-    SD_HIP(ctx, dCoarse.alloc(IB_COARSE_BINS));
-    SD_HIP(ctx, dErr.alloc(2));
     SD_HIP(ctx, dScratch.alloc((size_t) grid * 2 * PROFILE_PARTIAL_CAP));
-    notePeak();
-    const unsigned long long errInit[2] = {~0ull, 0ull};   // [0] first window beyond IP_LIST_MAX, [1] windows of the big tier
-    SD_HIP(ctx, hipMemcpy(dErr.p, errInit, sizeof(errInit), hipMemcpyHostToDevice));
     SD_HIP(ctx, hipMemsetAsync(dBig.p, 0, nWin + 1, ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dWinCount.p, 0, (nWin + 1) * sizeof(uint32_t), ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dCoarse.p, 0, IB_COARSE_BINS * sizeof(unsigned long long), ctx->stream));
-    const uint32_t binWidth = (uint32_t) ((t->tableSize + IB_COARSE_BINS - 1) / IB_COARSE_BINS);
     bool anyBig = false;
-    // the generator in one of its modes, on the tier(s) the windows run in
-    auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *winCount, const uint64_t *recBase, uint32_t *keys, uint64_t *vals, bool bigTier) {
+    // the generator in one of its modes, on the tier(s) the windows run in; b.dErr[1]: the windows mode 0 moved to the big tier
+    auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *winCount, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) -> int {
         constexpr int MODE = decltype(mode)::value;
-        hipLaunchKernelGGL((ib_profile_records_kernel<MODE>), dim3(bigTier ? gridBig : grid), dim3(64), 0, ctx->stream, nWin,
-                           (const uint64_t *) dWinBase.p, nSeq, (const uint8_t *) dLetters.p, (const uint64_t *) t->dSeqOff,
-                           (const int16_t *) dScore.p, (const uint8_t *) dIndex.p, kmerThr, bigTier ? dScratchBig.p : dScratch.p,
-                           bigTier ? PROFILE_PARTIAL_CAP_BIG : PROFILE_PARTIAL_CAP, dBig.p, bigTier ? 1 : 0, binWidth, dCoarse.p, dErr.p, lo, hi,
-                           winCount, recBase, keys, vals);
+        for (int bigTier = 0; bigTier <= (anyBig ? 1 : 0); bigTier++) {
+            hipLaunchKernelGGL((ib_profile_records_kernel<MODE>), dim3(bigTier ? gridBig : grid), dim3(64), 0, ctx->stream, nWin,
+                               (const uint64_t *) b.dWinBase.p, nSeq, (const uint8_t *) dLetters.p, (const uint64_t *) t->dSeqOff,
+                               (const int16_t *) dScore.p, (const uint8_t *) dIndex.p, kmerThr, bigTier ? dScratchBig.p : dScratch.p,
+                               bigTier ? PROFILE_PARTIAL_CAP_BIG : PROFILE_PARTIAL_CAP, dBig.p, bigTier, b.binWidth, b.dCoarse.p, b.dErr.p, lo, hi,
+                               winCount, recBase, keys, vals);
+            if (MODE == 0 && !bigTier) {   // which windows outgrew the wide tier's lists is known only now: they get their scratch
+                unsigned long long hErr[2] = {~0ull, 0ull};
+                SD_HIP(ctx, hipGetLastError());
+                SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                SD_HIP(ctx, hipMemcpy(hErr, b.dErr.p, sizeof(hErr), hipMemcpyDeviceToHost));
+                anyBig = hErr[1] != 0;
+                if (anyBig) SD_HIP(ctx, dScratchBig.alloc((size_t) gridBig * 2 * PROFILE_PARTIAL_CAP_BIG));
+            }
+        }
+        return SD_OK;
     };
-    std::vector<unsigned long long> coarse(IB_COARSE_BINS, 0);
-    if (nWin) {
-        unsigned long long hErr[2] = {~0ull, 0ull};
-        {
-            ProfScope ps(ctx, "index_profile_histogram");
-            generate(std::integral_constant<int, 0>(), 0u, 0u, dWinCount.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr, false);
-        }
-        SD_HIP(ctx, hipGetLastError());
-        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        SD_HIP(ctx, hipMemcpy(hErr, dErr.p, sizeof(hErr), hipMemcpyDeviceToHost));
-        anyBig = hErr[1] != 0;
-        if (anyBig) {
-            SD_HIP(ctx, dScratchBig.alloc((size_t) gridBig * 2 * PROFILE_PARTIAL_CAP_BIG));
-            notePeak();
-            {
-                ProfScope ps(ctx, "index_profile_histogram");
-                generate(std::integral_constant<int, 0>(), 0u, 0u, dWinCount.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr, true);
-            }
-            SD_HIP(ctx, hipGetLastError());
-            SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            SD_HIP(ctx, hipMemcpy(hErr, dErr.p, sizeof(hErr), hipMemcpyDeviceToHost));
-        }
-        if (hErr[0] != ~0ull) {
-            const uint32_t q = (uint32_t) (std::upper_bound(winBase.begin(), winBase.end(), (uint64_t) hErr[0]) - winBase.begin() - 1);
-            return sdFail(ctx, SD_EUNSUPPORTED, "target %u, position %llu: more than %u similar k-mers in one profile window (the reference's "
-                          "buffer ends there, KmerGenerator.h:45); raise the k-mer threshold", q, (unsigned long long) (hErr[0] - winBase[q]), IP_LIST_MAX);
-        }
-        SD_HIP(ctx, hipMemcpy(coarse.data(), dCoarse.p, IB_COARSE_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    }
-    uint64_t nRecords = 0, cap = 0;
-    if (int rcCap = ibPassCap(ctx, coarse, cap, nRecords)) return rcCap;
-    SD_HIP(ctx, hipMalloc((void **) &t->dEntries, (std::max<uint64_t>(nRecords, 1) + 8) * sizeof(uint2)));   // (from the counted records)
-    SD_HIP(ctx, hipMalloc((void **) &t->dOffsets, (t->tableSize + 1) * sizeof(uint32_t) + 64));
-    SD_HIP(ctx, hipMemsetAsync(t->dOffsets, 0, (t->tableSize + 1) * sizeof(uint32_t), ctx->stream));   // counts first
-    uint64_t nEntries = 0, nPasses = 0;
-    if (nRecords) {
-        auto countFn = [&](uint32_t lo, uint32_t hi, uint32_t *winCount) -> int {
-            if (lo == 0 && hi >= t->tableSize) {   // one pass holds every record: the list lengths are its counts
-                SD_HIP(ctx, hipMemcpyAsync(winCount, dWinCount.p, nWin * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-                return SD_OK;
-            }
-            generate(std::integral_constant<int, 1>(), lo, hi, winCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr, false);
-            if (anyBig) generate(std::integral_constant<int, 1>(), lo, hi, winCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr, true);
-            return SD_OK;
-        };
-        auto emitFn = [&](uint32_t lo, uint32_t hi, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) -> int {
-            generate(std::integral_constant<int, 2>(), lo, hi, (uint32_t *) nullptr, recBase, keys, vals, false);
-            if (anyBig) generate(std::integral_constant<int, 2>(), lo, hi, (uint32_t *) nullptr, recBase, keys, vals, true);
-            return SD_OK;
-        };
-        if (int rcP = ibPasses(ctx, t, "sd_target_build_profile", coarse, binWidth, nRecords, cap, (uint32_t) nWin, countFn, emitFn, notePeak, nEntries,
-                               nPasses))
-            return rcP;
-    }
-    if (int rcL = ibListStarts(ctx, t, "sd_target_build_profile", nEntries, notePeak)) return rcL;
-    t->nEntries = nEntries;
-    if (stats) {
-        stats[0] = nEntries;
-        stats[1] = 0;
-        stats[2] = nPasses;
-        stats[3] = nRecords;
-    }
-    guard.t = nullptr;
-    *out = t;
-    return SD_OK;
+    if (int rc = b.passes((uint32_t) nWin, true, generate)) return rc;
+    return b.finish(0, out, stats);
 }
 
 // The similar-k-mer index of a *sequence* target DB (--target-search-mode 1; the sequence branch of the same reference code,
@@ -1382,128 +1311,34 @@ extern "C" int sd_target_build_similar(sd_ctx *ctx, int kmerSize, int kmerThr, c
     if (kmerSize == 7)
         return sdFail(ctx, SD_EUNSUPPORTED, "k=7: the similar-k-mer index of a sequence target is built at k=6 only (the 3 x 3 array product; k=7 divides 2, 2, 3)");
     if (kmerSize != 6) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the similar-k-mer index of a sequence target is built at k=6", kmerSize);
-    const int span = 10;
-    std::vector<uint64_t> winBase((size_t) nSeq + 1, 0);
-    for (uint32_t i = 0; i < nSeq; i++) {
-        const uint64_t len = seqOffsets[i + 1] - seqOffsets[i];
-        if (len > 65535)   // (as sd_target_build)
-            return sdFail(ctx, SD_EINVAL, "target %u has %llu residues; index positions are 16 bit (limit 65535, --max-seq-len)", i,
-                          (unsigned long long) len);
-        winBase[i + 1] = winBase[i] + (len >= (uint64_t) span ? len - span + 1 : 0);
-    }
-    const uint64_t nWin = winBase[nSeq], total = seqOffsets[nSeq];
-    if (nWin >= 0xFFFFFFFFull) return sdFail(ctx, SD_EUNSUPPORTED, "%llu sequence windows (limit 2^32 per target)", (unsigned long long) nWin);
-    (void) hipSetDevice(ctx->device);
-    sd_target *t = new sd_target();
-    struct Guard {
-        sd_target *t;
-        ~Guard() { if (t) sd_target_destroy(t); }
-    } guard{t};
-    t->ctx = ctx;
-    t->k = kmerSize;
-    t->nSeq = nSeq;
+    IndexBuild b(ctx, {"sd_target_build_similar", "residues", "sequence", "index_similar_histogram",
+                       "target %u, position %llu: %u similar k-mers or more in one sequence window (the reference's buffer ends there, "
+                       "KmerGenerator.h:45); raise the k-mer threshold"});
+    if (int rc = b.open(kmerSize, 64000000ull, seqOffsets, nSeq, 10)) return rc;
+    sd_target *t = b.t;
     t->similar = true;
     t->similarSeq = true;
-    t->tableSize = 64000000ull;
-    t->hSeqOff.assign(seqOffsets, seqOffsets + nSeq + 1);
-    const PeakNote notePeak(t);
-    auto up = [&](void **d, const void *h, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes + 64);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*d, h, bytes, hipMemcpyDefault);
-    };
-    SD_HIP(ctx, up((void **) &t->dSeqOff, seqOffsets, ((size_t) nSeq + 1) * sizeof(uint64_t)));
-    SD_HIP(ctx, up((void **) &t->dMasked, residues, total));   // the lookup of the diagonal scoring: unmasked (IndexBuilder.cpp:125-127)
-    // the 3-mer tables serve the generator only: a query looks up its own k-mers, so they are released with the build
-    SD_HIP(ctx, up((void **) &t->dExt3Score, ext3Score, (size_t) 8000 * 8000 * sizeof(int16_t)));
-    SD_HIP(ctx, up((void **) &t->dExt3Index, ext3Index, (size_t) 8000 * 8000 * sizeof(uint16_t)));
-    if (int rcCum = sdBuildExt3Cum(ctx, t)) return rcCum;
-    auto dropTables = [&]() {
-        for (void **p : {(void **) &t->dExt3Score, (void **) &t->dExt3Index, (void **) &t->dExt3Cum}) {
-            if (*p) (void) hipFree(*p);
-            *p = nullptr;
-        }
-    };
-    Scoped<uint64_t> dWinBase;
-    Scoped<uint32_t> dWinCount;
-    Scoped<unsigned long long> dCoarse, dErr;
+    const uint64_t nWin = b.nWin;
+    SD_HIP(ctx, b.up(t->dMasked, residues, seqOffsets[nSeq]));   // the lookup of the diagonal scoring: unmasked (IndexBuilder.cpp:125-127)
+    // the 3-mer tables serve the generator only: a query looks up its own k-mers, so they are released before the list starts are made
+    SD_HIP(ctx, b.up(t->dExt3Score, ext3Score, (size_t) 8000 * 8000 * sizeof(int16_t)));
+    SD_HIP(ctx, b.up(t->dExt3Index, ext3Index, (size_t) 8000 * 8000 * sizeof(uint16_t)));
+    if (int rc = sdBuildExt3Cum(ctx, t)) return rc;
     const uint32_t grid = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(nWin, 1), IS_GRID);
-    SD_HIP(ctx, up((void **) &dWinBase.p, winBase.data(), winBase.size() * sizeof(uint64_t)));
-    SD_HIP(ctx, dWinCount.alloc(nWin + 1));
-    SD_HIP(ctx, dCoarse.alloc(IB_COARSE_BINS));
-    SD_HIP(ctx, dErr.alloc(1));
-    notePeak();
-    const unsigned long long errInit = ~0ull;
-    SD_HIP(ctx, hipMemcpy(dErr.p, &errInit, sizeof(errInit), hipMemcpyHostToDevice));
-    SD_HIP(ctx, hipMemsetAsync(dWinCount.p, 0, (nWin + 1) * sizeof(uint32_t), ctx->stream));
-    SD_HIP(ctx, hipMemsetAsync(dCoarse.p, 0, IB_COARSE_BINS * sizeof(unsigned long long), ctx->stream));
-    const uint32_t binWidth = (uint32_t) ((t->tableSize + IB_COARSE_BINS - 1) / IB_COARSE_BINS);
-    auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *winCount, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) {
+    auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *winCount, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) -> int {
         constexpr int MODE = decltype(mode)::value;
-        hipLaunchKernelGGL((ib_similar_records_kernel<MODE>), dim3(grid), dim3(64), 0, ctx->stream, nWin, (const uint64_t *) dWinBase.p, nSeq,
+        hipLaunchKernelGGL((ib_similar_records_kernel<MODE>), dim3(grid), dim3(64), 0, ctx->stream, nWin, (const uint64_t *) b.dWinBase.p, nSeq,
                            (const uint8_t *) t->dMasked, (const uint64_t *) t->dSeqOff, (const int16_t *) t->dExt3Score,
-                           (const uint16_t *) t->dExt3Index, (const uint16_t *) t->dExt3Cum, t->ext3Lo, kmerThr, binWidth, dCoarse.p, dErr.p, lo,
-                           hi, winCount, recBase, keys, vals);
+                           (const uint16_t *) t->dExt3Index, (const uint16_t *) t->dExt3Cum, t->ext3Lo, kmerThr, b.binWidth, b.dCoarse.p, b.dErr.p,
+                           lo, hi, winCount, recBase, keys, vals);
+        return SD_OK;
     };
-    std::vector<unsigned long long> coarse(IB_COARSE_BINS, 0);
-    if (nWin) {
-        {
-            ProfScope ps(ctx, "index_similar_histogram");
-            generate(std::integral_constant<int, 0>(), 0u, 0u, dWinCount.p, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-        }
-        SD_HIP(ctx, hipGetLastError());
-        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        unsigned long long hErr = ~0ull;
-        SD_HIP(ctx, hipMemcpy(&hErr, dErr.p, sizeof(hErr), hipMemcpyDeviceToHost));
-        if (hErr != ~0ull) {
-            const uint32_t q = (uint32_t) (std::upper_bound(winBase.begin(), winBase.end(), (uint64_t) hErr) - winBase.begin() - 1);
-            return sdFail(ctx, SD_EUNSUPPORTED, "target %u, position %llu: %u similar k-mers or more in one sequence window (the reference's "
-                          "buffer ends there, KmerGenerator.h:45); raise the k-mer threshold", q, (unsigned long long) (hErr - winBase[q]), IP_LIST_MAX);
-        }
-        SD_HIP(ctx, hipMemcpy(coarse.data(), dCoarse.p, IB_COARSE_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (int rc = b.passes((uint32_t) nWin, true, generate)) return rc;
+    for (void **p : {(void **) &t->dExt3Score, (void **) &t->dExt3Index, (void **) &t->dExt3Cum}) {
+        if (*p) (void) hipFree(*p);
+        *p = nullptr;
     }
-    uint64_t nRecords = 0, cap = 0;
-    if (int rcCap = ibPassCap(ctx, coarse, cap, nRecords)) return rcCap;
-    // the entry array is sized by the counted records (the dedupe only ever removes): hundreds of records per residue at the default threshold
-    if (hipMalloc((void **) &t->dEntries, (std::max<uint64_t>(nRecords, 1) + 8) * sizeof(uint2)) != hipSuccess) {
-        t->dEntries = nullptr;
-        (void) hipGetLastError();
-        return sdFail(ctx, SD_ENOMEM, "the similar-k-mer index of %llu records (%llu bytes of entries) does not fit the device memory; a higher "
-                      "--k-score (fewer similar k-mers per window) or a smaller target database is the way out", (unsigned long long) nRecords,
-                      (unsigned long long) ((nRecords + 8) * sizeof(uint2)));
-    }
-    SD_HIP(ctx, hipMalloc((void **) &t->dOffsets, (t->tableSize + 1) * sizeof(uint32_t) + 64));
-    SD_HIP(ctx, hipMemsetAsync(t->dOffsets, 0, (t->tableSize + 1) * sizeof(uint32_t), ctx->stream));   // counts first
-    uint64_t nEntries = 0, nPasses = 0;
-    if (nRecords) {
-        auto countFn = [&](uint32_t lo, uint32_t hi, uint32_t *winCount) -> int {
-            if (lo == 0 && hi >= t->tableSize) {   // one pass holds every record: the list lengths are its counts
-                SD_HIP(ctx, hipMemcpyAsync(winCount, dWinCount.p, nWin * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-                return SD_OK;
-            }
-            generate(std::integral_constant<int, 1>(), lo, hi, winCount, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint64_t *) nullptr);
-            return SD_OK;
-        };
-        auto emitFn = [&](uint32_t lo, uint32_t hi, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) -> int {
-            generate(std::integral_constant<int, 2>(), lo, hi, (uint32_t *) nullptr, recBase, keys, vals);
-            return SD_OK;
-        };
-        if (int rcP = ibPasses(ctx, t, "sd_target_build_similar", coarse, binWidth, nRecords, cap, (uint32_t) nWin, countFn, emitFn, notePeak, nEntries,
-                               nPasses))
-            return rcP;
-    }
-    dropTables();
-    if (int rcL = ibListStarts(ctx, t, "sd_target_build_similar", nEntries, notePeak)) return rcL;
-    t->nEntries = nEntries;
-    if (stats) {
-        stats[0] = nEntries;
-        stats[1] = 0;
-        stats[2] = nPasses;
-        stats[3] = nRecords;
-    }
-    guard.t = nullptr;
-    *out = t;
-    return SD_OK;
+    return b.finish(0, out, stats);
 }
 
 // The model behind `prefilter --split 0`: every hipMalloc of sd_target_build above, with the data-dependent sizes replaced by
@@ -1517,22 +1352,23 @@ extern "C" uint64_t sd_target_footprint(int kmerSize, uint64_t nSeq, uint64_t nR
     // resident from the start: sequence offsets, 3-mer and 2-mer matrices, the cumulative 3-mer table (+ its min/max pair), masked residues
     const uint64_t tables = a((S + 1) * 8 + 64) + 2 * a(8000ull * 8000 * 2 + 64) + a(8000ull * 256 * 2) + a(8) + 2 * a(400ull * 400 * 2 + 64) +
                             a(R + 64);
-    // 1. masking: the residues, the length order, and 64 lanes x (4 + 8 / TT_SCALE) bytes per row; a wavefront's rows are its longest
-    //    sequence rounded up to TT_SCALE; sorted by length, 64 x the rows of a wave are at most the residues of the next full wave, which
-    //    leaves the last two waves (at most 65 535 rows each) and the rounding
+    // 1. masking (ibMaskPhase): the residues, the length order, and 64 lanes x (4 + 8 / TT_SCALE) bytes per row; a wavefront's rows are
+    //    its longest sequence rounded up to TT_SCALE; sorted by length, 64 x the rows of a wave are at most the residues of the next full
+    //    wave, which leaves the last two waves (at most 65 535 rows each) and the rounding
     const uint64_t nWaves = (S + 63) / 64;
     const uint64_t rows = (R + 63) / 64 + 2 * 65535 + (nWaves + 2) * TT_SCALE;
     const uint64_t maskPhase = a(R + 64) + a(S * 4) + a((nWaves + 1) * 8) + a(rows * 64 * sizeof(float)) + a((rows / TT_SCALE * 64 + 64) * sizeof(double)) +
                                a(IB_ALPH * IB_ALPH * 8) + a(8);
-    // 2. records: the entries and counts stay; the sort's two (k-mer, record) buffer pairs and the scans' tiles go
+    // 2. records (IndexBuild::passes, ibPasses): the entries and counts stay; the histogram goes before the sort's two (k-mer, record)
+    //    buffer pairs, the slot and tile counts with their scanned bases (one element more each) and the scan's tile sums come
     const uint64_t entries = a((std::max<uint64_t>(R, 1) + 8) * 8) + a((T + 1) * 4 + 64);
     const uint64_t bufN = std::min<uint64_t>(1ull << 30, std::max<uint64_t>(R, 1));
     const uint64_t nWavesR = (S + IB_SEQ_PER_WAVE - 1) / IB_SEQ_PER_WAVE, tiles = (bufN + IK_TILE - 1) / IK_TILE;
     const uint64_t sortPhase = std::max<uint64_t>(a(IB_COARSE_BINS * 8),
-                                                  2 * a(bufN * 4) + 2 * a(bufN * 8) + a(nWavesR * 4) + a(nWavesR * 8) + a(tiles * 4) + a(tiles * 8) + a(8) +
-                                                      a(sdRadixSortCountsBytes()) + a((std::max(nWavesR, tiles) + IS_TILE - 1) / IS_TILE * 8));
-    // 3. list starts: 64-bit starts of the whole table, the scan's tiles, the wide index's block bases
-    const uint64_t startPhase = a((T + 1) * 8) + a(8) + a((T + IS_TILE) / IS_TILE * 8) + a((((T + 2) >> 16) + 1) * 8);
+                                                  2 * a(bufN * 4) + 2 * a(bufN * 8) + a((nWavesR + 1) * 4) + a((nWavesR + 1) * 8) + a((tiles + 1) * 4) +
+                                                      a((tiles + 1) * 8) + a(sdRadixSortCountsBytes()) + a(sdScanTmpBytes(std::max(nWavesR, tiles) + 1)));
+    // 3. list starts (ibListStarts): 64-bit starts of the whole table, the scan's tile sums, the wide index's block bases
+    const uint64_t startPhase = a((T + 1) * 8) + a(sdScanTmpBytes(T + 1)) + a((((T + 2) >> 16) + 1) * 8);
     // what the HIP runtime itself takes from the device when the build's kernels first run (code objects, kernel-argument and signal pools)
     const uint64_t runtime = 32ull << 20;
     return tables + std::max(maskPhase, entries + std::max(sortPhase, startPhase)) + runtime;
@@ -1593,12 +1429,12 @@ extern "C" int sd_target_sample_check(sd_ctx *ctx, const sd_target *t, const uin
                                       uint64_t resBegin, uint64_t resEnd, uint8_t *maskedOut) {
     if (!ctx || !t || !missing || !inSample || (n && (!kmer || !seq || !pos)) || (nSample && !sample)) return SD_EINVAL;
     (void) hipSetDevice(ctx->device);
-    Scoped<uint32_t> dK, dS, dP, dSample;
-    Scoped<unsigned long long> dOut;
-    SD_HIP(ctx, dK.alloc(n));
-    SD_HIP(ctx, dS.alloc(n));
-    SD_HIP(ctx, dP.alloc(n));
-    SD_HIP(ctx, dSample.alloc(nSample));
+    DevBuf<uint32_t> dK, dS, dP, dSample;
+    DevBuf<unsigned long long> dOut;
+    SD_HIP(ctx, dK.alloc(std::max<uint64_t>(n, 1)));   // (at least one element: the copies below take the pointers whatever n is)
+    SD_HIP(ctx, dS.alloc(std::max<uint64_t>(n, 1)));
+    SD_HIP(ctx, dP.alloc(std::max<uint64_t>(n, 1)));
+    SD_HIP(ctx, dSample.alloc(std::max<uint32_t>(nSample, 1)));
     SD_HIP(ctx, dOut.alloc(2));
     SD_HIP(ctx, hipMemcpy(dK.p, kmer, n * sizeof(uint32_t), hipMemcpyHostToDevice));
     SD_HIP(ctx, hipMemcpy(dS.p, seq, n * sizeof(uint32_t), hipMemcpyHostToDevice));

@@ -98,6 +98,32 @@ def test_many_passes_and_the_wide_form(gpu, host, small_proteomes, monkeypatch):
     _same(h, t.download())
 
 
+_SHORT = {}
+
+
+def _short(host, n_seq):
+    """n_seq random sequences of 12 residues (three k-mers each at k = 6) and their host-built index, built once per size"""
+    if n_seq not in _SHORT:
+        res = np.random.default_rng(n_seq).integers(0, 20, n_seq * 12).astype(np.uint8)
+        off = np.arange(n_seq + 1, dtype=np.uint64) * 12
+        _SHORT[n_seq] = (res, off, host.build_index(res, off, k=6, kmer_thr=0, mask=False))
+    return _SHORT[n_seq]
+
+
+@pytest.mark.parametrize('n_seq,pass_cap', [(65520, None), (65536, None), (65537, None), (65536, '50000')])
+def test_record_total_where_the_slots_cross_a_scan_tile(gpu, host, monkeypatch, n_seq, pass_cap):
+    """the records of a pass are totalled as the scanned value of one zero element behind the per-slot counts (a slot: 16 sequences): with
+    4 095, 4 096 and 4 097 slots that element is the last of the first scan tile of 4 096, the first of the second, and the second.
+    With several passes the same element is scanned again in each and must still be zero"""
+    res, off, h = _short(host, n_seq)
+    if pass_cap:
+        monkeypatch.setenv('SD_INDEX_PASS', pass_cap)
+    t = api.Target.build_on_device(gpu, host, res, off, k=6, kmer_thr=0, mask=False)
+    if pass_cap:
+        assert t.build_stats['passes'] > 1
+    _same(h, t.download())
+
+
 def test_prefilter_on_the_device_built_target(gpu, host, small_proteomes):
     ps = small_proteomes
     ident = np.arange(ps.n, dtype=np.uint32)
