@@ -237,6 +237,20 @@ int sd_selftest_score_class(int kernel /* 0 packed, 1 packed wide, 2 int32, 3 pa
  * task order.  SD_EINVAL for L == 0, nRows == 0 or a code above 21. */
 int sd_selftest_r2p_weights(sd_ctx *ctx, uint32_t nTasks, const uint32_t *nRows, const uint32_t *L, const uint8_t *cells, float *freq,
                             float *eff);
+/* sd_selftest_kmermatch_records: the records stage of sd_kmermatch_batch alone (csrc/hip/sd_kmermatch.hip: validation, upload,
+ * km_select_kernel, the scan of the record counts, km_emit_kernel -- the one function sd_kmermatch_batch itself calls first), copied
+ * out before any sort.  Inputs as sd_kmermatch_batch (declared below with sd_kmermatch_params).  Per sequence, in input order:
+ * seqConsidered[nSeq] kmerConsidered after the window count capped it, seqThreshold[nSeq] and seqExcess[nSeq] as km_select_kernel
+ * leaves them (threshold: one past the largest score taken; excess: windows up to the threshold beyond kmerConsidered; both 0 where
+ * nothing is considered), recOff[nSeq + 1] the record offsets.  Per record, in emission order (the identity record of a sequence, then
+ * its windows by position): recKey the 64-bit key, recId the DB key, recLen the sequence length, recPos the window's position.
+ * recCap is the room of the four record arrays in records; stats[1] (nullable) = records.  recCap < records: SD_ENOMEM with stats
+ * filled and no output array written (recCap 0 with null arrays is the count-only form). */
+struct sd_kmermatch_params_s;
+int sd_selftest_kmermatch_records(sd_ctx *ctx, const struct sd_kmermatch_params_s *par, uint64_t nSeq, const uint8_t *residues,
+                                  const uint64_t *offsets, const uint32_t *keys, const uint8_t *letterMap21, uint64_t recCap,
+                                  uint32_t *seqConsidered, uint32_t *seqThreshold, uint32_t *seqExcess, uint64_t *recOff, uint64_t *recKey,
+                                  uint32_t *recId, uint32_t *recLen, uint32_t *recPos, uint64_t *stats);
 
 int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
                                uint32_t nPairs, const uint32_t *pairQ, const uint32_t *pairT, const uint8_t *isIdentity,
@@ -1030,7 +1044,7 @@ int sd_host_clust_format(uint64_t n, const uint32_t *localKeys, const uint32_t *
  * null arrays is the count-only form).  Records that do not fit the device at once, or more than the device sort counts (2^32 - 4097):
  * SD_ENOMEM with the bytes needed in the message -- the reference's split by hash range is not implemented. */
 #define SD_KMERMATCH_BYTES_PER_RECORD 80   /* device bytes per record, counted from sd_kmermatch.hip's workspace */
-typedef struct {
+typedef struct sd_kmermatch_params_s {
     int32_t kmerSize;              /* -k (after the -k 0 rule) */
     int32_t alphabetSize;          /* reduced size: 13 or 21 */
     int32_t kmersPerSequence;      /* --kmer-per-seq (20 when 0) */

@@ -1070,6 +1070,37 @@ def kmermatch(ctx, par, residues, offsets, keys, letter_map=None, cap=None):
     return rep[:h], mem[:h], score[:h], diag[:h], named()
 
 
+def kmermatch_records(ctx, par, residues, offsets, keys, letter_map=None, cap=None):
+    """sd_selftest_kmermatch_records: the records stage of sd_kmermatch_batch alone -> dict(considered, threshold, excess uint32 [n],
+    rec_off uint64 [n + 1], key uint64, id, len, pos uint32 [records]), sequences in input order, records in emission order.  cap: room in
+    records (default: exactly enough, learned from a count-only call first)."""
+    L = _lib.load()
+    residues = np.ascontiguousarray(residues, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    keys = np.ascontiguousarray(keys, np.uint32)
+    n = len(offsets) - 1
+    assert len(keys) == n and len(residues) == int(offsets[-1])
+    if letter_map is None:
+        letter_map = reduced_alphabet(par.alphabetSize)[0]
+    letter_map = np.ascontiguousarray(letter_map, np.uint8)
+    stats = np.zeros(1, np.uint64)
+    call = lambda room, *out: L.sd_selftest_kmermatch_records(ctx.h, C.byref(par), n, ptr(residues), ptr(offsets), ptr(keys), ptr(letter_map),
+                                                              room, *out, ptr(stats))
+    if cap is None:
+        rc = call(0, *[None] * 8)
+        if rc != _lib.SD_ENOMEM or int(stats[0]) == 0:
+            _check(ctx.h, rc, 'sd_selftest_kmermatch_records')
+        cap = int(stats[0])
+    cons, thr, exc = (np.zeros(max(n, 1), np.uint32) for _ in range(3))
+    rec_off = np.zeros(n + 1, np.uint64)
+    key = np.zeros(max(cap, 1), np.uint64)
+    rid, rlen, rpos = (np.zeros(max(cap, 1), np.uint32) for _ in range(3))
+    _check(ctx.h, call(cap, ptr(cons), ptr(thr), ptr(exc), ptr(rec_off), ptr(key), ptr(rid), ptr(rlen), ptr(rpos)),
+           'sd_selftest_kmermatch_records')
+    r = int(stats[0])
+    return dict(considered=cons[:n], threshold=thr[:n], excess=exc[:n], rec_off=rec_off, key=key[:r], id=rid[:r], len=rlen[:r], pos=rpos[:r])
+
+
 def kmermatch_format(keys, rep, member, score, diag):
     """sd_host_kmermatch_format: the prefilter DB of the hits as dict key -> bytes (every sequence key has an entry)"""
     L = _lib.load()

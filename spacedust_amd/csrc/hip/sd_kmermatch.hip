@@ -14,6 +14,7 @@
 //   second sort        diagonal (biased), member, rep
 //   km_hitflag_kernel + scan + km_hit_kernel   one hit per (rep, member) run with member != rep
 // No kernel waits for another workgroup; every store is a plain vector store.
+// The records part is one function, kmRecordsStage, which sd_selftest_kmermatch_records calls too and copies out for tests/.
 //
 // The reference's element type T (short below a longest sequence of 32 767, int otherwise) only sets the width of seqLen, pos and the
 // diagonal: with short every length is below 32 767, so every position and every diagonal fits and nothing is truncated; the fields are
@@ -363,23 +364,29 @@ inline hipError_t kmSortByField(hipStream_t st, const KmSortBufs &b, const uint3
     return sdRadixSortPairs<uint32_t>(st, b.keyIn, b.permIn, b.keyA, b.permA, b.keyB, b.permB, n, 0, bits, b.counts);
 }
 
-}  // namespace
+// What the records stage leaves on the device: the per-sequence selection, the record offsets, the emitted records (r*) and the
+// workspace of everything behind it.  sd_kmermatch_batch goes on from here; sd_selftest_kmermatch_records copies it out.
+struct KmStage {
+    bool empty;   // no sequence: nothing was launched and no pointer is set
+    uint64_t bound, nRec, maxLen;
+    uint32_t maxKey;
+    uint64_t *dRecOff, *dScanTmp, *dAt;
+    uint32_t *dThr, *dExc, *dConsOut, *dLargest, *dRunStart, *dFlag;
+    uint32_t *rKeyHi, *rKeyLo, *rId, *rLen, *rPos, *sKeyHi, *sKeyLo, *sId, *sLen, *sPos;
+    KmSortBufs sb;
+};
 
-extern "C" {
-
-int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSeq, const uint8_t *residues, const uint64_t *offsets,
-                       const uint32_t *keys, const uint8_t *letterMap, uint64_t outCap, uint32_t *outRep, uint32_t *outMember,
-                       uint32_t *outScore, int32_t *outDiag, uint64_t *stats) {
-    if (!ctx || !par || !offsets || !letterMap) return SD_EINVAL;
-    (void) hipSetDevice(ctx->device);
-    sdD2HReset(ctx);
-    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+// Validation, workspace, upload, km_select_kernel, the scan of the record counts and km_emit_kernel (queued on the context's stream when
+// this returns).  `who` names the entry point in messages.
+int kmRecordsStage(sd_ctx *ctx, const char *who, const sd_kmermatch_params *par, uint64_t nSeq, const uint8_t *residues,
+                   const uint64_t *offsets, const uint32_t *keys, const uint8_t *letterMap, KmStage *stage) {
+    memset(stage, 0, sizeof(*stage));
     if (nSeq && (!residues || !keys)) return SD_EINVAL;
-    if (nSeq > (uint64_t) INT32_MAX) return sdFail(ctx, SD_EUNSUPPORTED, "sd_kmermatch_batch: %llu sequences in one call", (unsigned long long) nSeq);
-    if (par->alphabetSize < 2 || par->alphabetSize > 21) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: alphabet size %d", par->alphabetSize);
-    if (par->kmerSize < 1 || par->kmerSize > KM_MAXK) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: k-mer size %d (1 .. %d)", par->kmerSize, KM_MAXK);
-    if (par->kmersPerSequence < 1) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: --kmer-per-seq %d", par->kmersPerSequence);
-    if (par->covMode < 0 || par->covMode > 5) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: coverage mode %d", par->covMode);
+    if (nSeq > (uint64_t) INT32_MAX) return sdFail(ctx, SD_EUNSUPPORTED, "%s: %llu sequences in one call", who, (unsigned long long) nSeq);
+    if (par->alphabetSize < 2 || par->alphabetSize > 21) return sdFail(ctx, SD_EINVAL, "%s: alphabet size %d", who, par->alphabetSize);
+    if (par->kmerSize < 1 || par->kmerSize > KM_MAXK) return sdFail(ctx, SD_EINVAL, "%s: k-mer size %d (1 .. %d)", who, par->kmerSize, KM_MAXK);
+    if (par->kmersPerSequence < 1) return sdFail(ctx, SD_EINVAL, "%s: --kmer-per-seq %d", who, par->kmersPerSequence);
+    if (par->covMode < 0 || par->covMode > 5) return sdFail(ctx, SD_EINVAL, "%s: coverage mode %d", who, par->covMode);
     KmPar kp;
     memset(&kp, 0, sizeof(kp));
     kp.k = par->kmerSize;
@@ -390,15 +397,15 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
         for (int j = 0; j < kp.k; j++) {
             kp.pw[j] = pw;
             if (j + 1 < kp.k && pw > UINT64_MAX / (uint64_t) (par->alphabetSize - 1))
-                return sdFail(ctx, SD_EUNSUPPORTED, "sd_kmermatch_batch: %d^%d does not fit the 64-bit k-mer index", par->alphabetSize - 1, kp.k);
+                return sdFail(ctx, SD_EUNSUPPORTED, "%s: %d^%d does not fit the 64-bit k-mer index", who, par->alphabetSize - 1, kp.k);
             pw *= (uint64_t) (par->alphabetSize - 1);
         }
     }
     for (int a = 0; a < 21; a++) {
-        if (letterMap[a] >= par->alphabetSize) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: letter %d maps to %d of %d", a, letterMap[a], par->alphabetSize);
+        if (letterMap[a] >= par->alphabetSize) return sdFail(ctx, SD_EINVAL, "%s: letter %d maps to %d of %d", who, a, letterMap[a], par->alphabetSize);
         kp.map[a] = letterMap[a];
     }
-    if (offsets[0] != 0) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: offsets must start at 0");
+    if (offsets[0] != 0) return sdFail(ctx, SD_EINVAL, "%s: offsets must start at 0", who);
     // per sequence: kmerConsidered before the window count caps it (kmermatcher.cpp:204-206: sd_host_kmermatch_considered, the product
     // rounded to float before the sum, whatever this file's compiler would contract), and the record bound; checked here, so that no lane
     // indexes outside its arrays.  Timed as km_prepare; the first-use allocations behind it as km_alloc
@@ -407,9 +414,9 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
     uint64_t bound = 0, maxLen = 0;
     uint32_t maxKey = 0;
     for (uint64_t s = 0; s < nSeq; s++) {
-        if (offsets[s + 1] < offsets[s]) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: offsets descend at sequence %llu", (unsigned long long) s);
+        if (offsets[s + 1] < offsets[s]) return sdFail(ctx, SD_EINVAL, "%s: offsets descend at sequence %llu", who, (unsigned long long) s);
         const uint64_t L = offsets[s + 1] - offsets[s];
-        if (L > (uint64_t) INT32_MAX / 2) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: sequence %llu has %llu residues", (unsigned long long) s, (unsigned long long) L);
+        if (L > (uint64_t) INT32_MAX / 2) return sdFail(ctx, SD_EINVAL, "%s: sequence %llu has %llu residues", who, (unsigned long long) s, (unsigned long long) L);
         const uint64_t considered = sd_host_kmermatch_considered(par->kmersPerSequence, par->kmersPerSequenceScale, (uint32_t) L);
         const uint64_t windows = L >= (uint64_t) kp.k ? L - (uint64_t) kp.k + 1 : 0;
         cons[s] = (uint32_t) std::min(considered, windows);
@@ -423,12 +430,15 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
 #pragma omp parallel for schedule(static) reduction(min : bad) if (total > (1u << 16))
         for (uint64_t i = 0; i < total; i++)
             if (residues[i] >= 21 && i < bad) bad = i;
-        if (bad != UINT64_MAX) return sdFail(ctx, SD_EINVAL, "sd_kmermatch_batch: residue %llu has code %u (0 .. 20)", (unsigned long long) bad, residues[bad]);
+        if (bad != UINT64_MAX) return sdFail(ctx, SD_EINVAL, "%s: residue %llu has code %u (0 .. 20)", who, (unsigned long long) bad, residues[bad]);
     }
-    if (nSeq == 0) return SD_OK;
+    if (nSeq == 0) {
+        stage->empty = true;
+        return SD_OK;
+    }
     if (bound > KM_MAX_RECORDS)
-        return sdFail(ctx, SD_ENOMEM, "sd_kmermatch_batch: up to %llu records in one call (the device sort counts in 32 bits: at most %llu); %llu bytes needed",
-                      (unsigned long long) bound, (unsigned long long) KM_MAX_RECORDS, (unsigned long long) (bound * SD_KMERMATCH_BYTES_PER_RECORD + total));
+        return sdFail(ctx, SD_ENOMEM, "%s: up to %llu records in one call (the device sort counts in 32 bits: at most %llu); %llu bytes needed",
+                      who, (unsigned long long) bound, (unsigned long long) KM_MAX_RECORDS, (unsigned long long) (bound * SD_KMERMATCH_BYTES_PER_RECORD + total));
     // everything is resident at once (the reference would split by hash range here, with scores saturated to a byte: another output)
     {
         const uint64_t need = bound * SD_KMERMATCH_BYTES_PER_RECORD + total + nSeq * 40;
@@ -438,8 +448,8 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
         for (auto &e : ctx->ws)
             if (e.first.compare(0, 3, "km.") == 0) held += e.second.bytes;
         if (need > (uint64_t) freeB + held)
-            return sdFail(ctx, SD_ENOMEM, "sd_kmermatch_batch: %llu bytes needed for up to %llu records, %llu free on the device (splitting by hash range is not implemented)",
-                          (unsigned long long) need, (unsigned long long) bound, (unsigned long long) ((uint64_t) freeB + held));
+            return sdFail(ctx, SD_ENOMEM, "%s: %llu bytes needed for up to %llu records, %llu free on the device (splitting by hash range is not implemented)",
+                          who, (unsigned long long) need, (unsigned long long) bound, (unsigned long long) ((uint64_t) freeB + held));
     }
     const uint32_t n32 = (uint32_t) nSeq;
     hipStream_t st = ctx->stream;
@@ -501,13 +511,62 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
         SD_HIP(ctx, (sdScanLaunch<uint32_t, ScanSum64, false, uint64_t>(st, dCount, dRecOff, nSeq + 1, dScanTmp)));
         SD_HIP(ctx, sdD2H(ctx, &nRec, dRecOff + nSeq, 8));
         SD_HIP(ctx, sdStreamSync(ctx));
-        if (nRec > bound) return sdFail(ctx, SD_EHIP, "sd_kmermatch_batch: %llu records counted, at most %llu expected", (unsigned long long) nRec, (unsigned long long) bound);
+        if (nRec > bound) return sdFail(ctx, SD_EHIP, "%s: %llu records counted, at most %llu expected", who, (unsigned long long) nRec, (unsigned long long) bound);
         hipLaunchKernelGGL(km_emit_kernel, dim3(n32), dim3(64), 0, st, kp, (const uint8_t *) dRes, (const uint64_t *) dOff, (const uint32_t *) dKeys, n32,
                            (const uint64_t *) dRecOff, (const uint32_t *) dThr, (const uint32_t *) dExc, (const uint32_t *) dConsOut, rKeyHi, rKeyLo, rId,
                            rLen, rPos);
         SD_HIP(ctx, hipGetLastError());
         if (ctx->profiling) SD_HIP(ctx, sdStreamSync(ctx));
     }
+    stage->bound = bound;
+    stage->nRec = nRec;
+    stage->maxLen = maxLen;
+    stage->maxKey = maxKey;
+    stage->dRecOff = dRecOff;
+    stage->dScanTmp = dScanTmp;
+    stage->dAt = dAt;
+    stage->dThr = dThr;
+    stage->dExc = dExc;
+    stage->dConsOut = dConsOut;
+    stage->dLargest = dLargest;
+    stage->dRunStart = dRunStart;
+    stage->dFlag = dFlag;
+    stage->rKeyHi = rKeyHi;
+    stage->rKeyLo = rKeyLo;
+    stage->rId = rId;
+    stage->rLen = rLen;
+    stage->rPos = rPos;
+    stage->sKeyHi = sKeyHi;
+    stage->sKeyLo = sKeyLo;
+    stage->sId = sId;
+    stage->sLen = sLen;
+    stage->sPos = sPos;
+    stage->sb = sb;
+    return SD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSeq, const uint8_t *residues, const uint64_t *offsets,
+                       const uint32_t *keys, const uint8_t *letterMap, uint64_t outCap, uint32_t *outRep, uint32_t *outMember,
+                       uint32_t *outScore, int32_t *outDiag, uint64_t *stats) {
+    if (!ctx || !par || !offsets || !letterMap) return SD_EINVAL;
+    (void) hipSetDevice(ctx->device);
+    sdD2HReset(ctx);
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    KmStage stage;
+    const int rcStage = kmRecordsStage(ctx, "sd_kmermatch_batch", par, nSeq, residues, offsets, keys, letterMap, &stage);
+    if (rcStage != SD_OK || stage.empty) return rcStage;
+    hipStream_t st = ctx->stream;
+    const uint64_t nRec = stage.nRec, maxLen = stage.maxLen;
+    const uint32_t maxKey = stage.maxKey;
+    uint64_t *dScanTmp = stage.dScanTmp, *dAt = stage.dAt;
+    uint32_t *dLargest = stage.dLargest, *dRunStart = stage.dRunStart, *dFlag = stage.dFlag;
+    uint32_t *rKeyHi = stage.rKeyHi, *rKeyLo = stage.rKeyLo, *rId = stage.rId, *rLen = stage.rLen, *rPos = stage.rPos;
+    uint32_t *sKeyHi = stage.sKeyHi, *sKeyLo = stage.sKeyLo, *sId = stage.sId, *sLen = stage.sLen, *sPos = stage.sPos;
+    const KmSortBufs &sb = stage.sb;
     const uint32_t r32 = (uint32_t) nRec;
     if (stats) stats[0] = nRec;
     const int idBits = kmBits(maxKey), lenBits = kmBits(maxLen);
@@ -598,6 +657,42 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
         SD_HIP(ctx, hipMemcpyAsync(outDiag, dOutDiag, (size_t) nHits * 4, hipMemcpyDeviceToHost, st));
         SD_HIP(ctx, sdStreamSync(ctx));
     }
+    return SD_OK;
+}
+
+int sd_selftest_kmermatch_records(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSeq, const uint8_t *residues, const uint64_t *offsets,
+                                  const uint32_t *keys, const uint8_t *letterMap, uint64_t recCap, uint32_t *seqConsidered,
+                                  uint32_t *seqThreshold, uint32_t *seqExcess, uint64_t *recOff, uint64_t *recKey, uint32_t *recId,
+                                  uint32_t *recLen, uint32_t *recPos, uint64_t *stats) {
+    if (!ctx || !par || !offsets || !letterMap) return SD_EINVAL;
+    (void) hipSetDevice(ctx->device);
+    sdD2HReset(ctx);
+    if (stats) stats[0] = 0;
+    KmStage stage;
+    const int rcStage = kmRecordsStage(ctx, "sd_selftest_kmermatch_records", par, nSeq, residues, offsets, keys, letterMap, &stage);
+    if (rcStage != SD_OK) return rcStage;
+    if (stage.empty) {
+        if (recOff) recOff[0] = 0;
+        return SD_OK;
+    }
+    const uint64_t nRec = stage.nRec;
+    if (stats) stats[0] = nRec;
+    if (nRec > recCap)
+        return sdFail(ctx, SD_ENOMEM, "sd_selftest_kmermatch_records: %llu records, room for %llu", (unsigned long long) nRec, (unsigned long long) recCap);
+    if (!seqConsidered || !seqThreshold || !seqExcess || !recOff || !recKey || !recId || !recLen || !recPos) return SD_EINVAL;
+    hipStream_t st = ctx->stream;
+    std::vector<uint32_t> hi((size_t) nRec), lo((size_t) nRec);
+    SD_HIP(ctx, hipMemcpyAsync(seqConsidered, stage.dConsOut, (size_t) nSeq * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(seqThreshold, stage.dThr, (size_t) nSeq * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(seqExcess, stage.dExc, (size_t) nSeq * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(recOff, stage.dRecOff, ((size_t) nSeq + 1) * 8, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(hi.data(), stage.rKeyHi, (size_t) nRec * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(lo.data(), stage.rKeyLo, (size_t) nRec * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(recId, stage.rId, (size_t) nRec * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(recLen, stage.rLen, (size_t) nRec * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(recPos, stage.rPos, (size_t) nRec * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, sdStreamSync(ctx));
+    for (uint64_t i = 0; i < nRec; i++) recKey[i] = ((uint64_t) hi[i] << 32) | lo[i];
     return SD_OK;
 }
 

@@ -1,7 +1,9 @@
 """A plain numpy restatement of linclust's kmermatcher for amino-acid sequences in one split (M/src/linclust/kmermatcher.cpp):
 the reduced alphabet, the records of every sequence, the two sorts, assignGroup, writeKmerMatcherResult and the entries of the prefilter DB.
 It is what tests/test_kmermatch.py holds against the vectors recorded from the reference's own object code (tools/make_golden_kmermatch.py)
-and what the GPU tests hold the device against where nothing is recorded.
+and what the GPU tests hold the device against where nothing is recorded.  selection_info gives the selection of one sequence by itself
+(kmerConsidered, threshold, excess, last bin): the generator asserts its class properties with it, the GPU tests hold km_select_kernel's
+per-sequence output against it.
 
 `drop` names one of the reference's quirks to leave out -- the generator asserts that each omission changes a recorded entry:
   'last_bin'   lines 288-296: take every window below the threshold until kmerConsidered are taken
@@ -115,6 +117,31 @@ def can_be_covered(cov_thr, cov_mode, q_len, t_len):
         if cov_mode == 5:
             return np.minimum(t, q) / np.maximum(t, q) >= c
     return np.ones(np.shape(q), bool)
+
+
+def selection_info(par, seq, letter_map):
+    """(windows without X, kmerConsidered, threshold, excess e, size c of the last bin) of one sequence, as records() selects"""
+    k, A = par['k'], par['alph_size']
+    codes = np.asarray(letter_map)[seq].astype(np.uint64)
+    L = len(seq)
+    if L < k:
+        return 0, 0, 0, 0, 0
+    with np.errstate(over='ignore'):
+        idx = np.zeros(L - k + 1, np.uint64)
+        pw = np.uint64(1)
+        for j in range(k):
+            idx += codes[j:j + L - k + 1] * pw
+            pw = pw * np.uint64(A - 1)
+    xc = np.concatenate([[0], np.cumsum(codes == A - 1)])
+    ok = (xc[k:] - xc[:L - k + 1]) == 0
+    score = (xxh64_word(idx[ok], par['hash_shift']) & np.uint64(0xFFFF)).astype(np.int64)
+    want = np.float32(par['kmer_per_seq'] - 1) + np.float32(par['kmer_per_seq_scale']) * np.float32(L)
+    considered = min(int(want) if want > 0 else 0, len(score))
+    if considered == 0:
+        return len(score), 0, 0, 0, 0
+    thr = int(np.sort(score)[considered - 1]) + 1
+    in_bins = int((score < thr).sum())
+    return len(score), considered, thr, in_bins - considered, int((score == thr - 1).sum())
 
 
 def records(par, residues, offsets, keys, letter_map, drop=None):

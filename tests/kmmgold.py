@@ -1,5 +1,6 @@
-"""tests/golden/kmermatch_vectors.npz (tools/make_golden_kmermatch.py: letter maps, records and entries from the reference's own object
-code) as the kmermatcher tests read it."""
+"""tests/golden/kmermatch_vectors.npz and kmermatch_edges.npz (tools/make_golden_kmermatch.py: letter maps, records and entries from the
+reference's own object code) as the kmermatcher tests read them: one table of arrays.  The second file holds set E and further runs of
+sets of the first (<S>_more_runs of them, numbered on from <S>_runs)."""
 import functools
 import gzip
 import os
@@ -8,17 +9,33 @@ import numpy as np
 
 from dbutil import GOLD, write_db
 
-SETS = ['S', 'G', 'H', 'A', 'W', 'C1']
+SETS = ['S', 'G', 'H', 'A', 'W', 'C1', 'E']
 LETTERS = 'ACDEFGHIKLMNPQRSTVWYX'
+
+
+class _Files:
+    def __init__(self, *names):
+        self.files = [np.load(os.path.join(GOLD, n)) for n in names]
+
+    def __contains__(self, key):
+        return any(key in f.files for f in self.files)
+
+    def __getitem__(self, key):
+        for f in self.files:
+            if key in f.files:
+                return f[key]
+        raise KeyError(key)
 
 
 @functools.lru_cache(None)
 def golden():
-    return np.load(os.path.join(GOLD, 'kmermatch_vectors.npz'))
+    return _Files('kmermatch_vectors.npz', 'kmermatch_edges.npz')
 
 
 def runs(name):
-    return ['%s_r%d' % (name, r) for r in range(int(golden()[name + '_runs']))]
+    g = golden()
+    n = int(g[name + '_runs']) + (int(g[name + '_more_runs']) if name + '_more_runs' in g else 0)
+    return ['%s_r%d' % (name, r) for r in range(n)]
 
 
 ALL_RUNS = [r for s in SETS for r in runs(s)]

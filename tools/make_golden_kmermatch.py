@@ -28,6 +28,8 @@ Util and Debug, and is linked with section GC so that what kmermatcher.cpp's unu
     setLinearFilterDefault / setKmerLengthAndAlphabet   kmm_ref.params / kmm_ref.auto_k: the runs record the k and alphabet they used
 
     python tools/make_golden_kmermatch.py [reference root]          (needs `make -C oracle _ref/libsdref.so`; no GPU)
+    python tools/make_golden_kmermatch.py --edges [reference root]  (writes tests/golden/kmermatch_edges.npz alone: set E and further
+                                                                     runs of G, see main_edges(); reads kmermatch_vectors.npz)
     python tools/make_golden_kmermatch.py --time <file.npz> <threads>   (the driver's seconds on the sequences of tools/bench_kmermatcher.py --dump)
 
 Per set <S>: <S>_res (21-letter codes), <S>_off, and per run <S>_r<i>_{keys, par, map, rec_key, rec_pos, rec_off, db_keys, db_off, db_text}
@@ -35,6 +37,8 @@ Per set <S>: <S>_res (21-letter codes), <S>_off, and per run <S>_r<i>_{keys, par
 tests/golden/examples -- and no records).  <S>_class_names / <S>_class_seq name the sequences built for a class.  Sets: see set_s() ... below.
 main() asserts every class property with tests/kmm_ref.py before recording, that kmm_ref equals every recorded stage, and that leaving out
 each of the three quirks kmm_ref.py names changes a recorded entry of S or G.
+kmermatch_edges.npz has the same layout for set E (set_e(): the edges of the device's lane logic) and for the runs r6 .. r8 of G, whose
+sequences stay in the first file; <S>_more_runs counts the runs a set of the first file gains there.  tests/kmmgold.py reads both as one.
 """
 import gzip
 import io
@@ -54,6 +58,7 @@ import kmm_ref  # noqa: E402
 
 GOLD = os.path.join(ROOT, 'tests', 'golden')
 OUT = os.path.join(GOLD, 'kmermatch_vectors.npz')
+OUT_EDGES = os.path.join(GOLD, 'kmermatch_edges.npz')
 LETTERS = 'ACDEFGHIKLMNPQRSTVWYX'
 
 DRIVER = r'''
@@ -339,29 +344,7 @@ def flat(seqs):
     return (np.concatenate(seqs).astype(np.uint8) if seqs else np.zeros(0, np.uint8)), off
 
 
-def selection_info(par, seq, letter_map):
-    """(windows without X, kmerConsidered, threshold, excess e, size c of the last bin) of one sequence, as kmm_ref.records selects"""
-    k, A = par['k'], par['alph_size']
-    codes = np.asarray(letter_map)[seq].astype(np.uint64)
-    L = len(seq)
-    if L < k:
-        return 0, 0, 0, 0, 0
-    with np.errstate(over='ignore'):
-        idx = np.zeros(L - k + 1, np.uint64)
-        pw = np.uint64(1)
-        for j in range(k):
-            idx += codes[j:j + L - k + 1] * pw
-            pw = pw * np.uint64(A - 1)
-    xc = np.concatenate([[0], np.cumsum(codes == A - 1)])
-    ok = (xc[k:] - xc[:L - k + 1]) == 0
-    score = (kmm_ref.xxh64_word(idx[ok], par['hash_shift']) & np.uint64(0xFFFF)).astype(np.int64)
-    want = np.float32(par['kmer_per_seq'] - 1) + np.float32(par['kmer_per_seq_scale']) * np.float32(L)
-    considered = min(int(want) if want > 0 else 0, len(score))
-    if considered == 0:
-        return len(score), 0, 0, 0, 0
-    thr = int(np.sort(score)[considered - 1]) + 1
-    in_bins = int((score < thr).sum())
-    return len(score), considered, thr, in_bins - considered, int((score == thr - 1).sum())
+selection_info = kmm_ref.selection_info
 
 
 def set_s(lmap):
@@ -513,6 +496,126 @@ def set_w():
     return seqs, [keys, keys], [kmm_ref.params(k=10, kmer_per_seq_scale=0.05, c=0.0), kmm_ref.params(k=10)], {'long': 0}
 
 
+E_LENGTHS = (9, 10, 11, 63, 64, 65, 73, 74, 127, 128, 129, 137, 138, 201)   # k - 1, k, k + 1; 64, 65, 128 and 129 windows at k 10
+E_PERIODS = (1, 2, 3, 5, 7)
+
+
+def set_e(lmap):
+    """the edges of the device's lane logic (kmermatch_edges.npz): 64-window chunks, 64 lane blocks of the identity hash, X on chunk edges,
+    repeats (nothing is masked), thresholds at both ends of the score range.  Keys shuffled and not dense.  Runs: r0 defaults at k 10;
+    r1 / r2 --kmer-per-seq 150 / 300; r3 --kmer-per-seq-scale 1.0; r4 --kmer-per-seq 2; r5 k 14 on 21 letters; r6 --hash-shift -3"""
+    rng = np.random.default_rng(29)
+    runs = [kmm_ref.params(k=10), kmm_ref.params(k=10, kmer_per_seq=150), kmm_ref.params(k=10, kmer_per_seq=300),
+            kmm_ref.params(k=10, kmer_per_seq_scale=1.0), kmm_ref.params(k=10, kmer_per_seq=2), kmm_ref.params(k=14, alph_size=21),
+            kmm_ref.params(k=10, hash_shift=-3)]
+    seqs, classes = [], {}
+
+    def add(name, s):
+        classes[name] = len(seqs)
+        seqs.append(np.asarray(s, np.uint8))
+
+    for length in E_LENGTHS:
+        add('length_%d' % length, rnd(rng, length))
+    for name, at in (('x_at_63', [63]), ('x_at_64', [64]), ('x_at_73', [73]), ('ends_in_x', [199]),
+                     # every window that starts before 64 or from 128 on holds an X: windows 64 .. 127 alone are free
+                     ('free_in_second_chunk_only', list(range(3, 64, 10)) + list(range(137, 200, 10)))):
+        s = rnd(rng, 200)
+        s[at] = 20
+        add(name, s)
+    # letters of seven different classes of the 13-letter alphabet, so that the period stays what it is after reduction
+    unit = np.array([LETTERS.index(c) for c in 'ACDEFGH'], np.uint8)
+    assert len(set(lmap[unit].tolist())) == 7
+    for p in E_PERIODS:
+        add('period_%d' % p, np.tile(unit[:p], 400 // p + 1)[:400])
+    s = rnd(rng, 300)
+    s[90:210] = LETTERS.index('K')
+    add('homopolymer_inside', s)
+    top = bottom = coarse0 = None
+    while top is None or bottom is None:
+        s = rnd(rng, 300)
+        if top is None and selection_info(runs[3], s, lmap)[2] == 65536:
+            top = s
+        elif bottom is None and selection_info(runs[4], s, lmap)[2] == 1:
+            bottom = s
+    while coarse0 is None:
+        s = rnd(rng, 3000)
+        if selection_info(runs[0], s, lmap)[2] < 512:
+            coarse0 = s
+    add('threshold_65536', top)
+    add('threshold_1', bottom)
+    add('threshold_in_coarse_bin_0', coarse0)
+    base = len(seqs)
+    for c in ('length_201', 'length_138', 'x_at_64', 'free_in_second_chunk_only', 'homopolymer_inside', 'threshold_65536', 'threshold_1'):
+        seqs.append(mutate(rng, seqs[classes[c]], 0.04))
+    for p in E_PERIODS:   # a repeat with a few residues changed, and a shorter stretch of the same repeat
+        seqs.append(mutate(rng, seqs[classes['period_%d' % p]], 0.02))
+    seqs.append(seqs[classes['period_3']][:330].copy())
+    seqs.append(seqs[classes['period_7']][5:370].copy())
+    seqs.append(mutate(rng, coarse0, 0.02)[:2800])
+    classes['relatives_from'] = base
+    keys = (11 + 37 * rng.permutation(len(seqs))).astype(np.uint32)
+    return seqs, [keys] * len(runs), runs, classes
+
+
+def check_classes_e(recorded, lmap13):
+    """the class properties of set E, from the restatement alone"""
+    par, res, off, keys, lmap, db, seqs, cl = recorded['E_r0']
+    info = lambda run, c: selection_info(recorded['E_r%d' % run][0], seqs[cl[c]], lmap13)
+    for length in E_LENGTHS:
+        assert info(0, 'length_%d' % length)[0] == max(length - 9, 0)
+    assert [info(0, 'length_%d' % n)[0] for n in (73, 74, 137, 138)] == [64, 65, 128, 129]
+    assert [info(0, c)[0] for c in ('x_at_63', 'x_at_64', 'x_at_73', 'ends_in_x')] == [181, 181, 181, 190]
+    rec = kmm_ref.records(recorded['E_r1'][0], *flat([seqs[cl['free_in_second_chunk_only']]]), np.array([0], np.uint32), lmap13)
+    assert info(1, 'free_in_second_chunk_only')[:2] == (64, 64) and rec[3][1:].tolist() == list(range(64, 128))
+    # repeats: p different windows, each some 391 / p times -- whole score bins of equal windows
+    w, cons, thr, e, c = info(1, 'period_3')
+    assert (w, cons) == (391, 149) and e > 64 and c > 64
+
+    def from_last_bin(run, c):
+        """positions of the windows taken from the last bin"""
+        p = recorded['E_r%d' % run][0]
+        rec = kmm_ref.records(p, *flat([seqs[cl[c]]]), np.array([0], np.uint32), lmap13)
+        score = (kmm_ref.xxh64_word(rec[0][1:], p['hash_shift']) & np.uint64(0xFFFF)).astype(np.int64)
+        return rec[3][1:][score == info(run, c)[2] - 1], len(score)
+
+    # (kmerConsidered ends this selection, after 75 windows of the last bin in four 64-window chunks)
+    taken, selected = from_last_bin(1, 'period_3')
+    assert selected == cons and 64 < len(taken) < e and len(set((taken // 64).tolist())) >= 3
+    # the excess ends these two, in the second chunk or later: fewer than kmerConsidered windows are taken, and the count of last-bin
+    # windows seen has to be carried from chunk to chunk
+    for run, c in ((2, 'period_1'), (1, 'period_2')):
+        w, cons, thr, e, c_last = info(run, c)
+        taken, selected = from_last_bin(run, c)
+        assert 0 < e < c_last and len(taken) == e and selected < cons and int(taken.max()) >= 64, (run, c)
+    assert info(2, 'period_1')[3] > 64   # (more than a chunk of them)
+    w, cons, thr, e, c = info(0, 'period_1')
+    assert (w, cons, c) == (391, 19, 391) and e == 372 and e > cons
+    for p in E_PERIODS:
+        assert info(2, 'period_%d' % p)[4] >= 391 // p
+    assert info(3, 'threshold_65536')[1:3] == (291, 65536) and info(4, 'threshold_1')[1:3] == (1, 1)
+    assert info(0, 'threshold_in_coarse_bin_0')[2] < 512 and info(0, 'threshold_in_coarse_bin_0')[0] == 2991
+    assert sum(t.count(b'\n') > 1 for t in db.values()) >= 8   # the relatives give hits and groups
+    assert len(set(np.diff(np.sort(keys)).tolist())) == 1 and int(np.diff(np.sort(keys))[0]) == 37 and (np.diff(keys.astype(np.int64)) < 0).any()
+    assert recorded['E_r5'][0]['alph_size'] == 21 and recorded['E_r6'][0]['hash_shift'] == -3
+    rec = kmm_ref.records(recorded['E_r5'][0], *flat([seqs[cl['length_201']]]), np.array([0], np.uint32), recorded['E_r5'][4])
+    assert (rec[0][1:] >> np.uint64(32)).any()   # 20^13 and more: the k-mer index of 14 letters uses the key's high word
+
+
+def check_coverage_modes(recorded):
+    """G under --cov-mode 3, 4 and 5 at -c 0.8: the members of the `coverage` representative (100 residues; pieces of 80, 79, 80, 79).
+    A representative is the longest sequence of its run (the first sort's seqLen-descending field), so target / query = min / max <= 1
+    for every pair: modes 3 and 5 must coincide, here and everywhere.  Mode 4 asks query / target <= 1: only members as long as the
+    representative remain, none of `coverage` and the second of `identical`."""
+    par, res, off, keys, lmap, db, seqs, cl = recorded['G_r6']
+    lines = lambda d, k: [tuple(int(x) for x in l.split(b'\t')) for l in d[k].splitlines()]
+    k = [int(keys[cl['coverage'] + j]) for j in range(5)]
+    cov = lambda tag: [l[0] for l in lines(recorded[tag][5], k[0])][1:]
+    assert [recorded['G_r%d' % r][0]['cov_mode'] for r in (6, 7, 8)] == [3, 4, 5]
+    assert cov('G_r6') == [k[1], k[3]] and cov('G_r7') == [] and cov('G_r8') == [k[1], k[3]]
+    i = cl['identical']
+    assert [l[0] for l in lines(recorded['G_r7'][5], int(keys[i]))] == [int(keys[i]), int(keys[i + 1])]
+
+
 def set_c1():
     from spacedust_amd.api import Host
     host = Host()
@@ -544,13 +647,43 @@ def blosum_prob():
     return kmm_ref.matrix_prob(buf.value.decode())
 
 
+def record_run(out, recorded, exe, tmp, matrix, prob, name, r, par, keys, res, off, seqs, classes):
+    """one run of the driver into out / recorded, after the restatement has been held against every stage of it"""
+    got = run_driver(exe, tmp, matrix, par, res, off, keys, want_records=name != 'C1')
+    tag = '%s_r%d' % (name, r)
+    out[tag + '_keys'], out[tag + '_par'], out[tag + '_map'] = keys, par_array(par), got['map']
+    lmap = kmm_ref.reduced_alphabet(prob, par['alph_size'])
+    assert np.array_equal(lmap, got['map']), (tag, lmap, got['map'])
+    hits, stats, rec = kmm_ref.kmermatch(par, res, off, keys, lmap)
+    if name != 'C1':
+        # emission order: the driver reads in key order; per sequence (key, pos) as emitted
+        order = np.argsort(keys, kind='stable')
+        want_key = np.concatenate([rec[0][rec[4][i]:rec[4][i + 1]] for i in order])
+        want_pos = np.concatenate([rec[3][rec[4][i]:rec[4][i + 1]] for i in order])
+        want_id = np.concatenate([rec[1][rec[4][i]:rec[4][i + 1]] for i in order])
+        assert np.array_equal(got['rec_id'], want_id), tag
+        assert np.array_equal(got['rec_key'], want_key) and np.array_equal(got['rec_pos'], want_pos), tag
+        out[tag + '_rec_key'], out[tag + '_rec_pos'] = got['rec_key'], got['rec_pos'].astype(np.int32)
+        cnt = np.diff(rec[4])[order]
+        out[tag + '_rec_off'] = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint64)
+    assert kmm_ref.entries(keys, hits) == got['db'], tag
+    pack_db(out, tag + '_db', got['db'])
+    recorded[tag] = (par, res, off, keys, lmap, got['db'], seqs, classes)
+    print('%s: %d sequences, %d records, %d grouped, %d hits, largest group %d' % (tag, len(keys), stats['records'], stats['grouped'],
+                                                                                 stats['hits'], stats['largest_group']))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == '--time':
         return time_driver(sys.argv[2], int(sys.argv[3]))
-    ref_root = sys.argv[1] if len(sys.argv) > 1 else '/root/reference'
+    edges = len(sys.argv) > 1 and sys.argv[1] == '--edges'
+    args = sys.argv[2:] if edges else sys.argv[1:]
+    ref_root = args[0] if args else '/root/reference'
     matrix = os.path.join(ref_root, 'lib', 'mmseqs', 'data', 'blosum62.out')
     prob = blosum_prob()
     lmap13 = kmm_ref.reduced_alphabet(prob, 13)
+    if edges:
+        return main_edges(ref_root, matrix, prob, lmap13)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         exe = build_driver(ref_root, tmp)
@@ -564,28 +697,7 @@ def main():
             out[name + '_class_seq'] = np.array([classes[c] for c in sorted(classes)], np.int64)
             out[name + '_runs'] = np.int64(len(runs))
             for r, (par, keys) in enumerate(zip(runs, keys_of_run)):
-                got = run_driver(exe, tmp, matrix, par, res, off, keys, want_records=name != 'C1')
-                tag = '%s_r%d' % (name, r)
-                out[tag + '_keys'], out[tag + '_par'], out[tag + '_map'] = keys, par_array(par), got['map']
-                lmap = kmm_ref.reduced_alphabet(prob, par['alph_size'])
-                assert np.array_equal(lmap, got['map']), (tag, lmap, got['map'])
-                hits, stats, rec = kmm_ref.kmermatch(par, res, off, keys, lmap)
-                if name != 'C1':
-                    # emission order: the driver reads in key order; per sequence (key, pos) as emitted
-                    order = np.argsort(keys, kind='stable')
-                    want_key = np.concatenate([rec[0][rec[4][i]:rec[4][i + 1]] for i in order])
-                    want_pos = np.concatenate([rec[3][rec[4][i]:rec[4][i + 1]] for i in order])
-                    want_id = np.concatenate([rec[1][rec[4][i]:rec[4][i + 1]] for i in order])
-                    assert np.array_equal(got['rec_id'], want_id), tag
-                    assert np.array_equal(got['rec_key'], want_key) and np.array_equal(got['rec_pos'], want_pos), tag
-                    out[tag + '_rec_key'], out[tag + '_rec_pos'] = got['rec_key'], got['rec_pos'].astype(np.int32)
-                    cnt = np.diff(rec[4])[order]
-                    out[tag + '_rec_off'] = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint64)
-                assert kmm_ref.entries(keys, hits) == got['db'], tag
-                pack_db(out, tag + '_db', got['db'])
-                recorded[tag] = (par, res, off, keys, lmap, got['db'], seqs, classes)
-                print('%s: %d sequences, %d records, %d grouped, %d hits, largest group %d' % (tag, len(keys), stats['records'], stats['grouped'],
-                                                                                             stats['hits'], stats['largest_group']))
+                record_run(out, recorded, exe, tmp, matrix, prob, name, r, par, keys, res, off, seqs, classes)
         check_classes(recorded, lmap13)
         # each quirk left out changes a recorded entry of S or G
         for drop in ('last_bin', 'tie', 'len_desc'):
@@ -599,6 +711,35 @@ def main():
             print('without %s: %s differ' % (drop, ', '.join(changed)))
     save(OUT, out)
     print('wrote %s (%d bytes)' % (OUT, os.path.getsize(OUT)))
+
+
+def main_edges(ref_root, matrix, prob, lmap13):
+    """kmermatch_edges.npz: set E, and set G again under --cov-mode 3, 4 and 5 as its runs r6 .. r8 (G's sequences and keys are those of
+    kmermatch_vectors.npz, which this mode reads and does not write: <S>_more_runs counts the runs a set gains here)"""
+    old = np.load(OUT)
+    out, recorded = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = build_driver(ref_root, tmp)
+        seqs, keys_of_run, runs, classes = set_e(lmap13)
+        res, off = flat(seqs)
+        out['E_res'], out['E_off'] = res, off
+        out['E_class_names'] = np.array(sorted(classes), dtype='U40')
+        out['E_class_seq'] = np.array([classes[c] for c in sorted(classes)], np.int64)
+        out['E_runs'] = np.int64(len(runs))
+        for r, (par, keys) in enumerate(zip(runs, keys_of_run)):
+            record_run(out, recorded, exe, tmp, matrix, prob, 'E', r, par, keys, res, off, seqs, classes)
+        check_classes_e(recorded, lmap13)
+        seqs, keys_of_run, runs, classes = set_g(lmap13)
+        res, off = flat(seqs)
+        assert np.array_equal(res, old['G_res']) and np.array_equal(off, old['G_off']) and np.array_equal(keys_of_run[0], old['G_r0_keys'])
+        first = int(old['G_runs'])
+        out['G_more_runs'] = np.int64(3)
+        for r, mode in enumerate((3, 4, 5)):
+            record_run(out, recorded, exe, tmp, matrix, prob, 'G', first + r, kmm_ref.params(k=10, cov_mode=mode, c=0.8), keys_of_run[0], res, off,
+                       seqs, classes)
+        check_coverage_modes(recorded)
+    save(OUT_EDGES, out)
+    print('wrote %s (%d bytes)' % (OUT_EDGES, os.path.getsize(OUT_EDGES)))
 
 
 def check_classes(recorded, lmap13):
