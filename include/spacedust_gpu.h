@@ -214,6 +214,14 @@ int sd_sw_set_narrow_final(sd_ctx *ctx, int on);
  * in-memory iterations switch it on for their own contexts (SD_SW_SHARED_START=0 in the environment keeps it off there).  With
  * profiling enabled these launches appear in scopes of their own, sw_score_pk.s_seg5 .. s_seg24. */
 int sd_sw_set_shared_start(sd_ctx *ctx, int on);
+/* on != 0: in the alignment calls of this context the forward score passes run the paired narrow tasks of 129 .. 448 query rows
+ * (scopes sw_score_pk.a_seg5 .. a_seg14) on 16-lane groups: four task pairs of one query per wavefront, twice the rows per lane,
+ * instead of two pairs on 32-lane groups.  The same cells are evaluated and the end cell is chosen by the same rule (largest
+ * value, first column, smallest row), so records, flags and backtraces are the same bytes, and so are the scopes and the number of
+ * launches per scope; only the grids shrink.  Not affected: every other class, the start-position pass, unpaired tasks (query sets
+ * of 2^17 sequences or more) and calls on the int32 kernel.  Off by default; the streaming search (sd_search_*) and the in-memory
+ * iterations switch it on for their own contexts (SD_SW_GROUP16=0 in the environment keeps it off there). */
+int sd_sw_set_group16(sd_ctx *ctx, int on);
 
 /* ---- self-test entry points of the library's own device primitives (csrc/hip/sd_scan_sort.h), for tests/ ----------------------
  * sd_selftest_sort_pairs: stable sort of (key, value) pairs by the key bits [beginBit, endBit) -- what the alignment task order and

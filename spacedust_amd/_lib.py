@@ -264,6 +264,7 @@ def load():
         'sd_sw_download_bytes': (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         'sd_sw_set_narrow_final': (C.c_int, [_vp, C.c_int]),
         'sd_sw_set_shared_start': (C.c_int, [_vp, C.c_int]),
+        'sd_sw_set_group16': (C.c_int, [_vp, C.c_int]),
         'sd_r2p_create': (C.c_int, [C.POINTER(_vp)]),
         'sd_r2p_destroy': (None, [_vp]),
         'sd_r2p_batch': (C.c_int, [_vp, C.POINTER(R2pParams), C.c_uint32] + [_vp] * 12),

@@ -535,6 +535,11 @@ class Context:
         of the whole reversed query (scopes sw_score_pk.s_seg*); same records"""
         _check(self.h, self.L.sd_sw_set_shared_start(self.h, 1 if on else 0), 'sd_sw_set_shared_start')
 
+    def set_group16(self, on=True):
+        """sd_sw_set_group16: the paired forward score tasks of 129 .. 448 query rows run on 16-lane groups, four task pairs of one
+        query per wavefront (same records, scopes and launch counts; off by default)"""
+        _check(self.h, self.L.sd_sw_set_group16(self.h, 1 if on else 0), 'sd_sw_set_group16')
+
     def sw_download_bytes(self):
         a, b = C.c_uint64(), C.c_uint64()
         self.L.sd_sw_download_bytes(self.h, C.byref(a), C.byref(b))

@@ -103,6 +103,7 @@ struct Worker {
         if (r2p) sd_r2p_destroy(r2p);
         if (ctx) sd_sw_set_narrow_final(ctx, 0);
         if (ctx) sd_sw_set_shared_start(ctx, 0);
+        if (ctx) sd_sw_set_group16(ctx, 0);
         if (ctx) sd_ctx_destroy(ctx);
         if (host) sd_host_destroy(host);
     }
@@ -407,6 +408,8 @@ int iterativeClusterSearchInMemory(const Args &a, const std::string &Q, const st
         sd_sw_set_narrow_final(W.ctx, (getenv("SD_SW_NARROW_FINAL") && atoi(getenv("SD_SW_NARROW_FINAL")) == 0) ? 0 : 1);
         // narrow start-position tasks of one query share the query's profile (same records; SD_SW_SHARED_START=0: a profile per task)
         sd_sw_set_shared_start(W.ctx, (getenv("SD_SW_SHARED_START") && atoi(getenv("SD_SW_SHARED_START")) == 0) ? 0 : 1);
+        // paired forward tasks of 129 .. 448 rows on 16-lane groups, four pairs of a query per wavefront (same records; SD_SW_GROUP16=0: 32-lane groups)
+        sd_sw_set_group16(W.ctx, (getenv("SD_SW_GROUP16") && atoi(getenv("SD_SW_GROUP16")) == 0) ? 0 : 1);
     }
     // ---- the target: both indexes (the sequence search's k-mer threshold; every k-mer for the profile searches,
     // Prefiltering.cpp:525-527) and the sequences, resident for the whole run

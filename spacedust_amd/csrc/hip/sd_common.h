@@ -41,6 +41,7 @@ struct sd_ctx {
     size_t alignDevResN = 0;
     bool cigarPool = false;   // sd_sw_set_cigar_pool: the alignment calls return run-length text instead of backtrace letters
     bool sharedStart = false; // sd_sw_set_shared_start: narrow start-position tasks of a query of 129 .. 768 rows share the query's one profile
+    bool group16 = false;     // sd_sw_set_group16: the paired forward tasks of 129 .. 448 rows run on 16-lane groups, four pairs of a query per wavefront
     bool narrowFinal = false; // sd_sw_set_narrow_final: a narrow forward score below 1023 is final, only the other saturating pairs rerun wide
     uint64_t d2hRecordBytes = 0, d2hPoolBytes = 0;  // what the alignment calls brought back (sd_sw_download_bytes)
     // the last sd_expand_batch call as it lies in the workspace (valid until the next one): what sd_expand_backtraces walks again

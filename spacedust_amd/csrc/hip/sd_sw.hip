@@ -800,12 +800,29 @@ void launchScorePk(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, ui
                        t->dRes, dMat, go, ge, dOut, dBound, dOrder, (const int8_t *) q->dProf);
 }
 
+// Task pairs per wavefront of the shared side of class ci: two 32-lane groups, or -- sd_sw_set_group16, forward passes, the aligned
+// classes of up to GROUP16_ROWS_MAX rows, a_seg5 .. a_seg14 -- four 16-lane groups (defined beside pairedClass; the pairing kernels pad a query's run
+// of pairs to this many, and the launcher of the aligned kernel sizes its grid by it)
+// (the row code allows 2 * RT <= 32 rows per lane, i.e. up to 512 rows; a_seg15 and a_seg16 were measured no faster on 16 lanes than
+// on 32 -- DESIGN.md 4.1, profiles/sw_group16.json -- and stay there)
+constexpr int GROUP16_ROWS_MAX = 448;
+constexpr __host__ __device__ uint32_t pairsPerWave(uint32_t ci, int startOnly, int group16);
+constexpr uint32_t alignedClass(int RT) { return (uint32_t) RT - 4; }   // a_seg<RT>, checked below the class table
+
 template <int RT, bool SHARED, bool START = false>
 void launchScorePkAligned(sd_ctx *ctx, const SwTask *dTasks, const uint32_t *dOrder, uint32_t n, const sd_seqset *q, const sd_seqset *t,
                           const int8_t *dMat, int go, int ge, int32_t *dOut, uint2 * /* dBound: one strip */) {
     if (n == 0) return;
-    constexpr uint32_t perWave = 4;   // two 32-lane groups of a task pair each
+    // a task pair per group of lanes: two 32-lane groups, or four 16-lane ones (shared forward side only)
+    const uint32_t perWave = (SHARED && !START) ? 2 * pairsPerWave(alignedClass(RT), 0, ctx->group16 ? 1 : 0) : 4;
     dim3 grid((n + perWave - 1) / perWave), block(64);
+    if constexpr (SHARED && !START && 32 * RT <= GROUP16_ROWS_MAX) {
+        if (perWave == 8) {
+            hipLaunchKernelGGL((sdpk::sw_score_pk_aligned_kernel<RT, true, false, 16>), grid, block, 0, ctx->stream, dTasks, n, q->dRes, q->dBias,
+                               t->dRes, dMat, go, ge, dOut, dOrder, (const int8_t *) q->dProf);
+            return;
+        }
+    }
     hipLaunchKernelGGL((sdpk::sw_score_pk_aligned_kernel<RT, SHARED, START>), grid, block, 0, ctx->stream, dTasks, n, q->dRes, q->dBias, t->dRes,
                        dMat, go, ge, dOut, dOrder, (const int8_t *) q->dProf);
 }
@@ -1690,6 +1707,13 @@ constexpr int PAIR_QUERY_BITS = 17;
 __host__ __device__ __forceinline__ bool pairedClass(uint32_t ci, int startOnly) {
     return startOnly ? ci >= FIRST_START_CLASS && ci < N_SCORE_CLASSES : ci < FIRST_INT32_CLASS;
 }
+// Pairs per wavefront of a paired class (declared above launchScorePkAligned): a (class, query) run is padded to a multiple of it
+constexpr __host__ __device__ uint32_t pairsPerWave(uint32_t ci, int startOnly, int group16) {
+    return group16 && !startOnly && ci >= alignedClass(5) && ci <= alignedClass(GROUP16_ROWS_MAX / 32) ? 4u : 2u;
+}
+static_assert(SCORE_CLASSES[alignedClass(5)].form == SCORE_PK && SCORE_CLASSES[alignedClass(5)].rows == 5 * 32 &&
+              SCORE_CLASSES[alignedClass(24)].form == SCORE_PK && SCORE_CLASSES[alignedClass(24)].rows == 24 * 32,
+              "alignedClass: a_seg5 .. a_seg24 are the classes 1 .. 20");
 __global__ void __launch_bounds__(256)
 k_pair_keys(uint32_t n, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ pairQ, uint32_t *__restrict__ key2, int startOnly) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1709,11 +1733,11 @@ k_pair_heads(uint32_t n, const uint32_t *__restrict__ keyS, uint32_t *__restrict
     headPos[p] = head ? p : 0u;
 }
 // leader[p] = pairs that start at sorted position p: 1 for every second task of a (class, query) run; the run's last task adds
-// one EMPTY pair when the run holds an odd number of pairs, so that every wavefront of four tasks (two pairs) stays inside one
-// query (sw_score_pk_aligned_kernel<.., SHARED = true>: one profile per wavefront)
+// the EMPTY pairs that fill the run up to whole wavefronts (pairsPerWave: two pairs, or four on 16-lane groups), so that every
+// wavefront stays inside one query (sw_score_pk_aligned_kernel<.., SHARED = true>: one profile per wavefront)
 __global__ void __launch_bounds__(256)
 k_pair_leaders(uint32_t n, const uint32_t *__restrict__ keyS, const uint32_t *__restrict__ runStart, uint8_t *__restrict__ leader,
-               int startOnly) {
+               int startOnly, int group16) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p > n) return;
     uint8_t v = 0;
@@ -1722,7 +1746,8 @@ k_pair_leaders(uint32_t n, const uint32_t *__restrict__ keyS, const uint32_t *__
         v = (o & 1u) == 0 ? 1 : 0;
         const bool lastOfRun = p + 1 >= n || (keyS[p + 1] >> 9) != (keyS[p] >> 9);
         const uint32_t pairs = (o + 1 + 1) / 2;   // pairs of the run = ceil((o + 1) / 2)
-        if (lastOfRun) v += (uint8_t) (pairs & 1u);
+        const uint32_t ppw = pairsPerWave(keyS[p] >> 26, startOnly, group16);
+        if (lastOfRun) v += (uint8_t) ((ppw - pairs % ppw) % ppw);
     }
     leader[p] = v;
 }
@@ -1787,7 +1812,7 @@ int devRunScore(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs, const uint32_t *
         SD_HIP(ctx, wsGet(ctx, "sp.runstart", (size_t) nPairs, &dRunStart));
         SD_HIP(ctx, wsGet(ctx, "sp.leader", (size_t) nPairs + 1, &dLeader));
         SD_HIP(ctx, wsGet(ctx, "sp.pairidx", (size_t) nPairs + 1, &dPairIdx));
-        const size_t order2Cap = (size_t) 4 * nPairs + 8;   // worst case: every run one task, padded to a wavefront (two pairs)
+        const size_t order2Cap = (size_t) 8 * nPairs + 16;   // worst case: every run one task, padded to a wavefront (four pairs)
         SD_HIP(ctx, wsGet(ctx, "sp.order2", order2Cap, &dOrder2));
         SD_HIP(ctx, hipMemsetAsync(dOrder2, 0xFF, order2Cap * sizeof(uint32_t), ctx->stream));   // empty pairs: PAIR_NONE
         SD_HIP(ctx, wsGet(ctx, "sp.bounds", 64, &dPairBounds));
@@ -1798,7 +1823,8 @@ int devRunScore(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs, const uint32_t *
         hipLaunchKernelGGL(k_pair_heads, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dHead);
         rc = devInclusiveMax(ctx, dHead, dRunStart, nPairs);
         if (rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dRunStart, dLeader, startOnly);
+        hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dRunStart, dLeader, startOnly,
+                           ctx->group16 ? 1 : 0);
         rc = devExclusiveScan(ctx, (const uint8_t *) dLeader, dPairIdx, (size_t) nPairs + 1);
         if (rc != SD_OK) return rc;
         hipLaunchKernelGGL(k_pair_emit, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dVals2, dRunStart, dPairIdx, dOrder2, startOnly);
@@ -2762,6 +2788,12 @@ int sd_sw_set_narrow_final(sd_ctx *ctx, int on) {
 int sd_sw_set_shared_start(sd_ctx *ctx, int on) {
     if (!ctx) return SD_EINVAL;
     ctx->sharedStart = on != 0;
+    return SD_OK;
+}
+
+int sd_sw_set_group16(sd_ctx *ctx, int on) {
+    if (!ctx) return SD_EINVAL;
+    ctx->group16 = on != 0;
     return SD_OK;
 }
 

@@ -101,6 +101,19 @@ __device__ __forceinline__ uint32_t dppShr1(uint32_t v) {
     return (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
 }
 
+// the same inside every row of 16 lanes: the first lane of a row receives 0
+__device__ __forceinline__ uint32_t dppRowShr1(uint32_t v) {
+    return (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x111 /* row_shr:1 */, 0xf, 0xf, true);
+}
+// ... and the first lane of a row keeps `first`'s value instead
+__device__ __forceinline__ uint32_t dppRowShr1Keep(uint32_t first, uint32_t v) {
+    return (uint32_t) __builtin_amdgcn_update_dpp((int) first, (int) v, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
+}
+// lane i of a row receives lane i + 1 of the row, the last lane the first one's
+__device__ __forceinline__ uint32_t dppRowRol1(uint32_t v) {
+    return (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x12F /* row_ror:15 */, 0xf, 0xf, false);
+}
+
 // value (wave-uniform) into one lane of a VGPR
 template <int LANE>
 __device__ __forceinline__ uint32_t writeLane(uint32_t value, uint32_t old) {
@@ -429,8 +442,18 @@ __device__ __forceinline__ uint32_t addWord1(uint32_t base, uint32_t packed) {  
 // SHARED: false = every task has its own profile; true = ALL four tasks of the wavefront have the same query (the caller pads a
 // query's run of pairs to whole wavefronts): one profile per wavefront, a quarter of the LDS, which is what lets the memory-bound
 // prefilter workgroups of the other streams live on the same CUs.  Removed variants, each measured no faster (DESIGN.md §4.1,
-// profiles/r05_experiments.txt): 16-lane groups of two segments per lane, one profile per task pair, two wavefronts per
-// workgroup sharing the profile, and quads of one query chained through one wavefront.
+// profiles/r05_experiments.txt): one profile per task pair, two wavefronts per workgroup sharing the profile, and quads of one
+// query chained through one wavefront.  (16-lane groups were among them while a lane had to be a segment of the Fl chain -- two
+// segments per lane, with masks and resets -- and every task pair had its own profile; both are gone, and the groups are back as LW.)
+// LW (SHARED forward form only, sd_sw_set_group16): lanes per task pair.  32 = the layout above.  16 = four groups, EIGHT tasks of
+// one query per wavefront, a lane holds 2 RT rows (rows l * 2 RT ..), the one profile holds the same bytes dealt to 16 lanes:
+//   * a group is one DPP row: row_shr:1 with bound_ctrl hands G and Ff on and zero-fills the first lane of every group, and the
+//     residue stream is the chunk register turned by one lane per step (row_ror) plus one row_shr:1 move that keeps its first
+//     lane -- no v_readlane / v_writelane in the loop;
+//   * the per-step work (feed, hand-off, addresses, best-cell tracking) is paid once per twice as many cells, the ramp is 15 steps,
+//     and the SDWA groups pad 2 RT rows to a multiple of four instead of RT rows;
+//   * the row code's five bits hold 32 rows per lane: RT <= 16.  Which of those classes run on 16 lanes is the launcher's choice
+//     (sd_sw.hip, pairsPerWave: a_seg5 .. a_seg14 by measurement).
 // START (start-position pass, with SHARED): the four tasks scan suffixes of one profile.  A start-position task is the reversed
 // query cut at qEnd against the reversed target cut at tEnd; its rows are rows j0 = qLen - 1 - qEnd .. qLen - 1 of the profile of
 // the WHOLE reversed query, which the wavefront builds once (the first task names it: qOff - j0 * qStep, n + j0 rows).  Task row
@@ -441,21 +464,24 @@ __device__ __forceinline__ uint32_t addWord1(uint32_t base, uint32_t packed) {  
 //   * lanes before s compute cells of no task: they are left out of the final reduce;
 //   * the reported row is the profile row - j0.  Columns, the row code and the tie rule are those of the other forms.
 // The target still enters at lane 0, so a task pays s extra ramp steps out of the 31 that every launch pays anyway.
-template <int RT, bool SHARED, bool START = false>
+template <int RT, bool SHARED, bool START = false, int LW = 32>
 __global__ void __launch_bounds__(64)
 sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, const uint8_t *__restrict__ qRes,
                            const int8_t *__restrict__ qBias, const uint8_t *__restrict__ tRes, const int8_t *__restrict__ mat,
                            int go, int ge, int32_t *__restrict__ out, const uint32_t *__restrict__ order,
                            const int8_t *__restrict__ qProf) {
-    constexpr int LW = 32;
-    constexpr int WORDS = (RT + 3) / 4;
+    constexpr int RTL = RT * (32 / LW);    // rows per lane
+    constexpr int WORDS = (RTL + 3) / 4;
     constexpr int RTP = 4 * WORDS;
     constexpr int PSTRIDE = LW * WORDS;    // dwords per residue row of a profile
     constexpr int NGRP = 64 / LW;
     constexpr int NT = 2 * NGRP;           // tasks per wavefront: a task pair per group of LW lanes
     constexpr uint32_t ROWB = PSTRIDE * 4; // bytes per residue row
+    static_assert(LW == 32 || LW == 16, "a group is half a wavefront or one DPP row");
     static_assert(22 * ROWB < 65536, "row offsets travel in 16 bits");
     static_assert(SHARED || !START, "the start-row form has one profile per wavefront");
+    static_assert(LW == 32 || (SHARED && !START), "16-lane groups: the shared forward form only");
+    static_assert(RTL <= 32, "the row code has five row bits: 16-lane groups end at RT = 16 (512 rows), a_seg17 .. a_seg24 stay on 32 lanes");
     __shared__ uint32_t prof[SHARED ? 1 : NT][22][PSTRIDE];
     __shared__ int8_t smat[441];
     for (int i = threadIdx.x; i < 441; i += 64) smat[i] = mat[i];
@@ -496,7 +522,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     }
     const int steps = (maxN > 0 && maxTL > 0) ? maxTL + LW - 1 : 0;
     const uint32_t goP = (uint32_t) go | ((uint32_t) go << 16), geP = (uint32_t) ge | ((uint32_t) ge << 16);
-    const int q0 = l * RT;
+    const int q0 = l * RTL;
     // ---- query profiles (SmithWaterman::createQueryProfile, :163-187)
 #pragma unroll
     for (int x = 0; x < (SHARED ? 1 : 2); x++) {
@@ -515,7 +541,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
 #pragma unroll
             for (int b = 0; b < 4; b++) {
                 const int qi = q0 + 4 * w + b;
-                valid[b] = (4 * w + b < RT) && qi < pN;
+                valid[b] = (4 * w + b < RTL) && qi < pN;
                 res[b] = 20;
                 cb[b] = 0;
                 pidx[b] = 0;
@@ -592,8 +618,12 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
     uint32_t chunkNext = loadChunk(LW);
     // column 0's residues enter at the first lane of either group; every other lane starts on the neutral row
     uint32_t T = NEUT | (NEUT << 16);
-    T = writeLane<0>(readLane(chunk, 0), T);
-    T = writeLane<32>(readLane(chunk, 32), T);
+    if (LW == 32) {
+        T = writeLane<0>(readLane(chunk, 0), T);
+        T = writeLane<32>(readLane(chunk, 32), T);
+    } else {
+        T = l == 0 ? chunk : T;
+    }
     uint32_t pa[WORDS], pb[WORDS];
     {
         const uint32_t aA = addWord0(baseA, T), aB = addWord1(baseB, T);
@@ -613,10 +643,16 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
         if (i1 == 0) {
             chunk = chunkNext;
             chunkNext = loadChunk(k + 1 + LW);
+        } else if (LW == 16) {   // the chunk turns by one lane per step: column k + 1 stands in the first lane of its group
+            chunk = dppRowRol1(chunk);
         }
-        Tn = dppShr1(Tc);
-        Tn = writeLane<0>(readLane(chunk, i1), Tn);
-        Tn = writeLane<32>(readLane(chunk, 32 + i1), Tn);
+        if (LW == 32) {
+            Tn = dppShr1(Tc);
+            Tn = writeLane<0>(readLane(chunk, i1), Tn);
+            Tn = writeLane<32>(readLane(chunk, 32 + i1), Tn);
+        } else {
+            Tn = dppRowShr1Keep(chunk, Tc);
+        }
         {
             const uint32_t aA = addWord0(baseA, Tn), aB = addWord1(baseB, Tn);
 #pragma unroll
@@ -626,11 +662,11 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
             }
         }
         // ---- hand-off from lane l - 1 (nothing enters the first lane of a group)
-        uint32_t inG = dppShr1(outG), inFf = dppShr1(outFf);
+        uint32_t inG = LW == 32 ? dppShr1(outG) : dppRowShr1(outG), inFf = LW == 32 ? dppShr1(outFf) : dppRowShr1(outFf);
         if (START) {   // (nothing enters the lane a chain begins in; what enters the lanes before it belongs to no task)
             inG &= handMask;
             inFf &= handMask;
-        } else {
+        } else if (LW == 32) {   // (a row shift has zeroed the first lane of a 16-lane group)
             inG = writeLane<32>(0, inG);
             inFf = writeLane<32>(0, inFf);
         }
@@ -645,7 +681,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
         prevInG = inG;
         uint32_t Ff = inFf, cm = 0;
 #pragma unroll
-        for (int r = 0; r < RT; r++) {
+        for (int r = 0; r < RTL; r++) {
             const uint32_t hpre = pkMax(h[r], E[r]);
             const uint32_t g = pkMax(hpre, Ff);
             const uint32_t open = pkSubSat(hpre, goP);
@@ -655,7 +691,7 @@ sw_score_pk_aligned_kernel(const SwTask *__restrict__ tasks, uint32_t nTasks, co
             const uint32_t code = pkRowCode(g, 31 - r);
             cm = r == 0 ? code : pkMax(cm, code);
         }
-        outG = H[RT - 1];
+        outG = H[RTL - 1];
         outFf = Ff;
         // ---- a strictly larger value takes over (first column wins, smallest row inside)
         const uint32_t t = bestcm | 0x001F001Fu;

@@ -550,6 +550,19 @@ int sd_search_stream(sd_search *s, const sd_setdb *Q, int sameDb, uint32_t nRang
                 if (c) sd_sw_set_shared_start(c, 0);
         }
     } sharedStartMode(s, !(getenv("SD_SW_SHARED_START") && atoi(getenv("SD_SW_SHARED_START")) == 0));
+    // The lanes' paired forward tasks of 129 .. 448 query rows run on 16-lane groups, four task pairs of a query per wavefront
+    // (sd_sw_set_group16; same records).  SD_SW_GROUP16=0: 32-lane groups, as in a direct caller's context.
+    struct Group16Mode {
+        sd_ctx *al[4];
+        explicit Group16Mode(sd_search *s_, bool on) : al{s_->ctxAl, s_->ctxAl2, s_->ctxAlMore[0], s_->ctxAlMore[1]} {
+            for (sd_ctx *c : al)
+                if (c) sd_sw_set_group16(c, on ? 1 : 0);
+        }
+        ~Group16Mode() {
+            for (sd_ctx *c : al)
+                if (c) sd_sw_set_group16(c, 0);
+        }
+    } group16Mode(s, !(getenv("SD_SW_GROUP16") && atoi(getenv("SD_SW_GROUP16")) == 0));
     std::vector<uint32_t> qSetSize(Q->nSets, 0);
     if (aggregate)
         for (uint32_t i = 0; i < Q->n; i++)
