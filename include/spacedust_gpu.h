@@ -1080,6 +1080,41 @@ int sd_host_kmermatch_format(uint64_t nSeq, const uint32_t *keys, uint64_t nHits
                              const uint32_t *score, const int32_t *diag, uint32_t *entryKey, uint64_t *entryOff, uint64_t textCap,
                              char *text, uint64_t *textBytes);
 
+
+/* ---- clusthash: grouping of sequences that are identical, or nearly so, over their whole length (the amino-acid branch of
+ * M/src/util/clusthash.cpp:64-181).  Sequence ids are positions in the input, and the greedy pass depends on them: the
+ * caller passes the sequences in the reader's id order -- the reference opens its DB with LINEAR_ACCESS, so that is data-offset order, which
+ * is key order only for a DB whose data lies in key order (`sdgpu clusthash` passes SeqDb's LINEAR_ACCESS order).  residues are the 21-letter codes, letters the DB's own bytes in the same layout (offsets[nSeq + 1], 64-bit).
+ *
+ * sd_clusthash_batch (GPU): hash = Util::hash of the reduced codes (h = 31 h + letterMap21[code], 64-bit wrapping, all L residues).
+ * The sequences are sorted by (hash, length, id); inside every (hash, length) group, for i in id order: an i that is already found gets
+ * nothing; otherwise every j != i that is not found -- earlier representatives included -- is compared byte for byte (letters, case
+ * sensitive) and marked found by i where (float) equal / (float) L >= seqIdThr, decided as equal >= sd_host_clusthash_min_identical.
+ * foundBy[nSeq]: the id that marked the sequence, or UINT32_MAX; identical[nSeq]: the equal bytes of that pair (0 where not found);
+ * hash[nSeq] (nullable).  stats[4] (nullable): unique hashes, (hash, length) groups of more than one, pairs compared, largest group.
+ * The entry of sequence s is its self row and one row for every t with foundBy[t] == s, ascending t (sd_host_clusthash_format).
+ * alphabetSize other than 3 and 13 (the reference itself refuses 21: no reduced alphabet), or more than 2^32 - 4097 sequences: SD_EUNSUPPORTED; an input that does not fit the device at
+ * once: SD_ENOMEM with the bytes needed in the message.  The reference's sentinel (UINT_MAX, 0) behind its array, which a last group of
+ * hash 4 294 967 295 would read as a member, is not reproduced: the last group ends with the array. */
+#define SD_CLUSTHASH_BYTES_PER_SEQ 128   /* device bytes per sequence beside residues and letters, counted from sd_clusthash.hip's workspace */
+typedef struct sd_clusthash_params_s {
+    int32_t alphabetSize;   /* --alph-size: 3 (the module's default) or 13 */
+    float seqIdThr;         /* --min-seq-id (the module's default is 0.99) */
+} sd_clusthash_params;
+/* the smallest d in 0 .. L with (float) d / (float) L >= seqIdThr (the reference's comparison, clusthash.cpp:155-156; the quotient is
+ * monotone in d), L + 1 when there is none (L = 0: 0 / 0 is not >= anything).  What the device compares equal-byte counts with */
+uint32_t sd_host_clusthash_min_identical(float seqIdThr, uint32_t L);
+int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSeq, const uint8_t *residues, const uint64_t *offsets,
+                       const uint8_t *letters, const uint8_t *letterMap21, uint32_t *foundBy, uint32_t *identical, uint64_t *hash,
+                       uint64_t *stats);
+/* The alignment DB of the module (clusthash.cpp:129-177): one entry per sequence, in input order.  Self row
+ * "key\t255\t1.00\t0\t0\tL-1\tL\t0\tL-1\tL\n"; one row "key\t255\t<seqId>\t0\t0\tL-1\tL\t0\tL-1\tL\n" for every t with foundBy[t] == s,
+ * ascending t, seqId = (float) identical[t] / (float) L as Util::fastSeqIdToBuffer prints it into a C string ("1.000" for one; three
+ * truncated decimals otherwise); L - 1 in unsigned arithmetic.  entryOff [nSeq + 1]; text == NULL: only *textBytes is set; textCap too
+ * small: SD_ENOMEM; a foundBy that is neither UINT32_MAX nor below nSeq: SD_EINVAL. */
+int sd_host_clusthash_format(uint64_t nSeq, const uint32_t *keys, const uint64_t *offsets, const uint32_t *foundBy,
+                             const uint32_t *identical, uint64_t *entryOff, uint64_t textCap, char *text, uint64_t *textBytes);
+
 #ifdef __cplusplus
 }
 #endif

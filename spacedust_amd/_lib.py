@@ -72,6 +72,10 @@ class KmParams(C.Structure):
                 ('hashShift', C.c_int32), ('covMode', C.c_int32), ('covThr', C.c_float), ('includeOnlyExtendable', C.c_int32)]
 
 
+class ClusthashParams(C.Structure):   # sd_clusthash_params
+    _fields_ = [('alphabetSize', C.c_int32), ('seqIdThr', C.c_float)]
+
+
 class ChParams(C.Structure):
     _fields_ = [('maxGeneGap', C.c_uint32), ('clusterSize', C.c_uint32), ('alpha', C.c_double),
                 ('pCluThr', C.c_float), ('pMHThr', C.c_float)]
@@ -310,6 +314,9 @@ def load():
         'sd_selftest_kmermatch_records': (C.c_int, [_vp, C.POINTER(KmParams), C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64] + [_vp] * 9),
         'sd_host_kmermatch_format': (C.c_int, [C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp,
                                                C.POINTER(C.c_uint64)]),
+        'sd_host_clusthash_min_identical': (C.c_uint32, [C.c_float, C.c_uint32]),
+        'sd_clusthash_batch': (C.c_int, [_vp, C.POINTER(ClusthashParams), C.c_uint64] + [_vp] * 8),
+        'sd_host_clusthash_format': (C.c_int, [C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     }
     missing = []
     for name, (res, args) in sig.items():

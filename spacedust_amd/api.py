@@ -1121,3 +1121,48 @@ def kmermatch_format(keys, rep, member, score, diag):
                                             ptr(text), C.byref(nbytes)), 'sd_host_kmermatch_format')
     raw = text.tobytes()
     return {int(ekey[e]): raw[int(eoff[e]):int(eoff[e + 1])] for e in range(n)}
+
+
+def clusthash_min_identical(min_seq_id, length):
+    """sd_host_clusthash_min_identical: the smallest d with float32(d) / float32(length) >= min_seq_id, length + 1 when there is none"""
+    return int(_lib.load().sd_host_clusthash_min_identical(float(min_seq_id), int(length)))
+
+
+def clusthash(ctx, residues, offsets, letters, alph_size=3, min_seq_id=0.99, letter_map=None, want_hash=True):
+    """sd_clusthash_batch: (found_by uint32 [n] (UINT32_MAX: not found), identical uint32 [n], hash uint64 [n] or None, stats) of the
+    sequences in input order = id order; stats = dict(unique_hashes, groups, pairs, largest_group).  letters: the DB's own bytes, laid out
+    like residues.  letter_map: default reduced_alphabet(alph_size)."""
+    L = _lib.load()
+    residues = np.ascontiguousarray(residues, np.uint8)
+    letters = np.ascontiguousarray(letters, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    n = len(offsets) - 1
+    assert len(residues) == int(offsets[-1]) and len(letters) == len(residues)
+    if letter_map is None:
+        letter_map = reduced_alphabet(alph_size)[0]
+    letter_map = np.ascontiguousarray(letter_map, np.uint8)
+    par = _lib.ClusthashParams(int(alph_size), float(min_seq_id))
+    found_by, identical = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    hashes = np.zeros(max(n, 1), np.uint64) if want_hash else None
+    stats = np.zeros(4, np.uint64)
+    _check(ctx.h, L.sd_clusthash_batch(ctx.h, C.byref(par), n, ptr(residues), ptr(offsets), ptr(letters), ptr(letter_map), ptr(found_by),
+                                       ptr(identical), ptr(hashes), ptr(stats)), 'sd_clusthash_batch')
+    named = dict(unique_hashes=int(stats[0]), groups=int(stats[1]), pairs=int(stats[2]), largest_group=int(stats[3]))
+    return found_by[:n], identical[:n], (hashes[:n] if want_hash else None), named
+
+
+def clusthash_format(keys, offsets, found_by, identical):
+    """sd_host_clusthash_format: the alignment DB of clusthash as dict key -> bytes (one entry per sequence)"""
+    L = _lib.load()
+    keys, found_by, identical = (np.ascontiguousarray(x, np.uint32) for x in (keys, found_by, identical))
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    n = len(keys)
+    assert len(offsets) == n + 1 and len(found_by) == n and len(identical) == n
+    nbytes = C.c_uint64()
+    _check(None, L.sd_host_clusthash_format(n, ptr(keys), ptr(offsets), ptr(found_by), ptr(identical), None, 0, None, C.byref(nbytes)),
+           'sd_host_clusthash_format')
+    eoff, text = np.zeros(n + 1, np.uint64), np.zeros(nbytes.value + 1, np.uint8)
+    _check(None, L.sd_host_clusthash_format(n, ptr(keys), ptr(offsets), ptr(found_by), ptr(identical), ptr(eoff), nbytes.value, ptr(text),
+                                            C.byref(nbytes)), 'sd_host_clusthash_format')
+    raw = text.tobytes()
+    return {int(keys[e]): raw[int(eoff[e]):int(eoff[e + 1])] for e in range(n)}

@@ -179,6 +179,10 @@ int swapresultsModule(const Args &a);
 int expandalnModule(const Args &a);
 int clustModule(const Args &a);
 int kmermatcherModule(const Args &a);
+int clusthashModule(const Args &a);
+int createsubdbModule(const Args &a);
+int mergeclustersModule(const Args &a);
+int clusterModule(const Args &a);
 
 }  // namespace sdcli
 #endif

@@ -38,6 +38,10 @@ const Module kModules[] = {
     {"expandaln", expandalnModule, "A->B alignments carried over to the C's each B is aligned with, backtraces translated on the GPU: <queryDB> <targetDB> <resultDB_AB> <resultDB_BC> <outDB>"},
     {"clust", clustModule, "result DB of a set against itself -> cluster DB; the symmetric graph of --cluster-mode 0 / 1 is built on the GPU: <sequenceDB> <resultDB> <clusterDB>"},
     {"kmermatcher", kmermatcherModule, "linclust's first stage: sequences sharing a selected k-mer grouped under the longest, records sorted and grouped on the GPU: <sequenceDB> <prefDB>"},
+    {"clusthash", clusthashModule, "sequences of equal reduced-alphabet hash and length compared byte for byte, hashed, sorted and compared on the GPU: <sequenceDB> <resultDB>"},
+    {"createsubdb", createsubdbModule, "host glue: the entries of a DB that a key list or another DB's index names, copied (--subdb-mode 0) or soft-linked (1): <subsetFile|DB> <DB> <DB>"},
+    {"mergeclusters", mergeclustersModule, "host glue: the cluster DBs of successive steps merged into one: <sequenceDB> <clusterDB> <clusterDB1> [<clusterDB2> ...]"},
+    {"cluster", clusterModule, "--single-step-clustering 1: clusthash, clust, createsubdb, prefilter, align (or rescorediagonal), clust, mergeclusters in one process: <sequenceDB> <clusterDB> <tmpDir>"},
     {"createindex", createindexModule, "target k-mer index built once, in the reference's createindex file layout: <sequenceDB> <tmpDir>"},
     {"createsetdb", createsetdbModule, "FASTA files (Prodigal headers) -> setDB in the createsetdb layout"},
 };

@@ -1325,4 +1325,85 @@ int clustersearchModule(const Args &a0) {
     return clusterChain(a, Q, T, tmp);
 }
 
+// cluster <sequenceDB> <clusterDB> <tmpDir> --single-step-clustering 1  (M/src/workflow/Cluster.cpp:14-20,63-104,244-262 set the
+// parameters, M/data/workflow/clustering.sh is the chain): clusthash, clust, createsubdb --subdb-mode 1, prefilter of the sub DB against
+// itself, align (rescorediagonal --rescore-mode 2 under --alignment-mode 4), clust, mergeclusters, in this process; the DBs between them
+// lie under <tmpDir> with the reference's names.  DESIGN.md 4.18
+int clusterModule(const Args &a) {
+    if (a.pos.size() != 3) return fail("usage: cluster <sequenceDB> <clusterDB> <tmpDir> --single-step-clustering 1 [options]");
+    if (int rc = checkCommon(a)) return rc;
+    if (!a.flag("--single-step-clustering", false))
+        return fail("only --single-step-clustering 1 is implemented: the cascaded workflow starts with linclust, whose ungapped filter "
+                    "(rescorediagonal --filter-hits 1) needs the reference's --filter-hits threshold table");
+    if (a.flag("--cluster-reassign", false)) return fail("--cluster-reassign is not part of the single-step chain");
+    if (envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1) return fail("cluster runs on one rank");
+    const std::string in = a.pos[0], out = a.pos[1], tmp = a.pos[2];
+    {
+        const int bt = sddb::baseType(sddb::readDbType(in));
+        if (sddb::readDbType(in) == -1) return fail(in + ".dbtype not found");
+        if (bt == sddb::DBTYPE_NUCLEOTIDES) return fail("nucleotide DBs are not implemented (" + in + ")");
+        if (bt == sddb::DBTYPE_HMM_PROFILE) return fail("profile DBs are not implemented (" + in + ")");
+    }
+    if (sddb::fileExists(out + ".dbtype")) return fail(out + ".dbtype exists already");
+    mkdir(tmp.c_str(), 0777);
+    // setWorkflowDefaults and setClusterAutomagicParameters
+    const float seqId = (float) a.real("--min-seq-id", 0.0);
+    const bool ungapped = a.integer("--alignment-mode", 3) == 4;
+    const int covMode = (int) a.integer("--cov-mode", 0);
+    const std::string clusterMode = a.str("--cluster-mode", (covMode == 1 || covMode == 2) ? "2" : "0");
+    const std::string compBias = a.str("--comp-bias-corr", seqId >= 0.7f ? "0" : "1");
+    const std::string minUngapped = a.str("--min-ungapped-score", seqId >= 0.7f ? "60" : "15");
+    std::string sens = a.str("-s", "");
+    if (sens.empty()) {
+        const float s = seqId <= 0.3 ? 6.0f : seqId > 0.8 ? 1.0f : (float) (1.0 + (1.0 * (0.7 - seqId) * 10));   // setAutomaticThreshold
+        char buf[32];
+        snprintf(buf, sizeof(buf), "%g", s);
+        sens = buf;
+        info(a, "Set cluster sensitivity to -s %s\n", buf);
+    }
+    std::vector<std::string> common = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
+    const std::vector<std::string> hostOnly = common;
+    if (a.has("--device")) common = with(common, {"--device", a.str("--device", "")});
+    auto passed = [&](std::vector<std::string> v, std::initializer_list<const char *> flags) {
+        for (const char *f : flags)
+            if (a.has(f)) v = with(v, {f, a.str(f, "")});
+        return v;
+    };
+    const std::vector<std::string> hashPar = with(common, {"--alph-size", "3", "--min-seq-id", "0.99"});   // whatever the user gave
+    const std::vector<std::string> clustPar = passed(with(hostOnly, {"--cluster-mode", clusterMode}), {"--max-iterations", "--similarity-type"});
+    const std::vector<std::string> pref =
+        passed(with(common, {"-s", sens, "--max-seqs", a.str("--max-seqs", "20"), "-c", a.str("-c", "0.8"), "--cov-mode", std::to_string(covMode),
+                             "--min-ungapped-score", minUngapped, "--comp-bias-corr", compBias}),
+               {"-k", "--mask", "--mask-prob", "--spaced-kmer-mode", "--bin-size", "--chunk-queries", "--add-self-matches"});
+    const std::vector<std::string> hits = {"-e", a.str("-e", "0.001"), "-c", a.str("-c", "0.8"), "--cov-mode", std::to_string(covMode), "--min-seq-id",
+                                           a.str("--min-seq-id", "0")};
+    std::vector<std::string> aln = common;
+    aln.insert(aln.end(), hits.begin(), hits.end());
+    aln = ungapped ? with(aln, {"--rescore-mode", "2"}) : with(aln, {"--alignment-mode", a.str("--alignment-mode", "3"), "--comp-bias-corr", compBias});
+    aln = passed(aln, {"-a", "--min-aln-len", "--seq-id-mode", "--add-self-matches"});
+    struct ResidentScope {
+        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
+        ~ResidentScope() { resident().clear(); }
+    } residentScope;
+    const std::string alnRed = tmp + "/aln_redundancy", cluRed = tmp + "/clu_redundancy", sub = tmp + "/input_step_redundancy",
+                      prefDb = tmp + "/pref", alnDb = tmp + "/aln", clu0 = tmp + "/clu_step0";
+    for (const std::string &db : {alnRed, cluRed, sub, prefDb, alnDb, clu0}) sddb::removeDb(db);
+    if (int rc = runModule(clusthashModule, "clusthash", {in, alnRed}, hashPar)) return rc;
+    if (int rc = runModule(clustModule, "clust", {in, alnRed, cluRed}, clustPar)) return rc;
+    if (int rc = runModule(createsubdbModule, "createsubdb", {cluRed, in, sub}, {"-v", a.str("-v", "3"), "--subdb-mode", "1"})) return rc;
+    if (int rc = runModule(prefilterModule, "prefilter", {sub, sub, prefDb}, pref)) return rc;
+    if (ungapped) {
+        if (int rc = runModule(rescorediagonalModule, "rescorediagonal", {sub, sub, prefDb, alnDb}, aln)) return rc;
+    } else {
+        if (int rc = runModule(alignModule, "align", {sub, sub, prefDb, alnDb}, aln)) return rc;
+    }
+    if (int rc = runModule(clustModule, "clust", {sub, alnDb, clu0}, clustPar)) return rc;
+    if (int rc = runModule(mergeclustersModule, "mergeclusters", {in, out, cluRed, clu0}, hostOnly)) return rc;
+    if (a.flag("--remove-tmp-files", false)) {
+        for (const std::string &db : {prefDb, alnDb, clu0, cluRed, alnRed}) sddb::removeDb(db);
+        for (const char *suffix : {"", ".index", ".dbtype", "_h", "_h.index", "_h.dbtype", ".lookup", ".source"}) unlink((sub + suffix).c_str());
+    }
+    return 0;
+}
+
 }  // namespace sdcli

@@ -28,6 +28,7 @@
 namespace {
 
 #include "sd_scan_sort.h"
+#include "sd_seqhash.h"
 
 constexpr int KM_BLOCK = 256;
 constexpr int KM_MAXK = 24;
@@ -142,16 +143,6 @@ km_select_kernel(KmPar p, const uint8_t *__restrict__ residues, const uint64_t *
     }
 }
 
-__device__ __forceinline__ uint64_t kmPow31(uint32_t e) {
-    uint64_t r = 1, b = 31;
-    while (e) {
-        if (e & 1) r *= b;
-        b *= b;
-        e >>= 1;
-    }
-    return r;
-}
-
 __global__ void __launch_bounds__(64)
 km_emit_kernel(KmPar p, const uint8_t *__restrict__ residues, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ keys,
                uint32_t nSeq, const uint64_t *__restrict__ recOff, const uint32_t *__restrict__ thr, const uint32_t *__restrict__ exc,
@@ -170,15 +161,9 @@ km_emit_kernel(KmPar p, const uint8_t *__restrict__ residues, const uint64_t *__
     const uint64_t at0 = recOff[s];
     const uint32_t nRec = (uint32_t) (recOff[s + 1] - at0);   // 1 + selected windows: no lane writes beyond it
     const uint32_t key = keys[s];
-    // the identity record: XXH64(Util::hash(reduced codes, L)); Util::hash is h = 31 h + x, here as sum x_i 31^(L - 1 - i) over lane blocks
+    // the identity record: XXH64(Util::hash(reduced codes, L)); Util::hash is sdSeqHash31 (sd_seqhash.h, shared with sd_clusthash.hip)
     {
-        const uint32_t per = (L + 63) / 64;
-        const uint32_t from = (uint32_t) lane * per < L ? (uint32_t) lane * per : L;
-        const uint32_t to = from + per < L ? from + per : L;
-        uint64_t h = 0;
-        for (uint32_t i = from; i < to; i++) h = h * 31 + map[res[i]];
-        h *= kmPow31(L - to);
-        for (int o = 32; o > 0; o >>= 1) h += scanShflXor(h, o);
+        const uint64_t h = sdSeqHash31(map, res, L, lane);
         if (lane == 0) {
             const uint64_t k64 = kmXxh64Word(h, p.seed);
             rKeyHi[at0] = (uint32_t) (k64 >> 32);

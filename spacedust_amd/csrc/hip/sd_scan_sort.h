@@ -1,6 +1,6 @@
 // Device-wide prefix scans and a stable LSD radix sort of (uint32 key, 32- or 64-bit value) pairs -- this library's own (no hipCUB /
 // rocPRIM anywhere in the tree).  Included by sd_prefilter.hip, sd_sw.hip, sd_sw_alt.hip, sd_index_build.hip, sd_expand.hip,
-// sd_clust.hip and sd_kmermatch.hip inside their anonymous namespaces.
+// sd_clust.hip, sd_kmermatch.hip and sd_clusthash.hip inside their anonymous namespaces.
 //
 // Why not the library forms: the library's scan is a decoupled look-back (tiles spin on their predecessors) and its one-sweep
 // sort runs 1 024-thread workgroups that do the same; both are fine on an idle device and take milliseconds when three other
