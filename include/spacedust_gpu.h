@@ -230,6 +230,13 @@ int sd_sw_set_group16(sd_ctx *ctx, int on);
 int sd_selftest_sort_pairs(sd_ctx *ctx, const uint32_t *keys, const uint32_t *vals, uint32_t n, int beginBit, int endBit, uint32_t *outKeys,
                            uint32_t *outVals);
 int sd_selftest_scan(sd_ctx *ctx, const uint32_t *in, uint32_t n, uint64_t *exclusiveSum, uint32_t *runningMax);
+/* sd_selftest_field_sort: the chained sort by several fields that the grouping modules share (csrc/hip/sd_field_sort.h), through the
+ * functions they call.  fields: nFields (1 .. 5) arrays of n values, one after the other, the LEAST significant first (numpy.lexsort's
+ * order).  The key of field f is fields[f][i] (modes[f] 0), args[f] - fields[f][i] (1) or fields[f][i] + args[f] (2), in 32-bit
+ * arithmetic, and its low bits[f] (1 .. 32) bits are sorted; no key may need more.  outPerm[n]: the stable order by all keys;
+ * outFields: the fields gathered into it, laid out as fields. */
+int sd_selftest_field_sort(sd_ctx *ctx, uint32_t n, int nFields, const uint32_t *fields, const int32_t *modes, const uint32_t *args,
+                           const int32_t *bits, uint32_t *outPerm, uint32_t *outFields);
 /* sd_selftest_score_class: the class of the Smith-Waterman score-class table (csrc/hip/sd_sw.hip) that a task of n rows and tL columns
  * falls into, and the profile scope of the kernel that runs it, for tasks paired by query (shared != 0) or alone.  kernel: what the
  * gates ask for -- 0 the packed kernels, 1 the packed kernels with the wide row code (beyond wideRowLimit in both dimensions: the

@@ -9,7 +9,7 @@
 //   clust_src_kernel      src[e] = row of edge e                                      (binary search in rowOff)
 //   sdRadixSortPairs      (key elem[e], value e), stable, ceil(log2 n) key bits
 //   clust_bounds_kernel   tOff[c] = first sorted position with destination >= c
-//   clust_tsrc_kernel     tSrc[j] = src[value[j]]
+//   gatherFields          tSrc[j] = src[value[j]]                                     (fs_gather_kernel, sd_field_sort.h)
 //   clust_flag_kernel     flag[j] = destination c of j is not in tSrc[tOff[s] .. tOff[s + 1]), s = tSrc[j]
 //   sdScanLaunch          fScan = exclusive sum of flag over E + 1 entries: outRowOff[c] = rowOff[c] + fScan[tOff[c]]
 //   clust_copy_kernel     the input entries to their new places
@@ -21,10 +21,9 @@
 namespace {
 
 #include "sd_scan_sort.h"
+#include "sd_field_sort.h"
 
 constexpr int CL_BLOCK = 256;
-// the sort counts its elements in 32 bits and rounds the count up to whole tiles
-constexpr uint64_t CL_MAX_EDGES = (uint64_t) UINT32_MAX - RS_TILE;
 
 // the row r with off[r] <= e < off[r + 1] (rows may be empty)
 __device__ __forceinline__ uint32_t clRowOf(const uint64_t *__restrict__ off, uint32_t n, uint64_t e) {
@@ -56,12 +55,6 @@ clust_bounds_kernel(const uint32_t *__restrict__ sortedDst, uint32_t nEdges, uin
         else hi = mid;
     }
     tOff[c] = lo;
-}
-
-__global__ void __launch_bounds__(CL_BLOCK)
-clust_tsrc_kernel(const uint32_t *__restrict__ sortedEdge, const uint32_t *__restrict__ src, uint32_t nEdges, uint32_t *__restrict__ tSrc) {
-    const uint64_t j = (uint64_t) blockIdx.x * CL_BLOCK + threadIdx.x;
-    if (j < nEdges) tSrc[j] = src[sortedEdge[j]];
 }
 
 // flag has nEdges + 1 entries (the last one 0: the scan's total)
@@ -117,8 +110,6 @@ clust_append_kernel(const uint64_t *__restrict__ rowOff, const uint64_t *__restr
     outScore[at] = score[sortedEdge[j]];
 }
 
-inline unsigned clGrid(uint64_t items) { return (unsigned) ((items + CL_BLOCK - 1) / CL_BLOCK); }
-
 }  // namespace
 
 extern "C" {
@@ -135,9 +126,9 @@ int sd_clust_symmetrize(sd_ctx *ctx, uint64_t n, const uint64_t *rowOff, const u
     for (uint64_t r = 0; r < n; r++)
         if (rowOff[r + 1] < rowOff[r]) return sdFail(ctx, SD_EINVAL, "sd_clust_symmetrize: rowOff descends at row %llu", (unsigned long long) r);
     const uint64_t nEdges = rowOff[n];
-    if (nEdges > CL_MAX_EDGES)
+    if (nEdges > RS_MAX_ELEMENTS)
         return sdFail(ctx, SD_EUNSUPPORTED, "sd_clust_symmetrize: %llu entries in one call (the device sort counts in 32 bits: at most %llu)",
-                      (unsigned long long) nEdges, (unsigned long long) CL_MAX_EDGES);
+                      (unsigned long long) nEdges, (unsigned long long) RS_MAX_ELEMENTS);
     if (nEdges && (!elem || !score)) return SD_EINVAL;
     // checked here, so that no lane indexes outside its arrays
     {
@@ -186,19 +177,17 @@ int sd_clust_symmetrize(sd_ctx *ctx, uint64_t n, const uint64_t *rowOff, const u
     uint32_t *dTSrc = dValT;   // the sort's scratch pair is free once it has returned
     {
         HostScope hs(ctx, "clust_kernels");
-        int keyBits = 1;
-        while (keyBits < 32 && ((uint64_t) 1 << keyBits) < n) keyBits++;
-        hipLaunchKernelGGL(clust_src_kernel, dim3(clGrid(nEdges)), dim3(CL_BLOCK), 0, ctx->stream, (const uint64_t *) dRowOff, n32, e32, dSrc, dEdge);
+        const int keyBits = bitsFor(n - 1);   // the destinations are 0 .. n - 1 (nEdges > 0 here, so n >= 1)
+        hipLaunchKernelGGL(clust_src_kernel, dim3(gridFor(nEdges, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, (const uint64_t *) dRowOff, n32, e32, dSrc, dEdge);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, sdRadixSortPairs<uint32_t>(ctx->stream, dElem, dEdge, dKeyS, dValS, dKeyT, dValT, e32, 0, keyBits, dCounts));
-        hipLaunchKernelGGL(clust_bounds_kernel, dim3(clGrid(n + 1)), dim3(CL_BLOCK), 0, ctx->stream, (const uint32_t *) dKeyS, e32, n32, dTOff);
-        hipLaunchKernelGGL(clust_tsrc_kernel, dim3(clGrid(nEdges)), dim3(CL_BLOCK), 0, ctx->stream, (const uint32_t *) dValS, (const uint32_t *) dSrc,
-                           e32, dTSrc);
-        hipLaunchKernelGGL(clust_flag_kernel, dim3(clGrid(nEdges + 1)), dim3(CL_BLOCK), 0, ctx->stream, (const uint32_t *) dKeyS,
+        hipLaunchKernelGGL(clust_bounds_kernel, dim3(gridFor(n + 1, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, (const uint32_t *) dKeyS, e32, n32, dTOff);
+        SD_HIP(ctx, gatherFields(ctx->stream, dValS, e32, 1, &dSrc, &dTSrc));
+        hipLaunchKernelGGL(clust_flag_kernel, dim3(gridFor(nEdges + 1, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, (const uint32_t *) dKeyS,
                            (const uint32_t *) dTSrc, (const uint64_t *) dTOff, e32, dFlag);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, (sdScanLaunch<uint32_t, ScanSum64, false, uint64_t>(ctx->stream, dFlag, dFScan, nEdges + 1, dScanTmp)));
-        hipLaunchKernelGGL(clust_offsets_kernel, dim3(clGrid(n + 1)), dim3(CL_BLOCK), 0, ctx->stream, (const uint64_t *) dRowOff,
+        hipLaunchKernelGGL(clust_offsets_kernel, dim3(gridFor(n + 1, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, (const uint64_t *) dRowOff,
                            (const uint64_t *) dTOff, (const uint64_t *) dFScan, n32, dOutOff);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, sdD2H(ctx, &added, dFScan + nEdges, 8));
@@ -225,10 +214,10 @@ int sd_clust_symmetrize(sd_ctx *ctx, uint64_t n, const uint64_t *rowOff, const u
     SD_HIP(ctx, wsGet(ctx, "cl.outscore", (size_t) total, &dOutScore));
     {
         HostScope hs(ctx, "clust_kernels");
-        hipLaunchKernelGGL(clust_copy_kernel, dim3(clGrid(nEdges)), dim3(CL_BLOCK), 0, ctx->stream, (const uint64_t *) dRowOff,
+        hipLaunchKernelGGL(clust_copy_kernel, dim3(gridFor(nEdges, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, (const uint64_t *) dRowOff,
                            (const uint64_t *) dOutOff, (const uint32_t *) dSrc, (const uint32_t *) dElem, (const uint16_t *) dScore, e32, dOutElem,
                            dOutScore);
-        hipLaunchKernelGGL(clust_append_kernel, dim3(clGrid(nEdges)), dim3(CL_BLOCK), 0, ctx->stream, (const uint64_t *) dRowOff,
+        hipLaunchKernelGGL(clust_append_kernel, dim3(gridFor(nEdges, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, (const uint64_t *) dRowOff,
                            (const uint64_t *) dOutOff, (const uint64_t *) dTOff, (const uint64_t *) dFScan, (const uint32_t *) dFlag,
                            (const uint32_t *) dKeyS, (const uint32_t *) dValS, (const uint32_t *) dTSrc, (const uint16_t *) dScore, e32, dOutElem,
                            dOutScore);

@@ -2,8 +2,9 @@
 //
 //   ch_hash_kernel      one wavefront per sequence: Util::hash of the reduced codes (sdSeqHash31, shared with the kmermatcher's identity
 //                       record) and the length
-//   sort                chained stable sdRadixSortPairs passes over a permutation, least significant field first: length (the bits the
-//                       data needs), hash low, hash high.  The input is in id order and the passes are stable, so the result is sorted by
+//   sort                sortByField (sd_field_sort.h: fs_key_kernel + sdRadixSortPairs per link, stable, over a permutation), least
+//                       significant field first: length (the bits the data needs), hash low, hash high; then gatherFields
+//                       (fs_gather_kernel per field).  The input is in id order and the passes are stable, so the result is sorted by
 //                       (hash, length, id).  Only sequences of equal length ever interact in the reference's loop, so every (hash, length)
 //                       run is a group of its own.
 //   ch_start_kernel + max scan, ch_groupflag_kernel + sum scan, ch_grouplist_kernel
@@ -13,7 +14,7 @@
 //                       lane and step, 4 steps per chunk; the found flags are the foundBy array itself, behind a workgroup barrier after
 //                       every i that compared anything.
 // No workgroup waits for another; every store is a plain vector store (the pair counter is one vector atomic per wavefront and group).
-#include "sd_common.h"
+#include "sd_batch_check.h"
 
 #include <omp.h>
 
@@ -22,6 +23,7 @@
 namespace {
 
 #include "sd_scan_sort.h"
+#include "sd_field_sort.h"
 #include "sd_seqhash.h"
 
 constexpr int CH_BLOCK = 256;
@@ -35,7 +37,6 @@ constexpr int CH_WAVES = 8;
 constexpr int CH_PAD = 16;   // bytes in front of and behind the letters on the device: the aligned words around a sequence's ends exist
 constexpr uint32_t CH_NONE = UINT32_MAX;
 constexpr uint32_t CH_STOPPED = UINT32_MAX;
-constexpr uint64_t CH_MAX_SEQ = (uint64_t) UINT32_MAX - RS_TILE;   // the sort counts in 32 bits and rounds up to whole tiles
 constexpr unsigned CH_MAX_GRID = 1u << 20;
 
 struct ChMap {
@@ -59,23 +60,6 @@ ch_hash_kernel(ChMap m, const uint8_t *__restrict__ residues, const uint64_t *__
             len[s] = L;
         }
     }
-}
-
-// one link of the sort chain: keyOut[i] = field[perm[i]] (perm null: the identity)
-__global__ void __launch_bounds__(CH_BLOCK)
-ch_key_kernel(const uint32_t *__restrict__ field, const uint32_t *__restrict__ perm, uint32_t n, uint32_t *__restrict__ keyOut,
-              uint32_t *__restrict__ permOut) {
-    const uint64_t i = (uint64_t) blockIdx.x * CH_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t src = perm ? perm[i] : (uint32_t) i;
-    keyOut[i] = field[src];
-    permOut[i] = src;
-}
-
-__global__ void __launch_bounds__(CH_BLOCK)
-ch_gather_kernel(const uint32_t *__restrict__ field, const uint32_t *__restrict__ perm, uint32_t n, uint32_t *__restrict__ out) {
-    const uint64_t i = (uint64_t) blockIdx.x * CH_BLOCK + threadIdx.x;
-    if (i < n) out[i] = field[perm[i]];
 }
 
 // hashFlag has n + 1 entries (the last one 0: the scan's total)
@@ -244,23 +228,6 @@ ch_group_kernel(const uint8_t *__restrict__ base, const uint64_t *__restrict__ o
     }
 }
 
-inline unsigned chGrid(uint64_t items) { return (unsigned) ((items + CH_BLOCK - 1) / CH_BLOCK); }
-inline int chBits(uint64_t maxValue) {
-    int b = 1;
-    while (b < 32 && ((uint64_t) 1 << b) <= maxValue) b++;
-    return b;
-}
-
-struct ChSortBufs {
-    uint32_t *keyIn, *permIn, *keyA, *permA, *keyB, *permB, *counts;
-};
-
-// the sequences in their current order (perm, or the identity when null), stably sorted by field; the new order lands in b.permA
-inline hipError_t chSortByField(hipStream_t st, const ChSortBufs &b, const uint32_t *field, const uint32_t *perm, uint32_t n, int bits) {
-    hipLaunchKernelGGL(ch_key_kernel, dim3(chGrid(n)), dim3(CH_BLOCK), 0, st, field, perm, n, b.keyIn, b.permIn);
-    return sdRadixSortPairs<uint32_t>(st, b.keyIn, b.permIn, b.keyA, b.permA, b.keyB, b.permB, n, 0, bits, b.counts);
-}
-
 }  // namespace
 
 extern "C" {
@@ -277,27 +244,19 @@ int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSe
     // (21 is no reduced alphabet: the reference's ReducedMatrix refuses it, "Reduced alphabet has to be smaller than the original one")
     if (par->alphabetSize != 3 && par->alphabetSize != 13)
         return sdFail(ctx, SD_EUNSUPPORTED, "%s: alphabet size %d (3 and 13 are implemented)", who, par->alphabetSize);
-    if (nSeq > CH_MAX_SEQ)
+    if (nSeq > RS_MAX_ELEMENTS)
         return sdFail(ctx, SD_EUNSUPPORTED, "%s: %llu sequences in one call (the device sort counts in 32 bits: at most %llu)", who,
-                      (unsigned long long) nSeq, (unsigned long long) CH_MAX_SEQ);
+                      (unsigned long long) nSeq, (unsigned long long) RS_MAX_ELEMENTS);
+    std::unique_ptr<HostScope> phase(new HostScope(ctx, "ch_prepare"));
+    SdSeqBatch batch;
+    const int rcCheck = sdCheckSeqBatch(ctx, who, par->alphabetSize, nSeq, residues, offsets, letterMap, &batch);
+    if (rcCheck != SD_OK) return rcCheck;
     ChMap cm;
-    memset(&cm, 0, sizeof(cm));
-    for (int a = 0; a < 21; a++) {
-        if (letterMap[a] >= par->alphabetSize) return sdFail(ctx, SD_EINVAL, "%s: letter %d maps to %d of %d", who, a, letterMap[a], par->alphabetSize);
-        cm.map[a] = letterMap[a];
-    }
-    if (offsets[0] != 0) return sdFail(ctx, SD_EINVAL, "%s: offsets must start at 0", who);
+    memcpy(cm.map, batch.map, sizeof(cm.map));
+    const uint64_t maxLen = batch.maxLen, total = batch.total;
     // per sequence: the equal bytes the threshold asks for at its length (sd_host_clusthash_min_identical: the float comparison is the
     // host's, the device compares integers)
-    std::unique_ptr<HostScope> phase(new HostScope(ctx, "ch_prepare"));
     std::vector<uint32_t> need(nSeq ? nSeq : 1);
-    uint64_t maxLen = 0;
-    for (uint64_t s = 0; s < nSeq; s++) {
-        if (offsets[s + 1] < offsets[s]) return sdFail(ctx, SD_EINVAL, "%s: offsets descend at sequence %llu", who, (unsigned long long) s);
-        const uint64_t L = offsets[s + 1] - offsets[s];
-        if (L > (uint64_t) INT32_MAX / 2) return sdFail(ctx, SD_EINVAL, "%s: sequence %llu has %llu residues", who, (unsigned long long) s, (unsigned long long) L);
-        maxLen = std::max(maxLen, L);
-    }
     {
         uint32_t lastL = UINT32_MAX, lastNeed = 0;   // (neighbours often share a length)
         for (uint64_t s = 0; s < nSeq; s++) {
@@ -309,26 +268,15 @@ int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSe
             need[s] = lastNeed;
         }
     }
-    const uint64_t total = offsets[nSeq];
-    {
-        uint64_t bad = UINT64_MAX;
-#pragma omp parallel for schedule(static) reduction(min : bad) if (total > (1u << 16))
-        for (uint64_t i = 0; i < total; i++)
-            if (residues[i] >= 21 && i < bad) bad = i;
-        if (bad != UINT64_MAX) return sdFail(ctx, SD_EINVAL, "%s: residue %llu has code %u (0 .. 20)", who, (unsigned long long) bad, residues[bad]);
-    }
     if (nSeq == 0) return SD_OK;
     // everything is resident at once
     {
         const uint64_t bytes = nSeq * SD_CLUSTHASH_BYTES_PER_SEQ + 2 * total + 2 * CH_PAD + sdRadixSortCountsBytes() + 4096;
-        size_t freeB = 0, totalB = 0;
-        SD_HIP(ctx, hipMemGetInfo(&freeB, &totalB));
-        uint64_t held = 0;   // what this context's clusthash workspace already holds counts as available
-        for (auto &e : ctx->ws)
-            if (e.first.compare(0, 3, "ch.") == 0) held += e.second.bytes;
-        if (bytes > (uint64_t) freeB + held)
+        uint64_t avail = 0;   // (what this context's clusthash workspace already holds counts as available)
+        SD_HIP(ctx, wsAvailableBytes(ctx, "ch.", &avail));
+        if (bytes > avail)
             return sdFail(ctx, SD_ENOMEM, "%s: %llu bytes needed for %llu sequences of %llu residues, %llu free on the device", who,
-                          (unsigned long long) bytes, (unsigned long long) nSeq, (unsigned long long) total, (unsigned long long) ((uint64_t) freeB + held));
+                          (unsigned long long) bytes, (unsigned long long) nSeq, (unsigned long long) total, (unsigned long long) avail);
     }
     const uint32_t n32 = (uint32_t) nSeq;
     hipStream_t st = ctx->stream;
@@ -338,7 +286,7 @@ int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSe
     unsigned long long *dPairs = nullptr;
     uint32_t *dNeed, *hHi, *hLo, *hLen, *sHi, *sLo, *sLen, *dStart, *dRunStart, *dHashFlag, *dLargest, *dFoundBy, *dIdentical, *dSmallStart,
         *dSmallSize, *dLargeStart, *dLargeSize;
-    ChSortBufs sb;
+    FieldSortBufs sb;
     const size_t listCap = (size_t) nSeq / 2 + 1;
     SD_HIP(ctx, wsGet(ctx, "ch.res", (size_t) total, &dRes));
     SD_HIP(ctx, wsGet(ctx, "ch.let", (size_t) total + 2 * CH_PAD, &dLet));
@@ -350,13 +298,7 @@ int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSe
     SD_HIP(ctx, wsGet(ctx, "ch.shi", (size_t) nSeq, &sHi));
     SD_HIP(ctx, wsGet(ctx, "ch.slo", (size_t) nSeq, &sLo));
     SD_HIP(ctx, wsGet(ctx, "ch.slen", (size_t) nSeq, &sLen));
-    SD_HIP(ctx, wsGet(ctx, "ch.keyin", (size_t) nSeq, &sb.keyIn));
-    SD_HIP(ctx, wsGet(ctx, "ch.permin", (size_t) nSeq, &sb.permIn));
-    SD_HIP(ctx, wsGet(ctx, "ch.keya", (size_t) nSeq, &sb.keyA));
-    SD_HIP(ctx, wsGet(ctx, "ch.perma", (size_t) nSeq, &sb.permA));
-    SD_HIP(ctx, wsGet(ctx, "ch.keyb", (size_t) nSeq, &sb.keyB));
-    SD_HIP(ctx, wsGet(ctx, "ch.permb", (size_t) nSeq, &sb.permB));
-    SD_HIP(ctx, wsGet(ctx, "ch.counts", sdRadixSortCountsBytes() / sizeof(uint32_t), &sb.counts));
+    SD_HIP(ctx, fieldSortBufsGet(ctx, "ch.", (size_t) nSeq, &sb));
     SD_HIP(ctx, wsGet(ctx, "ch.start", (size_t) nSeq, &dStart));
     SD_HIP(ctx, wsGet(ctx, "ch.runstart", (size_t) nSeq, &dRunStart));
     SD_HIP(ctx, wsGet(ctx, "ch.hashflag", (size_t) nSeq + 1, &dHashFlag));
@@ -396,14 +338,12 @@ int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSe
     {
         HostScope hs(ctx, "ch_sort");
         // (hash, length, id), least significant field first; the input is in id order and every pass is stable.  The hash takes all 64 bits
-        SD_HIP(ctx, chSortByField(st, sb, hLen, nullptr, n32, chBits(maxLen)));
-        SD_HIP(ctx, chSortByField(st, sb, hLo, sb.permA, n32, 32));
-        SD_HIP(ctx, chSortByField(st, sb, hHi, sb.permA, n32, 32));
+        SD_HIP(ctx, sortByField(st, sb, hLen, nullptr, n32, FS_PLAIN, 0, bitsFor(maxLen)));
+        SD_HIP(ctx, sortByField(st, sb, hLo, sb.permA, n32, FS_PLAIN, 0, 32));
+        SD_HIP(ctx, sortByField(st, sb, hHi, sb.permA, n32, FS_PLAIN, 0, 32));
         const uint32_t *src[3] = {hHi, hLo, hLen};
         uint32_t *dst[3] = {sHi, sLo, sLen};
-        for (int f = 0; f < 3; f++)
-            hipLaunchKernelGGL(ch_gather_kernel, dim3(chGrid(nSeq)), dim3(CH_BLOCK), 0, st, src[f], (const uint32_t *) sb.permA, n32, dst[f]);
-        SD_HIP(ctx, hipGetLastError());
+        SD_HIP(ctx, gatherFields(st, sb.permA, n32, 3, src, dst));
         if (ctx->profiling) SD_HIP(ctx, sdStreamSync(ctx));
     }
     const uint32_t *sId = sb.permA;   // the sorted ids: the sort's buffers are not touched again
@@ -411,12 +351,12 @@ int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSe
     uint32_t largest = 0;
     {
         HostScope hs(ctx, "ch_groups");
-        hipLaunchKernelGGL(ch_start_kernel, dim3(chGrid(nSeq + 1)), dim3(CH_BLOCK), 0, st, (const uint32_t *) sHi, (const uint32_t *) sLo,
+        hipLaunchKernelGGL(ch_start_kernel, dim3(gridFor(nSeq + 1, CH_BLOCK)), dim3(CH_BLOCK), 0, st, (const uint32_t *) sHi, (const uint32_t *) sLo,
                            (const uint32_t *) sLen, n32, dStart, dHashFlag);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, (sdScanLaunch<uint32_t, ScanMax32, true, uint32_t>(st, dStart, dRunStart, nSeq, (uint32_t *) dScanTmp)));
         SD_HIP(ctx, (sdScanLaunch<uint32_t, ScanSum64, false, uint64_t>(st, dHashFlag, dHashAt, nSeq + 1, dScanTmp)));
-        hipLaunchKernelGGL(ch_groupflag_kernel, dim3(chGrid(nSeq + 1)), dim3(CH_BLOCK), 0, st, (const uint32_t *) sHi, (const uint32_t *) sLo,
+        hipLaunchKernelGGL(ch_groupflag_kernel, dim3(gridFor(nSeq + 1, CH_BLOCK)), dim3(CH_BLOCK), 0, st, (const uint32_t *) sHi, (const uint32_t *) sLo,
                            (const uint32_t *) sLen, (const uint32_t *) dRunStart, n32, dFlag, dLargest);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, (sdScanLaunch<uint64_t, ScanSum64, false, uint64_t>(st, dFlag, dAt, nSeq + 1, dScanTmp)));
@@ -432,7 +372,7 @@ int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSe
     {
         HostScope hs(ctx, "ch_pass");
         if (nSmall + nLarge > 0) {
-            hipLaunchKernelGGL(ch_grouplist_kernel, dim3(chGrid(nSeq)), dim3(CH_BLOCK), 0, st, (const uint64_t *) dFlag, (const uint64_t *) dAt,
+            hipLaunchKernelGGL(ch_grouplist_kernel, dim3(gridFor(nSeq, CH_BLOCK)), dim3(CH_BLOCK), 0, st, (const uint64_t *) dFlag, (const uint64_t *) dAt,
                                (const uint32_t *) dRunStart, n32, nSmall, nLarge, dSmallStart, dSmallSize, dLargeStart, dLargeSize);
             SD_HIP(ctx, hipGetLastError());
         }
@@ -461,8 +401,7 @@ int sd_clusthash_batch(sd_ctx *ctx, const sd_clusthash_params *par, uint64_t nSe
             SD_HIP(ctx, hipMemcpyAsync(lo.data(), hLo, (size_t) nSeq * 4, hipMemcpyDeviceToHost, st));
         }
         SD_HIP(ctx, sdStreamSync(ctx));
-        if (hash)
-            for (uint64_t s = 0; s < nSeq; s++) hash[s] = ((uint64_t) hi[s] << 32) | lo[s];
+        if (hash) sdJoinHiLo(hi.data(), lo.data(), nSeq, hash);
     }
     if (stats) {
         stats[0] = uniqueHashes;

@@ -8,7 +8,8 @@
 //   sdScanLaunch       record offsets
 //   km_emit_kernel     the identity record and the selected windows in position order (ballot ranks), last-bin rule included
 // Grouping (doComputation, assignGroup, writeKmerMatcherResult; kmermatcher.cpp:426-625, 876-991):
-//   first sort         chained stable sdRadixSortPairs passes over a permutation: pos, id, maxLen - seqLen, key low, key high
+//   first sort         sortByField (sd_field_sort.h: fs_key_kernel + sdRadixSortPairs per link, stable, over a permutation): pos, id,
+//                      maxLen - seqLen, key low, key high; then gatherFields (fs_gather_kernel per field)
 //   km_start_kernel + max scan   first record of every run of equal keys = the representative
 //   km_groupflag_kernel + scan + km_groupwrite_kernel   (rep, member, diagonal) of every record that assignGroup keeps
 //   second sort        diagonal (biased), member, rep
@@ -19,7 +20,7 @@
 // The reference's element type T (short below a longest sequence of 32 767, int otherwise) only sets the width of seqLen, pos and the
 // diagonal: with short every length is below 32 767, so every position and every diagonal fits and nothing is truncated; the fields are
 // 32-bit here in both cases.
-#include "sd_common.h"
+#include "sd_batch_check.h"
 
 #include <omp.h>
 
@@ -28,12 +29,12 @@
 namespace {
 
 #include "sd_scan_sort.h"
+#include "sd_field_sort.h"
 #include "sd_seqhash.h"
 
 constexpr int KM_BLOCK = 256;
 constexpr int KM_MAXK = 24;
 constexpr int KM_CHUNK = 64;   // windows per step of a wavefront
-constexpr uint64_t KM_MAX_RECORDS = (uint64_t) UINT32_MAX - RS_TILE;   // the sort counts in 32 bits and rounds up to whole tiles
 
 struct KmPar {
     uint64_t pw[KM_MAXK];   // (alphabetSize - 1)^j: Indexer(alphabetSize - 1, k)
@@ -203,25 +204,6 @@ km_emit_kernel(KmPar p, const uint8_t *__restrict__ residues, const uint64_t *__
     }
 }
 
-// ---- sorting by chained fields: keyOut[i] = f(field[perm[i]]) --------------------------------------------------------------------
-enum { KM_PLAIN = 0, KM_FROM_TOP = 1, KM_BIASED = 2 };
-__global__ void __launch_bounds__(KM_BLOCK)
-km_field_kernel(const uint32_t *__restrict__ field, const uint32_t *__restrict__ perm, uint32_t n, int mode, uint32_t arg,
-                uint32_t *__restrict__ keyOut, uint32_t *__restrict__ permOut) {
-    const uint64_t i = (uint64_t) blockIdx.x * KM_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t src = perm ? perm[i] : (uint32_t) i;
-    const uint32_t v = field[src];
-    keyOut[i] = mode == KM_FROM_TOP ? arg - v : mode == KM_BIASED ? v + arg : v;
-    if (permOut) permOut[i] = src;
-}
-
-__global__ void __launch_bounds__(KM_BLOCK)
-km_gather_kernel(const uint32_t *__restrict__ field, const uint32_t *__restrict__ perm, uint32_t n, uint32_t *__restrict__ out) {
-    const uint64_t i = (uint64_t) blockIdx.x * KM_BLOCK + threadIdx.x;
-    if (i < n) out[i] = field[perm[i]];
-}
-
 // ---- assignGroup --------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(KM_BLOCK)
 km_start_kernel(const uint32_t *__restrict__ keyHi, const uint32_t *__restrict__ keyLo, uint32_t n, uint32_t *__restrict__ startOrZero) {
@@ -330,25 +312,6 @@ km_hit_kernel(const uint32_t *__restrict__ hRep, const uint32_t *__restrict__ hI
     outDiag[o] = diagonal;
 }
 
-inline unsigned kmGrid(uint64_t items) { return (unsigned) ((items + KM_BLOCK - 1) / KM_BLOCK); }
-inline int kmBits(uint64_t maxValue) {
-    int b = 1;
-    while (b < 32 && ((uint64_t) 1 << b) <= maxValue) b++;
-    return b;
-}
-
-struct KmSortBufs {
-    uint32_t *keyIn, *permIn, *keyA, *permA, *keyB, *permB, *counts;
-};
-
-// one link of the chain: the records in their current order (perm, or the identity when null), stably sorted by f(field); the new
-// order lands in bufs.permA
-inline hipError_t kmSortByField(hipStream_t st, const KmSortBufs &b, const uint32_t *field, const uint32_t *perm, uint32_t n, int mode,
-                                uint32_t arg, int bits) {
-    hipLaunchKernelGGL(km_field_kernel, dim3(kmGrid(n)), dim3(KM_BLOCK), 0, st, field, perm, n, mode, arg, b.keyIn, b.permIn);
-    return sdRadixSortPairs<uint32_t>(st, b.keyIn, b.permIn, b.keyA, b.permA, b.keyB, b.permB, n, 0, bits, b.counts);
-}
-
 // What the records stage leaves on the device: the per-sequence selection, the record offsets, the emitted records (r*) and the
 // workspace of everything behind it.  sd_kmermatch_batch goes on from here; sd_selftest_kmermatch_records copies it out.
 struct KmStage {
@@ -358,7 +321,7 @@ struct KmStage {
     uint64_t *dRecOff, *dScanTmp, *dAt;
     uint32_t *dThr, *dExc, *dConsOut, *dLargest, *dRunStart, *dFlag;
     uint32_t *rKeyHi, *rKeyLo, *rId, *rLen, *rPos, *sKeyHi, *sKeyLo, *sId, *sLen, *sPos;
-    KmSortBufs sb;
+    FieldSortBufs sb;
 };
 
 // Validation, workspace, upload, km_select_kernel, the scan of the record counts and km_emit_kernel (queued on the context's stream when
@@ -386,55 +349,41 @@ int kmRecordsStage(sd_ctx *ctx, const char *who, const sd_kmermatch_params *par,
             pw *= (uint64_t) (par->alphabetSize - 1);
         }
     }
-    for (int a = 0; a < 21; a++) {
-        if (letterMap[a] >= par->alphabetSize) return sdFail(ctx, SD_EINVAL, "%s: letter %d maps to %d of %d", who, a, letterMap[a], par->alphabetSize);
-        kp.map[a] = letterMap[a];
-    }
-    if (offsets[0] != 0) return sdFail(ctx, SD_EINVAL, "%s: offsets must start at 0", who);
-    // per sequence: kmerConsidered before the window count caps it (kmermatcher.cpp:204-206: sd_host_kmermatch_considered, the product
-    // rounded to float before the sum, whatever this file's compiler would contract), and the record bound; checked here, so that no lane
-    // indexes outside its arrays.  Timed as km_prepare; the first-use allocations behind it as km_alloc
+    // Timed as km_prepare; the first-use allocations behind it as km_alloc
     std::unique_ptr<HostScope> phase(new HostScope(ctx, "km_prepare"));
+    SdSeqBatch batch;
+    const int rcCheck = sdCheckSeqBatch(ctx, who, par->alphabetSize, nSeq, residues, offsets, letterMap, &batch);
+    if (rcCheck != SD_OK) return rcCheck;
+    memcpy(kp.map, batch.map, sizeof(kp.map));
+    const uint64_t maxLen = batch.maxLen, total = batch.total;
+    // per sequence: kmerConsidered before the window count caps it (kmermatcher.cpp:204-206: sd_host_kmermatch_considered, the product
+    // rounded to float before the sum, whatever this file's compiler would contract), and the record bound
     std::vector<uint32_t> cons(nSeq ? nSeq : 1);
-    uint64_t bound = 0, maxLen = 0;
+    uint64_t bound = 0;
     uint32_t maxKey = 0;
     for (uint64_t s = 0; s < nSeq; s++) {
-        if (offsets[s + 1] < offsets[s]) return sdFail(ctx, SD_EINVAL, "%s: offsets descend at sequence %llu", who, (unsigned long long) s);
         const uint64_t L = offsets[s + 1] - offsets[s];
-        if (L > (uint64_t) INT32_MAX / 2) return sdFail(ctx, SD_EINVAL, "%s: sequence %llu has %llu residues", who, (unsigned long long) s, (unsigned long long) L);
         const uint64_t considered = sd_host_kmermatch_considered(par->kmersPerSequence, par->kmersPerSequenceScale, (uint32_t) L);
         const uint64_t windows = L >= (uint64_t) kp.k ? L - (uint64_t) kp.k + 1 : 0;
         cons[s] = (uint32_t) std::min(considered, windows);
         bound += 1 + cons[s];
-        maxLen = std::max(maxLen, L);
         maxKey = std::max(maxKey, keys[s]);
-    }
-    const uint64_t total = offsets[nSeq];
-    {
-        uint64_t bad = UINT64_MAX;
-#pragma omp parallel for schedule(static) reduction(min : bad) if (total > (1u << 16))
-        for (uint64_t i = 0; i < total; i++)
-            if (residues[i] >= 21 && i < bad) bad = i;
-        if (bad != UINT64_MAX) return sdFail(ctx, SD_EINVAL, "%s: residue %llu has code %u (0 .. 20)", who, (unsigned long long) bad, residues[bad]);
     }
     if (nSeq == 0) {
         stage->empty = true;
         return SD_OK;
     }
-    if (bound > KM_MAX_RECORDS)
+    if (bound > RS_MAX_ELEMENTS)
         return sdFail(ctx, SD_ENOMEM, "%s: up to %llu records in one call (the device sort counts in 32 bits: at most %llu); %llu bytes needed",
-                      who, (unsigned long long) bound, (unsigned long long) KM_MAX_RECORDS, (unsigned long long) (bound * SD_KMERMATCH_BYTES_PER_RECORD + total));
+                      who, (unsigned long long) bound, (unsigned long long) RS_MAX_ELEMENTS, (unsigned long long) (bound * SD_KMERMATCH_BYTES_PER_RECORD + total));
     // everything is resident at once (the reference would split by hash range here, with scores saturated to a byte: another output)
     {
         const uint64_t need = bound * SD_KMERMATCH_BYTES_PER_RECORD + total + nSeq * 40;
-        size_t freeB = 0, totalB = 0;
-        SD_HIP(ctx, hipMemGetInfo(&freeB, &totalB));
-        uint64_t held = 0;   // what this context's kmermatcher workspace already holds counts as available
-        for (auto &e : ctx->ws)
-            if (e.first.compare(0, 3, "km.") == 0) held += e.second.bytes;
-        if (need > (uint64_t) freeB + held)
+        uint64_t avail = 0;   // (what this context's kmermatcher workspace already holds counts as available)
+        SD_HIP(ctx, wsAvailableBytes(ctx, "km.", &avail));
+        if (need > avail)
             return sdFail(ctx, SD_ENOMEM, "%s: %llu bytes needed for up to %llu records, %llu free on the device (splitting by hash range is not implemented)",
-                          who, (unsigned long long) need, (unsigned long long) bound, (unsigned long long) ((uint64_t) freeB + held));
+                          who, (unsigned long long) need, (unsigned long long) bound, (unsigned long long) avail);
     }
     const uint32_t n32 = (uint32_t) nSeq;
     hipStream_t st = ctx->stream;
@@ -455,7 +404,7 @@ int kmRecordsStage(sd_ctx *ctx, const char *who, const sd_kmermatch_params *par,
     SD_HIP(ctx, wsGet(ctx, "km.scantmp", sdScanTmpBytes(std::max(bound, nSeq) + 1) / sizeof(uint64_t), &dScanTmp));
     // per record: the five fields as emitted (r*), the same sorted (s*), the sort's three (key, permutation) pairs, run start, flag, place
     uint32_t *rKeyHi, *rKeyLo, *rId, *rLen, *rPos, *sKeyHi, *sKeyLo, *sId, *sLen, *sPos, *dRunStart, *dFlag;
-    KmSortBufs sb;
+    FieldSortBufs sb;
     SD_HIP(ctx, wsGet(ctx, "km.rkeyhi", (size_t) bound, &rKeyHi));
     SD_HIP(ctx, wsGet(ctx, "km.rkeylo", (size_t) bound, &rKeyLo));
     SD_HIP(ctx, wsGet(ctx, "km.rid", (size_t) bound, &rId));
@@ -466,13 +415,7 @@ int kmRecordsStage(sd_ctx *ctx, const char *who, const sd_kmermatch_params *par,
     SD_HIP(ctx, wsGet(ctx, "km.sid", (size_t) bound, &sId));
     SD_HIP(ctx, wsGet(ctx, "km.slen", (size_t) bound, &sLen));
     SD_HIP(ctx, wsGet(ctx, "km.spos", (size_t) bound, &sPos));
-    SD_HIP(ctx, wsGet(ctx, "km.keyin", (size_t) bound, &sb.keyIn));
-    SD_HIP(ctx, wsGet(ctx, "km.permin", (size_t) bound, &sb.permIn));
-    SD_HIP(ctx, wsGet(ctx, "km.keya", (size_t) bound, &sb.keyA));
-    SD_HIP(ctx, wsGet(ctx, "km.perma", (size_t) bound, &sb.permA));
-    SD_HIP(ctx, wsGet(ctx, "km.keyb", (size_t) bound, &sb.keyB));
-    SD_HIP(ctx, wsGet(ctx, "km.permb", (size_t) bound, &sb.permB));
-    SD_HIP(ctx, wsGet(ctx, "km.counts", sdRadixSortCountsBytes() / sizeof(uint32_t), &sb.counts));
+    SD_HIP(ctx, fieldSortBufsGet(ctx, "km.", (size_t) bound, &sb));
     SD_HIP(ctx, wsGet(ctx, "km.runstart", (size_t) bound, &dRunStart));
     SD_HIP(ctx, wsGet(ctx, "km.flag", (size_t) bound + 1, &dFlag));
     SD_HIP(ctx, wsGet(ctx, "km.at", (size_t) bound + 1, &dAt));
@@ -551,23 +494,21 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
     uint32_t *dLargest = stage.dLargest, *dRunStart = stage.dRunStart, *dFlag = stage.dFlag;
     uint32_t *rKeyHi = stage.rKeyHi, *rKeyLo = stage.rKeyLo, *rId = stage.rId, *rLen = stage.rLen, *rPos = stage.rPos;
     uint32_t *sKeyHi = stage.sKeyHi, *sKeyLo = stage.sKeyLo, *sId = stage.sId, *sLen = stage.sLen, *sPos = stage.sPos;
-    const KmSortBufs &sb = stage.sb;
+    const FieldSortBufs &sb = stage.sb;
     const uint32_t r32 = (uint32_t) nRec;
     if (stats) stats[0] = nRec;
-    const int idBits = kmBits(maxKey), lenBits = kmBits(maxLen);
+    const int idBits = bitsFor(maxKey), lenBits = bitsFor(maxLen);
     {
         HostScope hs(ctx, "km_sort1");
         // compareRepSequenceAndIdAndPos, least significant field first.  The identity records are 64-bit hashes: the key takes all its bits
-        SD_HIP(ctx, kmSortByField(st, sb, rPos, nullptr, r32, KM_PLAIN, 0, lenBits));
-        SD_HIP(ctx, kmSortByField(st, sb, rId, sb.permA, r32, KM_PLAIN, 0, idBits));
-        SD_HIP(ctx, kmSortByField(st, sb, rLen, sb.permA, r32, KM_FROM_TOP, (uint32_t) maxLen, lenBits));
-        SD_HIP(ctx, kmSortByField(st, sb, rKeyLo, sb.permA, r32, KM_PLAIN, 0, 32));
-        SD_HIP(ctx, kmSortByField(st, sb, rKeyHi, sb.permA, r32, KM_PLAIN, 0, 32));
+        SD_HIP(ctx, sortByField(st, sb, rPos, nullptr, r32, FS_PLAIN, 0, lenBits));
+        SD_HIP(ctx, sortByField(st, sb, rId, sb.permA, r32, FS_PLAIN, 0, idBits));
+        SD_HIP(ctx, sortByField(st, sb, rLen, sb.permA, r32, FS_FROM_TOP, (uint32_t) maxLen, lenBits));
+        SD_HIP(ctx, sortByField(st, sb, rKeyLo, sb.permA, r32, FS_PLAIN, 0, 32));
+        SD_HIP(ctx, sortByField(st, sb, rKeyHi, sb.permA, r32, FS_PLAIN, 0, 32));
         const uint32_t *src[5] = {rKeyHi, rKeyLo, rId, rLen, rPos};
         uint32_t *dst[5] = {sKeyHi, sKeyLo, sId, sLen, sPos};
-        for (int f = 0; f < 5; f++)
-            hipLaunchKernelGGL(km_gather_kernel, dim3(kmGrid(nRec)), dim3(KM_BLOCK), 0, st, src[f], (const uint32_t *) sb.permA, r32, dst[f]);
-        SD_HIP(ctx, hipGetLastError());
+        SD_HIP(ctx, gatherFields(st, sb.permA, r32, 5, src, dst));
         if (ctx->profiling) SD_HIP(ctx, sdStreamSync(ctx));
     }
     uint64_t nGroup = 0;
@@ -576,15 +517,15 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
     uint32_t *gRep = rKeyHi, *gId = rKeyLo, *gDiag = rId, *hRep = rLen, *hId = rPos, *hDiag = sKeyHi;
     {
         HostScope hs(ctx, "km_group");
-        hipLaunchKernelGGL(km_start_kernel, dim3(kmGrid(nRec)), dim3(KM_BLOCK), 0, st, (const uint32_t *) sKeyHi, (const uint32_t *) sKeyLo, r32, dFlag);
+        hipLaunchKernelGGL(km_start_kernel, dim3(gridFor(nRec, KM_BLOCK)), dim3(KM_BLOCK), 0, st, (const uint32_t *) sKeyHi, (const uint32_t *) sKeyLo, r32, dFlag);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, (sdScanLaunch<uint32_t, ScanMax32, true, uint32_t>(st, dFlag, dRunStart, nRec, (uint32_t *) dScanTmp)));
-        hipLaunchKernelGGL(km_groupflag_kernel, dim3(kmGrid(nRec + 1)), dim3(KM_BLOCK), 0, st, (const uint32_t *) sKeyHi, (const uint32_t *) sKeyLo,
+        hipLaunchKernelGGL(km_groupflag_kernel, dim3(gridFor(nRec + 1, KM_BLOCK)), dim3(KM_BLOCK), 0, st, (const uint32_t *) sKeyHi, (const uint32_t *) sKeyLo,
                            (const uint32_t *) sLen, (const uint32_t *) sPos, (const uint32_t *) dRunStart, r32, par->includeOnlyExtendable ? 1 : 0,
                            par->covMode, par->covThr, dFlag, dLargest);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, (sdScanLaunch<uint32_t, ScanSum64, false, uint64_t>(st, dFlag, dAt, nRec + 1, dScanTmp)));
-        hipLaunchKernelGGL(km_groupwrite_kernel, dim3(kmGrid(nRec)), dim3(KM_BLOCK), 0, st, (const uint32_t *) sId, (const uint32_t *) sPos,
+        hipLaunchKernelGGL(km_groupwrite_kernel, dim3(gridFor(nRec, KM_BLOCK)), dim3(KM_BLOCK), 0, st, (const uint32_t *) sId, (const uint32_t *) sPos,
                            (const uint32_t *) dRunStart, (const uint32_t *) dFlag, (const uint64_t *) dAt, r32, gRep, gId, gDiag);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, sdD2H(ctx, &nGroup, dAt + nRec, 8));
@@ -601,18 +542,16 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
         {
             HostScope hs(ctx, "km_sort2");
             // compareRepSequenceAndIdAndDiag; the diagonal is signed: biased by the longest sequence it sorts as an unsigned value
-            SD_HIP(ctx, kmSortByField(st, sb, gDiag, nullptr, w32, KM_BIASED, (uint32_t) maxLen, kmBits(2 * maxLen)));
-            SD_HIP(ctx, kmSortByField(st, sb, gId, sb.permA, w32, KM_PLAIN, 0, idBits));
-            SD_HIP(ctx, kmSortByField(st, sb, gRep, sb.permA, w32, KM_PLAIN, 0, idBits));
+            SD_HIP(ctx, sortByField(st, sb, gDiag, nullptr, w32, FS_BIASED, (uint32_t) maxLen, bitsFor(2 * maxLen)));
+            SD_HIP(ctx, sortByField(st, sb, gId, sb.permA, w32, FS_PLAIN, 0, idBits));
+            SD_HIP(ctx, sortByField(st, sb, gRep, sb.permA, w32, FS_PLAIN, 0, idBits));
             const uint32_t *src[3] = {gRep, gId, gDiag};
             uint32_t *dst[3] = {hRep, hId, hDiag};
-            for (int f = 0; f < 3; f++)
-                hipLaunchKernelGGL(km_gather_kernel, dim3(kmGrid(nGroup)), dim3(KM_BLOCK), 0, st, src[f], (const uint32_t *) sb.permA, w32, dst[f]);
-            SD_HIP(ctx, hipGetLastError());
+            SD_HIP(ctx, gatherFields(st, sb.permA, w32, 3, src, dst));
             if (ctx->profiling) SD_HIP(ctx, sdStreamSync(ctx));
         }
         HostScope hs(ctx, "km_hits");
-        hipLaunchKernelGGL(km_hitflag_kernel, dim3(kmGrid(nGroup + 1)), dim3(KM_BLOCK), 0, st, (const uint32_t *) hRep, (const uint32_t *) hId, w32, dFlag);
+        hipLaunchKernelGGL(km_hitflag_kernel, dim3(gridFor(nGroup + 1, KM_BLOCK)), dim3(KM_BLOCK), 0, st, (const uint32_t *) hRep, (const uint32_t *) hId, w32, dFlag);
         SD_HIP(ctx, hipGetLastError());
         SD_HIP(ctx, (sdScanLaunch<uint32_t, ScanSum64, false, uint64_t>(st, dFlag, dAt, nGroup + 1, dScanTmp)));
         SD_HIP(ctx, sdD2H(ctx, &nHits, dAt + nGroup, 8));
@@ -628,7 +567,7 @@ int sd_kmermatch_batch(sd_ctx *ctx, const sd_kmermatch_params *par, uint64_t nSe
     int32_t *dOutDiag = (int32_t *) sb.keyB;
     {
         HostScope hs(ctx, "km_hits");
-        hipLaunchKernelGGL(km_hit_kernel, dim3(kmGrid(nGroup)), dim3(KM_BLOCK), 0, st, (const uint32_t *) hRep, (const uint32_t *) hId,
+        hipLaunchKernelGGL(km_hit_kernel, dim3(gridFor(nGroup, KM_BLOCK)), dim3(KM_BLOCK), 0, st, (const uint32_t *) hRep, (const uint32_t *) hId,
                            (const uint32_t *) hDiag, (const uint32_t *) sId, (const uint32_t *) sPos, w32, r32, (const uint32_t *) dFlag,
                            (const uint64_t *) dAt, dOutRep, dOutMember, dOutScore, dOutDiag);
         SD_HIP(ctx, hipGetLastError());
@@ -677,7 +616,37 @@ int sd_selftest_kmermatch_records(sd_ctx *ctx, const sd_kmermatch_params *par, u
     SD_HIP(ctx, hipMemcpyAsync(recLen, stage.rLen, (size_t) nRec * 4, hipMemcpyDeviceToHost, st));
     SD_HIP(ctx, hipMemcpyAsync(recPos, stage.rPos, (size_t) nRec * 4, hipMemcpyDeviceToHost, st));
     SD_HIP(ctx, sdStreamSync(ctx));
-    for (uint64_t i = 0; i < nRec; i++) recKey[i] = ((uint64_t) hi[i] << 32) | lo[i];
+    sdJoinHiLo(hi.data(), lo.data(), nRec, recKey);
+    return SD_OK;
+}
+
+int sd_selftest_field_sort(sd_ctx *ctx, uint32_t n, int nFields, const uint32_t *fields, const int32_t *modes, const uint32_t *args,
+                           const int32_t *bits, uint32_t *outPerm, uint32_t *outFields) {
+    if (!ctx || nFields < 1 || nFields > 5 || !modes || !args || !bits || (n && (!fields || !outPerm || !outFields))) return SD_EINVAL;
+    for (int f = 0; f < nFields; f++)
+        if (modes[f] < FS_PLAIN || modes[f] > FS_BIASED || bits[f] < 1 || bits[f] > 32) return SD_EINVAL;
+    if (n > RS_MAX_ELEMENTS) return SD_EUNSUPPORTED;
+    (void) hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t all = (size_t) nFields * n;
+    uint32_t *dIn = nullptr, *dOut = nullptr;
+    FieldSortBufs sb;
+    SD_HIP(ctx, wsGet(ctx, "fs.in", all, &dIn));
+    SD_HIP(ctx, wsGet(ctx, "fs.out", all, &dOut));
+    SD_HIP(ctx, fieldSortBufsGet(ctx, "fs.", n, &sb));
+    if (n) SD_HIP(ctx, hipMemcpyAsync(dIn, fields, all * 4, hipMemcpyHostToDevice, st));
+    const uint32_t *src[5];
+    uint32_t *dst[5];
+    for (int f = 0; f < nFields; f++) {
+        src[f] = dIn + (size_t) f * n;
+        dst[f] = dOut + (size_t) f * n;
+        SD_HIP(ctx, sortByField(st, sb, src[f], f ? sb.permA : nullptr, n, modes[f], args[f], bits[f]));
+    }
+    SD_HIP(ctx, gatherFields(st, sb.permA, n, nFields, src, dst));
+    if (n == 0) return SD_OK;   // (the shared functions launch nothing then)
+    SD_HIP(ctx, hipMemcpyAsync(outPerm, sb.permA, (size_t) n * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipMemcpyAsync(outFields, dOut, all * 4, hipMemcpyDeviceToHost, st));
+    SD_HIP(ctx, hipStreamSynchronize(st));
     return SD_OK;
 }
 

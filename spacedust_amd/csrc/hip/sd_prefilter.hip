@@ -2652,16 +2652,13 @@ __global__ void cand_stats_kernel(uint32_t nCand, const uint32_t *__restrict__ c
 
 // device-wide scans and the radix sort: this library's own kernels (sd_scan_sort.h)
 #include "sd_scan_sort.h"
+// exclusive sum of n values (any unsigned width) into 64-bit offsets
 template <typename T, typename Tmp>
-int exclusiveScanWiden(sd_ctx *ctx, const T *in, uint64_t *out, uint64_t n, Tmp &tmp) {
+int exclusiveScan(sd_ctx *ctx, const T *in, uint64_t *out, uint64_t n, Tmp &tmp) {
     if (n == 0) return SD_OK;
     if (tmp.n < sdScanTmpBytes(n)) SD_HIP(ctx, tmp.alloc(sdScanTmpBytes(n) + 256));
     SD_HIP(ctx, (sdScanLaunch<T, ScanSum64, false, uint64_t>(ctx->stream, in, out, n, (uint64_t *) tmp.p)));
     return SD_OK;
-}
-template <typename T, typename Tmp>
-int exclusiveScan(sd_ctx *ctx, const T *in, uint64_t *out, uint64_t n, Tmp &tmp) {
-    return exclusiveScanWiden(ctx, in, out, n, tmp);
 }
 // stable sort of (key, value) pairs by the key bits [beginBit, endBit) into (kOut, vOut); scratch in the workspace
 int sortPairs(sd_ctx *ctx, const uint32_t *kIn, uint32_t *kOut, const uint32_t *vIn, uint32_t *vOut, uint64_t n, int beginBit, int endBit) {
@@ -3091,7 +3088,7 @@ int PfBatch::stageCountKmers() {
     }
     if (nPos > 0) {
         SD_RC(launchKmerPass(KMERS_COUNT));
-        SD_RC(exclusiveScanWiden(ctx, dKmerCount.p, dKmerBase.p, nPos + 1, c.scanTmp));
+        SD_RC(exclusiveScan(ctx, dKmerCount.p, dKmerBase.p, nPos + 1, c.scanTmp));
         int hErrCount = 0;
         if (joinCandidate) {
             SD_HIP(ctx, dQKmerBase.alloc(bq + 1));
@@ -3141,7 +3138,7 @@ int PfBatch::emitLookup() {
     SD_HIP(ctx, hipMemsetAsync(dKLen.p, 0, (nKmers + 1) * sizeof(uint32_t), ctx->stream));
     if (nKmers > 0) {
         SD_RC(launchKmerPass(KMERS_EMIT_LOOKUP));
-        SD_RC(exclusiveScanWiden(ctx, dKLen.p, dHitBase.p, nKmers + 1, c.scanTmp));
+        SD_RC(exclusiveScan(ctx, dKLen.p, dHitBase.p, nKmers + 1, c.scanTmp));
         SD_HIP(ctx, sdD2H(ctx, &nHits, dHitBase.p + nKmers, sizeof(uint64_t)));
         SD_HIP(ctx, sdStreamSync(ctx));
     }
@@ -3170,7 +3167,7 @@ int PfBatch::lookupSplits() {
         // the queries taken out: their index lists emptied, the offsets scanned again
         SD_RC(markUnsupportedQueries("have >= 2^32 index hits or overflow the reference's hit buffer more than 32 times"));
         hipLaunchKernelGGL(drop_query_kmers_kernel, dim3(gridFor(nKmers, 256)), dim3(256), 0, ctx->stream, nKmers, dKPos.p, dQSplit.p, dKLen.p);
-        SD_RC(exclusiveScanWiden(ctx, dKLen.p, dHitBase.p, nKmers + 1, c.scanTmp));
+        SD_RC(exclusiveScan(ctx, dKLen.p, dHitBase.p, nKmers + 1, c.scanTmp));
         SD_HIP(ctx, sdD2H(ctx, &nHits, dHitBase.p + nKmers, sizeof(uint64_t)));
         SD_HIP(ctx, hipMemsetAsync(dSplitFlag.p, 0, sizeof(int), ctx->stream));
         querySplit();
@@ -3371,7 +3368,7 @@ int PfBatch::hotFilter(HitStream &s) {
         hipLaunchKernelGGL(hot_filter_kernel, dim3(hfGrid), dim3(HF_NT), 0, ctx->stream, nVQ, s.pHitBase, s.tBitsV, (uint32_t *) s.pKey, (uint32_t *) s.pVal,
                            (uint2 *) s.pKV, widePos ? s.tBitsV : 0, c.knobs.filterMin, dHotCount.p);
     }
-    SD_RC(exclusiveScanWiden(ctx, dHotCount.p, dHotBase.p, (uint64_t) nVQ + 1, c.scanTmp));
+    SD_RC(exclusiveScan(ctx, dHotCount.p, dHotBase.p, (uint64_t) nVQ + 1, c.scanTmp));
     SD_HIP(ctx, sdD2H(ctx, &s.nLeft, dHotBase.p + nVQ, sizeof(uint64_t)));
     SD_HIP(ctx, sdStreamSync(ctx));
     s.pSegCount = dHotCount.p;
@@ -3433,7 +3430,7 @@ int PfBatch::bucketMatch(const HitStream &s) {
                            s.pHitBase, tBitsV, s.pKey, s.pVal, s.pKV, dKVB.p, dQLog2.p, dBktStart.p, dBktCount.p, dFlag.p, s.pSegCount, s.pOutBase, pSegDone);
     }
     hipLaunchKernelGGL(bin_count_kernel, dim3(gridFor(nVQ + 1, 256)), dim3(256), 0, ctx->stream, nVQ, dQLog2.p, dQBins.p);
-    SD_RC(exclusiveScanWiden(ctx, dQBins.p, dBinBase.p, nVQ + 1, c.scanTmp));
+    SD_RC(exclusiveScan(ctx, dQBins.p, dBinBase.p, nVQ + 1, c.scanTmp));
     int hFlag = 0;
     uint64_t totalBins = 0;
     SD_HIP(ctx, sdD2H(ctx, &hFlag, dFlag.p, sizeof(int)));
@@ -3465,7 +3462,7 @@ int PfBatch::bucketMatch(const HitStream &s) {
                                (uint32_t *) nullptr, 0u, dQSplit.p, dQParts.p, dQSplits.p, cBits, wideBits, (const uint32_t *) dBigCount, first);
         };
         launchBig(0, std::min<uint32_t>(BIG_GRID, bigCap));
-        SD_RC(exclusiveScanWiden(ctx, dBktEmit.p, dEmitOff.p, nSlots + 1, c.scanTmp));
+        SD_RC(exclusiveScan(ctx, dBktEmit.p, dEmitOff.p, nSlots + 1, c.scanTmp));
         uint64_t nc64 = 0;
         uint32_t nBig = 0;
         SD_HIP(ctx, sdD2H(ctx, &nBig, dBigCount, sizeof(uint32_t)));
@@ -3474,7 +3471,7 @@ int PfBatch::bucketMatch(const HitStream &s) {
         SD_HIP(ctx, sdStreamSync(ctx));
         if (hFlag == 0 && nBig > BIG_GRID && nBig <= bigCap) {   // the rest of a long list, then the offsets again
             for (uint32_t first = BIG_GRID; first < nBig; first += 1u << 20) launchBig(first, std::min<uint32_t>(nBig - first, 1u << 20));
-            SD_RC(exclusiveScanWiden(ctx, dBktEmit.p, dEmitOff.p, nSlots + 1, c.scanTmp));
+            SD_RC(exclusiveScan(ctx, dBktEmit.p, dEmitOff.p, nSlots + 1, c.scanTmp));
             SD_HIP(ctx, sdD2H(ctx, &hFlag, dFlag.p, sizeof(int)));
             SD_HIP(ctx, sdD2H(ctx, &nc64, dEmitOff.p + nSlots, sizeof(uint64_t)));
             SD_HIP(ctx, sdStreamSync(ctx));
@@ -3514,7 +3511,7 @@ int PfBatch::sortFallback() {
             hipLaunchKernelGGL(match_diag_kernel, dim3(gridFor(nHits, 256)), dim3(256), 0, ctx->stream, nHits, dKeyB.p, dValB.p, dQSplit.p, c.tBits, dEmit.p);
         }
         SD_HIP(ctx, hipMemsetAsync(dEmit.p + nHits, 0, 1, ctx->stream));
-        SD_RC(exclusiveScanWiden(ctx, dEmit.p, dEmitPos.p, nHits + 1, c.scanTmp));
+        SD_RC(exclusiveScan(ctx, dEmit.p, dEmitPos.p, nHits + 1, c.scanTmp));
         uint64_t nc64 = 0;
         SD_HIP(ctx, sdD2H(ctx, &nc64, dEmitPos.p + nHits, sizeof(uint64_t)));
         SD_HIP(ctx, sdStreamSync(ctx));

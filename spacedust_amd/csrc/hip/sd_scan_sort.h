@@ -1,6 +1,7 @@
 // Device-wide prefix scans and a stable LSD radix sort of (uint32 key, 32- or 64-bit value) pairs -- this library's own (no hipCUB /
 // rocPRIM anywhere in the tree).  Included by sd_prefilter.hip, sd_sw.hip, sd_sw_alt.hip, sd_index_build.hip, sd_expand.hip,
-// sd_clust.hip, sd_kmermatch.hip and sd_clusthash.hip inside their anonymous namespaces.
+// sd_clust.hip, sd_kmermatch.hip and sd_clusthash.hip inside their anonymous namespaces (the last three with sd_field_sort.h, the
+// chained sort by several fields, behind it).
 //
 // Why not the library forms: the library's scan is a decoupled look-back (tiles spin on their predecessors) and its one-sweep
 // sort runs 1 024-thread workgroups that do the same; both are fine on an idle device and take milliseconds when three other
@@ -151,6 +152,24 @@ inline hipError_t sdScanLaunch(hipStream_t stream, const T *in, Out *out, uint64
 }
 inline size_t sdScanTmpBytes(uint64_t n) { return ((n + SCAN_TILE - 1) / SCAN_TILE + 1) * sizeof(uint64_t); }
 
+// The same on a context's stream, with the scratch in the context's workspace under tmpKey (sd_sw.hip, sd_sw_alt.hip).
+// exclusive sum of n values (any unsigned width) into 64-bit offsets
+template <typename T>
+int sdCtxExclusiveScan(sd_ctx *ctx, const char *tmpKey, const T *in, uint64_t *out, size_t n) {
+    uint64_t *tmp = nullptr;
+    SD_HIP(ctx, wsGet(ctx, tmpKey, sdScanTmpBytes(n) / sizeof(uint64_t) + 32, &tmp));
+    SD_HIP(ctx, (sdScanLaunch<T, ScanSum64, false, uint64_t>(ctx->stream, in, out, n, tmp)));
+    return SD_OK;
+}
+// running maximum (inclusive) of n values of up to 32 bits (templates, like the sort below: an includer gets the kernels of what it calls)
+template <typename T>
+int sdCtxInclusiveMax(sd_ctx *ctx, const char *tmpKey, const T *in, T *out, size_t n) {
+    uint32_t *tmp = nullptr;
+    SD_HIP(ctx, wsGet(ctx, tmpKey, sdScanTmpBytes(n) / sizeof(uint32_t) + 32, &tmp));
+    SD_HIP(ctx, (sdScanLaunch<T, ScanMax32, true, T>(ctx->stream, in, out, n, tmp)));
+    return SD_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // stable LSD radix sort of (key, value) pairs, 8 bits per pass
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -159,6 +178,8 @@ constexpr int RS_PER = 16;                 // elements per thread and tile
 constexpr int RS_TILE = RS_NT * RS_PER;    // 4 096 elements: 32 KB of staging
 constexpr int RS_BINS = 256;
 constexpr int RS_WGS_MAX = 1024;           // persistent workgroups (rows of the count matrix)
+// most elements of one sort: it counts in 32 bits and rounds the count up to whole tiles
+constexpr uint64_t RS_MAX_ELEMENTS = (uint64_t) UINT32_MAX - RS_TILE;
 
 __device__ __forceinline__ uint32_t rsDigit(uint32_t key, int shift, uint32_t mask) { return (key >> shift) & mask; }
 
@@ -338,6 +359,21 @@ inline hipError_t sdRadixSortPairs(hipStream_t stream, const uint32_t *kIn, cons
         sv = dv;
     }
     return hipGetLastError();
+}
+
+// ... on a context's stream by the key bits [0, endBit), with the scratch pair and the counts in the context's workspace under
+// <keyPrefix>K, <keyPrefix>V and <keyPrefix>Counts
+template <typename V>
+int sdCtxSortPairs(sd_ctx *ctx, const char *keyPrefix, const uint32_t *kIn, uint32_t *kOut, const V *vIn, V *vOut, size_t n, int endBit) {
+    if (n == 0) return SD_OK;
+    const std::string p(keyPrefix);
+    uint32_t *kTmp = nullptr, *cnt = nullptr;
+    V *vTmp = nullptr;
+    SD_HIP(ctx, wsGet(ctx, (p + "K").c_str(), n, &kTmp));
+    SD_HIP(ctx, wsGet(ctx, (p + "V").c_str(), n, &vTmp));
+    SD_HIP(ctx, wsGet(ctx, (p + "Counts").c_str(), sdRadixSortCountsBytes() / sizeof(uint32_t), &cnt));
+    SD_HIP(ctx, sdRadixSortPairs(ctx->stream, kIn, vIn, kOut, vOut, kTmp, vTmp, (uint32_t) n, 0, endBit, cnt));
+    return SD_OK;
 }
 
 #endif

@@ -1647,33 +1647,6 @@ k_accept_compact(uint32_t nPairs, const sd_sw_result *__restrict__ res, const ui
 // without inter-workgroup waiting -- they run between the score wavefronts of the other lanes
 #include "sd_scan_sort.h"
 
-// exclusive sum of n values (any unsigned width) into 64-bit offsets
-template <typename T>
-int devExclusiveScan(sd_ctx *ctx, const T *in, uint64_t *out, size_t n) {
-    uint64_t *tmp = nullptr;
-    SD_HIP(ctx, wsGet(ctx, "al.scantmp", sdScanTmpBytes(n) / sizeof(uint64_t) + 32, &tmp));
-    SD_HIP(ctx, (sdScanLaunch<T, ScanSum64, false, uint64_t>(ctx->stream, in, out, n, tmp)));
-    return SD_OK;
-}
-// running maximum (inclusive) of n 32-bit values
-int devInclusiveMax(sd_ctx *ctx, const uint32_t *in, uint32_t *out, size_t n) {
-    uint32_t *tmp = nullptr;
-    SD_HIP(ctx, wsGet(ctx, "al.scantmp32", sdScanTmpBytes(n) / sizeof(uint32_t) + 32, &tmp));
-    SD_HIP(ctx, (sdScanLaunch<uint32_t, ScanMax32, true, uint32_t>(ctx->stream, in, out, n, tmp)));
-    return SD_OK;
-}
-
-// stable sort of (key, value) pairs by the key bits [0, endBit)
-int devSortPairs(sd_ctx *ctx, const uint32_t *kIn, uint32_t *kOut, const uint32_t *vIn, uint32_t *vOut, size_t n, int endBit) {
-    if (n == 0) return SD_OK;
-    uint32_t *kTmp = nullptr, *vTmp = nullptr, *cnt = nullptr;
-    SD_HIP(ctx, wsGet(ctx, "al.sortK", n, &kTmp));
-    SD_HIP(ctx, wsGet(ctx, "al.sortV", n, &vTmp));
-    SD_HIP(ctx, wsGet(ctx, "al.sortCounts", sdRadixSortCountsBytes() / sizeof(uint32_t), &cnt));
-    SD_HIP(ctx, sdRadixSortPairs(ctx->stream, kIn, vIn, kOut, vOut, kTmp, vTmp, (uint32_t) n, 0, endBit, cnt));
-    return SD_OK;
-}
-
 __global__ void __launch_bounds__(256)
 k_bound_need(uint32_t nPairs, const SwTask *__restrict__ tasks, const uint32_t *__restrict__ keys, uint64_t *__restrict__ need) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1817,29 +1790,29 @@ int devRunScore(sd_ctx *ctx, const AlignWs &w, uint32_t nPairs, const uint32_t *
         SD_HIP(ctx, hipMemsetAsync(dOrder2, 0xFF, order2Cap * sizeof(uint32_t), ctx->stream));   // empty pairs: PAIR_NONE
         SD_HIP(ctx, wsGet(ctx, "sp.bounds", 64, &dPairBounds));
         hipLaunchKernelGGL(k_pair_keys, dim3(grid), dim3(256), 0, ctx->stream, nPairs, dKeys, dPairQ, dKey2, startOnly);
-        rc = devSortPairs(ctx, dKey2, w.dKeysS, w.dVals, dVals2, nPairs, 32);
+        rc = sdCtxSortPairs(ctx, "al.sort", dKey2, w.dKeysS, w.dVals, dVals2, nPairs, 32);
         if (rc != SD_OK) return rc;
         dOrder = dVals2;
         hipLaunchKernelGGL(k_pair_heads, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dHead);
-        rc = devInclusiveMax(ctx, dHead, dRunStart, nPairs);
+        rc = sdCtxInclusiveMax(ctx, "al.scantmp32", dHead, dRunStart, nPairs);
         if (rc != SD_OK) return rc;
         hipLaunchKernelGGL(k_pair_leaders, dim3((nPairs + 256) / 256), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dRunStart, dLeader, startOnly,
                            ctx->group16 ? 1 : 0);
-        rc = devExclusiveScan(ctx, (const uint8_t *) dLeader, dPairIdx, (size_t) nPairs + 1);
+        rc = sdCtxExclusiveScan(ctx, "al.scantmp", (const uint8_t *) dLeader, dPairIdx, (size_t) nPairs + 1);
         if (rc != SD_OK) return rc;
         hipLaunchKernelGGL(k_pair_emit, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dKeysS, dVals2, dRunStart, dPairIdx, dOrder2, startOnly);
         hipLaunchKernelGGL(k_pair_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, dPairIdx, dPairBounds,
                            (int) N_SCORE_CLASSES + 1);
         hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, 1u << 26, w.dBounds, (int) N_SCORE_CLASSES + 1);
     } else {
-        rc = devSortPairs(ctx, dKeys, w.dKeysS, w.dVals, w.dOrder, nPairs, 16);
+        rc = sdCtxSortPairs(ctx, "al.sort", dKeys, w.dKeysS, w.dVals, w.dOrder, nPairs, 16);
         if (rc != SD_OK) return rc;
         hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, 1024u, w.dBounds, (int) N_SCORE_CLASSES + 1);
     }
     // strip hand-off workspace for queries longer than one 1024-row strip
     hipLaunchKernelGGL(k_bound_need, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, dKeys, w.dScanA);
     SD_HIP(ctx, hipMemsetAsync(w.dScanA + nPairs, 0, sizeof(uint64_t), ctx->stream));
-    rc = devExclusiveScan(ctx, w.dScanA, w.dScanB, (size_t) nPairs + 1);
+    rc = sdCtxExclusiveScan(ctx, "al.scantmp", w.dScanA, w.dScanB, (size_t) nPairs + 1);
     if (rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_bound_apply, dim3(grid), dim3(256), 0, ctx->stream, nPairs, w.dTasks, w.dScanB);
     uint32_t hb[N_SCORE_CLASSES + 1], hpb[N_SCORE_CLASSES + 1];
@@ -2382,11 +2355,11 @@ static int runTracebackRounds(sd_ctx *ctx, const AlignCall &a, const AlignWs &w)
     bool budgetRaised = false;
     for (int round = 0; round < 4096; round++) {   // band doublings, and slices of what the direction scratch holds at a time
         SD_HIP(ctx, hipMemsetAsync(w.dDirBytes + N, 0, sizeof(uint64_t), ctx->stream));
-        int rc = devExclusiveScan(ctx, w.dDirBytes, w.dDirOff, N + 1);
+        int rc = sdCtxExclusiveScan(ctx, "al.scantmp", w.dDirBytes, w.dDirOff, N + 1);
         if (rc != SD_OK) return rc;
         hipLaunchKernelGGL(k_tb_round, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, w.dKeys, w.dDirOff, w.dDirBytes, SCRATCH_BUDGET, dKeysRound);
         hipLaunchKernelGGL(k_tb_offsets, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, dKeysRound, w.dDirOff, w.dBtOff, w.dTb);
-        rc = devSortPairs(ctx, dKeysRound, w.dKeysS, w.dVals, w.dOrder, nPairs, 16);
+        rc = sdCtxSortPairs(ctx, "al.sort", dKeysRound, w.dKeysS, w.dVals, w.dOrder, nPairs, 16);
         if (rc != SD_OK) return rc;
         hipLaunchKernelGGL(k_bounds, dim3(1), dim3(64), 0, ctx->stream, w.dKeysS, nPairs, 4096u, w.dBounds, (int) N_TB_CLASSES + 1);
         uint32_t hb[N_TB_CLASSES + 1];
@@ -2511,7 +2484,7 @@ static int downloadRecords(sd_ctx *ctx, const AlignCall &a, const AlignWs &w, bo
         hipLaunchKernelGGL(k_bt_cigar<false>, dim3((nPairs + 3) / 4), dim3(256), 0, ctx->stream, nPairs, (const uint64_t *) w.dBtLen,
                            (const uint64_t *) nullptr, (const TbTask *) w.dTb, (const char *) w.dBt, (char *) nullptr, dCigLen, (sd_sw_result *) nullptr);
     }
-    const int rc = devExclusiveScan(ctx, cigarPool ? dCigLen : w.dBtLen, w.dDense, N + 1);
+    const int rc = sdCtxExclusiveScan(ctx, "al.scantmp", cigarPool ? dCigLen : w.dBtLen, w.dDense, N + 1);
     if (rc != SD_OK) return rc;
     uint64_t &poolBytes = rec.poolBytes = 0;
     int hErr[4] = {0, 0, 0, 0};
@@ -2562,7 +2535,7 @@ static int downloadRecords(sd_ctx *ctx, const AlignCall &a, const AlignWs &w, bo
         SD_HIP(ctx, wsGet(ctx, "al.idxc", N, &dIdxC));
         hipLaunchKernelGGL(k_accept, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, w.dRes, w.dIdent, dAcc);
         SD_HIP(ctx, hipMemsetAsync(dAcc + N, 0, 1, ctx->stream));
-        const int rcS = devExclusiveScan(ctx, (const uint8_t *) dAcc, dAccPos, N + 1);
+        const int rcS = sdCtxExclusiveScan(ctx, "al.scantmp", (const uint8_t *) dAcc, dAccPos, N + 1);
         if (rcS != SD_OK) return rcS;
         hipLaunchKernelGGL(k_accept_compact, dim3(w.grid), dim3(256), 0, ctx->stream, nPairs, w.dRes, dAcc, dAccPos, dResC, dIdxC);
         uint64_t nAcc = 0;
@@ -2748,7 +2721,7 @@ static int alignBatchImpl(sd_ctx *ctx, const AlignCall &a) {
     hipLaunchKernelGGL(k_gate_tb, dim3(grid), dim3(256), 0, ctx->stream, nPairs, gp, w.dPQ, w.dPT, queries->dOff, targets->dOff, w.dOutRev,
                        w.dRevKeys, w.dTb, w.dKeys, w.dVals, w.dDirBytes, w.dBtBytes, w.dRes, w.dErr);
     SD_HIP(ctx, hipMemsetAsync(w.dBtBytes + N, 0, sizeof(uint64_t), ctx->stream));
-    rc = devExclusiveScan(ctx, w.dBtBytes, w.dBtOff, N + 1);
+    rc = sdCtxExclusiveScan(ctx, "al.scantmp", w.dBtBytes, w.dBtOff, N + 1);
     if (rc != SD_OK) return rc;
     uint64_t btScratch = 0;
     SD_HIP(ctx, sdD2H(ctx, &btScratch, w.dBtOff + N, sizeof(uint64_t)));
@@ -2857,11 +2830,11 @@ int sd_selftest_scan(sd_ctx *ctx, const uint32_t *in, uint32_t n, uint64_t *excl
     SD_HIP(ctx, dOut.alloc((size_t) n + 1));
     SD_HIP(ctx, hipMemset(dIn.p, 0, ((size_t) n + 1) * 4));
     SD_HIP(ctx, hipMemcpy(dIn.p, in, (size_t) n * 4, hipMemcpyHostToDevice));
-    int rc = devExclusiveScan(ctx, (const uint32_t *) dIn.p, dOut.p, (size_t) n + 1);
+    int rc = sdCtxExclusiveScan(ctx, "al.scantmp", (const uint32_t *) dIn.p, dOut.p, (size_t) n + 1);
     if (rc != SD_OK) return rc;
     if (runningMax) {
         SD_HIP(ctx, dMax.alloc(n));
-        rc = devInclusiveMax(ctx, dIn.p, dMax.p, n);
+        rc = sdCtxInclusiveMax(ctx, "al.scantmp32", dIn.p, dMax.p, n);
         if (rc != SD_OK) return rc;
     }
     SD_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -165,14 +165,6 @@ k_alt_compact(uint32_t G, const uint8_t *__restrict__ live, const uint64_t *__re
     if (live[g]) liveList[pos[g]] = g;
 }
 
-template <typename T>
-int altScan(sd_ctx *ctx, const T *in, uint64_t *out, size_t n) {
-    uint64_t *tmp = nullptr;
-    SD_HIP(ctx, wsGet(ctx, "alt.scantmp", sdScanTmpBytes(n) / sizeof(uint64_t) + 32, &tmp));
-    SD_HIP(ctx, (sdScanLaunch<T, ScanSum64, false, uint64_t>(ctx->stream, in, out, n, tmp)));
-    return SD_OK;
-}
-
 // A target set that exists on the device only: what the batch path needs of targets that are never identity pairs (see
 // alignBatchImpl, sd_sw.hip).  No host copies, no bias, no profile; the buffers stay the caller's.
 void sdDeviceSeqView(sd_seqset &v, sd_ctx *ctx, uint32_t n, uint8_t *dRes, uint64_t *dOff) {
@@ -303,7 +295,7 @@ int sd_sw_align_alt_batch(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
                 ProfScope ps(ctx, "alt_mask_copy");
                 hipLaunchKernelGGL(k_alt_lengths, dim3(grid), dim3(256), 0, ctx->stream, G, (const uint32_t *) dSeedT,
                                    (const uint64_t *) targets->dOff, (const uint8_t *) dLive, dLen);
-                const int rcS = altScan(ctx, (const uint32_t *) dLen, dSOff, 2 * (size_t) G + 1);
+                const int rcS = sdCtxExclusiveScan(ctx, "alt.scantmp", (const uint32_t *) dLen, dSOff, 2 * (size_t) G + 1);
                 if (rcS != SD_OK) return rcS;
                 const unsigned cgrid = std::min<unsigned>((nLive + 3) / 4, 2048u);
                 hipLaunchKernelGGL(k_alt_mask_copy, dim3(cgrid), dim3(256), 0, ctx->stream, (const uint32_t *) dNLive, (const uint32_t *) dLiveList,
@@ -342,7 +334,7 @@ int sd_sw_align_alt_batch(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset 
                 hipLaunchKernelGGL(k_alt_accept, dim3(grid), dim3(256), 0, ctx->stream, G, stride, crit, dRes,
                                    (const uint32_t *) dSeedQ, (const uint32_t *) dSeedT, (const uint64_t *) queries->dOff,
                                    (const uint64_t *) targets->dOff, dIvl, dNIvl, dLive, dCnt);
-                const int rcS = altScan(ctx, (const uint8_t *) dLive, dPos, (size_t) G + 1);
+                const int rcS = sdCtxExclusiveScan(ctx, "alt.scantmp", (const uint8_t *) dLive, dPos, (size_t) G + 1);
                 if (rcS != SD_OK) return rcS;
                 hipLaunchKernelGGL(k_alt_compact, dim3(grid), dim3(256), 0, ctx->stream, G, (const uint8_t *) dLive, (const uint64_t *) dPos,
                                    dLiveList, dNLive);
