@@ -510,6 +510,13 @@ int sd_expand_last_stats(sd_ctx *ctx, uint64_t *pairs, uint64_t *runsRead, uint6
 int sd_host_map_profiles(const char *profileData, const uint64_t *byteOffsets, uint32_t n, uint8_t *queryLetters,
                          uint8_t *consensus, int8_t *alnProfile /* total x 21 */, int16_t *sortedScore /* total x 20 */,
                          uint8_t *sortedIndex /* total x 20 */, uint64_t *posOffsets);
+/* profile2consensus (M/src/util/profile2seq.cpp:37-46): per profile entry the consensus residue of every position
+ * (Sequence::mapProfile's numConsensusSequence, cut at maxSeqLen positions) through the matrix's num2aa, then '\n'.
+ * outText holds sum(min(positions, maxSeqLen) + 1) bytes; textOffsets[n+1] receives where each entry's text begins.
+ * A consensus code outside the alphabet is SD_EINVAL. */
+struct sd_host;
+int sd_host_profile_consensus(struct sd_host *h, const char *profileData, const uint64_t *byteOffsets, uint32_t n, uint32_t maxSeqLen,
+                              char *outText, uint64_t *textOffsets);
 /* Prefiltering::getKmerThreshold for profile searches without context pseudo counts (Prefiltering.cpp:1031-1043) */
 int sd_host_profile_kmer_threshold(float sensitivity, int kmerSize);
 /* sd_prefilter_batch for profile queries: QueryMatcher::matchQuery with a DBTYPE_HMM_PROFILE Sequence --
@@ -1002,6 +1009,27 @@ int sd_r2p_batch_device(sd_ctx *ctx, sd_r2p *r, const sd_r2p_params *par, uint32
                         const uint64_t *edgeOff, const uint32_t *edgeT, const int32_t *edgeQStart, const int32_t *edgeTStart,
                         const char *btPool, const uint64_t *btOff, const uint8_t *tResidues, const uint64_t *tOff, char *outProfiles,
                         uint8_t *outConsensus);
+/* The stage in front of the two calls above for result DB rows that carry no alignment (a cluster DB's one-column rows; any row of
+ * at most 10 columns): result2profile aligns such a member to its centre itself (M/src/util/result2profile.cpp:224-233),
+ *   matcher.getSWResult(&edge, INT_MAX, false, 0, 0.0, FLT_MAX, Matcher::SCORE_COV_SEQID, 0, false)
+ * with a Matcher over SubstitutionMatrix(blosum62, 2.0, -0.2) -- sd_host_matrix's matrix 2, NOT the align module's --, gap costs
+ * 11 / 1, no coverage and no E-value gate, never scoreIdentical, and with compBiasCorr != 0 the centre's local composition bias
+ * against that same matrix (sd_host_sw_comp_bias(h, 2, ...)).  Centres and edges in the layout of sd_r2p_batch_device.
+ * edgeRealign[e] != 0 marks the edges to realign (NULL: all of them).  On entry btPool / btOff[nEdges + 1] hold the backtraces of the
+ * unmarked edges, the marked ones empty spans; all marked pairs of the call run as ONE batch through sd_sw_align_batch (score, start
+ * position and traceback passes).  On SD_OK edgeQStart / edgeTStart of the marked edges are the alignment's start positions, and
+ * btPool / btOff hold every edge's expanded backtrace in edge order (the unmarked ones moved, not changed).
+ * targets: the target sequences resident on `ctx` (NULL: the call uploads tResidues / tOff[nT + 1] itself and frees them).
+ * btCap is the capacity of btPool; the batch writes behind the backtraces it holds.  SD_ENOMEM (sd_sw_align_batch's, with its
+ * message) when that is too small: offsets and start positions are unchanged, and *btNeed is a capacity that always suffices (the
+ * unmarked backtraces + sum(qLen + tLen) of the marked pairs).  A context with sd_sw_set_cigar_pool(ctx, 1) returns run-length text,
+ * which is not what the MSA reads: SD_EUNSUPPORTED.
+ * A pair whose alignment scores 0 has no defined start positions in the reference: SD_EINVAL with *badEdge its edge index
+ * (UINT64_MAX otherwise). */
+int sd_r2p_realign(sd_ctx *ctx, sd_host *h, uint32_t nQ, const uint8_t *qLetters, const uint64_t *qOff, const uint64_t *edgeOff,
+                   const uint32_t *edgeT, const uint8_t *edgeRealign, int32_t compBiasCorr, const sd_seqset *targets,
+                   const uint8_t *tResidues, const uint64_t *tOff, uint32_t nT, int32_t *edgeQStart, int32_t *edgeTStart,
+                   char *btPool, uint64_t btCap, uint64_t *btOff, uint64_t *btNeed, uint64_t *badEdge);
 
 
 /* ---- clust: a result DB of a set against itself -> a cluster DB (M/src/clustering).  Local ids are the reference's

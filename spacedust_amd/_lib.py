@@ -273,6 +273,9 @@ def load():
         'sd_r2p_destroy': (None, [_vp]),
         'sd_r2p_batch': (C.c_int, [_vp, C.POINTER(R2pParams), C.c_uint32] + [_vp] * 12),
         'sd_r2p_batch_device': (C.c_int, [_vp, _vp, C.POINTER(R2pParams), C.c_uint32] + [_vp] * 12),
+        'sd_r2p_realign': (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp,
+                                     C.c_uint64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        'sd_host_profile_consensus': (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
         'sd_selftest_r2p_weights': (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
         'sd_selftest_score_class': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
         'sd_shard_query_sets': (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint32)]),

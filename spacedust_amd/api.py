@@ -212,6 +212,80 @@ def result2profile(q_letters, q_off, edge_off, edge_t, edge_qstart, edge_tstart,
     return out[:-1].tobytes()
 
 
+def r2p_realign(ctx, host, q_letters, q_off, edge_off, edge_t, t_residues, t_off, realign=None, edge_qstart=None, edge_tstart=None,
+                backtraces=None, comp_bias=1, targets=None, pool_cap=None, retry=True, want_stats=False):
+    """sd_r2p_realign: result2profile's alignment of the edges that carry none (matrix with score bias -0.2, the centre's composition
+    bias against it, no gates), in the layout of `result2profile` above.  realign: per edge, nonzero = realign (None: every edge); the
+    others keep edge_qstart / edge_tstart / backtraces (a list of strings, '' for the marked ones).  targets: a SeqSet of t_residues on
+    ctx (None: uploaded by the call).  pool_cap: the first guess of the backtrace pool (None: the library's bound); with retry, a call
+    that reports SD_ENOMEM is repeated once with the capacity it names.  Returns (qstart int32, tstart int32, backtraces list of str)
+    and, with want_stats, the number of calls made."""
+    L = _lib.load()
+    q_letters = np.ascontiguousarray(np.concatenate([np.asarray(q_letters, np.uint8), np.zeros(1, np.uint8)]))
+    q_off = np.ascontiguousarray(q_off, np.uint64)
+    edge_off = np.ascontiguousarray(edge_off, np.uint64)
+    n_e = int(edge_off[-1])
+    edge_t = np.ascontiguousarray(np.concatenate([np.asarray(edge_t, np.uint32), np.zeros(1, np.uint32)]))
+    t_residues = np.ascontiguousarray(t_residues, np.uint8)
+    t_off = np.ascontiguousarray(t_off, np.uint64)
+    flags = None if realign is None else np.ascontiguousarray(np.concatenate([np.asarray(realign, np.uint8), np.zeros(1, np.uint8)]))
+    qs = np.zeros(n_e + 1, np.int32)
+    ts = np.zeros(n_e + 1, np.int32)
+    if edge_qstart is not None:
+        qs[:n_e] = edge_qstart
+        ts[:n_e] = edge_tstart
+    held = list(backtraces) if backtraces is not None else [''] * n_e
+    bt_off0 = np.zeros(n_e + 1, np.uint64)
+    if n_e:
+        np.cumsum([len(b) for b in held], out=bt_off0[1:])
+    text = ''.join(held).encode()
+    need, bad = C.c_uint64(), C.c_uint64()
+    cap = pool_cap
+    calls = 0
+    while True:
+        if cap is None:   # the bound itself, formed as the library forms *btNeed: held backtraces + sum(qLen + tLen) of the marked pairs
+            bound_cap = len(text) + 1
+            for q in range(len(q_off) - 1):
+                for e in range(int(edge_off[q]), int(edge_off[q + 1])):
+                    if flags is None or flags[e]:
+                        t = int(edge_t[e])
+                        bound_cap += int(q_off[q + 1] - q_off[q]) + int(t_off[t + 1] - t_off[t])
+            cap = bound_cap + 64
+        cap = max(int(cap), len(text) + 1)
+        pool = np.zeros(cap + 1, np.uint8)
+        pool[:len(text)] = np.frombuffer(text, np.uint8)
+        bt_off = bt_off0.copy()
+        calls += 1
+        rc = L.sd_r2p_realign(ctx.h, host.h, len(q_off) - 1, ptr(q_letters), ptr(q_off), ptr(edge_off), ptr(edge_t), ptr(flags), int(comp_bias),
+                              targets.h if targets is not None else None, ptr(t_residues), ptr(t_off), len(t_off) - 1, ptr(qs), ptr(ts),
+                              ptr(pool), cap, ptr(bt_off), C.byref(need), C.byref(bad))
+        if rc == _lib.SD_ENOMEM and retry and calls == 1:
+            cap = need.value
+            continue
+        if rc == _lib.SD_EINVAL and bad.value != 2 ** 64 - 1:
+            raise SdError('sd_r2p_realign: the alignment of edge %d scores 0 (the reference leaves its start positions unset)' % bad.value)
+        _check(ctx.h, rc, 'sd_r2p_realign')
+        break
+    raw = pool.tobytes()
+    bts = [raw[int(bt_off[e]):int(bt_off[e + 1])].decode() for e in range(n_e)]
+    out = (qs[:n_e].copy(), ts[:n_e].copy(), bts)
+    return out + (calls,) if want_stats else out
+
+
+def profile_consensus(host, data, byte_offsets, max_seq_len=65535):
+    """sd_host_profile_consensus: profile DB entries (25 bytes per position, byte_offsets[n+1]) -> list of bytes, one per entry: the
+    consensus letters and a newline (profile2consensus' entries)"""
+    data = np.ascontiguousarray(np.frombuffer(bytes(data) + b'\0', np.uint8))
+    bo = np.ascontiguousarray(byte_offsets, np.uint64)
+    n = len(bo) - 1
+    lens = np.minimum((bo[1:] - bo[:-1]) // 25, np.uint64(max_seq_len)).astype(np.int64)
+    text = np.zeros(int(lens.sum()) + n + 1, np.uint8)
+    off = np.zeros(n + 1, np.uint64)
+    _check(None, host.L.sd_host_profile_consensus(host.h, ptr(data), ptr(bo), n, int(max_seq_len), ptr(text), ptr(off)), 'sd_host_profile_consensus')
+    raw = text.tobytes()
+    return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
 def r2p_weights(tasks, ctx=None):
     """sd_selftest_r2p_weights: the weights stage of result2profile alone on alignments given as uint8 cell matrices [nRows, L]
     (row 0 the centre; 0..19 residue, 20 any, 21 gap) -- on the device through sd_r2p_batch_device's staging with a Context, by

@@ -99,12 +99,23 @@ struct Resident {
     };
     std::map<std::string, TargetEntry> targets;                      // "path|k|threshold|mask|prob|device"
     std::map<std::string, sd_seqset *> seqSets;                      // "path|device"
+    std::vector<std::string> seqSetLog;                              // residentSeqSet's decisions in order: "uploaded <path>" / "reused <path>"
     sd_ctx *ctx(int device, int *rc);                                // the device's context (created on first use)
     std::map<int, sd_host *> hostOfThreads;                          // the host objects (matrices, extended k-mer tables) by thread count
     sd_host *host(int threads);                                      // created on first use; NULL on failure
     void clear();                                                    // destroys everything (sequence sets and targets before their contexts)
 };
 Resident &resident();
+// What a workflow holds while its modules run: it switches the resident set on (SD_RESIDENT=0 in the environment: not) and clears it
+// when it ends.  A workflow that runs inside another (clusterdb's `cluster` step) finds the set on already and leaves it to the outer
+// one: what its modules put there stays for the steps behind it.
+struct ResidentScope {
+    bool outer;
+    ResidentScope();
+    ~ResidentScope();
+    ResidentScope(const ResidentScope &) = delete;
+    ResidentScope &operator=(const ResidentScope &) = delete;
+};
 // the target DB of a module: from the resident cache when it is on, else loaded for this call
 std::shared_ptr<SeqDb> loadTargetDb(const std::string &path, sd_host *host, std::string *err);
 
@@ -183,6 +194,8 @@ int clusthashModule(const Args &a);
 int createsubdbModule(const Args &a);
 int mergeclustersModule(const Args &a);
 int clusterModule(const Args &a);
+int profile2consensusModule(const Args &a);
+int clusterdbModule(const Args &a);
 
 }  // namespace sdcli
 #endif

@@ -121,7 +121,15 @@ void Resident::clear() {
     ctxOfDevice.clear();
     seqDbs.clear();
     seqDbSig.clear();
+    seqSetLog.clear();
     enabled = false;
+}
+
+ResidentScope::ResidentScope() : outer(resident().enabled) {
+    if (!outer) resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0);
+}
+ResidentScope::~ResidentScope() {
+    if (!outer) resident().clear();
 }
 
 std::shared_ptr<SeqDb> loadTargetDb(const std::string &path, sd_host *host, std::string *err) {

@@ -42,6 +42,8 @@ const Module kModules[] = {
     {"createsubdb", createsubdbModule, "host glue: the entries of a DB that a key list or another DB's index names, copied (--subdb-mode 0) or soft-linked (1): <subsetFile|DB> <DB> <DB>"},
     {"mergeclusters", mergeclustersModule, "host glue: the cluster DBs of successive steps merged into one: <sequenceDB> <clusterDB> <clusterDB1> [<clusterDB2> ...]"},
     {"cluster", clusterModule, "--single-step-clustering 1: clusthash, clust, createsubdb, prefilter, align (or rescorediagonal), clust, mergeclusters in one process: <sequenceDB> <clusterDB> <tmpDir>"},
+    {"profile2consensus", profile2consensusModule, "host: the consensus residue of every profile position as an amino-acid DB: <profileDB> <sequenceDB>"},
+    {"makeclusterdb", clusterdbModule, "the reference's clusterdb workflow with --single-step-clustering 1: cluster, createsubdb, result2profile (members realigned on the GPU), profile2consensus, align -a in one process; writes <setDB>_clu_rep_profile, <setDB>_clu, <setDB>_clu_aln: <setDB> <tmpDir>"},
     {"createindex", createindexModule, "target k-mer index built once, in the reference's createindex file layout: <sequenceDB> <tmpDir>"},
     {"createsetdb", createsetdbModule, "FASTA files (Prodigal headers) -> setDB in the createsetdb layout"},
 };
@@ -79,6 +81,9 @@ int main(int argc, const char **argv) {
         omp_set_num_threads(threadsOf(a));
         return m.fn(a);
     }
-    fprintf(stderr, "sdgpu: unknown module \"%s\" (sdgpu --help lists the modules)\n", argv[1]);
+    if (!strcmp(argv[1], "clusterdb"))
+        fprintf(stderr, "sdgpu: unknown module \"clusterdb\" (the reference's clusterdb workflow is the module makeclusterdb here)\n");
+    else
+        fprintf(stderr, "sdgpu: unknown module \"%s\" (sdgpu --help lists the modules)\n", argv[1]);
     return 1;
 }

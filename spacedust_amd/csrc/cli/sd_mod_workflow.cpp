@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <dirent.h>
 #include <fstream>
 #include <map>
 #include <memory>
@@ -489,6 +490,21 @@ int runSearch(const Args &a, bool withClusters) {
 
 }  // namespace
 
+// the ancillary files a DB derived from a sequence DB shares with it (DBReader::softlinkDb(..., SEQUENCE_ANCILLARY))
+static void softlinkSequenceAncillary(const std::string &from, const std::string &to) {
+    for (const char *suffix : {"_h", "_h.index", "_h.dbtype", ".lookup", ".source"}) {
+        const std::string src = from + suffix, dst = to + suffix;
+        ::remove(dst.c_str());
+        if (sddb::fileExists(src)) {
+            char *real = realpath(src.c_str(), nullptr);
+            if (real) {
+                if (symlink(real, dst.c_str()) != 0) { /* best effort, as the reference */ }
+                free(real);
+            }
+        }
+    }
+}
+
 int r2pSetupFromArgs(const Args &a, R2pSetup &s) {
     if (a.integer("--compressed", 0) != 0) return fail("--compressed 1 is not supported");
     if (a.integer("--profile-output-mode", 0) != 0) return fail("--profile-output-mode 0 only");
@@ -547,8 +563,8 @@ int result2profileModule(const Args &a) {
     const bool hostWeights = a.integer("--profile-weights-host", 0) != 0;
     sd_ctx *r2pCtx = nullptr;
     bool ownCtx = true;
+    const int device = a.has("--device") ? (int) a.integer("--device", 0) : envInt("LOCAL_RANK", 0);
     if (!hostWeights) {
-        const int device = a.has("--device") ? (int) a.integer("--device", 0) : envInt("LOCAL_RANK", 0);
         int rcCtx = SD_OK;
         if (resident().enabled) {
             r2pCtx = resident().ctx(device, &rcCtx);
@@ -573,12 +589,19 @@ int result2profileModule(const Args &a) {
     std::vector<uint64_t> qOff, edgeOff, btOff;
     std::vector<uint32_t> edgeT, keys;
     std::vector<int32_t> eQ, eT;
+    std::vector<uint8_t> eRealign;
     std::string pool;
     std::vector<char> profiles;
+    // rows without a backtrace (a cluster DB's one-column rows) are aligned to their centre here (:224-233), by sd_r2p_realign; the
+    // target sequences go to the device once per run, or are the workflow's resident set
+    SeqSetH realignTargets;
+    uint64_t pairsRealigned = 0, realignUploaded = 0;
+    double tRealign = 0;
     struct ParsedEntry {
         bool valid = false;
         size_t qId = 0;
         std::vector<uint32_t> edgeT;
+        std::vector<uint8_t> realign;
         std::vector<int32_t> eQ, eT;
         std::vector<uint64_t> btEnd;
         std::string pool, error;
@@ -594,6 +617,7 @@ int result2profileModule(const Args &a) {
         edgeT.clear();
         eQ.clear();
         eT.clear();
+        eRealign.clear();
         keys.clear();
         pool.clear();
         // the entries of the chunk parsed on all threads, each into lists of its own, then laid out back to back in entry order
@@ -606,6 +630,7 @@ int result2profileModule(const Args &a) {
             pe.edgeT.clear();
             pe.eQ.clear();
             pe.eT.clear();
+            pe.realign.clear();
             pe.btEnd.clear();
             pe.pool.clear();
             const uint32_t qKey = aln.key(id);
@@ -629,16 +654,20 @@ int result2profileModule(const Args &a) {
                 double evalue = 0.0;
                 if (nc >= 4) evalue = strtod(col[3], nullptr);
                 if (!(evalue < evalProfile)) continue;
-                if (nc < 11) {
-                    pe.error = "alignment DB without backtraces (run align with -a); recomputing them is the align module's job";
-                    break;
-                }
                 const size_t tId = tdb->rd.idOfKey(tKey);
                 if (tId == SIZE_MAX) {
                     pe.error = "Sequence " + std::to_string(tKey) + " does not exist in target sequence database";
                     break;
                 }
                 pe.edgeT.push_back((uint32_t) tId);
+                if (nc < 11) {   // at most Matcher::ALN_RES_WITHOUT_BT_COL_CNT columns: no backtrace to parse (:224-233)
+                    pe.realign.push_back(1);
+                    pe.eQ.push_back(0);
+                    pe.eT.push_back(0);
+                    pe.btEnd.push_back(pe.pool.size());
+                    continue;
+                }
+                pe.realign.push_back(0);
                 pe.eQ.push_back((int32_t) strtol(col[4], nullptr, 10));
                 pe.eT.push_back((int32_t) strtol(col[7], nullptr, 10));
                 // Matcher::uncompressAlignment (Matcher.cpp:187-201)
@@ -663,6 +692,7 @@ int result2profileModule(const Args &a) {
             edgeT.insert(edgeT.end(), pe.edgeT.begin(), pe.edgeT.end());
             eQ.insert(eQ.end(), pe.eQ.begin(), pe.eQ.end());
             eT.insert(eT.end(), pe.eT.begin(), pe.eT.end());
+            eRealign.insert(eRealign.end(), pe.realign.begin(), pe.realign.end());
             const uint64_t base = pool.size();
             pool.append(pe.pool);
             for (uint64_t e : pe.btEnd) btOff.push_back(base + e);
@@ -670,6 +700,60 @@ int result2profileModule(const Args &a) {
         }
         const uint32_t nQ = (uint32_t) keys.size();
         profiles.assign(qOff.back() * 25 + 1, 0);
+        uint64_t nRealign = 0;
+        for (uint8_t f : eRealign) nRealign += f;
+        if (nRealign) {
+            if (qdb->profile) return fail("rows without a backtrace next to a profile query DB are not supported");
+            // the reference builds this Matcher from --gap-open, --gap-extend and --comp-bias-corr-scale; the stage has the presets only
+            if (a.multi("--gap-open", "aa", "11") != "11" || a.multi("--gap-extend", "aa", "1") != "1")
+                return fail("rows without a backtrace are aligned with --gap-open 11 --gap-extend 1 only (other gap costs need other E-value "
+                            "parameters than the built-in preset)");
+            if (a.real("--comp-bias-corr-scale", 1.0) != 1.0) return fail("rows without a backtrace are aligned with --comp-bias-corr-scale 1 only");
+            if (!r2pCtx)
+                return fail("the result DB has rows without a backtrace: result2profile aligns them on the GPU, and --profile-weights-host 1 "
+                            "runs without a device (align them first: align -a)");
+            const double tr0 = now();
+            if (!realignTargets.s) {
+                const bool had = resident().enabled && resident().seqSets.count(a.pos[1] + "|" + std::to_string(device));
+                const int rcT = residentSeqSet(r2pCtx, a.pos[1], device, *tdb, realignTargets);
+                if (rcT != SD_OK) return failCtx(r2pCtx, rcT, "sd_seqset_create(targets)");
+                if (!had) realignUploaded += tdb->totalResidues();
+            }
+            // the pool's first guess, as the align module's: about min(qLen, tLen) columns per pair; sd_r2p_realign names what suffices
+            uint64_t cap = pool.size() + (1u << 20), est = 0;
+            for (uint32_t q = 0; q < nQ; q++)
+                for (uint64_t e = edgeOff[q]; e < edgeOff[q + 1]; e++)
+                    if (eRealign[e]) est += std::min<uint64_t>(qOff[q + 1] - qOff[q], (uint64_t) tdb->lens[edgeT[e]]) + 16;
+            cap += est + est / 4;
+            // (test-only: tests/test_gpu_r2p_realign.py sets it to a few bytes so that the retry below runs; no tuning value)
+            if (const char *forced = getenv("SD_R2P_REALIGN_POOL")) cap = std::max<uint64_t>(pool.size(), strtoull(forced, nullptr, 10));
+            for (bool exact = false;;) {
+                const uint64_t heldBytes = pool.size();
+                pool.resize(cap);
+                uint64_t need = 0, bad = UINT64_MAX;
+                const int rcR = sd_r2p_realign(r2pCtx, host.h, nQ, qLetters.data(), qOff.data(), edgeOff.data(), edgeT.data(), eRealign.data(),
+                                               p.compBiasCorr, realignTargets.s, tdb->residues.data(), tdb->offsets.data(), tdb->n, eQ.data(),
+                                               eT.data(), &pool[0], cap, btOff.data(), &need, &bad);
+                if (rcR == SD_ENOMEM && !exact) {
+                    pool.resize(heldBytes);
+                    cap = need;
+                    exact = true;
+                    continue;
+                }
+                if (rcR == SD_EINVAL && bad != UINT64_MAX) {
+                    uint32_t q = 0;
+                    while (edgeOff[q + 1] <= bad) q++;
+                    return fail("the alignment of member " + std::to_string(tdb->keys[edgeT[bad]]) + " with its centre " + std::to_string(keys[q]) +
+                                " scores 0: the reference leaves its start positions unset");
+                }
+                if (rcR != SD_OK) return failCtx(r2pCtx, rcR, "sd_r2p_realign");
+                break;
+            }
+            pool.resize(btOff.back());
+            pairsRealigned += nRealign;
+            realignUploaded += qOff.back() * 2 + nRealign * 8;
+            tRealign += now() - tr0;
+        }
         pool.push_back(' ');
         qLetters.push_back(0);
         edgeT.push_back(0);
@@ -692,22 +776,60 @@ int result2profileModule(const Args &a) {
     lap.mark("chunks");
     info(a, "result2profile: parse %.2f s, profiles %.2f s (%d threads, weights on the %s), write %.2f s\n", tParse, tCompute, threads,
          r2pCtx ? "GPU" : "host", tWrite);
+    if (pairsRealigned)
+        // (the bytes are an estimate: residues, bias and pair lists; the offset arrays and the batch's own staging are not counted)
+        info(a, "result2profile: %llu pairs realigned in %.2f s (%.0f pairs/s), about %llu bytes uploaded for them\n", (unsigned long long) pairsRealigned,
+             tRealign, tRealign > 0 ? pairsRealigned / tRealign : 0.0, (unsigned long long) realignUploaded);
     (void) tLoaded;
     if (!out.close(&err)) return fail(err);
     // the profile DB shares the query DB's ancillary files (DBReader::softlinkDb(..., SEQUENCE_ANCILLARY), :318-320)
-    for (const char *suffix : {"_h", "_h.index", "_h.dbtype", ".lookup", ".source"}) {
-        const std::string src = a.pos[0] + suffix, dst = a.pos[3] + suffix;
-        ::remove(dst.c_str());
-        if (sddb::fileExists(src)) {
-            char *real = realpath(src.c_str(), nullptr);
-            if (real) {
-                if (symlink(real, dst.c_str()) != 0) { /* best effort, as the reference */ }
-                free(real);
-            }
-        }
-    }
+    softlinkSequenceAncillary(a.pos[0], a.pos[3]);
     lap.mark("close + links");
     info(a, "%zu profiles written\n", n);
+    return 0;
+}
+
+// profile2consensus <profileDB> <sequenceDB>  (M/src/util/profile2seq.cpp:13-58): the consensus residue of every profile position as
+// an amino-acid DB.  One byte per position: a host module (sd_host_profile_consensus).
+int profile2consensusModule(const Args &a) {
+    if (a.pos.size() != 2) return fail("usage: profile2consensus <profileDB> <sequenceDB> [options]");
+    if (a.integer("--compressed", 0) != 0) return fail("--compressed 1 is not supported");
+    if (a.multi("--sub-mat", "aa", "blosum62.out") != "blosum62.out") return fail("--sub-mat: only blosum62.out is built into this path");
+    const long long maxSeqLen = a.integer("--max-seq-len", 65535);
+    if (maxSeqLen < 1 || maxSeqLen > UINT32_MAX) return fail("--max-seq-len " + a.str("--max-seq-len", "") + " is out of range");
+    if (sddb::readDbType(a.pos[0]) == -1) return fail(a.pos[0] + ".dbtype not found");
+    if (sddb::baseType(sddb::readDbType(a.pos[0])) != sddb::DBTYPE_HMM_PROFILE) return fail(a.pos[0] + " is not a profile database");
+    if (sddb::isCompressed(sddb::readDbType(a.pos[0]))) return fail("compressed databases are not supported (" + a.pos[0] + ")");
+    HostH host;
+    if (host.open(threadsOf(a)) != SD_OK) return fail("sd_host_create failed");
+    std::string err;
+    sddb::Reader rd;
+    if (!rd.open(a.pos[0], sddb::Reader::USE_INDEX | sddb::Reader::USE_DATA, sddb::Reader::LINEAR_ACCESS, &err)) return fail(err);
+    sddb::Writer out;
+    if (!out.open(a.pos[1], sddb::DBTYPE_AMINO_ACIDS, &err)) return fail(err);
+    const size_t n = rd.size(), chunk = 65536;
+    std::vector<char> raw, text;
+    std::vector<uint64_t> byteOff, textOff;
+    for (size_t c0 = 0; c0 < n; c0 += chunk) {
+        const size_t c1 = std::min(n, c0 + chunk);
+        byteOff.assign(1, 0);
+        for (size_t id = c0; id < c1; id++) byteOff.push_back(byteOff.back() + (std::max<size_t>(rd.entryLength(id), 1) - 1) / 25 * 25);
+        raw.resize(byteOff.back() + 1);
+        uint64_t positions = 0;
+        for (size_t id = c0; id < c1; id++) {
+            memcpy(raw.data() + byteOff[id - c0], rd.data(id), (size_t) (byteOff[id - c0 + 1] - byteOff[id - c0]));
+            positions += std::min<uint64_t>((byteOff[id - c0 + 1] - byteOff[id - c0]) / 25, (uint64_t) maxSeqLen) + 1;
+        }
+        text.resize(positions + 1);
+        textOff.resize(c1 - c0 + 1);
+        const int rc = sd_host_profile_consensus(host.h, raw.data(), byteOff.data(), (uint32_t) (c1 - c0), (uint32_t) maxSeqLen, text.data(), textOff.data());
+        if (rc != SD_OK) return fail("sd_host_profile_consensus failed (" + std::to_string(rc) + "): " + a.pos[0] + " holds a consensus code outside the alphabet");
+        for (size_t id = c0; id < c1; id++)
+            if (!out.write(rd.key(id), text.data() + textOff[id - c0], (size_t) (textOff[id - c0 + 1] - textOff[id - c0]))) return fail("cannot write " + a.pos[1]);
+    }
+    if (!out.close(&err)) return fail(err);
+    softlinkSequenceAncillary(a.pos[0], a.pos[1]);
+    info(a, "%zu consensus sequences written\n", n);
     return 0;
 }
 
@@ -927,10 +1049,7 @@ int iterativeSearch(const Args &a, const std::string &Q, const std::string &T, c
     }
     // the modules below run in this process: the target DB, its index on the device and its sequence set stay resident between them
     // (sd_cli.h: Resident) instead of being reloaded / rebuilt by every module
-    struct ResidentScope {
-        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
-        ~ResidentScope() { resident().clear(); }
-    } residentScope;
+    ResidentScope residentScope;
     std::string query = Q;
     for (int step = 0; step < numIt; step++) {
         const std::string s = std::to_string(step), s1 = std::to_string(step - 1);
@@ -1022,10 +1141,7 @@ int ungappedAlignSearch(const Args &a, const std::string &Q, const std::string &
                                                      "--sort-results", a.str("--sort-results", "0")});
     for (const char *f : {"--device", "--add-self-matches", "--filter-hits", "--wrapped-scoring"})
         if (a.has(f)) rescore = with(rescore, {f, a.str(f, "")});
-    struct ResidentScope {
-        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
-        ~ResidentScope() { resident().clear(); }
-    } residentScope;
+    ResidentScope residentScope;
     const std::string prefDb = tmp + "/pref_0";
     if (ungapped) {
         if (int rc = runModule(ungappedprefilterModule, "ungappedprefilter", {Q, T, prefDb}, pref)) return rc;
@@ -1070,10 +1186,7 @@ int altAliSearch(const Args &a, const std::string &Q, const std::string &T, cons
                                                  "--comp-bias-corr", a.str("--comp-bias-corr", "1")});
     for (const char *f : {"--device", "--add-self-matches"})
         if (a.has(f)) aln = with(aln, {f, a.str(f, "")});
-    struct ResidentScope {
-        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
-        ~ResidentScope() { resident().clear(); }
-    } residentScope;
+    ResidentScope residentScope;
     const std::string prefDb = tmp + "/pref_0";
     if (ungapped) {
         if (int rc = runModule(ungappedprefilterModule, "ungappedprefilter", {Q, T, prefDb}, pref)) return rc;
@@ -1121,10 +1234,7 @@ int targetProfileSearch(const Args &a, const std::string &Q, const std::string &
     // Two targets are resident in turn: the profile DB with its index for `prefilter`, the sequence DB with its sequence set for
     // `align` (Resident keys both by DB path, so they are entries of their own).  The index has no reader after the prefilter and is
     // freed before `align` uploads.
-    struct ResidentScope {
-        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
-        ~ResidentScope() { resident().clear(); }
-    } residentScope;
+    ResidentScope residentScope;
     const std::string prefDb = tmp + "/pref", prefSwapped = tmp + "/pref_swapped", alnSwapped = tmp + "/aln_swapped";
     const bool keep = a.integer("--keep-tmp", 0) != 0;
     struct RemoveTmp {
@@ -1381,10 +1491,7 @@ int clusterModule(const Args &a) {
     aln.insert(aln.end(), hits.begin(), hits.end());
     aln = ungapped ? with(aln, {"--rescore-mode", "2"}) : with(aln, {"--alignment-mode", a.str("--alignment-mode", "3"), "--comp-bias-corr", compBias});
     aln = passed(aln, {"-a", "--min-aln-len", "--seq-id-mode", "--add-self-matches"});
-    struct ResidentScope {
-        ResidentScope() { resident().enabled = !(getenv("SD_RESIDENT") && atoi(getenv("SD_RESIDENT")) == 0); }
-        ~ResidentScope() { resident().clear(); }
-    } residentScope;
+    ResidentScope residentScope;
     const std::string alnRed = tmp + "/aln_redundancy", cluRed = tmp + "/clu_redundancy", sub = tmp + "/input_step_redundancy",
                       prefDb = tmp + "/pref", alnDb = tmp + "/aln", clu0 = tmp + "/clu_step0";
     for (const std::string &db : {alnRed, cluRed, sub, prefDb, alnDb, clu0}) sddb::removeDb(db);
@@ -1402,6 +1509,96 @@ int clusterModule(const Args &a) {
     if (a.flag("--remove-tmp-files", false)) {
         for (const std::string &db : {prefDb, alnDb, clu0, cluRed, alnRed}) sddb::removeDb(db);
         for (const char *suffix : {"", ".index", ".dbtype", "_h", "_h.index", "_h.dbtype", ".lookup", ".source"}) unlink((sub + suffix).c_str());
+    }
+    return 0;
+}
+
+// clusterdb <setDB> <tmpDir>  (R/src/workflow/clusterdb.cpp:9-85 sets the parameters, the non-foldseek branch of R/data/clusterdb.sh:97-143
+// is the chain): cluster, createsubdb, result2profile on the cluster DB (its one-column rows realigned by sd_r2p_realign), profile2consensus,
+// align -a on the cluster DB, in this process under one resident scope.  It leaves <T>_clu_rep_profile, <T>_clu and <T>_clu_aln, what
+// `clustersearch --profile-cluster-search 1` reads.  DESIGN.md 4.19
+int clusterdbModule(const Args &a) {
+    if (a.pos.size() != 2) return fail("usage: makeclusterdb <setDB> <tmpDir> --single-step-clustering 1 [options]");
+    if (int rc = checkCommon(a)) return rc;
+    if (a.integer("--search-mode", 0) != 0)
+        return fail("--search-mode " + a.str("--search-mode", "") + " clusters structures with foldseek, which is not part of this build");
+    const std::string T = a.pos[0], tmp = a.pos[1];
+    {
+        const int dbtype = sddb::readDbType(T);
+        if (dbtype == -1) return fail(T + ".dbtype not found");
+        if (sddb::baseType(dbtype) == sddb::DBTYPE_NUCLEOTIDES) return fail("nucleotide DBs are not implemented (" + T + ")");
+        if (sddb::baseType(dbtype) == sddb::DBTYPE_HMM_PROFILE) return fail("profile DBs are not implemented (" + T + ")");
+    }
+    if (!a.flag("--single-step-clustering", false))
+        return fail("only --single-step-clustering 1 is implemented: the cascaded workflow starts with linclust, whose ungapped filter "
+                    "(rescorediagonal --filter-hits 1) needs the reference's --filter-hits threshold table");
+    if (envInt("WORLD_SIZE", 1) > 1 || a.integer("--world-size", 1) > 1) return fail("makeclusterdb runs on one rank");
+    mkdir(tmp.c_str(), 0777);
+    // CLUSTER_PAR: the cluster workflow's flags as the user gave them over setclusterDbDefaults; THREADS_PAR for result2profile and align
+    // (the user's -e, -c, ... do not reach them); CONSENSUS_PAR; VERBOSITY
+    std::vector<std::string> cluPar;
+    {
+        Args c = a;
+        for (const char *f : {"--search-mode", "--foldseek-path"}) c.opt.erase(f);
+        auto def = [&](const char *f, const char *v) { if (!c.has(f)) c.opt[f] = v; };
+        def("--min-seq-id", "0.7");
+        def("-c", "0.8");
+        def("--cov-mode", "0");
+        c.opt["--threads"] = std::to_string(threadsOf(a));
+        c.opt["-v"] = a.str("-v", "3");
+        cluPar = c.flagsAsArgv();
+    }
+    const std::vector<std::string> verbosity = {"-v", a.str("-v", "3")};
+    std::vector<std::string> threadsPar = {"--threads", std::to_string(threadsOf(a)), "-v", a.str("-v", "3")};
+    std::vector<std::string> consPar = threadsPar;
+    if (a.has("--device")) threadsPar = with(threadsPar, {"--device", a.str("--device", "")});
+    for (const char *f : {"--sub-mat", "--max-seq-len"})
+        if (a.has(f)) consPar = with(consPar, {f, a.str(f, "")});
+    const std::string clu = tmp + "/cluster_mmseqs", dbClu = tmp + "/db_clu", prof = T + "_clu_rep_profile", cons = T + "_clu", aln = T + "_clu_aln";
+    struct Step {
+        int (*fn)(const Args &);
+        const char *name;
+        std::string out;
+        std::vector<std::string> pos, flags;
+        bool skip = false;
+    };
+    std::vector<std::string> alnPar = {"-a", "1"};
+    alnPar.insert(alnPar.end(), threadsPar.begin(), threadsPar.end());
+    std::vector<Step> steps = {
+        {clusterModule, "cluster", clu, {T, clu, tmp + "/cluster"}, cluPar},
+        {createsubdbModule, "createsubdb", dbClu, {clu, T, dbClu}, verbosity},
+        {result2profileModule, "result2profile", prof, {dbClu, T, clu, prof}, threadsPar},
+        {profile2consensusModule, "profile2consensus", cons, {prof, cons}, consPar},
+        {alignModule, "align", aln, {T, T, clu, aln}, alnPar},
+    };
+    // a step whose output exists is not run again (notExists "<out>.dbtype" in the script); the plan is printed before the first step
+    for (Step &s : steps) {
+        s.skip = sddb::fileExists(s.out + ".dbtype");
+        std::string line = s.name;
+        for (const std::string &x : s.pos) line += " " + x;
+        for (const std::string &x : s.flags) line += " " + x;
+        info(a, "makeclusterdb %s: %s\n", s.skip ? "skips" : "runs", line.c_str());
+    }
+    ResidentScope residentScope;
+    for (const Step &s : steps) {
+        if (s.skip) continue;
+        const double t0 = omp_get_wtime();
+        if (int rc = runModule(s.fn, s.name, s.pos, s.flags)) return rc;
+        info(a, "makeclusterdb: %s took %.2f s\n", s.name, omp_get_wtime() - t0);
+    }
+    // what became of the target sequence sets the steps asked for (the set result2profile uploads is the one `align` finds resident)
+    for (const std::string &l : resident().seqSetLog) info(a, "makeclusterdb: sequence set %s\n", l.c_str());
+    if (a.flag("--remove-tmp-files", false)) {
+        // what the script removes: the cluster DB and the cluster workflow's directory (db_clu stays, as it does there)
+        info(a, "Remove temporary files\n");
+        sddb::removeDb(clu);
+        const std::string dir = tmp + "/cluster";
+        if (DIR *d = opendir(dir.c_str())) {
+            while (struct dirent *e = readdir(d))
+                if (strcmp(e->d_name, ".") != 0 && strcmp(e->d_name, "..") != 0) unlink((dir + "/" + e->d_name).c_str());
+            closedir(d);
+            rmdir(dir.c_str());
+        }
     }
     return 0;
 }

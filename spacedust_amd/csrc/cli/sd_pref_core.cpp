@@ -124,12 +124,14 @@ int residentSeqSet(sd_ctx *ctx, const std::string &db, int device, const SeqDb &
     if (resident().enabled && resident().seqSets.count(key)) {
         out.s = resident().seqSets[key];   // the target sequences are on the device already
         out.own = false;
+        resident().seqSetLog.push_back("reused " + db);
         return SD_OK;
     }
     const int rc = sd_seqset_create(ctx, tdb.residues.data(), tdb.offsets.data(), tdb.n, nullptr, &out.s);
     if (rc == SD_OK && resident().enabled) {
         resident().seqSets[key] = out.s;
         out.own = false;
+        resident().seqSetLog.push_back("uploaded " + db);
     }
     return rc;
 }

@@ -181,6 +181,31 @@ int sd_host_map_profiles(const char *profileData, const uint64_t *byteOffsets, u
     return SD_OK;
 }
 
+int sd_host_profile_consensus(sd_host *h, const char *profileData, const uint64_t *byteOffsets, uint32_t n, uint32_t maxSeqLen,
+                              char *outText, uint64_t *textOffsets) {
+    if (!h || !profileData || !byteOffsets || !outText || !textOffsets) return SD_EINVAL;
+    textOffsets[0] = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (byteOffsets[i + 1] < byteOffsets[i] || (byteOffsets[i + 1] - byteOffsets[i]) % sd::PROFILE_RECORD) return SD_EINVAL;
+        const uint64_t L = std::min<uint64_t>((byteOffsets[i + 1] - byteOffsets[i]) / sd::PROFILE_RECORD, maxSeqLen);
+        textOffsets[i + 1] = textOffsets[i] + L + 1;
+    }
+    bool bad = false;
+#pragma omp parallel for schedule(dynamic, 64) num_threads(h->threads) reduction(|| : bad)
+    for (uint32_t i = 0; i < n; i++) {
+        const char *rec = profileData + byteOffsets[i];
+        char *out = outText + textOffsets[i];
+        const uint64_t L = textOffsets[i + 1] - textOffsets[i] - 1;
+        for (uint64_t l = 0; l < L; l++) {
+            const uint8_t c = (uint8_t) rec[l * sd::PROFILE_RECORD + 21];   // PROFILE_CONSENSUS (Sequence.cpp:255)
+            if (c >= sd::ALPH) bad = true;
+            out[l] = c < sd::ALPH ? h->blosum2.num2aa[c] : 'X';
+        }
+        out[L] = '\n';
+    }
+    return bad ? SD_EINVAL : SD_OK;
+}
+
 int sd_host_profile_kmer_threshold(float sensitivity, int kmerSize) { return sd::profileKmerThreshold(sensitivity, kmerSize); }
 
 int sd_host_index_info(sd_host_index *ix, uint64_t *tableSize, uint64_t *nEntries, uint64_t *maskedResidues) {
