@@ -284,7 +284,7 @@ int sd_sw_last_cells(sd_ctx *ctx, uint64_t *forwardCells, uint64_t *reverseCells
 
 /* ---- prefilter ------------------------------------------------------------------------ */
 typedef struct {
-    int32_t kmerSize;        /* 6 or 7 */
+    int32_t kmerSize;        /* 5, 6 or 7 (the target's; the automatic choice, sd_host_auto_kmer_size, gives 6 or 7) */
     int32_t kmerThr;         /* Prefiltering::getKmerThreshold (Prefiltering.cpp:1005) */
     int32_t maxHitsPerQuery; /* --max-seqs */
     int32_t minDiagScore;    /* --min-ungapped-score, must be >= 1 */
@@ -306,6 +306,8 @@ typedef struct {
  *   kmerOffsets[20^k+1] (u32), entrySeq/entryPos: lists sorted by (seqId,pos) (IndexTable.h:182-189)
  *   maskedResidues/seqOffsets: SequenceLookup (M/src/prefiltering/SequenceLookup.h)
  *   ext2/ext3: ExtendedSubstitutionMatrix::calcScoreMatrix rows (score int16, index u16), 400x400 and 8000x8000
+ * kmerSize: 5 (spaced seed 110010000101, k-mer generator 2 + 3), 6 (1101010011, 3 + 3) or 7 (11010110011, 2 + 2 + 3); ext2 may be
+ * NULL at k = 6 only.  A k = 5 index never needs the wide form (20^5 lists).
  * kmerOffsets, kmerBlockBase, entrySeq, entryPos and maskedResidues may be device pointers (an index that arrived by a
  * device-to-device broadcast is made resident without a host round trip); seqOffsets is read on the host. */
 int sd_target_create(sd_ctx *ctx, int kmerSize, const uint32_t *kmerOffsets, const uint32_t *entrySeq,
@@ -323,6 +325,7 @@ int sd_target_create_wide(sd_ctx *ctx, int kmerSize, const uint32_t *kmerOffsets
  * IndexTable.h:131-189,376-392) -- replaces sd_host_build_index + sd_target_create_wide (minutes of host time for 10^4
  * proteomes).  residues: host or device pointer.  maskRatios / selfScore: sd_host_index_tables.  The result equals the
  * host-built index entry for entry (tests/test_gpu_index_build.py); the wide form is chosen from the entry count.
+ * kmerSize 5, 6 or 7; ext2Score / ext2Index are needed at 5 and 7 (SD_EINVAL without them).
  * stats (nullable): [0] entries, [1] masked residues, [2] k-mer range passes, [3] k-mer records before the per-target dedupe. */
 int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask, double maskProb, const uint8_t *residues,
                     const uint64_t *seqOffsets, uint32_t nSeq, const double *maskRatios, const int8_t *selfScore,
@@ -339,8 +342,10 @@ int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask, double mas
  * QueryMatcher.cpp:249-252): par->kmerThr and qKmerBias are ignored, stats[4q] is the number of windows without X;
  * sd_prefilter_profile_batch refuses it (Prefiltering.cpp:144-148).  The target holds no 2-mer / 3-mer tables; sd_target_download,
  * sd_target_sample_check and sd_target_build_peak work on it.  The build's scratch is bounded by the pass size (SD_INDEX_PASS records,
- * 2^30 by default), not by the record total.  k = 6 only (SD_EUNSUPPORTED otherwise, and for a window of more than 2^23 similar
- * k-mers, KmerGenerator.h:45); a profile of more than 65 535 positions is SD_EINVAL.
+ * 2^30 by default), not by the record total.  k = 5 (the reference's k for a sequence query DB against a profile target DB when -k is
+ * not given, Search.cpp:251-257) and k = 6 only (SD_EUNSUPPORTED otherwise, and for a window of more than 2^23 similar k-mers,
+ * KmerGenerator.h:45); a profile of more than 65 535 positions is SD_EINVAL; SD_ENOMEM when the entry array, sized by the counted
+ * records, does not fit.
  * stats (nullable): [0] entries, [1] 0, [2] k-mer range passes, [3] k-mer records before the per-target dedupe. */
 int sd_target_build_profile(sd_ctx *ctx, int kmerSize, int kmerThr, const uint8_t *queryLetters, const uint8_t *consensus,
                             const int16_t *sortedScore /* positions x 20 */, const uint8_t *sortedIndex /* positions x 20 */,
@@ -374,7 +379,7 @@ void sd_target_destroy(sd_target *t);
  * entries -- plus the scratch of the build's largest phase: masking, record sort or list-start scan) -- what the target split
  * (`prefilter --split 0`, --split-mode 2) compares with the free device memory.  It assumes the worst case of one index record
  * per residue, counts every allocation rounded up to a 2 MiB granule and adds 32 MiB for the runtime's own first-use allocations.
- * 0 for a k other than 6 or 7. */
+ * 0 for a k other than 6 or 7: a k = 5 target is not modelled and is searched unsplit. */
 uint64_t sd_target_footprint(int kmerSize, uint64_t nSeq, uint64_t nResidues);
 /* the device memory sd_target_build actually held at the fullest point of each of its phases while it built `t` (the drop of
  * hipMemGetInfo's free bytes since the call began; 0 for a target made by sd_target_create*) */

@@ -685,7 +685,7 @@ class Target:
 
     @classmethod
     def build_on_device(cls, ctx, host, residues, offsets, k=6, kmer_thr=112, mask=True, mask_prob=0.9):
-        """sd_target_build: masking, k-mer collection and list construction on the GPU (no host index)"""
+        """sd_target_build: masking, k-mer collection and list construction on the GPU (no host index); k = 5, 6 or 7"""
         self = cls.__new__(cls)
         self.ctx, self.host, self.index = ctx, host, None
         residues = np.ascontiguousarray(residues, np.uint8)
@@ -709,7 +709,7 @@ class Target:
 
     @classmethod
     def build_profile_on_device(cls, ctx, host, prof, k=6, kmer_thr=None):
-        """sd_target_build_profile: the similar-k-mer index of a profile target DB, built on the GPU.  prof: the dict
+        """sd_target_build_profile: the similar-k-mer index of a profile target DB, built on the GPU (k = 5 or 6).  prof: the dict
         Host.map_profiles returns; kmer_thr: the profile threshold (default: Host.profile_kmer_threshold(4.0, k)).  Sequence
         queries (api.prefilter) look up their own k-mers only against it; api.prefilter_profile refuses it."""
         self = cls.__new__(cls)

@@ -129,7 +129,7 @@ int createindexModule(const Args &a) {
     if (db.profile) return fail("profile databases are not indexed on this path");
     int k = (int) a.integer("-k", 0);
     if (k == 0) k = sd_host_auto_kmer_size(db.totalResidues());
-    if (k != 6 && k != 7) return fail("-k: k-mer sizes 6 and 7 are implemented");
+    if (k < 5 || k > 7) return fail("-k: k-mer sizes 5, 6 and 7 are implemented");
     // createindex defaults to the search sensitivity 7.5 (M/src/commons/Parameters.cpp); --k-score overrides
     const float sens = (float) a.real("-s", 7.5);
     const long long kScore = strtoll(a.multi("--k-score", "seq", "2147483647").c_str(), nullptr, 10);

@@ -84,6 +84,13 @@ int resolveSplit(const Args &a, const sddb::Reader &target, uint64_t residues, u
     };
     p.n = 1;
     p.target = false;
+    // a k = 5 target is searched unsplit: sd_target_footprint does not model its index (it returns 0), so --split 0 has nothing to decide
+    // with (it means 1) and a split the user asks for is refused
+    if (kArg == 5) {
+        if (split > 1) return fail("--split " + std::to_string(split) + ": a k=5 target index is searched unsplit (--split 0 or 1)");
+        if (planFor(1)) return fail("sd_host_split_plan failed");
+        return 0;
+    }
     const bool detect = split == 0 || mode == 2;
     uint64_t limit = 0, whole = 0, perSplit = 0;
     bool fits = true;
@@ -155,7 +162,7 @@ int prefilterSetupFromArgs(const Args &a, sd_host *host, const SeqDb &tdb, bool 
     // parameters the way Prefiltering's constructor derives them (Prefiltering.cpp:180-215,1005-1065)
     s.k = kOverride ? kOverride : (int) a.integer("-k", 0);
     if (s.k == 0) s.k = sd_host_auto_kmer_size(tdb.totalResidues());
-    if (s.k != 6 && s.k != 7) return fail("-k " + std::to_string(s.k) + ": k-mer sizes 6 and 7 are implemented");
+    if (s.k < 5 || s.k > 7) return fail("-k " + std::to_string(s.k) + ": k-mer sizes 5, 6 and 7 are implemented");
     const float sens = (float) a.real("-s", 4.0);
     const long long kScore = strtoll(a.multi("--k-score", profileQueries ? "prof" : "seq", "2147483647").c_str(), nullptr, 10);
     s.kmerThr = kScore != INT_MAX ? (int) kScore
@@ -321,6 +328,15 @@ int prefilterModule(const Args &a) {
     // searched unsplit, as a profile target is: hundreds of index records per residue, which sd_target_footprint does not model
     if (similarTarget && a.integer("--split", 0) > 1)
         return fail("--split " + std::to_string(a.integer("--split", 0)) + ": --target-search-mode 1 searches the target unsplit (--split 0 or 1)");
+    // what -k itself rules out is said before a device is asked for (an automatic size, -k 0, is judged where it is resolved, below)
+    if (const int kArg = (int) a.integer("-k", 0)) {
+        if (kArg < 5 || kArg > 7) return fail("-k " + std::to_string(kArg) + ": k-mer sizes 5, 6 and 7 are implemented");
+        if (profileTarget && kArg == 7) return fail("-k 7: the index of a profile target is built at k=5 and k=6 only");
+        if (similarTarget && kArg != 6)
+            return fail("-k " + std::to_string(kArg) + ": the similar-k-mer index of --target-search-mode 1 is built at k=6 only");
+        if (kArg == 5 && !profileTarget && a.integer("--split", 0) > 1)
+            return fail("--split " + std::to_string(a.integer("--split", 0)) + ": a k=5 target index is searched unsplit (--split 0 or 1)");
+    }
     lap.mark("load DBs");
     info(a, "Query database size: %u type: %s\nTarget database size: %u type: %s\n", qdb->n, qdb->profile ? "Profile" : "Aminoacid", tdb->n,
          profileTarget ? "Profile" : "Aminoacid");
@@ -348,7 +364,7 @@ int prefilterModule(const Args &a) {
     // a profile on either side makes it a profile search: the profile threshold, -s / --k-score prof: (Prefiltering.cpp:196-202)
     if (int rcS = prefilterSetupFromArgs(a, host.h, *tdb, qdb->profile || profileTarget, PS, plan.k)) return rcS;
     if (profileTarget) {
-        if (PS.k != 6) return fail("-k " + std::to_string(PS.k) + ": the index of a profile target is built at k=6 only");
+        if (PS.k != 5 && PS.k != 6) return fail("-k " + std::to_string(PS.k) + ": the index of a profile target is built at k=5 and k=6 only");
         PS.indexThr = PS.kmerThr;   // the similar k-mers are generated at the threshold itself
         PS.mask = false;            // --mask is ignored: nothing of a profile is masked (Prefiltering.cpp:172-174)
     }

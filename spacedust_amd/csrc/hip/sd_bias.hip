@@ -57,13 +57,10 @@ bias_cb_kernel(uint64_t total, const uint8_t *__restrict__ res, const uint64_t *
 
 __global__ void __launch_bounds__(256)
 bias_round_kernel(uint64_t total, const uint64_t *__restrict__ off, uint32_t n, const float *__restrict__ cbSeed,
-                  const float *__restrict__ cbBlosum, int k, int span, int8_t *__restrict__ sw8, int8_t *__restrict__ dg8,
-                  int16_t *__restrict__ km16) {
+                  const float *__restrict__ cbBlosum, int k, int span, uint64_t seedBytes /* the k seed positions, a byte each */,
+                  int8_t *__restrict__ sw8, int8_t *__restrict__ dg8, int16_t *__restrict__ km16) {
     __shared__ uint8_t seedPos[8];
-    if (threadIdx.x < 8) {
-        const uint8_t s6[8] = {0, 1, 3, 5, 8, 9, 0, 0}, s7[8] = {0, 1, 3, 5, 6, 9, 10, 0};
-        seedPos[threadIdx.x] = k == 6 ? s6[threadIdx.x] : s7[threadIdx.x];
-    }
+    if (threadIdx.x < 8) seedPos[threadIdx.x] = (uint8_t) (seedBytes >> (8 * threadIdx.x));
     __syncthreads();
     const uint64_t g = (uint64_t) blockIdx.x * 256 + threadIdx.x;
     if (g >= total) return;
@@ -94,7 +91,8 @@ bias_round_kernel(uint64_t total, const uint64_t *__restrict__ off, uint32_t n, 
 extern "C" int sd_comp_bias_batch(sd_ctx *ctx, sd_host *h, const uint8_t *residues, const uint64_t *offsets, uint32_t n, int kmerSize,
                                   int8_t *swBias, int8_t *diagBias, int16_t *kmerBias) {
     if (!ctx || !h || !residues || !offsets || !swBias || !diagBias || !kmerBias) return SD_EINVAL;
-    if (kmerSize != 6 && kmerSize != 7) return SD_EINVAL;
+    const SdKmerShape *shape = sdKmerShape(kmerSize);
+    if (!shape) return SD_EINVAL;
     (void) hipSetDevice(ctx->device);
     sdD2HReset(ctx);   // (reads an earlier, failed call left pending)
     const uint64_t total = offsets[n];
@@ -135,12 +133,14 @@ extern "C" int sd_comp_bias_batch(sd_ctx *ctx, sd_host *h, const uint8_t *residu
     SD_HIP(ctx, hipMemcpyAsync(dRes, residues, total, hipMemcpyHostToDevice, ctx->stream));
     SD_HIP(ctx, hipMemcpyAsync(dOff, offsets, ((size_t) n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     const unsigned grid = (unsigned) ((total + 255) / 256);
-    const int span = kmerSize == 6 ? 10 : 11;
+    const int span = shape->span;
+    uint64_t seedBytes = 0;
+    for (int p = 0; p < 8; p++) seedBytes |= (uint64_t) shape->seed[p] << (8 * p);
     {
         ProfScope ps(ctx, "comp_bias");
         hipLaunchKernelGGL(bias_cb_kernel, dim3(grid), dim3(256), 0, ctx->stream, total, dRes, dOff, n, dMatS, dMatB, dTabS, h->biasLoSeed,
                            h->biasSpanSeed, dTabB, h->biasLoBlosum, h->biasSpanBlosum, dCbS, dCbB);
-        hipLaunchKernelGGL(bias_round_kernel, dim3(grid), dim3(256), 0, ctx->stream, total, dOff, n, dCbS, dCbB, kmerSize, span, dSw, dDg, dKm);
+        hipLaunchKernelGGL(bias_round_kernel, dim3(grid), dim3(256), 0, ctx->stream, total, dOff, n, dCbS, dCbB, kmerSize, span, seedBytes, dSw, dDg, dKm);
     }
     SD_HIP(ctx, hipGetLastError());
     SD_HIP(ctx, sdD2H(ctx, swBias, dSw, total));   // (the caller's arrays are pageable: see sdD2H)

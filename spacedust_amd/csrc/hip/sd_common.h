@@ -350,6 +350,22 @@ struct sd_target {
 };
 constexpr int EXT3_CUM_SPAN = 256;   // scores a row of dExt3Cum spans (sdBuildExt3Cum)
 
+// The k-mer sizes of the k-mer prefilter, one row per size: the spaced seed (Sequence.h:21-24: positions and span) and 20^k.  A size
+// that is not here is not implemented (sdKmerShape returns null).
+struct SdKmerShape {
+    int k, span;
+    uint8_t seed[8];
+    uint64_t tableSize;
+};
+inline const SdKmerShape *sdKmerShape(int k) {
+    static const SdKmerShape rows[] = {{5, 12, {0, 1, 4, 9, 11, 0, 0, 0}, 3200000ull},        // 110010000101
+                                       {6, 10, {0, 1, 3, 5, 8, 9, 0, 0}, 64000000ull},        // 1101010011
+                                       {7, 11, {0, 1, 3, 5, 6, 9, 10, 0}, 1280000000ull}};    // 11010110011
+    for (const SdKmerShape &r : rows)
+        if (r.k == k) return &r;
+    return nullptr;
+}
+
 // What the similar-k-mer enumerations share (the query side in sd_prefilter.hip / sd_pf_join.h, the target side of --target-search-mode 1
 // in sd_index_build.hip).
 // number of entries >= cutoff in a descending row of n int16

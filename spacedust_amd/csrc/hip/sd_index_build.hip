@@ -1,6 +1,6 @@
 // Target index construction on the device.  Three builders, one per kind of target index:
 //   sd_target_build          the plain sequence index (k = 6 or 7): every target tantan-masked, its own k-mers at or above kmerThr
-//   sd_target_build_profile  a profile target DB (k = 6): the similar k-mers of every profile window, nothing masked
+//   sd_target_build_profile  a profile target DB (k = 5 or 6): the similar k-mers of every profile window, nothing masked
 //   sd_target_build_similar  a sequence target under --target-search-mode 1 (k = 6): the similar k-mers of every sequence window
 //
 // What IndexBuilder::fillDatabase does on the host for the first (M/src/prefiltering/IndexBuilder.cpp:55-239; sd_index.cpp is the
@@ -416,9 +416,11 @@ ib_records_kernel(const uint8_t *__restrict__ masked, const uint64_t *__restrict
 // windows flagged for the big tier.
 constexpr uint32_t IP_GRID = 1024, IP_GRID_BIG = 16;
 constexpr uint32_t IP_LIST_MAX = 1u << 23;
-__constant__ uint8_t c_ipSeed6[6] = {0, 1, 3, 5, 8, 9};   // spaced seed 1101010011 (M/src/commons/Sequence.h:23)
+// spaced seeds of the windowed builders, row k - 5 (M/src/commons/Sequence.h:21,23; SdKmerShape, sd_common.h)
+__constant__ uint8_t c_ipSeed[2][8] = {{0, 1, 4, 9, 11, 0, 0, 0},    // k = 5: 110010000101
+                                       {0, 1, 3, 5, 8, 9, 0, 0}};    // k = 6: 1101010011
 
-template <int MODE>
+template <int K, int MODE>
 __global__ void __launch_bounds__(64)
 ib_profile_records_kernel(uint64_t nWin, const uint64_t *__restrict__ winBase /* first window of every target, nSeq + 1 */, uint32_t nSeq,
                           const uint8_t *__restrict__ letters, const uint64_t *__restrict__ posOff, const int16_t *__restrict__ sortedScore,
@@ -426,7 +428,7 @@ ib_profile_records_kernel(uint64_t nWin, const uint64_t *__restrict__ winBase /*
                           uint8_t *__restrict__ big, int bigTier, uint32_t binWidth, unsigned long long *__restrict__ coarse,
                           unsigned long long *__restrict__ errWin, uint32_t lo, uint32_t hi, uint32_t *__restrict__ winCount,
                           const uint64_t *__restrict__ recBase, uint32_t *__restrict__ keys, uint64_t *__restrict__ vals) {
-    constexpr int K = 6;
+    static_assert(K == 5 || K == 6, "c_ipSeed");
     __shared__ int16_t rowS[K][20];
     __shared__ uint8_t rowI[K][20];
     __shared__ uint32_t hist[MODE == 0 ? IB_COARSE_BINS : 1];
@@ -458,12 +460,12 @@ ib_profile_records_kernel(uint64_t nWin, const uint64_t *__restrict__ winBase /*
         const int i = (int) (p - winBase[tl]);
         const uint64_t r0 = posOff[q] + (uint64_t) i;
         bool hasX = false;
-        for (int x = 0; x < K; x++) hasX |= letters[r0 + c_ipSeed6[x]] >= 20;   // kmerContainsX on the query letters (Sequence.h:397-403)
+        for (int x = 0; x < K; x++) hasX |= letters[r0 + c_ipSeed[K - 5][x]] >= 20;   // kmerContainsX on the query letters (Sequence.h:397-403)
         __syncthreads();   // the previous window's rows are no longer read
         for (int x = lane; x < K * 20; x += 64) {
             const int sIdx = x / 20, e = x % 20;
-            rowS[sIdx][e] = sortedScore[(r0 + c_ipSeed6[sIdx]) * 20 + e];
-            rowI[sIdx][e] = sortedIndex[(r0 + c_ipSeed6[sIdx]) * 20 + e];
+            rowS[sIdx][e] = sortedScore[(r0 + c_ipSeed[K - 5][sIdx]) * 20 + e];
+            rowI[sIdx][e] = sortedIndex[(r0 + c_ipSeed[K - 5][sIdx]) * 20 + e];
         }
         __syncthreads();
         uint32_t totalOut = 0;   // MODE 0: the list length; MODE 1 / 2: its records in [lo, hi)
@@ -631,7 +633,7 @@ ib_similar_records_kernel(uint64_t nWin, const uint64_t *__restrict__ winBase /*
         bool hasX = false;
 #pragma unroll
         for (int x = 0; x < 6; x++) {
-            w[x] = s[c_ipSeed6[x]];
+            w[x] = s[c_ipSeed[6 - 5][x]];
             hasX |= w[x] >= 20u;   // kmerContainsX (Sequence.h:397-403)
         }
         uint32_t totalOut = 0;   // MODE 0: the list length; MODE 1 / 2: its records in [lo, hi)
@@ -1198,17 +1200,17 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
                                const int16_t *ext2Score, const uint16_t *ext2Index, const int16_t *ext3Score,
                                const uint16_t *ext3Index, sd_target **out, uint64_t *stats) {
     if (!ctx || !out || !residues || !seqOffsets || !maskRatios || !selfScore || !ext3Score || !ext3Index) return SD_EINVAL;
-    if (kmerSize != 6 && kmerSize != 7) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the device implements k=6 and k=7", kmerSize);
-    if (kmerSize == 7 && (!ext2Score || !ext2Index)) return sdFail(ctx, SD_EINVAL, "k=7 needs the 2-mer score matrix");
+    const SdKmerShape *shape = sdKmerShape(kmerSize);
+    if (!shape) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the device implements k=5, k=6 and k=7", kmerSize);
+    if (kmerSize != 6 && (!ext2Score || !ext2Index)) return sdFail(ctx, SD_EINVAL, "k=%d needs the 2-mer score matrix", kmerSize);
     // the kernels read their tables (seed positions, powers, tantan constants) from __constant__ memory: one build at a time
     static std::mutex buildMutex;
     std::lock_guard<std::mutex> buildLock(buildMutex);
     IndexBuild b(ctx, {"sd_target_build", "residues", nullptr, "index_kmer_histogram", nullptr});
-    if (int rc = b.open(kmerSize, kmerSize == 6 ? 64000000ull : 1280000000ull, seqOffsets, nSeq, 0)) return rc;
+    if (int rc = b.open(kmerSize, shape->tableSize, seqOffsets, nSeq, 0)) return rc;
     sd_target *t = b.t;
-    const int span = kmerSize == 6 ? 10 : 11;
+    const int span = shape->span;
     {
-        static const uint8_t s6[8] = {0, 1, 3, 5, 8, 9, 0, 0}, s7[8] = {0, 1, 3, 5, 6, 9, 10, 0};
         uint32_t pw[8] = {0};
         uint32_t p = 1;
         for (int i = 0; i < kmerSize; i++) {
@@ -1217,7 +1219,7 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
         }
         int self[IB_ALPH];
         for (int a = 0; a < IB_ALPH; a++) self[a] = selfScore[a];
-        SD_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_ibSeed), kmerSize == 6 ? s6 : s7, 8));
+        SD_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_ibSeed), shape->seed, 8));
         SD_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_ibPow), pw, sizeof(pw)));
         SD_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_ibSelf), self, sizeof(self)));
     }
@@ -1235,7 +1237,7 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
     const uint32_t nWavesR = (uint32_t) (((uint64_t) nSeq + IB_SEQ_PER_WAVE - 1) / IB_SEQ_PER_WAVE);
     auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *waveCount, const uint64_t *waveBase, uint32_t *keys, uint64_t *vals) -> int {
         constexpr int MODE = decltype(mode)::value;
-        const auto kernel = kmerSize == 6 ? ib_records_kernel<6, MODE> : ib_records_kernel<7, MODE>;
+        const auto kernel = kmerSize == 5 ? ib_records_kernel<5, MODE> : kmerSize == 6 ? ib_records_kernel<6, MODE> : ib_records_kernel<7, MODE>;
         hipLaunchKernelGGL(kernel, dim3((nWavesR + 3) / 4), dim3(256), 0, ctx->stream, (const uint8_t *) t->dMasked, (const uint64_t *) t->dSeqOff,
                            nSeq, span, kmerThr, b.binWidth, b.dCoarse.p, lo, hi, waveCount, waveBase, keys, vals);
         return SD_OK;
@@ -1255,12 +1257,13 @@ extern "C" int sd_target_build_profile(sd_ctx *ctx, int kmerSize, int kmerThr, c
                                        sd_target **out, uint64_t *stats) {
     if (!ctx || !out || !queryLetters || !consensus || !sortedScore || !sortedIndex || !posOffsets) return SD_EINVAL;
     if (kmerSize == 7)
-        return sdFail(ctx, SD_EUNSUPPORTED, "k=7: the index of a profile target is built at k=6 only (no k=7 golden index of the reference to test against)");
-    if (kmerSize != 6) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the index of a profile target is built at k=6", kmerSize);
+        return sdFail(ctx, SD_EUNSUPPORTED, "k=7: the index of a profile target is built at k=5 and k=6 only (no k=7 golden index of the reference to test against)");
+    if (kmerSize != 5 && kmerSize != 6) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the index of a profile target is built at k=5 and k=6", kmerSize);
+    const SdKmerShape *shape = sdKmerShape(kmerSize);
     IndexBuild b(ctx, {"sd_target_build_profile", "positions", "profile", "index_profile_histogram",
                        "target %u, position %llu: more than %u similar k-mers in one profile window (the reference's buffer ends there, "
                        "KmerGenerator.h:45); raise the k-mer threshold"});
-    if (int rc = b.open(kmerSize, 64000000ull, posOffsets, nSeq, 10)) return rc;
+    if (int rc = b.open(kmerSize, shape->tableSize, posOffsets, nSeq, shape->span)) return rc;
     sd_target *t = b.t;
     t->similar = true;
     const uint64_t nWin = b.nWin, total = posOffsets[nSeq];
@@ -1280,8 +1283,9 @@ extern "C" int sd_target_build_profile(sd_ctx *ctx, int kmerSize, int kmerThr, c
     // the generator in one of its modes, on the tier(s) the windows run in; b.dErr[1]: the windows mode 0 moved to the big tier
     auto generate = [&](auto mode, uint32_t lo, uint32_t hi, uint32_t *winCount, const uint64_t *recBase, uint32_t *keys, uint64_t *vals) -> int {
         constexpr int MODE = decltype(mode)::value;
+        const auto kernel = kmerSize == 5 ? ib_profile_records_kernel<5, MODE> : ib_profile_records_kernel<6, MODE>;
         for (int bigTier = 0; bigTier <= (anyBig ? 1 : 0); bigTier++) {
-            hipLaunchKernelGGL((ib_profile_records_kernel<MODE>), dim3(bigTier ? gridBig : grid), dim3(64), 0, ctx->stream, nWin,
+            hipLaunchKernelGGL(kernel, dim3(bigTier ? gridBig : grid), dim3(64), 0, ctx->stream, nWin,
                                (const uint64_t *) b.dWinBase.p, nSeq, (const uint8_t *) dLetters.p, (const uint64_t *) t->dSeqOff,
                                (const int16_t *) dScore.p, (const uint8_t *) dIndex.p, kmerThr, bigTier ? dScratchBig.p : dScratch.p,
                                bigTier ? PROFILE_PARTIAL_CAP_BIG : PROFILE_PARTIAL_CAP, dBig.p, bigTier, b.binWidth, b.dCoarse.p, b.dErr.p, lo, hi,

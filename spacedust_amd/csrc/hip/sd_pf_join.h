@@ -114,17 +114,18 @@ emit_kmers_join_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint
 
 // ---- sequence queries against a *similar* target (sd_target::similar, a profile DB's index): takeOnlyBestKmer
 // (Prefiltering.cpp:176-179, QueryMatcher.cpp:249-252).  Every window without X looks up its own k-mer and nothing else; the k-mer
-// threshold and the k-mer composition bias play no part.  A thread per position.  K1: the count (1 or 0) ...
+// threshold and the k-mer composition bias play no part.  A thread per position; K = 5 or 6 (decodePos).  K1: the count (1 or 0) ...
+template <int K>
 __global__ void __launch_bounds__(256)
 exact_count_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t nQ, const uint8_t *__restrict__ qRes,
                    const uint64_t *__restrict__ qOff, const int16_t *__restrict__ kmerBias, const uint32_t *__restrict__ posQuery,
                    uint32_t *__restrict__ kmerCount) {
     const uint64_t p = (uint64_t) blockIdx.x * 256 + threadIdx.x;
     if (p >= nPos) return;
-    kmerCount[p] = decodePos(p, posBase, nQ, qRes, qOff, kmerBias, 0, posQuery).ok ? 1u : 0u;
+    kmerCount[p] = decodePos<K>(p, posBase, nQ, qRes, qOff, kmerBias, 0, posQuery).ok ? 1u : 0u;
 }
 // ... K2: the k-mer itself, as the join's stream element (JOIN) or with its index list for the lookup path
-template <bool JOIN, bool WIDE>
+template <bool JOIN, bool WIDE, int K>
 __global__ void __launch_bounds__(256)
 exact_emit_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t nQ, const uint8_t *__restrict__ qRes,
                   const uint64_t *__restrict__ qOff, const int16_t *__restrict__ kmerBias, const uint32_t *__restrict__ posQuery,
@@ -133,9 +134,9 @@ exact_emit_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t 
                   uint32_t *__restrict__ kLen, uint32_t *__restrict__ kPos) {
     const uint64_t p = (uint64_t) blockIdx.x * 256 + threadIdx.x;
     if (p >= nPos) return;
-    const PosInfo pi = decodePos(p, posBase, nQ, qRes, qOff, kmerBias, 0, posQuery);
+    const PosInfo pi = decodePos<K>(p, posBase, nQ, qRes, qOff, kmerBias, 0, posQuery);
     if (!pi.ok) return;
-    const uint32_t km = pi.idx0 + 8000u * pi.idx1;   // Indexer::int2index of the window
+    const uint32_t km = pi.idx0 + (uint32_t) TwoStep<K>::FIRST_ROW * pi.idx1;   // Indexer::int2index of the window
     const uint64_t w = kmerBase[p];
     if (JOIN) {
         elems[w] = jpElem(km, w, pi.i);
@@ -778,7 +779,7 @@ __device__ __forceinline__ uint16_t diagFromResidues(const DiagSrc &S, uint32_t 
         bool x = false;
 #pragma unroll
         for (int p = 0; p < 6; p++) {
-            const uint32_t a = ts[j + c_seed6[p]];
+            const uint32_t a = ts[j + c_seed[6 - KMER_MIN][p]];
             x |= a >= 20u;
             idx += a * pw;
             pw *= 20u;

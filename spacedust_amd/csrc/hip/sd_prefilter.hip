@@ -47,8 +47,12 @@ struct WsView {
     }
 };
 
+// spaced seeds by k-mer size, row k - KMER_MIN (M/src/commons/Sequence.h:21-24; the host's copy with the spans: SdKmerShape, sd_common.h)
+constexpr int KMER_MIN = 5;
 constexpr int SPAN6 = 10;
-__constant__ uint8_t c_seed6[6] = {0, 1, 3, 5, 8, 9};   // spaced seed 1101010011 (M/src/commons/Sequence.h:23)
+__constant__ uint8_t c_seed[3][8] = {{0, 1, 4, 9, 11, 0, 0, 0},      // k = 5: 110010000101, span 12
+                                     {0, 1, 3, 5, 8, 9, 0, 0},       // k = 6: 1101010011, span 10
+                                     {0, 1, 3, 5, 6, 9, 10, 0}};     // k = 7: 11010110011, span 11
 
 struct PosInfo {
     uint32_t q;
@@ -58,6 +62,8 @@ struct PosInfo {
     int thr;
 };
 
+// K = 6: the two 3-mers of the window; K = 5: its 2-mer (idx0) and its 3-mer (idx1) -- the two steps of the k-mer generator either way
+template <int K = 6>
 __device__ __forceinline__ PosInfo decodePos(uint64_t p, const uint64_t *__restrict__ posBase, uint32_t nQ,
                                              const uint8_t *__restrict__ qRes, const uint64_t *__restrict__ qOff,
                                              const int16_t *__restrict__ kmerBias, int kmerThr,
@@ -78,16 +84,22 @@ __device__ __forceinline__ PosInfo decodePos(uint64_t p, const uint64_t *__restr
     r.q = lo;
     r.i = (int) (p - posBase[lo]);
     const uint8_t *s = qRes + qOff[lo] + r.i;
-    uint8_t w[6];
+    static_assert(K == 5 || K == 6, "two-step generators");
+    uint8_t w[K];
     bool hasX = false;
 #pragma unroll
-    for (int x = 0; x < 6; x++) {
-        w[x] = s[c_seed6[x]];
+    for (int x = 0; x < K; x++) {
+        w[x] = s[c_seed[K - KMER_MIN][x]];
         hasX |= (w[x] >= 20);
     }
     r.ok = !hasX;
-    r.idx0 = w[0] + 20u * w[1] + 400u * w[2];
-    r.idx1 = w[3] + 20u * w[4] + 400u * w[5];
+    if (K == 5) {
+        r.idx0 = w[0] + 20u * w[1];
+        r.idx1 = w[2] + 20u * w[3] + 400u * w[4];
+    } else {
+        r.idx0 = w[0] + 20u * w[1] + 400u * w[2];
+        r.idx1 = w[3] + 20u * w[4] + 400u * w[5];
+    }
     int b = kmerBias[qOff[lo] + r.i];
     int t = kmerThr - b;
     r.thr = t > 0 ? t : 0;
@@ -159,23 +171,42 @@ ext3_cum_kernel(const int16_t *__restrict__ score, int lo, uint16_t *__restrict_
     cum[(size_t) blockIdx.x * EXT3_CUM_SPAN + threadIdx.x] = (uint16_t) sum;
 }
 
+// The two-step generators: k = 6 divides 3 + 3, k = 5 divides 2 + 3 (KmerGenerator.cpp:69-85 with the reversal: the 2-mer step comes
+// first).  One array product either way -- parents a of the first step's row with s0[a] >= short(thr - best1), children b of the 3-mer
+// row with s1[b] >= short(thr - s0[a]), k-mer i0[a] + FIRST_ROW i1[b] -- so the kernels below are one template: at K = 5 the first
+// step's rows come from the 2-mer matrix (firstScore / firstIndex, rows of 400) and are searched (the cumulative table is the 3-mer
+// matrix's), at K = 6 they are the 3-mer matrix itself.
+template <int K>
+struct TwoStep {
+    static constexpr int FIRST_ROW = K == 5 ? 400 : 8000;   // entries of a first-step row = 20^(its residues) = the second step's multiplier
+};
+
 // K1: count similar k-mers per position
+template <int K>
 __global__ void __launch_bounds__(256)
 count_kmers_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t nQ, const uint8_t *__restrict__ qRes,
                    const uint64_t *__restrict__ qOff, const int16_t *__restrict__ kmerBias, int kmerThr,
-                   const int16_t *__restrict__ ext3Score, uint32_t *__restrict__ kmerCount,
+                   const int16_t *__restrict__ firstScore, const int16_t *__restrict__ ext3Score, uint32_t *__restrict__ kmerCount,
                    const uint16_t *__restrict__ ext3Cum /* nullable */, int ext3Lo, const uint32_t *__restrict__ posQuery /* nullable */) {
+    constexpr int R0 = TwoStep<K>::FIRST_ROW;
     const uint64_t p = (uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (p >= nPos) return;
-    PosInfo pi = decodePos(p, posBase, nQ, qRes, qOff, kmerBias, kmerThr, posQuery);
+    PosInfo pi = decodePos<K>(p, posBase, nQ, qRes, qOff, kmerBias, kmerThr, posQuery);
     uint32_t total = 0;
     if (pi.ok) {
-        const int16_t *row0 = ext3Score + (size_t) pi.idx0 * 8000;
+        const int16_t *row0 = firstScore + (size_t) pi.idx0 * R0;
         const int16_t *row1 = ext3Score + (size_t) pi.idx1 * 8000;
         const int best1 = row1[0];
         const int cutoff1 = (int) (short) (pi.thr - best1);
-        if (ext3Cum) {
+        if (K == 5) {
+            const uint16_t *cum1 = ext3Cum ? ext3Cum + (size_t) pi.idx1 * EXT3_CUM_SPAN : nullptr;
+            const int n0 = countGE(row0, R0, cutoff1);
+            for (int a = lane; a < n0; a += 64) {
+                const int cutoff2 = (int) (short) (pi.thr - (int) row0[a]);
+                total += (uint32_t) (cum1 ? countGETab(cum1, ext3Lo, cutoff2) : countGE(row1, 8000, cutoff2));
+            }
+        } else if (ext3Cum) {
             const uint16_t *cum0 = ext3Cum + (size_t) pi.idx0 * EXT3_CUM_SPAN, *cum1 = ext3Cum + (size_t) pi.idx1 * EXT3_CUM_SPAN;
             const int n0 = countGETab(cum0, ext3Lo, cutoff1);
             for (int a = lane; a < n0; a += 64) total += (uint32_t) countGETab(cum1, ext3Lo, (int) (short) (pi.thr - (int) row0[a]));
@@ -205,8 +236,6 @@ __global__ void interleave_entries_kernel(uint64_t n, const uint32_t *__restrict
 // (KmerGenerator.cpp:107-216) nest as  for a in list0: for b in list1(a): for c in list2(a,b)  with the `short` cutoffs
 //   a: s0[a] >= thr - best1 - best2;  b: s1[b] >= thr - s0[a] - best2;  c: s2[c] >= thr - (s0[a] + s1[b])
 // and k-mer index i0[a] + 400 i1[b] + 160000 i2[c]; that loop order is the order of the hit stream.
-constexpr int SPAN7 = 11;
-__constant__ uint8_t c_seed7[7] = {0, 1, 3, 5, 6, 9, 10};
 
 struct PosInfo7 {
     uint32_t q;
@@ -238,7 +267,7 @@ __device__ __forceinline__ PosInfo7 decodePos7(uint64_t p, const uint64_t *__res
     bool hasX = false;
 #pragma unroll
     for (int x = 0; x < 7; x++) {
-        w[x] = s[c_seed7[x]];
+        w[x] = s[c_seed[7 - KMER_MIN][x]];
         hasX |= (w[x] >= 20);
     }
     r.ok = !hasX;
@@ -405,7 +434,7 @@ profile_kmers_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32
     const int lane = threadIdx.x;
     uint2 *listA = scratch + (size_t) blockIdx.x * 2 * cap;
     uint2 *listB = listA + cap;
-    const uint8_t *seed = k == 6 ? c_seed6 : c_seed7;
+    const uint8_t *seed = c_seed[k - KMER_MIN];
     const int thr = kmerThr > 0 ? kmerThr : 0;   // no composition bias for profiles (QueryMatcher.cpp:93-99,237-238)
     for (uint64_t p = blockIdx.x; p < nPos; p += gridDim.x) {
         if ((big[p] != 0) != (bigTier != 0)) continue;   // block-uniform
@@ -522,10 +551,11 @@ profile_kmers_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32
 }
 
 // K2: emit k-mers (+ index list start/len, + owning position) in the reference's enumeration order
-template <bool WIDE>
+template <bool WIDE, int K>
 __global__ void __launch_bounds__(256)
 emit_kmers_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t nQ, const uint8_t *__restrict__ qRes,
                   const uint64_t *__restrict__ qOff, const int16_t *__restrict__ kmerBias, int kmerThr,
+                  const int16_t *__restrict__ firstScore, const uint16_t *__restrict__ firstIndex,
                   const int16_t *__restrict__ ext3Score, const uint16_t *__restrict__ ext3Index,
                   const uint32_t *__restrict__ idxOffsets, const uint64_t *__restrict__ kmerBase,
                   uint32_t *__restrict__ kStart, uint32_t *__restrict__ kLen, uint32_t *__restrict__ kPos,
@@ -535,15 +565,16 @@ emit_kmers_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t 
     const uint64_t p = (uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (p >= nPos) return;
-    PosInfo pi = decodePos(p, posBase, nQ, qRes, qOff, kmerBias, kmerThr, posQuery);
+    constexpr int R0 = TwoStep<K>::FIRST_ROW;
+    PosInfo pi = decodePos<K>(p, posBase, nQ, qRes, qOff, kmerBias, kmerThr, posQuery);
     if (!pi.ok) return;
-    const int16_t *row0 = ext3Score + (size_t) pi.idx0 * 8000;
+    const int16_t *row0 = firstScore + (size_t) pi.idx0 * R0;
     const int16_t *row1 = ext3Score + (size_t) pi.idx1 * 8000;
-    const uint16_t *ix0 = ext3Index + (size_t) pi.idx0 * 8000;
+    const uint16_t *ix0 = firstIndex + (size_t) pi.idx0 * R0;
     const uint16_t *ix1 = ext3Index + (size_t) pi.idx1 * 8000;
     const int best1 = row1[0];
     const int cutoff1 = (int) (short) (pi.thr - best1);
-    const int n0 = ext3Cum ? countGETab(ext3Cum + (size_t) pi.idx0 * EXT3_CUM_SPAN, ext3Lo, cutoff1) : countGE(row0, 8000, cutoff1);
+    const int n0 = K == 6 && ext3Cum ? countGETab(ext3Cum + (size_t) pi.idx0 * EXT3_CUM_SPAN, ext3Lo, cutoff1) : countGE(row0, R0, cutoff1);
     uint64_t base = kmerBase[p];
     const uint32_t qi = (pi.q << 16) | (uint32_t) pi.i;   // owning query (< 2^16 per sub-batch) and position (< 2^16)
     // The lanes first own prefixes (a) and count their suffix runs; the runs are then flattened: output slot t of the chunk
@@ -586,7 +617,7 @@ emit_kmers_kernel(uint64_t nPos, const uint64_t *__restrict__ posBase, uint32_t 
                         else lo = mid + 1;
                     }
                     const uint32_t before = lo ? myIncl[lo - 1] : 0u;
-                    km[u] = myK0[lo] + 8000u * (uint32_t) ix1[t - before];
+                    km[u] = myK0[lo] + (uint32_t) R0 * (uint32_t) ix1[t - before];
                 }
             }
             uint32_t h4[4];
@@ -2716,8 +2747,9 @@ int sd_target_create_wide(sd_ctx *ctx, int kmerSize, const uint32_t *kmerOffsets
                           const uint64_t *seqOffsets, uint32_t nSeq, const int16_t *ext2Score, const uint16_t *ext2Index,
                           const int16_t *ext3Score, const uint16_t *ext3Index, sd_target **out) {
     if (!ctx || !out || !kmerOffsets || !maskedResidues || !seqOffsets || !ext3Score || !ext3Index) return SD_EINVAL;
-    if (kmerSize != 6 && kmerSize != 7) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the device implements k=6 and k=7", kmerSize);
-    if (kmerSize == 7 && (!ext2Score || !ext2Index)) return sdFail(ctx, SD_EINVAL, "k=7 needs the 2-mer score matrix");
+    const SdKmerShape *shape = sdKmerShape(kmerSize);
+    if (!shape) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the device implements k=5, k=6 and k=7", kmerSize);
+    if (kmerSize != 6 && (!ext2Score || !ext2Index)) return sdFail(ctx, SD_EINVAL, "k=%d needs the 2-mer score matrix", kmerSize);
     if (nEntries > 0xFFFFFFFFull && !kmerBlockBase)
         return sdFail(ctx, SD_EINVAL, "an index of %llu entries needs the block bases of a wide index (sd_host_index_block_base)",
                       (unsigned long long) nEntries);
@@ -2731,7 +2763,7 @@ int sd_target_create_wide(sd_ctx *ctx, int kmerSize, const uint32_t *kmerOffsets
     t->k = kmerSize;
     t->nSeq = nSeq;
     t->nEntries = nEntries;
-    t->tableSize = kmerSize == 6 ? 64000000ull : 1280000000ull;   // 20^k
+    t->tableSize = shape->tableSize;   // 20^k
     t->hSeqOff.assign(seqOffsets, seqOffsets + nSeq + 1);
     const uint64_t total = seqOffsets[nSeq];
     auto up = [&](void **d, const void *h, size_t bytes) -> bool {
@@ -2978,7 +3010,7 @@ int PfBatch::profileKmerPass(const ProfileKmerOut &o) {
     return SD_OK;
 }
 
-// The only ladder over (profile queries | similar-k-mer target | k = 6 | k = 7) x (narrow | wide index); the join takes k = 6 and narrow indexes only
+// The only ladder over (profile queries | similar-k-mer target | k = 5 | k = 6 | k = 7) x (narrow | wide index); the join takes k = 6 and narrow indexes only
 int PfBatch::launchKmerPass(KmerPass pass) {
     const sd_target *T = c.T;
     const int kmerThr = c.par->kmerThr;
@@ -3001,28 +3033,41 @@ int PfBatch::launchKmerPass(KmerPass pass) {
         // the per-position products again, this time writing the stream (the tiers the count pass chose)
         return profileKmerPass<true>({nullptr, nullptr, dKmerBase.p, nullptr, nullptr, nullptr, nullptr, nullptr, dElems.p});
     }
-    if (T->similar) {   // the query's own k-mers only; par->kmerThr and the k-mer bias are not read
+    if (pass == KMERS_EMIT_JOIN && T->k != 6) return sdFail(ctx, SD_EHIP, "the k-mer-major join was chosen at k=%d", T->k);   // (stageCountKmers never does)
+    if (T->similar) {   // the query's own k-mers only; par->kmerThr and the k-mer bias are not read (an index of k = 5 or 6: the builders')
+        const bool k5 = T->k == 5;
         if (pass == KMERS_COUNT)
-            hipLaunchKernelGGL(exact_count_kernel, perThread, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, posQuery, dKmerCount.p);
+            hipLaunchKernelGGL((k5 ? exact_count_kernel<5> : exact_count_kernel<6>), perThread, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p,
+                               posQuery, dKmerCount.p);
         else if (pass == KMERS_EMIT_JOIN)
-            hipLaunchKernelGGL((exact_emit_kernel<true, false>), perThread, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, posQuery, dKmerBase.p,
+            hipLaunchKernelGGL((exact_emit_kernel<true, false, 6>), perThread, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, posQuery, dKmerBase.p,
                                dElems.p, (const uint32_t *) nullptr, (const uint64_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr,
                                (uint32_t *) nullptr);
         else
-            hipLaunchKernelGGL((wideIdx ? exact_emit_kernel<false, true> : exact_emit_kernel<false, false>), perThread, block, 0, ctx->stream, nPos, dPosBase.p, bq,
-                               dQ.p, dQOff.p, dKB.p, posQuery, dKmerBase.p, (uint64_t *) nullptr, T->dOffsets, blockBase, dKStart.p, kStartHi, dKLen.p, dKPos.p);
-    } else if (T->k == 6) {
+            hipLaunchKernelGGL((k5 ? (wideIdx ? exact_emit_kernel<false, true, 5> : exact_emit_kernel<false, false, 5>)
+                                   : (wideIdx ? exact_emit_kernel<false, true, 6> : exact_emit_kernel<false, false, 6>)), perThread, block, 0, ctx->stream, nPos,
+                               dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, posQuery, dKmerBase.p, (uint64_t *) nullptr, T->dOffsets, blockBase, dKStart.p, kStartHi, dKLen.p,
+                               dKPos.p);
+    } else if (T->k == 5) {   // 2 + 3: the first step's rows are the 2-mer matrix's
         if (pass == KMERS_COUNT)
-            hipLaunchKernelGGL(count_kmers_kernel, perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, kmerThr, T->dExt3Score, dKmerCount.p,
-                               cum, T->ext3Lo, posQuery);
+            hipLaunchKernelGGL(count_kmers_kernel<5>, perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, kmerThr, T->dExt2Score,
+                               T->dExt3Score, dKmerCount.p, cum, T->ext3Lo, posQuery);
+        else
+            hipLaunchKernelGGL((wideIdx ? emit_kmers_kernel<true, 5> : emit_kmers_kernel<false, 5>), perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p,
+                               dQOff.p, dKB.p, kmerThr, T->dExt2Score, T->dExt2Index, T->dExt3Score, T->dExt3Index, T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p,
+                               dKPos.p, blockBase, kStartHi, cum, T->ext3Lo, posQuery);
+    } else if (T->k == 6) {   // 3 + 3
+        if (pass == KMERS_COUNT)
+            hipLaunchKernelGGL(count_kmers_kernel<6>, perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, kmerThr, T->dExt3Score,
+                               T->dExt3Score, dKmerCount.p, cum, T->ext3Lo, posQuery);
         else if (pass == KMERS_EMIT_JOIN)
             hipLaunchKernelGGL(emit_kmers_join_kernel, perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, kmerThr, T->dExt3Score,
                                T->dExt3Index, dKmerBase.p, dElems.p, cum, T->ext3Lo, posQuery);
         else
-            hipLaunchKernelGGL((wideIdx ? emit_kmers_kernel<true> : emit_kmers_kernel<false>), perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p,
-                               dKB.p, kmerThr, T->dExt3Score, T->dExt3Index, T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p, dKPos.p, blockBase, kStartHi, cum,
-                               T->ext3Lo, posQuery);
-    } else {
+            hipLaunchKernelGGL((wideIdx ? emit_kmers_kernel<true, 6> : emit_kmers_kernel<false, 6>), perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p,
+                               dQOff.p, dKB.p, kmerThr, T->dExt3Score, T->dExt3Index, T->dExt3Score, T->dExt3Index, T->dOffsets, dKmerBase.p, dKStart.p, dKLen.p,
+                               dKPos.p, blockBase, kStartHi, cum, T->ext3Lo, posQuery);
+    } else {   // 2 + 2 + 3
         if (pass == KMERS_COUNT)
             hipLaunchKernelGGL(count_kmers7_kernel, perWave, block, 0, ctx->stream, nPos, dPosBase.p, bq, dQ.p, dQOff.p, dKB.p, kmerThr, T->dExt2Score,
                                T->dExt3Score, dKmerCount.p, cum, T->ext3Lo, posQuery);
@@ -3041,9 +3086,10 @@ int PfBatch::stageUpload() {
     hOff.assign(bq + 1, 0);
     hPos.assign(bq + 1, 0);
     for (uint32_t x = 0; x <= bq; x++) hOff[x] = c.qOffsets[qBeg + x] - r0;
+    const int span = sdKmerShape(c.T->k)->span;   // (a target of another size does not exist: sd_target_create*, the builders)
     for (uint32_t x = 0; x < bq; x++) {
         const int64_t L = (int64_t) (hOff[x + 1] - hOff[x]);
-        hPos[x + 1] = hPos[x] + (uint64_t) std::max<int64_t>(0, L - (c.T->k == 6 ? SPAN6 : SPAN7) + 1);
+        hPos[x + 1] = hPos[x] + (uint64_t) std::max<int64_t>(0, L - span + 1);
     }
     nPos = hPos[bq];
     if (nPos * 64 >= (1ull << 32) && bq > 1) return retry(PF_RETRY_HALF);   // a wavefront per position: a dispatch carries at most 2^32 work-items

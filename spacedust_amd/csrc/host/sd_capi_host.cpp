@@ -102,7 +102,7 @@ int sd_host_sw_comp_bias(sd_host *h, int which, const uint8_t *residues, const u
 
 int sd_host_index_build(sd_host *h, const uint8_t *residues, const uint64_t *offsets, uint32_t n, int kmerSize,
                         int kmerThr, int mask, double maskProb, sd_host_index **out) {
-    if (!out || (kmerSize != 6 && kmerSize != 7)) return SD_EINVAL;
+    if (!out || kmerSize < 5 || kmerSize > 7) return SD_EINVAL;
     // positions in the index are 16 bit (IndexEntryLocal::position_j, M/src/prefiltering/IndexTable.h): sequences beyond
     // 65 535 residues (--max-seq-len) are the caller's to split, not something to wrap silently
     for (uint32_t i = 0; i < n; i++)

@@ -251,14 +251,18 @@ void kmerThrBias16From(const float *cb, int N, const uint8_t *seedPos, int k, in
 }
 
 int spacedPattern(int k, uint8_t *pos) {
+    // one row per k-mer size (Sequence.h:21-24)
+    static const int8_t s5[] = {1, 1, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1};
     static const int8_t s6[] = {1, 1, 0, 1, 0, 1, 0, 0, 1, 1};
     static const int8_t s7[] = {1, 1, 0, 1, 0, 1, 1, 0, 0, 1, 1};
-    const int8_t *s = k == 6 ? s6 : s7;
-    int span = k == 6 ? 10 : 11;
+    static const struct { int k, span; const int8_t *s; } rows[] = {{5, 12, s5}, {6, 10, s6}, {7, 11, s7}};
+    const auto *r = &rows[2];
+    for (const auto &x : rows)
+        if (x.k == k) r = &x;
     int n = 0;
-    for (int i = 0; i < span; i++)
-        if (s[i]) pos[n++] = (uint8_t) i;
-    return span;
+    for (int i = 0; i < r->span; i++)
+        if (r->s[i]) pos[n++] = (uint8_t) i;
+    return r->span;
 }
 
 void buildExtMatrix(const SubMat &seed8, int wordLen, ExtMatrix &out, int threads) {
@@ -315,11 +319,13 @@ void buildExtMatrix(const SubMat &seed8, int wordLen, ExtMatrix &out, int thread
 
 size_t generateKmerList(const ExtMatrix &three, const ExtMatrix &two, int k, const uint8_t *window, int thr,
                         std::vector<uint32_t> &out) {
-    // divide strategy after the reversal at KmerGenerator.cpp:84-85: k=6 -> [3,3]; k=7 -> [2,2,3]
+    // divide strategy after the reversal at KmerGenerator.cpp:84-85: k=5 -> [2,3]; k=6 -> [3,3]; k=7 -> [2,2,3]
     const ExtMatrix *mats[3];
     int steps[3];
     int nSteps;
-    if (k == 6) {
+    if (k == 5) {
+        nSteps = 2; steps[0] = 2; steps[1] = 3; mats[0] = &two; mats[1] = &three;
+    } else if (k == 6) {
         nSteps = 2; steps[0] = 3; steps[1] = 3; mats[0] = &three; mats[1] = &three;
     } else {
         nSteps = 3; steps[0] = 2; steps[1] = 2; steps[2] = 3; mats[0] = &two; mats[1] = &two; mats[2] = &three;

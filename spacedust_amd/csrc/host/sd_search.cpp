@@ -314,7 +314,7 @@ static int searchCreate(int device, const sd_search_params *par, const sd_setdb 
     }
     const uint64_t tRes = target->offsets[target->n];
     s->k = ungapped ? 0 : (par->kmerSize ? par->kmerSize : sd_host_auto_kmer_size(tRes));   // (ungapped: no k-mers anywhere; the stats report 0)
-    if (!ungapped && s->k != 6 && s->k != 7) return SD_EUNSUPPORTED;
+    if (!ungapped && (s->k < 5 || s->k > 7)) return SD_EUNSUPPORTED;
     s->kmerThr = ungapped ? 0 : par->profileQueries ? sd_host_profile_kmer_threshold(par->sensitivity, s->k) : sd_host_kmer_threshold(par->sensitivity, s->k);
     const int indexThr = par->profileQueries ? 0 : s->kmerThr;   // profile searches index every k-mer (Prefiltering.cpp:525-527)
     if (view && (view->kmerSize != s->k || view->kmerThr != indexThr)) return SD_EINVAL;

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """What the prefilter against a profile target costs on the device: set G of tests/golden/profile_vectors.npz (18 crafted profiles,
 5 084 positions) repeated to about 10^6 positions, indexed by sd_target_build_profile at the default profile threshold
-(Host.profile_kmer_threshold(4.0, 6)), then 8 192 sequence queries (the golden sequences, repeated) through sd_prefilter_batch.
+(Host.profile_kmer_threshold(4.0, k); -k 6 unless given, -k 5 is the reference's k for this search), then 8 192 sequence queries (the golden sequences, repeated) through sd_prefilter_batch.
 Every timed call ends in a device synchronise inside the library; the first build and the first query pass are warm-up.
 
-    python tools/bench_target_profile.py [--positions 1000000] [--queries 8192] [--runs 3] [--out profiles/target_profile.txt]
+    python tools/bench_target_profile.py [-k 6] [--positions 1000000] [--queries 8192] [--runs 3] [--out profiles/target_profile.txt]
     python tools/bench_target_profile.py --search      (adds: the same input as DBs through `sdgpu prefilter | swapresults | align |
                                                         swapresults` one by one and through `sdgpu search`, wall time of each process)
 
@@ -36,7 +36,7 @@ def write_db(path, payloads, dbtype):
         f.write(struct.pack('<i', dbtype))
 
 
-def search_leg(log, data, poff, seqs, sensitivity, runs):
+def search_leg(log, data, poff, seqs, sensitivity, runs, k):
     """the target-profile search on DBs: the four modules one by one, then `sdgpu search` (which runs them in one process with the
     target resident); every time is the wall time of one process, DB loads and writes included"""
     sdgpu = os.path.join(ROOT, 'spacedust_amd', 'sdgpu')
@@ -46,7 +46,7 @@ def search_leg(log, data, poff, seqs, sensitivity, runs):
         write_db(q, [s.encode() + b'\n' for s in seqs], 0)
         write_db(t, [data[int(poff[i]):int(poff[i + 1])] for i in range(len(poff) - 1)], 2)
         common = ['--threads', threads, '-v', '0']
-        pref = ['-s', str(sensitivity), '--max-seqs', '300', '-c', '0', '--cov-mode', '0', '--comp-bias-corr', '1', '--min-ungapped-score', '15']
+        pref = ['-k', str(k), '-s', str(sensitivity), '--max-seqs', '300', '-c', '0', '--cov-mode', '0', '--comp-bias-corr', '1', '--min-ungapped-score', '15']
         aln = ['-a', '1', '-e', '0.001', '--max-seqs', '2147483647', '-c', '0', '--cov-mode', '0']
         steps = (('prefilter', [q, t, tmp + '/pref'] + pref), ('swapresults (prefilter rows)', [q, t, tmp + '/pref', tmp + '/pref_swapped', '-e', '0.001']),
                  ('align', [t, q, tmp + '/pref_swapped', tmp + '/aln_swapped'] + aln),
@@ -74,6 +74,7 @@ def search_leg(log, data, poff, seqs, sensitivity, runs):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('-k', type=int, default=6, help='k-mer size of the index and of the search: 5 or 6')
     ap.add_argument('--positions', type=int, default=1000000)
     ap.add_argument('--queries', type=int, default=8192)
     ap.add_argument('--runs', type=int, default=3)
@@ -95,15 +96,15 @@ def main():
     one = d['poff'].astype(np.uint64)
     poff = np.concatenate([[0], (one[1:][None, :] + (np.arange(reps, dtype=np.uint64) * one[-1])[:, None]).reshape(-1)]).astype(np.uint64)
     prof = host.map_profiles(data, poff)
-    thr = host.profile_kmer_threshold(a.sensitivity, 6)
+    thr = host.profile_kmer_threshold(a.sensitivity, a.k)
     n_prof, n_pos = len(poff) - 1, int(prof['offsets'][-1])
     log('device: %s' % gpu.device_name())
-    log('target: set G x %d = %d profiles, %d positions; k = 6, profile threshold %d (-s %.1f)' % (reps, n_prof, n_pos, thr, a.sensitivity))
+    log('target: set G x %d = %d profiles, %d positions; k = %d, profile threshold %d (-s %.1f)' % (reps, n_prof, n_pos, a.k, thr, a.sensitivity))
     times, t = [], None
     for r in range(a.runs + 1):
         del t
         t0 = time.time()
-        t = api.Target.build_profile_on_device(gpu, host, prof, k=6, kmer_thr=thr)
+        t = api.Target.build_profile_on_device(gpu, host, prof, k=a.k, kmer_thr=thr)
         dt = time.time() - t0
         if r:
             times.append(dt)
@@ -117,8 +118,8 @@ def main():
     base = [blob[off[i]:off[i + 1]] for i in range(len(off) - 1)]
     seqs = [base[i % len(base)] for i in range(a.queries)]
     res, qoff = host.map_sequences(seqs)
-    _, dg_b, km_b = host.comp_bias(res, qoff)
-    par = api.prefilter_params(host, n_prof, kmer_thr=thr, max_hits=300, cov_mode=0, cov_thr=0.0, k=6)
+    _, dg_b, km_b = host.comp_bias(res, qoff, a.k)
+    par = api.prefilter_params(host, n_prof, kmer_thr=thr, max_hits=300, cov_mode=0, cov_thr=0.0, k=a.k)
     ident = np.full(len(seqs), 0xFFFFFFFF, np.uint32)
     times = []
     for r in range(a.runs + 1):
@@ -134,7 +135,7 @@ def main():
         % (len(seqs), int(qoff[-1]), med, len(times), int(stats[:, 0].sum()), int(stats[:, 1].sum()), int(cnt.sum()), len(seqs) / med))
     if a.search:
         del t
-        search_leg(log, data, poff, seqs, a.sensitivity, a.runs)
+        search_leg(log, data, poff, seqs, a.sensitivity, a.runs, a.k)
     if a.out:
         with open(a.out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
