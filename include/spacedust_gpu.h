@@ -266,6 +266,15 @@ int sd_selftest_kmermatch_records(sd_ctx *ctx, const struct sd_kmermatch_params_
                                   const uint64_t *offsets, const uint32_t *keys, const uint8_t *letterMap21, uint64_t recCap,
                                   uint32_t *seqConsidered, uint32_t *seqThreshold, uint32_t *seqExcess, uint64_t *recOff, uint64_t *recKey,
                                   uint32_t *recId, uint32_t *recLen, uint32_t *recPos, uint64_t *stats);
+/* sd_selftest_mask: the masking phase of sd_target_build alone (csrc/hip/sd_index_build.hip: the sequences dealt to the wavefronts
+ * by length, ib_mask_kernel in slices against SD_INDEX_MASK_BUDGET -- the one function sd_target_build itself calls) with the
+ * likelihood ratios of `host`, without the 20^k tables of an index.  maskedOut: seqOffsets[nSeq] bytes, the residues with X (20)
+ * where the float posterior, widened to double, is >= maskProb; nMaskedOut (nullable): how many positions that holds for, residues
+ * that were X already included.  Taken at the doubles of a float v and of the next float above it, a residue masked at the first
+ * and not at the second has the posterior v to the bit (tests/test_gpu_tantan.py). */
+struct sd_host;
+int sd_selftest_mask(sd_ctx *ctx, struct sd_host *host,const uint8_t *residues, const uint64_t *seqOffsets, uint32_t nSeq,
+                     double maskProb, uint8_t *maskedOut, uint64_t *nMaskedOut);
 
 int sd_sw_align_batch_hostpath(sd_ctx *ctx, const sd_sw_params *par, const sd_seqset *queries, const sd_seqset *targets,
                                uint32_t nPairs, const uint32_t *pairQ, const uint32_t *pairT, const uint8_t *isIdentity,

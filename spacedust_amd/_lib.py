@@ -316,6 +316,7 @@ def load():
         'sd_kmermatch_batch': (C.c_int, [_vp, C.POINTER(KmParams), C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
         'sd_selftest_kmermatch_records': (C.c_int, [_vp, C.POINTER(KmParams), C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64] + [_vp] * 9),
         'sd_selftest_field_sort': (C.c_int, [_vp, C.c_uint32, C.c_int] + [_vp] * 6),
+        'sd_selftest_mask': (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_double, _vp, C.POINTER(C.c_uint64)]),
         'sd_host_kmermatch_format': (C.c_int, [C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp,
                                                C.POINTER(C.c_uint64)]),
         'sd_host_clusthash_min_identical': (C.c_uint32, [C.c_float, C.c_uint32]),

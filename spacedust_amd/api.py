@@ -305,6 +305,18 @@ def r2p_weights(tasks, ctx=None):
     return [(freq[at[k]:at[k + 1]].copy(), eff[at[k]:at[k + 1]].copy()) for k in range(len(mats))]
 
 
+def mask_on_device(ctx, host, residues, offsets, mask_prob=0.9):
+    """sd_selftest_mask: the masking phase of sd_target_build alone (no index) -> (masked residues uint8, masked count)"""
+    residues = np.ascontiguousarray(residues, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    assert len(residues) == int(offsets[-1])
+    out = np.zeros(len(residues) + 1, np.uint8)
+    n = C.c_uint64()
+    _check(ctx.h, ctx.L.sd_selftest_mask(ctx.h, host.h, ptr(residues) if len(residues) else ptr(out), ptr(offsets), len(offsets) - 1,
+                                         float(mask_prob), ptr(out), C.byref(n)), 'sd_selftest_mask')
+    return out[:len(residues)], int(n.value)
+
+
 class HostIndex:
     def __init__(self, host, residues, offsets, k, kmer_thr, mask, mask_prob):
         self.host = host

@@ -22,8 +22,9 @@
 //                      length).  The 50 repeat-offset states of tantan's HMM live in 100 VGPRs, the window of the last 50
 //                      residues in 53 more, the 21 x 21 likelihood ratios in LDS; forward pass, backward pass, mask bytes.
 //                      Double precision with the operation order and the fused multiply-adds of the host build (4 partial
-//                      sums over the offsets combined as (s0 + s2) + (s1 + s3), see sd_tantan.cpp), so the float posterior
-//                      that is compared with --mask-prob has the same bits.  The forward posteriors (one float per residue)
+//                      sums over the offsets combined as (s0 + s2) + (s1 + s3), see sd_tantan.cpp); that the float posterior
+//                      compared with --mask-prob then has the reference's bits is checked residue by residue in
+//                      tests/test_gpu_tantan.py (through sd_selftest_mask).  The forward posteriors (one float per residue)
 //                      and the rescaling factors are kept between the passes in a scratch buffer laid out [position][lane].
 //   ib_records_kernel<K, MODE>  the plain builder's generator.  Per k-mer range [lo, hi) that fits the sort buffers: (k-mer - lo,
 //                      target << 16 | position) records of the masked sequences in (target, position) order -- a wavefront walks
@@ -1193,6 +1194,12 @@ struct IndexBuild {
     }
 };
 
+// the kernels read their tables (seed positions, powers, tantan constants) from __constant__ memory: one build at a time
+std::mutex &ibBuildMutex() {
+    static std::mutex m;
+    return m;
+}
+
 }  // namespace
 
 extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask, double maskProb, const uint8_t *residues,
@@ -1203,9 +1210,7 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
     const SdKmerShape *shape = sdKmerShape(kmerSize);
     if (!shape) return sdFail(ctx, SD_EUNSUPPORTED, "k=%d: the device implements k=5, k=6 and k=7", kmerSize);
     if (kmerSize != 6 && (!ext2Score || !ext2Index)) return sdFail(ctx, SD_EINVAL, "k=%d needs the 2-mer score matrix", kmerSize);
-    // the kernels read their tables (seed positions, powers, tantan constants) from __constant__ memory: one build at a time
-    static std::mutex buildMutex;
-    std::lock_guard<std::mutex> buildLock(buildMutex);
+    std::lock_guard<std::mutex> buildLock(ibBuildMutex());
     IndexBuild b(ctx, {"sd_target_build", "residues", nullptr, "index_kmer_histogram", nullptr});
     if (int rc = b.open(kmerSize, shape->tableSize, seqOffsets, nSeq, 0)) return rc;
     sd_target *t = b.t;
@@ -1244,6 +1249,28 @@ extern "C" int sd_target_build(sd_ctx *ctx, int kmerSize, int kmerThr, int mask,
     };
     if (int rc = b.passes(nWavesR, false, generate)) return rc;
     return b.finish(nMaskedResidues, out, stats);
+}
+
+// The masking phase alone, for tests/ (tests/test_gpu_tantan.py reads the kernel's float posteriors through maskProb): ibMaskPhase as
+// sd_target_build calls it -- same knobs, same dealing of the sequences, same launches of ib_mask_kernel -- on a target that holds
+// the offsets and the masked residues only; the bytes and the count are copied out.
+extern "C" int sd_selftest_mask(sd_ctx *ctx, sd_host *host, const uint8_t *residues, const uint64_t *seqOffsets, uint32_t nSeq, double maskProb,
+                                uint8_t *maskedOut, uint64_t *nMaskedOut) {
+    if (!ctx || !host || !residues || !seqOffsets || !maskedOut) return SD_EINVAL;
+    double ratios[IB_ALPH * IB_ALPH];
+    int8_t self[IB_ALPH];
+    if (int rc = sd_host_index_tables(host, ratios, self)) return rc;
+    std::lock_guard<std::mutex> buildLock(ibBuildMutex());
+    IndexBuild b(ctx, {"sd_selftest_mask", "residues", nullptr, nullptr, nullptr});
+    if (int rc = b.open(6, 0, seqOffsets, nSeq, 0)) return rc;
+    sd_target *t = b.t;
+    const uint64_t total = seqOffsets[nSeq];
+    SD_HIP(ctx, hipMalloc((void **) &t->dMasked, std::max<uint64_t>(total, 1) + 64));
+    uint64_t nMaskedResidues = 0;
+    if (int rc = ibMaskPhase(ctx, t, b.knobs, residues, seqOffsets, nSeq, 1, maskProb, ratios, b.notePeak, nMaskedResidues)) return rc;
+    SD_HIP(ctx, hipMemcpy(maskedOut, t->dMasked, total, hipMemcpyDeviceToHost));
+    if (nMaskedOut) *nMaskedOut = nMaskedResidues;
+    return SD_OK;
 }
 
 // The index of a *profile* target DB (the profile branch of IndexBuilder::fillDatabase, IndexBuilder.cpp:61-62,94-128,200-219): the lists

@@ -3,8 +3,11 @@
 // repeatOffsetProbDecay 0.9, no gaps, minMaskProb 0.9, mask letter X).
 // Algorithm: forward/backward HMM of M/lib/tantan/tantan.cpp:308-460 (the endGapProb == 0
 // branches).  The summation order of the reference's AVX2 build is kept (4 running partial
-// sums combined as (s0+s2)+(s1+s3), tantan.cpp:320-352 with mcf_simd.h:175-179) so the float
-// posteriors agree bit for bit with that build.
+// sums combined as (s0+s2)+(s1+s3), tantan.cpp:320-352 with mcf_simd.h:175-179) and the
+// multiply-adds are left to the compiler to fuse (-ffp-contract=fast, as in that build).  That the
+// float posteriors then have that build's bits, residue by residue, is what
+// tests/test_tantan_posteriors.py checks against posteriors read from the reference through its
+// mask threshold (tests/golden/tantan_vectors.npz); nothing else guarantees it.
 #include "sd_host.h"
 
 #include <cmath>

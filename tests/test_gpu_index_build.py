@@ -1,6 +1,7 @@
 """sd_target_build (index construction on the device: tantan masking, k-mer records, per-target dedupe, list order) against the
 host-built index (sd_host_index_build, itself pinned entry for entry on the reference's IndexTable / Masker through libsdref in
-tests/test_oracle_golden.py, tests/test_oracle_ref.py) -- masked bytes, list starts and every (sequence, position) entry."""
+tests/test_oracle_golden.py; tantan's posteriors bit for bit in tests/test_tantan_posteriors.py, the device's in
+tests/test_gpu_tantan.py) -- masked bytes, list starts and every (sequence, position) entry."""
 import numpy as np
 import pytest
 
